@@ -2,6 +2,7 @@
 """bench.py — MC-samples/sec (fwd+ELBO) of the MI355X Monte-Carlo variational forward path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload bert_base|bert_base_serial|bert_large_qa|bert_base_train|bert_large_qa_train|linear768|linear768_m32|mlp]
+                    [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment (WORLD_SIZE unset) this process only LAUNCHES the job: it starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py <same flags>` as a child process (it never touches a
@@ -70,7 +71,15 @@ def parse():
                          "forward workloads through sampling.GraphedSampler: on one rank always, on several ranks when a "
                          "rank's shard is <= 4 samples; the training workloads through training.GraphedTrainingStep on one rank "
                          "(S-sharded ranks run the eager step: bucketed gradient all-reduce under backward)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy "
+                         "(float32 / float64, rank 0): per-sample outputs, their means, log_prior, "
+                         "log_variational_posterior and elbo; the training workloads: elbo and the trainable parameters "
+                         "after the step.  An array over 4M elements is stored as a fixed, seeded sample of 4M of them")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 _STRONG = False  # --strong: S is the total per step
@@ -242,10 +251,12 @@ def make_bert(device, S, dtype, train=False, train_mode=False, serial=False, gra
     labels_d = labels.to(device)
 
     harness = _Harness(bmodel, inputs, S * _world())
+    outs = {}  # the last step's outputs as its caller receives them (--dump-outputs)
 
     def step():
         with torch.no_grad():
             raw, mean, lp, lq = harness()
+            outs["step"] = (raw, mean, lp, lq)
             nll = torch.nn.functional.cross_entropy(mean[0].float(), labels_d)
             return elbo(lp, lq, nll.double(), n_batches)
 
@@ -263,8 +274,10 @@ def make_bert(device, S, dtype, train=False, train_mode=False, serial=False, gra
                     lps.append(bmodel.log_prior())
                     lqs.append(bmodel.log_variational_posterior())
                 mean = torch.stack(logits).float().mean(0)
+                lp, lq = torch.stack(lps).double().mean(), torch.stack(lqs).double().mean()
+                outs["step"] = ((logits,), (mean,), lp, lq)
                 nll = torch.nn.functional.cross_entropy(mean, labels_d)
-                return elbo(torch.stack(lps).double().mean(), torch.stack(lqs).double().mean(), nll.double(), n_batches)
+                return elbo(lp, lq, nll.double(), n_batches)
 
     if train:
         # the reference's training step (examples/bert_glue.py:227-241) — forward, ELBO, backward through
@@ -316,6 +329,7 @@ def make_bert(device, S, dtype, train=False, train_mode=False, serial=False, gra
                                         if serial else "fwd+ELBO")), "samples_per_gpu": S,
             "batch": B, "seq_len": L, "bayesian_linears": len(bmodel.fused_children()), "bayesian_scalars": 85609730}
     cfgd.update(info)
+    step.outputs = outs
     return step, cpu_baseline, cfgd, bmodel
 
 
@@ -346,10 +360,12 @@ def make_bert_large_qa(device, S, dtype, train=False, train_mode=False, graph_tr
     inputs = {"input_ids": ids.to(device), "attention_mask": torch.ones(B, L, dtype=torch.long, device=device)}
 
     harness = _Harness(bmodel, inputs, S * _world())
+    outs = {}
 
     def step():
         with torch.no_grad():
             raw, mean, lp, lq = harness()
+            outs["step"] = (raw, mean, lp, lq)
             ce = torch.nn.functional.cross_entropy
             nll = 0.5 * (ce(mean[0].float(), sp) + ce(mean[1].float(), ep))  # examples/bert_squad.py:474-481
             return elbo(lp, lq, nll.double(), n_batches)
@@ -400,6 +416,7 @@ def make_bert_large_qa(device, S, dtype, train=False, train_mode=False, graph_tr
             "seq_len": L, "bayesian_linears": len(bmodel.fused_children()), "gelu_fused_into_gemm": n_fused,
             "residual_layernorm_fused": n_ln, "qkv_in_one_launch": n_qkv,
             "attention_kernel": bool(attn), "embeddings_in_one_launch": n_emb}
+    step.outputs = outs
     return step, cpu_baseline, cfgd, bmodel
 
 
@@ -416,10 +433,12 @@ def make_linear(device, S, dtype, M):
     if dtype != "fp32":
         xd = xd.to(torch.bfloat16 if dtype == "bf16" else torch.float16)
     tgt = torch.randint(0, 768, (M,), device=device)
+    outs = {}
 
     def step():
         with torch.no_grad():
             raw, mean, lp, lq = sample_bayesian(model, xd, S * _world())
+            outs["step"] = (raw, mean, lp, lq)
             nll = torch.nn.functional.cross_entropy(mean[0].float(), tgt)
             return elbo(lp, lq, nll.double(), 100)
 
@@ -438,6 +457,7 @@ def make_linear(device, S, dtype, M):
 
     cfgd = {"workload": f"bnn.Linear(768,768) default init + mixture prior, x=[{M},768], fwd+ELBO",
             "samples_per_gpu": S, "batch": M}
+    step.outputs = outs
     return step, cpu_baseline, cfgd, model
 
 
@@ -451,12 +471,16 @@ def make_mlp(device, S, dtype):
     bmodel = bf.to_bayesian(mlp, delta=0.05).to(device)
     x = torch.rand(128, 784)
     xd, labels = x.to(device), torch.randint(0, 10, (128,), device=device)
+    outs = {}
 
     def step():
         with torch.no_grad():
             raw, mean, lp, lq = sample_bayesian(bmodel, xd, S * _world())
+            outs["step"] = (raw, mean, lp, lq)
             nll = torch.nn.functional.nll_loss(mean[0], labels, reduction="sum")
             return elbo(lp, lq, nll.double(), 469)
+
+    step.outputs = outs
 
     def cpu_baseline():
         from oracle.model_oracle import log_probs, to_oracle
@@ -772,6 +796,64 @@ def _train_graph_note(step):
     return st["note"] or ("GraphedTrainingStep" if st["g"] is not None and st["g"].graph is not None else False)
 
 
+DUMP_CAP = 1 << 22  # elements; a larger array is dumped as a fixed, seeded sample of this many (16 MiB in float32)
+
+
+def _dump_sample(n):
+    """Sorted flat indices (with repeats) of the seeded sample kept of an n-element array; None: the array is kept whole.
+    They depend on n alone, so two runs of the same workload sample the same elements."""
+    if n <= DUMP_CAP:
+        return None
+    return torch.randint(0, n, (DUMP_CAP,), generator=torch.Generator().manual_seed(0)).sort().values
+
+
+def dump_outputs(out_dir, outputs, elbo_value, params):
+    """--dump-outputs: the last timed step's results as DIR/<name>.npy.  outputs["step"] = (raw, mean, log_prior, lvp) of
+    the forward workloads, as sample_bayesian returns them (bert_base_serial: raw[0] is the list of its S logits);
+    params: the trainable parameters of the training workloads, one virtual concatenation in parameters() order.
+    Returns {name: {"shape": shape before sampling, "sampled": bool}} for the JSON line."""
+    import numpy as np
+
+    kept = {}  # name: (flat values kept, shape before sampling)
+
+    def keep(name, t):
+        t = t.detach()
+        idx = _dump_sample(t.numel())
+        kept[name] = (t.reshape(-1) if idx is None else t.reshape(-1)[idx.to(t.device)], list(t.shape))
+
+    if "step" in outputs:
+        raw, mean, lp, lq = outputs["step"]
+        for i, r in enumerate(raw):
+            keep(f"samples_{i}", torch.stack(r) if isinstance(r, (list, tuple)) else r)
+        for i, m in enumerate(mean):
+            keep(f"mean_{i}", m)
+        keep("log_prior", lp)
+        keep("log_variational_posterior", lq)
+    if params:
+        sizes = [p.numel() for p in params]
+        idx, parts, off = _dump_sample(sum(sizes)), [], 0
+        for p, n in zip(params, sizes):
+            flat = p.detach().reshape(-1)
+            if idx is not None:
+                lo, hi = (int(v) for v in torch.searchsorted(idx, torch.tensor([off, off + n])))
+                flat = flat[(idx[lo:hi] - off).to(flat.device)]
+            parts.append(flat.float())
+            off += n
+        kept["parameters"] = (torch.cat(parts), [off])
+    kept["elbo"] = (torch.tensor(elbo_value, dtype=torch.float64), [])
+    host, info = {}, {}
+    for name, (flat, shape) in kept.items():
+        sampled = flat.numel() != int(np.prod(shape))
+        a = flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32).cpu().numpy()
+        host[name] = a if sampled else a.reshape(shape)
+        info[name] = {"shape": shape, "sampled": sampled}
+    assert sum(a.nbytes for a in host.values()) <= 64 << 20  # at most two arrays of any workload reach DUMP_CAP
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return info
+
+
 DEFAULTS = {"bert_base": (10, "bf16"), "bert_base_serial": (10, "bf16"), "bert_base_train": (10, "bf16"), "bert_large_qa": (10, "fp16"),
             "bert_large_qa_train": (10, "bf16"), "linear768": (10, "bf16"), "linear768_m32": (10, "bf16"), "mlp": (5, "bf16")}
 
@@ -793,7 +875,9 @@ def main():
               f"`python bench.py --gpus {args.gpus}` or torch.distributed.run --nproc-per-node {args.gpus}",
               file=sys.stderr)
         sys.exit(2)
-    have_gpu = torch.cuda.is_available()
+    # no visible GPU (HIP_VISIBLE_DEVICES="" included) is settled from sysfs first: asking the HIP runtime opens the device
+    # even then, in every rank of a CPU dry run
+    have_gpu = visible_gpus() != 0 and torch.cuda.is_available()
     if args.dry_run and not have_gpu:
         if world > 1:
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -861,6 +945,7 @@ def main():
         step, cpu_baseline, cfgd, bmodel = make_linear(device, S, dtype, 32)
     else:
         step, cpu_baseline, cfgd, bmodel = make_mlp(device, S, dtype)
+    step_outputs = step.outputs  # (a step captured below writes the graph's own buffers into it)
 
     def barrier():
         if world > 1:
@@ -924,6 +1009,10 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
+    if args.dump_outputs and rank == 0:
+        # before the roofline leg: its steps would overwrite the last timed step's buffers
+        params = [p for p in bmodel.parameters() if p.requires_grad] if args.workload.endswith("_train") else None
+        cfgd["dump_outputs"] = dump_outputs(args.dump_outputs, step_outputs, last, params)
 
     # roofline leg: the same steps again with HIP events around every GEMM / sampling launch
     lib = _C.lib()

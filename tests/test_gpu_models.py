@@ -1013,6 +1013,37 @@ def test_bench_line_carries_the_contract_keys():
     assert "HSA_ENABLE_IPC_MODE_LEGACY" in d["config"]["env"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """bench.py --dump-outputs (the MLP workload: the whole step replayed from a HIP graph): the arrays are the last timed
+    step's — elbo.npy is the line's last_elbo, mean_0 the mean of samples_0 — and a second run with the same arguments
+    writes the same values (the forward has no float atomics: bit for bit)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "mlp", "--steps", "3", "--warmup", "1",
+                            "--no-traffic", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 3 and d["config"]["hip_graph"] is True
+        arrays = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert set(arrays) == set(d["config"]["dump_outputs"]) == {"samples_0", "mean_0", "log_prior",
+                                                                  "log_variational_posterior", "elbo"}
+        got.append((d, arrays))
+    (d, a), (_, b) = got
+    assert a["samples_0"].shape == (5, 128, 10) and a["samples_0"].dtype == np.float32
+    assert a["mean_0"].shape == (128, 10) and a["elbo"].dtype == np.float64 and float(a["elbo"]) == d["config"]["last_elbo"]
+    assert np.isfinite(a["samples_0"]).all() and np.isfinite(float(a["log_prior"])) and np.isfinite(float(a["elbo"]))
+    np.testing.assert_allclose(a["mean_0"], a["samples_0"].mean(0), rtol=2e-2, atol=2e-2)   # (bf16 outputs)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 @pytest.mark.parametrize("dtype", ["bf16", "fp16", "fp32"])
 def test_bench_bert_line_accounts_for_the_sampling_launch_and_the_positions(dtype):
     """every dtype's line charges the cross-layer sampling launch with the plan's bytes (fp32 used to report
