@@ -111,7 +111,19 @@ SYMBOLS = {
     "bf_profile_read": (_i, [_i, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double),
                              ctypes.POINTER(ctypes.c_double)]),
     "bf_profile_read_launches": (_sz, [_i, _vp, _vp, _sz]),
+    "bf_mc_predictive_bytes": (_sz, [_i64, _i64, _i, _i, ctypes.POINTER(ctypes.c_size_t)]),
+    "bf_mc_predictive_workspace_bytes": (_sz, [_i]),
+    "bf_mc_predictive_partial": (_i, [_vp, _i, _i64, _i64, _i, _i64, _i64, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp]),
+    "bf_mc_predictive_finish": (_i, [_vp, _i64, _i64, _i, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
+
+
+class bf_predictive_out_t(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "d_probs", "d_predictive_entropy", "d_expected_entropy", "d_mutual_information", "d_prediction",
+        "d_log_likelihood", "d_correct_per_sample", "d_scalars", "d_counts")]
+
+
 class bf_pgrad_t(ctypes.Structure):
     _fields_ = [("d_dw", ctypes.c_void_p), ("d_rho", ctypes.c_void_p), ("d_dmu", ctypes.c_void_p), ("d_drho", ctypes.c_void_p),
                 ("n", ctypes.c_uint64), ("stream_id", ctypes.c_uint32), ("splits", ctypes.c_int32)]

@@ -946,3 +946,76 @@ def layernorm_supported(x: Tensor, residual: Optional[Tensor], ln) -> bool:
     return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float16, torch.float32) and n % 8 == 0 and n <= 4096 and
             (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype)) and
             ln.weight.dtype in (torch.float32, x.dtype) and ln.bias is not None and ln.bias.dtype == ln.weight.dtype)
+
+
+# ------------------------------------------------------------------------------------- Monte-Carlo predictive statistics
+_PREDICTIVE_WS = {}
+
+
+def predictive_layout(R: int, C: int, S_total: int, has_labels: bool):
+    """(bytes, offsets) of the packed partials of bf_mc_predictive_partial: offsets = (sum_p, sum_h, sum_py, sum_logpy,
+    counts, end) in bytes; sum_p / sum_h are fp32, the rest fp64 (starting at offsets[2], 8-byte aligned)."""
+    offs = (ctypes.c_size_t * 6)()
+    n = _C.lib().bf_mc_predictive_bytes(int(R), int(C), int(S_total), int(bool(has_labels)), offs)
+    if n == 0:
+        raise ValueError(f"predictive_layout: bad shape R={R} C={C} S_total={S_total}")
+    return int(n), tuple(int(o) for o in offs)
+
+
+def predictive_workspace(device: torch.device, S_total: int) -> Tensor:
+    """Zero-filled workspace of the predictive kernels, one per (device, stream): the kernels leave it zeroed for the next
+    launch (their tickets), so it is filled once, when it is allocated or grown.  It holds state between launches, so two
+    launches must not use it at once.  Under a stream capture every call gets its own: every capture runs on the same
+    capture stream, and two graphs replayed concurrently must not share tickets (the captured zero-fill then runs at the
+    start of every replay)."""
+    need = int(_C.lib().bf_mc_predictive_workspace_bytes(int(S_total)))
+    if torch.cuda.is_current_stream_capturing():
+        return torch.zeros(need, dtype=torch.uint8, device=device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), _stream_ptr())
+    ws = _PREDICTIVE_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.zeros(need, dtype=torch.uint8, device=device)
+        _PREDICTIVE_WS[key] = ws
+    return ws
+
+
+def predictive_partial(logits: Tensor, labels: Optional[Tensor], ignore_index: int, sample_base: int, S_total: int,
+                       partial: Tensor, ws: Tensor) -> Tensor:
+    """bf_mc_predictive_partial of logits [S_local, R, C] (last dim contiguous) into the uint8 buffer `partial`."""
+    _require_device(logits, "mc_predictive logits")
+    S_local, R, C = logits.shape
+    if logits.stride(2) != 1 and C > 1:
+        raise ValueError("mc_predictive: the class dimension must be contiguous")
+    _C.check(_C.lib().bf_mc_predictive_partial(
+        logits.data_ptr(), _TORCH2BF[logits.dtype], logits.stride(0), logits.stride(1) if R > 1 else C, S_local, R, C,
+        labels.data_ptr() if labels is not None else None, int(ignore_index), int(sample_base), int(S_total),
+        partial.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_mc_predictive_partial")
+    return partial
+
+
+def predictive_outputs(R: int, C: int, S_total: int, has_labels: bool, device) -> dict:
+    """Fresh output tensors of bf_mc_predictive_finish."""
+    f32 = dict(dtype=torch.float32, device=device)
+    out = {"probs": torch.empty((R, C), **f32), "predictive_entropy": torch.empty(R, **f32),
+           "expected_entropy": torch.empty(R, **f32), "mutual_information": torch.empty(R, **f32),
+           "prediction": torch.empty(R, dtype=torch.int64, device=device)}
+    if has_labels:
+        out["log_likelihood"] = torch.empty(R, dtype=torch.float64, device=device)
+        out["correct_per_sample"] = torch.empty(S_total, dtype=torch.int64, device=device)
+        out["scalars"] = torch.empty(2, dtype=torch.float64, device=device)
+        out["counts"] = torch.empty(2, dtype=torch.int64, device=device)
+    return out
+
+
+def predictive_finish(partial: Tensor, R: int, C: int, S_total: int, labels: Optional[Tensor], ignore_index: int,
+                      out: dict, ws: Tensor) -> dict:
+    """bf_mc_predictive_finish: complete partials -> the tensors of `out` (predictive_outputs)."""
+    o = _C.bf_predictive_out_t()
+    for name in ("probs", "predictive_entropy", "expected_entropy", "mutual_information", "prediction",
+                 "log_likelihood", "correct_per_sample", "scalars", "counts"):
+        t = out.get(name)
+        setattr(o, "d_" + name, t.data_ptr() if t is not None else None)
+    _C.check(_C.lib().bf_mc_predictive_finish(
+        partial.data_ptr(), int(R), int(C), int(S_total), labels.data_ptr() if labels is not None else None,
+        int(ignore_index), ctypes.byref(o), ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_mc_predictive_finish")
+    return out

@@ -11,7 +11,8 @@ over the ranks of a torch.distributed group: rank r runs the global sample indic
 all-reduce (RCCL over xGMI on MI355X) of the packed [sum of outputs | sum log_prior | sum lvp] buffer finishes the
 step.  The message is KB-sized, i.e. latency-bound: one collective per step, on the compute stream.
 """
-from typing import Any, Callable, Dict, Optional, Sequence, Tuple, Union
+from dataclasses import dataclass, fields
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -213,6 +214,217 @@ def sample_bayesian(model: Model, inputs, samples: int, select: Optional[Callabl
     return raw, tuple(means), log_prior, lvp
 
 
+@dataclass
+class Predictive:
+    """Monte-Carlo predictive statistics of one output over the step's S samples (bf_mc_predictive_*).  Every field is a
+    device tensor (reading one is the caller's synchronisation).  Row shapes are the output's without its sample and class
+    axes ([B] for sequence classification, [B, T] for token classification; start/end logits: [B], the classes being the
+    positions).
+
+        probs                [..., C] fp32  Bayesian-model-average probabilities, mean over s of softmax(l_s)
+        predictive_entropy   [...]   fp32  H(probs)                            (total uncertainty)
+        expected_entropy     [...]   fp32  mean over s of H(softmax(l_s))     (aleatoric)
+        mutual_information   [...]   fp32  max(0, predictive - expected)      (epistemic)
+        prediction           [...]   int64 argmax probs (first index on ties)
+    with labels (else None):
+        correct_per_sample   [S]     int64 rows each sample classifies correctly (the reference's per-sample count)
+        acc_std              0-d     fp64  population std of correct_per_sample (np.std, bert_glue.py:237)
+        bma_correct          0-d     int64 rows `prediction` gets right
+        log_likelihood       [...]   fp64  log mean over s of p_s(label); NaN on ignored rows
+        nll                  0-d     fp64  -mean log_likelihood over the valid rows
+        invalid_labels       0-d     int64 labels neither ignore_index nor in [0, C) (treated as ignored)
+    from sample_predictive (else None): mean (the output's mean over S), log_prior, log_variational_posterior."""
+    probs: Tensor
+    predictive_entropy: Tensor
+    expected_entropy: Tensor
+    mutual_information: Tensor
+    prediction: Tensor
+    mean: Optional[Tensor] = None
+    log_prior: Optional[Tensor] = None
+    log_variational_posterior: Optional[Tensor] = None
+    correct_per_sample: Optional[Tensor] = None
+    acc_std: Optional[Tensor] = None
+    bma_correct: Optional[Tensor] = None
+    log_likelihood: Optional[Tensor] = None
+    nll: Optional[Tensor] = None
+    invalid_labels: Optional[Tensor] = None
+
+    def clone(self) -> "Predictive":
+        return Predictive(**{f.name: (None if getattr(self, f.name) is None else getattr(self, f.name).clone())
+                             for f in fields(self)})
+
+
+def _predictive_rows(raw: Tensor, labels: Optional[Tensor], what: str = "mc_predictive", idle: bool = False):
+    """raw [S, B, ..., C] -> ([S, R, C] view, labels [R] int64 or None); shapes are checked before devices.  idle: raw is
+    the empty [0, B, ..., C] of a rank without a sample (its view is then None)."""
+    if not isinstance(raw, Tensor) or raw.dim() < 2:
+        raise ValueError(f"{what}: expected per-sample outputs [S, B, ..., C], got {getattr(raw, 'shape', type(raw))}")
+    S, C = raw.shape[0], raw.shape[-1]
+    rows = tuple(raw.shape[1:-1])
+    if (S < 1 and not idle) or C < 1 or any(n == 0 for n in rows):
+        raise ValueError(f"{what}: empty outputs {tuple(raw.shape)}")
+    if raw.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise TypeError(f"{what}: logits must be fp32, bf16 or fp16, not {raw.dtype}")
+    if labels is not None:
+        if not isinstance(labels, Tensor) or tuple(labels.shape) != rows:
+            raise ValueError(f"{what}: labels must have the output's row shape {rows} (outputs {tuple(raw.shape)}), "
+                             f"got {tuple(labels.shape) if isinstance(labels, Tensor) else type(labels)}")
+        if labels.dtype.is_floating_point or labels.dtype == torch.bool:
+            raise TypeError(f"{what}: labels must be integer class indices, not {labels.dtype}")
+    from . import ops
+    from ._C import BayeFormersAMDError
+
+    ops._require_device(raw, f"{what} outputs")
+    if labels is not None and labels.device != raw.device:
+        raise BayeFormersAMDError(f"{what}: labels live on '{labels.device}', the outputs on '{raw.device}'")
+    lab = None if labels is None else labels.reshape(-1).to(torch.int64).contiguous()
+    if idle:
+        return None, lab
+    r3 = raw.reshape(S, -1, C)
+    if C > 1 and r3.stride(2) != 1:
+        r3 = r3.contiguous()
+    return r3, lab
+
+
+class _PredictiveItem(NamedTuple):
+    """One output of a predictive step: its per-sample shape [..., C] without the sample axis, rows, classes, labels [R]
+    (or None), and the packed partials with their fp32 and fp64 parts (views of `partial`)."""
+    shape: tuple
+    R: int
+    C: int
+    labels: Optional[Tensor]
+    partial: Tensor
+    f32: Tensor
+    f64: Tensor
+
+
+class _PredictiveStep:
+    """The predictive statistics of one step's outputs: the partial launch of every output (this rank's samples), the
+    partials' ride in the step's collective, and the finish launches.  ws: the kernels' workspace (default: the cached one
+    of the current device and stream, ops.predictive_workspace)."""
+
+    def __init__(self, raw, labels, ignore_index: int, samples: int, sample_base: int = 0, idle: bool = False,
+                 ws: Optional[Tensor] = None, what: str = "sample_predictive"):
+        from . import ops
+
+        self.items: List[_PredictiveItem] = []
+        self.samples, self.ignore_index, self.ws = int(samples), int(ignore_index), ws
+        for r, lab in zip(raw, labels):
+            r3, lab = _predictive_rows(r, lab, what, idle)
+            C = r.shape[-1]
+            R = int(torch.Size(r.shape[1:-1]).numel())
+            nbytes, offs = ops.predictive_layout(R, C, samples, lab is not None)
+            if self.ws is None:
+                self.ws = ops.predictive_workspace(r.device, samples)
+            partial = torch.empty(nbytes, dtype=torch.uint8, device=r.device)
+            if idle:  # this rank ran no sample: it enters the sums with zeros
+                partial.zero_()
+            else:
+                ops.predictive_partial(r3, lab, ignore_index, sample_base, samples, partial, self.ws)
+            self.items.append(_PredictiveItem(tuple(r.shape[1:]), R, C, lab, partial, partial[:offs[2]].view(torch.float32),
+                                              partial[offs[2]:offs[5]].view(torch.float64)))
+
+    def pack(self, local):
+        """The step's collective buffers with the partials appended: ONE fp64 buffer when the step has one (the fp32 sums
+        ride as fp64), else (fp32 sums | fp32 partials, fp64 sums | fp64 partials)."""
+        if len(local) == 1:
+            return (torch.cat([local[0]] + [it.f32.double() for it in self.items] + [it.f64 for it in self.items]),)
+        return (torch.cat([local[0]] + [it.f32 for it in self.items]), torch.cat([local[1]] + [it.f64 for it in self.items]))
+
+    def unpack(self, packed, local):
+        """Copy the reduced partials back; returns the step's own reduced buffers (shaped as `local`)."""
+        if len(local) == 1:
+            parts = [[it.f32 for it in self.items] + [it.f64 for it in self.items]]
+        else:
+            parts = [[it.f32 for it in self.items], [it.f64 for it in self.items]]
+        out = []
+        for buf, own, dsts in zip(packed, local, parts):
+            off = own.numel()
+            for t in dsts:
+                t.copy_(buf[off:off + t.numel()])
+                off += t.numel()
+            out.append(buf[:own.numel()])
+        return tuple(out)
+
+    def finish(self, means=None, log_prior=None, lvp=None) -> List[Predictive]:
+        from . import ops
+
+        res = []
+        for k, it in enumerate(self.items):
+            has_labels = it.labels is not None
+            o = ops.predictive_outputs(it.R, it.C, self.samples, has_labels, it.partial.device)
+            ops.predictive_finish(it.partial, it.R, it.C, self.samples, it.labels, self.ignore_index, o, self.ws)
+            rows = it.shape[:-1]
+            p = Predictive(probs=o["probs"].view(it.shape), predictive_entropy=o["predictive_entropy"].view(rows),
+                           expected_entropy=o["expected_entropy"].view(rows),
+                           mutual_information=o["mutual_information"].view(rows), prediction=o["prediction"].view(rows),
+                           mean=None if means is None else means[k], log_prior=log_prior, log_variational_posterior=lvp)
+            if has_labels:
+                p.correct_per_sample, p.log_likelihood = o["correct_per_sample"], o["log_likelihood"].view(rows)
+                p.acc_std, p.nll = o["scalars"][0], o["scalars"][1]
+                p.bma_correct, p.invalid_labels = o["counts"][0], o["counts"][1]
+            res.append(p)
+        return res
+
+
+def mc_predictive(raw: Tensor, labels: Optional[Tensor] = None, ignore_index: int = -100) -> Predictive:
+    """Predictive statistics of S per-sample outputs raw [S, B, ..., C] (e.g. `raw[0]` of sample_bayesian): the dims between
+    the sample and class axes fold into rows (token classification [S, B, T, C]: R = B*T).  labels: integer [B, ...] or
+    None.  Two launches, no host synchronisation; single process (an S-sharded step: sample_predictive).  A CPU tensor
+    raises: the statistics run in HIP kernels only."""
+    samples = raw.shape[0] if isinstance(raw, Tensor) and raw.dim() >= 2 else 0
+    return _PredictiveStep((raw,), (labels,), ignore_index, samples, what="mc_predictive").finish()[0]
+
+
+def _labels_per_output(labels, n_out: int):
+    if labels is None:
+        return (None,) * n_out
+    if isinstance(labels, Tensor):
+        labels = (labels,)
+    labels = tuple(labels)
+    if len(labels) != n_out:
+        raise ValueError(f"sample_predictive: {len(labels)} label tensors for {n_out} selected outputs (question answering: "
+                         "pass (start_positions, end_positions))")
+    return labels
+
+
+def _label_sig(labels):
+    if labels is None:
+        return None
+    if isinstance(labels, Tensor):
+        labels = (labels,)
+    return tuple(None if t is None else (tuple(t.shape), t.dtype, t.device) for t in labels)
+
+
+def sample_predictive(model: Model, inputs, samples: int, labels=None, select: Optional[Callable] = None,
+                      group: Optional["dist.ProcessGroup"] = None, ignore_index: int = -100, graph: bool = False
+                      ) -> Tuple[Predictive, ...]:
+    """The step of `sample_bayesian` (same forward, same samples, same mean / log_prior / lvp) plus the predictive statistics
+    of every selected output: one `Predictive` per output.  labels: an integer tensor of the output's row shape, or one per
+    output (question answering: (start_positions, end_positions)), or None.
+
+    Sharded over an S-shard group, each rank computes the partial sums of its samples and they ride in the step's own
+    collective (ONE all-reduce when the outputs are small, as in sample_bayesian; two otherwise); there is no all-gather.
+    graph=True replays the step and the statistics from a HIP graph (`GraphedSampler(predictive=True)`, cached as for
+    sample_bayesian; the results are copies).  The results are detached: evaluation statistics."""
+    if graph:
+        if torch.is_grad_enabled():
+            raise RuntimeError("sample_predictive: graph=True replays a captured forward — call it under torch.no_grad()")
+        return _graphed(model, inputs, samples, select, group, predictive=True, labels=labels, ignore_index=ignore_index)
+    distributed, rank, world = _shard_group(group)
+    with torch.no_grad():
+        raw, sizes, local = _local_step(model, inputs, samples, select, rank, world)
+        start, count = shard_span(samples, rank, world)
+        step = _PredictiveStep(raw, _labels_per_output(labels, len(raw)), ignore_index, samples, start, count == 0)
+        if distributed:
+            packed = step.pack(local)
+            for t in packed:
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+            local = step.unpack(packed, local)
+        means, log_prior, lvp = _finish_step(raw, sizes, local, samples, None, False)
+        return tuple(step.finish(means, log_prior, lvp))
+
+
 _GRAPHED_KEEP = 2  # GraphedSamplers kept per model by sample_bayesian(graph=True): the last two batch signatures
 
 
@@ -271,17 +483,23 @@ def _select_key(select):
     return ("function", code, select.__defaults__, tuple(cells), getattr(select, "__self__", None))
 
 
-def _graphed(model: Model, inputs, samples: int, select, group):
+def _graphed(model: Model, inputs, samples: int, select, group, predictive: bool = False, labels=None,
+             ignore_index: int = -100):
     cache = graphed_samplers(model)
     skey = _select_key(select)
+    pkw = dict(predictive=True, labels=labels, ignore_index=ignore_index) if predictive else {}
     if skey is None:  # a selection that cannot be recognised again: capture for this call only
-        sampler = GraphedSampler(model, inputs, samples, select=select, group=group)
+        sampler = GraphedSampler(model, inputs, samples, select=select, group=group, **pkw)
         try:
+            if predictive:
+                return tuple(p.clone() for p in sampler(inputs, labels))
             raw, means, log_prior, lvp = sampler(inputs)
             return tuple(r.clone() for r in raw), tuple(m.clone() for m in means), log_prior.clone(), lvp.clone()
         finally:
             sampler.close()
     key = (GraphedSampler._sig(inputs), int(samples), skey, group)
+    if predictive:
+        key = key + (("predictive", _label_sig(labels), int(ignore_index)),)
     sampler = None
     for i, (k, sm) in enumerate(cache):
         if k == key and sm.graph is not None:
@@ -291,8 +509,10 @@ def _graphed(model: Model, inputs, samples: int, select, group):
     if sampler is None:
         while len(cache) >= _GRAPHED_KEEP:
             cache.pop(0)[1].close()
-        sampler = GraphedSampler(model, inputs, samples, select=select, group=group)
+        sampler = GraphedSampler(model, inputs, samples, select=select, group=group, **pkw)
         cache.append((key, sampler))
+    if predictive:  # copies, as for the means below
+        return tuple(p.clone() for p in sampler(inputs, labels))
     raw, means, log_prior, lvp = sampler(inputs)
     # the convenience path hands out COPIES of the small results (an evaluation loop that collects `mean[0]` per batch
     # must not end up with the last batch in every entry); `raw` stays the graph's buffer, valid until the next call
@@ -327,10 +547,17 @@ class GraphedSampler:
     plan (which priors are aliases of their frozen means, where the sampled weights live).  `__call__` compares them with
     the current state and captures again when one changed (`bf.manual_seed(other)`, `set_compute_dtype`, an edited prior),
     so a replay never draws from a stale key or dtype.  The capture's warm-up steps give their sample indices back:
-    `manual_seed(s); GraphedSampler(...)()` equals the eager call from the same state, and replay k the k-th eager step."""
+    `manual_seed(s); GraphedSampler(...)()` equals the eager call from the same state, and replay k the k-th eager step.
+
+    predictive=True captures the predictive statistics too (`sample_predictive`): a call returns one `Predictive` per
+    output (the graph's buffers, like the rest).  labels: the labels of the first batch (a tensor, one per output, or None
+    for the label-free statistics); they are copied into captured buffers, and `sampler(inputs, labels)` copies new ones
+    in, so labels are never baked in by address.  With an S-shard group the partials ride in the step's collective after
+    the replay, then the finish launches run."""
 
     def __init__(self, model: Model, inputs, samples: int, select: Optional[Callable] = None,
-                 group: Optional["dist.ProcessGroup"] = None, warmup: int = 2) -> None:
+                 group: Optional["dist.ProcessGroup"] = None, warmup: int = 2, predictive: bool = False, labels=None,
+                 ignore_index: int = -100) -> None:
         from . import graphs
 
         if model.training:
@@ -347,6 +574,21 @@ class GraphedSampler:
         self._signature = self._sig(inputs)
         with torch.inference_mode(False):  # (buffers that later calls write, in whatever mode they run: never inference tensors)
             self._rep = self._map(inputs, lambda v: v.repeat(self._s_local, *([1] * (v.dim() - 1))) if v.dim() > 0 else v.clone())
+        self.predictive, self.ignore_index = bool(predictive), int(ignore_index)
+        self._labels = None
+        if labels is not None and not self.predictive:
+            raise ValueError("GraphedSampler: labels are for predictive=True")
+        if self.predictive:
+            from . import ops
+
+            if labels is not None:
+                labels = (labels,) if isinstance(labels, Tensor) else tuple(labels)
+                with torch.inference_mode(False):
+                    self._labels = tuple(None if t is None else t.to(self.device, torch.int64).clone() for t in labels)
+            # the predictive kernels' workspace is the sampler's own (zero-filled once; the kernels leave it zeroed)
+            with torch.inference_mode(False):
+                self._pws = torch.zeros(ops._C.lib().bf_mc_predictive_workspace_bytes(self.samples), dtype=torch.uint8,
+                                        device=self.device)
         # the captured kernels hold the counter's ADDRESS: it must stay on the device until the last sampler is closed
         graphs.acquire_counter(self.device)
         self._open = True
@@ -413,9 +655,18 @@ class GraphedSampler:
 
     def _step(self):
         raw, sizes, local = _local_step(self.model, self._rep, self.samples, self.select, self.rank, self.world, repeated=True)
+        pred = None
+        if self.predictive:
+            start, count = shard_span(self.samples, self.rank, self.world)
+            labels = self._labels if self._labels is not None else _labels_per_output(None, len(raw))
+            pred = _PredictiveStep(raw, _labels_per_output(labels, len(raw)), self.ignore_index, self.samples, start,
+                                   count == 0, ws=self._pws)
         if self.distributed:
-            return raw, sizes, local, None
-        return raw, sizes, local, _finish_step(raw, sizes, local, self.samples, None, False)
+            return raw, sizes, local, None, pred
+        done = _finish_step(raw, sizes, local, self.samples, None, False)
+        if pred is not None:
+            pred = pred.finish(*done)
+        return raw, sizes, local, done, pred
 
     def load(self, inputs) -> None:
         """Copy a new batch (same structure, shapes, dtypes, device) into the captured input buffers."""
@@ -427,7 +678,20 @@ class GraphedSampler:
             if isinstance(src, Tensor):
                 (dst.view(S, *src.shape) if src.dim() > 0 else dst).copy_(src)
 
-    def __call__(self, inputs=None):
+    def load_labels(self, labels) -> None:
+        """Copy new labels (same shapes as the captured ones) into the captured label buffers."""
+        if not self.predictive or self._labels is None:
+            raise ValueError("GraphedSampler: labels need a sampler built with predictive=True and labels")
+        labels = (labels,) if isinstance(labels, Tensor) else tuple(labels)
+        if len(labels) != len(self._labels) or any(
+                (a is None) != (b is None) or (a is not None and tuple(a.shape) != tuple(b.shape))
+                for a, b in zip(self._labels, labels)):
+            raise ValueError("GraphedSampler: the labels differ in number or shape from the captured ones")
+        for dst, src in zip(self._labels, labels):
+            if dst is not None:
+                dst.copy_(src)
+
+    def __call__(self, inputs=None, labels=None):
         if self.graph is None:
             raise RuntimeError("GraphedSampler: closed")
         if self.model.training:
@@ -437,8 +701,19 @@ class GraphedSampler:
             self._capture()
         if inputs is not None:
             self.load(inputs)
+        if labels is not None:
+            self.load_labels(labels)
         self.graph.replay()
-        raw, sizes, local, done = self._static
+        raw, sizes, local, done, pred = self._static
+        if pred is not None:
+            if done is None:  # the collective (partials appended to the step's buffers), then the finish launches
+                with torch.no_grad():
+                    packed = pred.pack(local)
+                    for t in packed:
+                        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+                    done = _finish_step(raw, sizes, pred.unpack(packed, local), self.samples, None, False)
+                    return tuple(pred.finish(*done))
+            return tuple(pred)
         if done is None:  # the S-shard group's collective, on clones: the graph's buffers stay what the replay wrote
             with torch.no_grad():
                 done = _finish_step(raw, sizes, tuple(t.clone() for t in local), self.samples, self.group, True)

@@ -466,6 +466,56 @@ int bf_fused_small_rows_for(int N, int K);
  * HBM reads and Infinity-Cache hits (rocprofv3 exposes no memory-side counter on gfx950).  d_sink: 4 writable bytes. */
 int bf_probe_stream_read(const void* d_buf, size_t bytes, void* d_sink, void* stream);
 
+/* Monte-Carlo predictive statistics of S per-sample logits.  Replaces the host loop the reference's evaluation runs after
+ * sample_bayesian — acc_std = np.std of the per-sample correct counts, one .item() per sample
+ * (reference examples/bert_glue.py:186, 237, 281; examples/bert_squad.py:478-483) — and adds the softmax statistics
+ * of the Bayesian model average.  Per row r and sample s of logits l_s [C] (all arithmetic fp32 unless noted):
+ *     lse_s = logsumexp(l_s),  p_s = exp(l_s - lse_s),  H_s = lse_s - sum_c p_s(c) l_s(c),  argmax_s (first index on ties)
+ * -inf logits give p = 0 and add nothing (0 log 0 = 0); a row of -inf only has p = 0, H = 0, argmax 0.  A mean probability
+ * below FLT_MIN (an fp32 subnormal) adds nothing to the predictive entropy either (each such term is below 1e-36).
+ *
+ * Packed partials (bf_mc_predictive_bytes; sums over the samples of one rank, so that an all-reduce SUM merges ranks):
+ *     offsets[0]  float  sum_p     [R][C]    sum_s p_s
+ *     offsets[1]  float  sum_h     [R]       sum_s H_s
+ *     offsets[2]  double sum_py    [R]       sum_s p_s(y)        (labels only; 0 on ignored rows)
+ *     offsets[3]  double sum_logpy [R]       sum_s log p_s(y)    (labels only; 0 on ignored rows)
+ *     offsets[4]  double counts    [S_total] rows with argmax_s == y of the GLOBAL sample s (labels only; only this rank's
+ *                                            slots [sample_base, sample_base + S_local) are non-zero)
+ *     offsets[5]  end = the return value.  The fp32 part ends 8-byte aligned; the fp64 part starts at offsets[2].
+ * A label that is neither ignore_index nor in [0, C) counts as ignored (and in invalid_labels); it is never read.
+ *
+ * bf_mc_predictive_partial: logits[s][r][c] at d_logits + s*sample_stride + r*row_stride + c elements (BF_DT_*), any R, C >= 1,
+ *     1 <= S_local <= 1024, S_total <= 2^20.  d_labels: int64 [R] or NULL.  One launch.
+ * bf_mc_predictive_finish: from COMPLETE partials (all S_total samples), one launch:
+ *     probs = sum_p / S_total, predictive_entropy = H(probs), expected_entropy = sum_h / S_total,
+ *     mutual_information = max(0, predictive - expected), prediction = argmax probs;
+ *     with labels: log_likelihood = log(sum_py / S_total) in fp64, NaN on ignored rows (it is -inf where every sample's
+ *     log p(y) is below about -745, where exp underflows in fp64), correct_per_sample, scalars {acc_std (population std
+ *     of the counts, np.std), nll = -mean log_likelihood over the valid rows (NaN without one)}, counts {correct rows of
+ *     the prediction (the Bayesian model average), invalid labels}.
+ * Workspace (both calls, bf_mc_predictive_workspace_bytes(S_total)): device memory ZERO-FILLED ONCE before its first use;
+ * every launch leaves it ready for the next one on the same stream.  It holds state: two launches must not use it at once.
+ * No allocation, no synchronisation: capturable. */
+typedef struct bf_predictive_out {
+    float* d_probs;                  /* [R][C] */
+    float* d_predictive_entropy;     /* [R] */
+    float* d_expected_entropy;       /* [R] */
+    float* d_mutual_information;     /* [R] */
+    int64_t* d_prediction;           /* [R] */
+    double* d_log_likelihood;        /* [R], labels only (else NULL) */
+    int64_t* d_correct_per_sample;   /* [S_total], labels only */
+    double* d_scalars;               /* [2] {acc_std, nll}, labels only */
+    int64_t* d_counts;               /* [2] {bma_correct, invalid_labels}, labels only */
+} bf_predictive_out_t;
+size_t bf_mc_predictive_bytes(int64_t R, int64_t C, int S_total, int has_labels, size_t* offsets);
+size_t bf_mc_predictive_workspace_bytes(int S_total);
+int bf_mc_predictive_partial(const void* d_logits, int dtype, int64_t sample_stride, int64_t row_stride, int S_local,
+                             int64_t R, int64_t C, const int64_t* d_labels, int64_t ignore_index, int sample_base,
+                             int S_total, void* d_partial, void* d_workspace, size_t workspace_bytes, void* stream);
+int bf_mc_predictive_finish(const void* d_partial, int64_t R, int64_t C, int S_total, const int64_t* d_labels,
+                            int64_t ignore_index, const bf_predictive_out_t* out, void* d_workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
