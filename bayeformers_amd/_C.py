@@ -102,6 +102,8 @@ SYMBOLS = {
                                       ctypes.c_float, _u64, _u32, _u32, _u64, _vp, _vp]),
     "bf_attention_bwd_colsum": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64,
                                      ctypes.c_float, ctypes.c_float, _vp, _i, _vp, _vp, _vp]),
+    "bf_attention_fwd_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
+    "bf_attention_bwd_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
     "bf_profile_enable": (_i, [_i]),
     "bf_profile_reset": (_i, []),
     "bf_probe_stream_read": (_i, [_vp, _sz, _vp, _vp]),
@@ -122,6 +124,12 @@ class bf_predictive_out_t(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name in (
         "d_probs", "d_predictive_entropy", "d_expected_entropy", "d_mutual_information", "d_prediction",
         "d_log_likelihood", "d_correct_per_sample", "d_scalars", "d_counts")]
+
+
+class bf_attn_gqa_t(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("T", ctypes.c_int32), ("H", ctypes.c_int32), ("Hkv", ctypes.c_int32),
+                ("head_dim", ctypes.c_int32), ("causal", ctypes.c_int32), ("q_stride", ctypes.c_int64 * 3),
+                ("k_stride", ctypes.c_int64 * 3), ("v_stride", ctypes.c_int64 * 3)]
 
 
 class bf_pgrad_t(ctypes.Structure):

@@ -343,8 +343,16 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     from . import ops
 
     need_grad = torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad)
+    # causal: a mask _padding_mask_interface marked causal (the mask itself carries the structure), else what the caller
+    # says with is_causal, else — with no mask — the module's own flag (HF decoders set module.is_causal and pass no mask
+    # when nothing is padded); an explicit is_causal wins over the module flag, as in the framework's sdpa_attention_forward
+    explicit = kwargs.get("is_causal", None)
+    causal = bool(getattr(attention_mask, "_bf_causal", False)) or (
+        bool(explicit) if explicit is not None else (attention_mask is None and bool(getattr(module, "is_causal", False))))
+    if causal:
+        return _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs)
     # attention_probs_dropout (training mode) runs inside the kernels, forward and backward, for any supported length
-    usable = not kwargs.get("is_causal", False) and ops.attention_supported(query, key, value)
+    usable = ops.attention_supported(query, key, value)
     key_mask = mask_off = None
     ready = getattr(attention_mask, "_bf_key_mask", None) if attention_mask is not None else None
     if usable and ready is not None and ready.shape == (query.shape[0], query.shape[2]):
@@ -374,6 +382,32 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     return ops.attention_forward(query, key, value, key_mask, scale, mask_off, drop=drop), None
 
 
+def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):
+    """The causal half of _attention_interface: bf_attention_fwd_gqa (bf_attention_bwd_gqa behind it) for equal query and
+    key lengths with no mask or _padding_mask_interface's causal mask; decoding with a KV cache, other masks and
+    attention dropout go to the framework's scaled-dot-product attention."""
+    from transformers.integrations.sdpa_attention import sdpa_attention_forward
+
+    from . import ops
+
+    key_mask = mask_off = None
+    usable = (dropout == 0.0 and query.shape[2] == key.shape[2]
+              and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1]))
+    if usable and attention_mask is not None:
+        key_mask = getattr(attention_mask, "_bf_key_mask", None)
+        usable = getattr(attention_mask, "_bf_causal", False) and key_mask is not None and \
+            tuple(key_mask.shape) == (query.shape[0], key.shape[2])
+        mask_off = getattr(attention_mask, "_bf_mask_off", None)
+    if not usable:
+        if attention_mask is not None and attention_mask.dtype not in (torch.bool, query.dtype):
+            attention_mask = attention_mask.to(query.dtype)
+        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
+    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+    if need_grad:
+        return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True), None
+    return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off), None
+
+
 def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=0, kv_offset=0, mask_function=None,
                             attention_mask=None, **kwargs):
     """Mask function in the HuggingFace `AttentionMaskInterface` convention for models routed through
@@ -383,8 +417,24 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     a device synchronisation in every forward, and a different code path under HIP-graph capture).  The 4-D tensor
     returned ([B, 1, 1, T] additive) is what the framework's attention takes when the kernel does not apply.
     Anything else (4-D masks, extra mask functions, cached keys) goes to the framework's scaled-dot-product mask."""
-    from transformers.masking_utils import bidirectional_mask_function, sdpa_mask
+    from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
 
+    if (mask_function is causal_mask_function and q_offset == 0 and kv_offset == 0 and q_length == kv_length
+            and not kwargs.get("use_vmap", False)
+            and (attention_mask is None or (attention_mask.dim() == 2 and attention_mask.shape == (batch_size, kv_length)))):
+        # a decoder's causal mask over the cache-free sequence: None when nothing is padded (the framework's answer too:
+        # the attention is then causal by module.is_causal); with a padding mask, sdpa_mask's [B, 1, T, T] bool mask built
+        # on the device without a host round trip, carrying the key mask and "causal" for bf_attention_fwd_gqa
+        if attention_mask is None:
+            return None
+        visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
+        additive = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
+        tri = torch.ones((q_length, kv_length), dtype=torch.bool, device=visible.device).tril()
+        out = tri[None, None, :, :] & visible[:, None, None, :]
+        out._bf_key_mask = additive
+        out._bf_mask_off = visible.all().reshape(1)
+        out._bf_causal = True
+        return out
     plain = (attention_mask is not None and attention_mask.dim() == 2 and mask_function is bidirectional_mask_function
              and not kwargs.get("use_vmap", False) and q_offset == 0 and kv_offset == 0
              and attention_mask.shape == (batch_size, kv_length))

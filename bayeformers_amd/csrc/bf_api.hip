@@ -470,6 +470,19 @@ int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const fl
                                    dtype, B, T, H, head_dim, token_stride, scaling, (hipStream_t)stream);
 }
 
+int bf_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
+    return bf_launch_attention_fwd_gqa(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, scaling,
+                                       (hipStream_t)stream);
+}
+
+int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                         void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
+    return bf_launch_attention_bwd_gqa(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv,
+                                       dtype, shape, scaling, (hipStream_t)stream);
+}
+
 static bf_dropout_t make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,
                                  const uint32_t* d_call = nullptr) {
     bf_dropout_t d;

@@ -1,0 +1,594 @@
+// bf_attention_gqa.hip — causal and grouped-query attention, forward and backward, for the decoder-only transformers
+// the reference converts (to_bayesian turns every nn.Linear of e.g. HF LlamaForCausalLM into a Bayesian layer:
+// /root/reference/bayeformers/convert.py; the attention between q/k/v_proj and o_proj is the wrapped model's own).
+//
+//   out[b,t,h,:] = sum_{j <= t (causal), key j visible in b} softmax_j(scale q[b,t,h] . k[b,j,g] + mask[b,j]) v[b,j,g,:],
+//   g = h / (H / Hkv).
+//
+// Siblings of bf_attention.hip / bf_attention_bwd.hip (same fragment layouts, same online softmax, same LDS images), made
+// generic over the head size (64, 128), the key / query tile of the inner loop, causality and the K/V head group, and
+// reading q, k and v through their own (batch, head, token) strides.  The BERT entries keep their own kernels: the new
+// entry hands the case they cover (non-causal, one K/V head per query head, head size 64, packed heads) to them.
+//   * forward — one 256-thread workgroup per (128 queries, head, sequence), 4 waves x 32 queries, walking key tiles of KT.
+//     Causal: query tile i visits key tiles up to the diagonal only, the tiles that cross it are masked element-wise, and
+//     a wave skips the 16-query blocks a tile lies wholly above.  The grid runs the query tiles in reverse on its slowest
+//     dimension: the heaviest workgroups are dispatched first, spread over the XCDs.
+//   * dq kernel — as the forward (plus delta = <dO, O> per query), key tiles of KT.
+//   * dk/dv kernel — one 512-thread workgroup per (128 keys, K/V head, sequence), 8 waves x 16 keys, walking the query
+//     tiles (QT) of every query head of the group in turn: the group sum stays in registers, no atomics, deterministic.
+//     Causal: key tile j visits query tiles from j on; the low key tiles (heavy) come first in the grid.
+// Rows with no visible key (left padding under a causal mask) output 0 and store lse = +inf, so the backward recomputes
+// P = 0 for them and their gradients are 0.
+#include "bf_common.h"
+
+namespace {
+
+constexpr int TQ = 128;   // queries per forward / dq workgroup, keys per dk/dv workgroup
+constexpr float LOG2E = 1.4426950408889634f;
+
+typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+typedef __attribute__((ext_vector_type(8))) short s16x8_t;
+typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
+
+template <typename T>
+struct Mfma;
+template <>
+struct Mfma<__bf16> {
+    using frag = bf16x8_t;
+    using half4 = bf16x4_t;
+    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
+template <>
+struct Mfma<_Float16> {
+    using frag = f16x8_t;
+    using half4 = f16x4_t;
+    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+};
+
+struct GqaParams {
+    const void* q;
+    const void* k;
+    const void* v;
+    const float* mask;              // [B][T] additive over the keys, nullable
+    const unsigned char* mask_off;  // nullable device flag: non-zero = skip the mask
+    const void* o;                  // backward: the forward's output, [B][T][H][D]
+    const void* dout;               // backward: its gradient, [B][T][H][D]
+    void* out;                      // forward: [B][T][H][D]
+    float* lse;                     // [B][H][T], log2 units
+    float* delta;                   // [B][H][T]
+    void* dq;                       // [B][T][H][D]
+    void* dk;                       // [B][T][Hkv][D]
+    void* dv;
+    long long qs[3], ks[3], vs[3];  // (batch, head, token) element strides
+    int B, T, H, Hkv, group;
+    float scale, scale_log2e;
+};
+
+// Row stride of the LDS images: swizzled (16-byte chunk ^= row & 7, for direct row-operand reads) and padded (+32 B, for
+// the transpose reads)
+template <int HD>
+struct Rows {
+    static constexpr int SWZ = HD * 2;
+    static constexpr int PAD = HD * 2 + 32;
+};
+
+// stage rows row0 .. row0 + NR - 1 of a [tokens][stride] tensor into the swizzled and / or the padded image
+template <typename T, int HD, int NR, int NT>
+__device__ __forceinline__ void stage(const T* base, long long stride, int row0, char* swz, char* pad, int tid) {
+    constexpr int CPR = HD / 8;  // 16-byte chunks per row
+    static_assert((NR * CPR) % NT == 0, "whole passes");
+#pragma unroll
+    for (int i = 0; i < NR * CPR / NT; ++i) {
+        const int c = tid + NT * i, row = c / CPR, c8 = c % CPR;
+        const f32x4_t x = *reinterpret_cast<const f32x4_t*>(base + (long long)(row0 + row) * stride + c8 * 8);
+        if (swz) *reinterpret_cast<f32x4_t*>(swz + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = x;
+        if (pad) *reinterpret_cast<f32x4_t*>(pad + row * Rows<HD>::PAD + (c8 << 4)) = x;
+    }
+}
+
+// row-operand fragment (16 rows x 32 features, half dh) of block `blk` of a swizzled image: lane (row li, k group lg)
+template <typename T, int HD>
+__device__ __forceinline__ typename Mfma<T>::frag row_frag(const char* swz, int blk, int dh, int li, int lg) {
+    const int row = blk * 16 + li;
+    return *reinterpret_cast<const typename Mfma<T>::frag*>(swz + row * Rows<HD>::SWZ + (((dh * 4 + lg) ^ (row & 7)) << 4));
+}
+
+// transposed fragment: rows = features db*16 + li, k = the 32 image rows {(2c)*16 + 4 lg + 0..3, (2c+1)*16 + 4 lg + 0..3}
+template <typename T, int HD>
+__device__ __forceinline__ typename Mfma<T>::frag tr_frag(const char* pad, int c, int db, int li, int lg) {
+    constexpr int ROW = Rows<HD>::PAD;
+    const char* blk = pad + (lg * 4 + (li >> 2)) * ROW + (db * 16 + (li & 3) * 4) * 2;
+    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c) * 16 * ROW));
+    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c + 1) * 16 * ROW));
+    const s16x8_t ab = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    return __builtin_bit_cast(typename Mfma<T>::frag, ab);
+}
+
+template <typename T>
+__device__ __forceinline__ typename Mfma<T>::frag pack2(const f32x4_t a, const f32x4_t b) {
+    const f32x8_t v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    return __builtin_convertvector(v, typename Mfma<T>::frag);
+}
+
+// ---------------------------------------------------------------------------------------------------- forward
+template <typename T, int HD, int KT, bool CAUSAL, int MINB>
+__global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
+    using frag = typename Mfma<T>::frag;
+    using half4 = typename Mfma<T>::half4;
+    constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
+    constexpr int K_BYTES = KT * Rows<HD>::SWZ, V_BYTES = KT * Rows<HD>::PAD;
+    __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES + KT * 4];
+    char* const ks = smem;
+    char* const vs = smem + K_BYTES;
+    float* const ms = reinterpret_cast<float*>(smem + K_BYTES + V_BYTES);  // this tile's key mask, log2 units
+    const float* const mask = (p.mask && !(p.mask_off && *p.mask_off)) ? p.mask : nullptr;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int li = lane & 15, lg = lane >> 4;
+    const int qt = (int)gridDim.z - 1 - (int)blockIdx.z;  // heavy query tiles first (see launch_fwd)
+    const int q0 = qt * TQ + wid * 32, h = blockIdx.x, b = blockIdx.y, g = h / p.group;
+    const T* qb = reinterpret_cast<const T*>(p.q) + b * p.qs[0] + h * p.qs[1];
+    const T* kb = reinterpret_cast<const T*>(p.k) + b * p.ks[0] + g * p.ks[1];
+    const T* vb = reinterpret_cast<const T*>(p.v) + b * p.vs[0] + g * p.vs[1];
+
+    frag qf[2][NDH];
+#pragma unroll
+    for (int qi = 0; qi < 2; ++qi)
+#pragma unroll
+        for (int dh = 0; dh < NDH; ++dh)
+            qf[qi][dh] = *reinterpret_cast<const frag*>(qb + (long long)(q0 + qi * 16 + li) * p.qs[2] + dh * 32 + lg * 8);
+
+    f32x4_t o[2][NDB];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NDB; ++j) o[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float run_max[2] = {-INFINITY, -INFINITY}, run_sum[2] = {0.f, 0.f};
+
+    const int kend = CAUSAL ? (qt + 1) * TQ : p.T;
+    for (int key0 = 0; key0 < kend; key0 += KT) {
+        if (key0) __syncthreads();
+        stage<T, HD, KT, 256>(kb, p.ks[2], key0, ks, nullptr, tid);
+        stage<T, HD, KT, 256>(vb, p.vs[2], key0, nullptr, vs, tid);
+        if (mask && tid < KT / 4)
+            *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
+                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
+        __syncthreads();
+
+#pragma unroll
+        for (int qi = 0; qi < 2; ++qi) {
+            const int qr0 = q0 + qi * 16;  // the block's first query
+            if (CAUSAL && key0 > qr0 + 15) continue;  // the tile lies wholly above the diagonal for these 16 queries
+            f32x4_t s[NKB];
+#pragma unroll
+            for (int kbk = 0; kbk < NKB; ++kbk) {
+                s[kbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int dh = 0; dh < NDH; ++dh) s[kbk] = Mfma<T>::run(row_frag<T, HD>(ks, kbk, dh, li, lg), qf[qi][dh], s[kbk]);
+            }
+            const bool diag = CAUSAL && key0 + KT - 1 > qr0;
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kbk = 0; kbk < NKB; ++kbk) {
+                f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
+                if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
+                    if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) s[kbk][j] = -INFINITY;
+                    mx = fmaxf(mx, s[kbk][j]);
+                }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const float new_max = fmaxf(run_max[qi], mx);
+            const float ref = new_max == -INFINITY ? 0.f : new_max;  // nothing visible yet: every term is 0
+            const float corr = __builtin_amdgcn_exp2f(run_max[qi] - ref);
+            float sum = 0.f;
+#pragma unroll
+            for (int kbk = 0; kbk < NKB; ++kbk)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    s[kbk][j] = __builtin_amdgcn_exp2f(s[kbk][j] - ref);
+                    sum += s[kbk][j];
+                }
+            sum += __shfl_xor(sum, 16);
+            sum += __shfl_xor(sum, 32);
+            run_sum[qi] = run_sum[qi] * corr + sum;
+            run_max[qi] = new_max;
+#pragma unroll
+            for (int db = 0; db < NDB; ++db) o[qi][db] *= corr;
+#pragma unroll
+            for (int c = 0; c < KT / 32; ++c) {
+                const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) o[qi][db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[qi][db]);
+            }
+        }
+    }
+
+    T* ob = reinterpret_cast<T*>(p.out) + ((long long)b * p.T * p.H + h) * HD;
+#pragma unroll
+    for (int qi = 0; qi < 2; ++qi) {
+        const float inv = run_sum[qi] > 0.f ? 1.0f / run_sum[qi] : 0.f;
+        if (p.lse && lg == 0)
+            p.lse[((long long)b * p.H + h) * p.T + q0 + qi * 16 + li] =
+                run_sum[qi] > 0.f ? run_max[qi] + __builtin_amdgcn_logf(run_sum[qi]) : INFINITY;
+        T* orow = ob + (long long)(q0 + qi * 16 + li) * p.H * HD;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+            *reinterpret_cast<half4*>(orow + db * 16 + lg * 4) = __builtin_convertvector(o[qi][db] * inv, half4);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- dQ (+ delta)
+template <typename T, int HD, int KT, bool CAUSAL>
+__global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
+    using frag = typename Mfma<T>::frag;
+    using half4 = typename Mfma<T>::half4;
+    constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
+    constexpr int S_BYTES = KT * Rows<HD>::SWZ, P_BYTES = KT * Rows<HD>::PAD;
+    __shared__ __attribute__((aligned(16))) char smem[2 * S_BYTES + P_BYTES + KT * 4];
+    char* const ks = smem;                // K, swizzled: row operand of S^T
+    char* const vs = smem + S_BYTES;      // V, swizzled: row operand of dP^T
+    char* const kp = smem + 2 * S_BYTES;  // K, padded: K^T through the transpose read
+    float* const ms = reinterpret_cast<float*>(smem + 2 * S_BYTES + P_BYTES);
+    const float* const mask = (p.mask && !(p.mask_off && *p.mask_off)) ? p.mask : nullptr;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int li = lane & 15, lg = lane >> 4;
+    const int qt = (int)gridDim.z - 1 - (int)blockIdx.z;  // heavy query tiles first (see launch_fwd)
+    const int q0 = qt * TQ + wid * 32, h = blockIdx.x, b = blockIdx.y, g = h / p.group;
+    const T* qb = reinterpret_cast<const T*>(p.q) + b * p.qs[0] + h * p.qs[1];
+    const T* kb = reinterpret_cast<const T*>(p.k) + b * p.ks[0] + g * p.ks[1];
+    const T* vb = reinterpret_cast<const T*>(p.v) + b * p.vs[0] + g * p.vs[1];
+    const long long ostride = (long long)p.H * HD;
+    const long long ooff = (long long)b * p.T * ostride + (long long)h * HD;
+    const T* ob = reinterpret_cast<const T*>(p.o) + ooff;
+    const T* dob = reinterpret_cast<const T*>(p.dout) + ooff;
+
+    frag qf[2][NDH], dof[2][NDH];
+    float delta[2], lse[2];
+#pragma unroll
+    for (int qi = 0; qi < 2; ++qi) {
+        const long long q = q0 + qi * 16 + li;
+        float part = 0.f;
+#pragma unroll
+        for (int dh = 0; dh < NDH; ++dh) {
+            qf[qi][dh] = *reinterpret_cast<const frag*>(qb + q * p.qs[2] + dh * 32 + lg * 8);
+            dof[qi][dh] = *reinterpret_cast<const frag*>(dob + q * ostride + dh * 32 + lg * 8);
+            const frag of = *reinterpret_cast<const frag*>(ob + q * ostride + dh * 32 + lg * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) part = fmaf((float)dof[qi][dh][e], (float)of[e], part);
+        }
+        part += __shfl_xor(part, 16);
+        part += __shfl_xor(part, 32);
+        delta[qi] = part;
+        lse[qi] = p.lse[((long long)b * p.H + h) * p.T + q];
+        if (lg == 0) p.delta[((long long)b * p.H + h) * p.T + q] = part;
+    }
+
+    f32x4_t dq[2][NDB];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NDB; ++j) dq[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const int kend = CAUSAL ? (qt + 1) * TQ : p.T;
+    for (int key0 = 0; key0 < kend; key0 += KT) {
+        if (key0) __syncthreads();
+        stage<T, HD, KT, 256>(kb, p.ks[2], key0, ks, kp, tid);
+        stage<T, HD, KT, 256>(vb, p.vs[2], key0, vs, nullptr, tid);
+        if (mask && tid < KT / 4)
+            *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
+                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
+        __syncthreads();
+#pragma unroll
+        for (int qi = 0; qi < 2; ++qi) {
+            const int qr0 = q0 + qi * 16;
+            if (CAUSAL && key0 > qr0 + 15) continue;
+            f32x4_t s[NKB], dp[NKB];
+#pragma unroll
+            for (int kbk = 0; kbk < NKB; ++kbk) {
+                s[kbk] = dp[kbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int dh = 0; dh < NDH; ++dh) {
+                    s[kbk] = Mfma<T>::run(row_frag<T, HD>(ks, kbk, dh, li, lg), qf[qi][dh], s[kbk]);
+                    dp[kbk] = Mfma<T>::run(row_frag<T, HD>(vs, kbk, dh, li, lg), dof[qi][dh], dp[kbk]);
+                }
+            }
+            const bool diag = CAUSAL && key0 + KT - 1 > qr0;
+#pragma unroll
+            for (int kbk = 0; kbk < NKB; ++kbk) {
+                f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
+                if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
+                    if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
+                    s[kbk][j] = pr * (dp[kbk][j] - delta[qi]);  // dS^T
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < KT / 32; ++c) {
+                const frag dsf = pack2<T>(s[2 * c], s[2 * c + 1]);
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) dq[qi][db] = Mfma<T>::run(tr_frag<T, HD>(kp, c, db, li, lg), dsf, dq[qi][db]);
+            }
+        }
+    }
+    T* dqb = reinterpret_cast<T*>(p.dq) + ooff;
+#pragma unroll
+    for (int qi = 0; qi < 2; ++qi) {
+        T* row = dqb + (long long)(q0 + qi * 16 + li) * ostride;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+            *reinterpret_cast<half4*>(row + db * 16 + lg * 4) = __builtin_convertvector(dq[qi][db] * p.scale, half4);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- dK, dV
+template <typename T, int HD, int QT, bool CAUSAL, int MINB>
+__global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams p) {
+    using frag = typename Mfma<T>::frag;
+    using half4 = typename Mfma<T>::half4;
+    constexpr int NDH = HD / 32, NDB = HD / 16, NQB = QT / 16;
+    constexpr int S_BYTES = QT * Rows<HD>::SWZ, P_BYTES = QT * Rows<HD>::PAD;
+    __shared__ __attribute__((aligned(16))) char smem[2 * S_BYTES + 2 * P_BYTES + 2 * QT * 4];
+    char* const qs = smem;                           // Q, swizzled: row operand of S
+    char* const dos = smem + S_BYTES;                // dO, swizzled: row operand of dP
+    char* const qp = smem + 2 * S_BYTES;             // Q, padded: Q^T through the transpose read
+    char* const dop = smem + 2 * S_BYTES + P_BYTES;  // dO, padded: dO^T through the transpose read
+    float* const lse_s = reinterpret_cast<float*>(smem + 2 * S_BYTES + 2 * P_BYTES);
+    float* const del_s = lse_s + QT;
+    const float* const mask = (p.mask && !(p.mask_off && *p.mask_off)) ? p.mask : nullptr;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int li = lane & 15, lg = lane >> 4;
+    const int kt = blockIdx.z, g = blockIdx.x, b = blockIdx.y;  // causal: the low key tiles are the heavy ones
+    const int wkey0 = kt * TQ + wid * 16;                        // the wave's first key
+    const long long key = wkey0 + li;
+    const T* kb = reinterpret_cast<const T*>(p.k) + b * p.ks[0] + g * p.ks[1];
+    const T* vb = reinterpret_cast<const T*>(p.v) + b * p.vs[0] + g * p.vs[1];
+    const long long ostride = (long long)p.H * HD;
+
+    frag kf[NDH], vf[NDH];
+#pragma unroll
+    for (int dh = 0; dh < NDH; ++dh) {
+        kf[dh] = *reinterpret_cast<const frag*>(kb + key * p.ks[2] + dh * 32 + lg * 8);
+        vf[dh] = *reinterpret_cast<const frag*>(vb + key * p.vs[2] + dh * 32 + lg * 8);
+    }
+    const float mk = mask ? mask[(long long)b * p.T + key] * LOG2E : 0.f;
+    f32x4_t dk[NDB], dv[NDB];
+#pragma unroll
+    for (int j = 0; j < NDB; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    const int qbeg = CAUSAL ? kt * TQ : 0;
+    bool first = true;
+    for (int h = g * p.group; h < (g + 1) * p.group; ++h) {  // the group's query heads, in order: a fixed summation order
+        const T* qb = reinterpret_cast<const T*>(p.q) + b * p.qs[0] + h * p.qs[1];
+        const T* dob = reinterpret_cast<const T*>(p.dout) + (long long)b * p.T * ostride + (long long)h * HD;
+        const float* lse_g = p.lse + ((long long)b * p.H + h) * p.T;
+        const float* del_g = p.delta + ((long long)b * p.H + h) * p.T;
+        for (int q0 = qbeg; q0 < p.T; q0 += QT) {
+            if (!first) __syncthreads();
+            first = false;
+            stage<T, HD, QT, 512>(qb, p.qs[2], q0, qs, qp, tid);
+            stage<T, HD, QT, 512>(dob, ostride, q0, dos, dop, tid);
+            if (tid < QT / 4) {
+                *reinterpret_cast<f32x4_t*>(lse_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(lse_g + q0 + tid * 4);
+                *reinterpret_cast<f32x4_t*>(del_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(del_g + q0 + tid * 4);
+            }
+            __syncthreads();
+            if (CAUSAL && q0 + QT - 1 < wkey0) continue;  // every query of the tile precedes the wave's keys
+            f32x4_t s[NQB], dp[NQB];
+#pragma unroll
+            for (int qbk = 0; qbk < NQB; ++qbk) {
+                s[qbk] = dp[qbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int dh = 0; dh < NDH; ++dh) {
+                    s[qbk] = Mfma<T>::run(row_frag<T, HD>(qs, qbk, dh, li, lg), kf[dh], s[qbk]);
+                    dp[qbk] = Mfma<T>::run(row_frag<T, HD>(dos, qbk, dh, li, lg), vf[dh], dp[qbk]);
+                }
+            }
+            const bool diag = CAUSAL && q0 < wkey0 + 15;
+#pragma unroll
+            for (int qbk = 0; qbk < NQB; ++qbk) {
+                const f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(lse_s + qbk * 16 + lg * 4);
+                const f32x4_t d4 = *reinterpret_cast<const f32x4_t*>(del_s + qbk * 16 + lg * 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
+                    if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
+                    s[qbk][j] = pr;                          // P
+                    dp[qbk][j] = pr * (dp[qbk][j] - d4[j]);  // dS
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < QT / 32; ++c) {
+                const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
+                const frag dsf = pack2<T>(dp[2 * c], dp[2 * c + 1]);
+#pragma unroll
+                for (int db = 0; db < NDB; ++db) {
+                    dv[db] = Mfma<T>::run(tr_frag<T, HD>(dop, c, db, li, lg), pf, dv[db]);
+                    dk[db] = Mfma<T>::run(tr_frag<T, HD>(qp, c, db, li, lg), dsf, dk[db]);
+                }
+            }
+        }
+    }
+    const long long kvstride = (long long)p.Hkv * HD;
+    T* dkb = reinterpret_cast<T*>(p.dk) + ((long long)b * p.T * p.Hkv + g) * HD;
+    T* dvb = reinterpret_cast<T*>(p.dv) + ((long long)b * p.T * p.Hkv + g) * HD;
+#pragma unroll
+    for (int db = 0; db < NDB; ++db) {
+        *reinterpret_cast<half4*>(dkb + key * kvstride + db * 16 + lg * 4) = __builtin_convertvector(dk[db] * p.scale, half4);
+        *reinterpret_cast<half4*>(dvb + key * kvstride + db * 16 + lg * 4) = __builtin_convertvector(dv[db], half4);
+    }
+}
+
+// Tile shapes.  Head size 64: the BERT kernels' (128-key tiles; dk/dv over 128-query tiles, 72 KiB of LDS, 2 workgroups per
+// CU).  Head size 128: 128-key tiles in the forward (68 KiB of LDS: 2 workgroups per CU), 64-key tiles in the dq kernel and
+// 64-query tiles in the dk/dv kernel (50 / 68 KiB), whose 128-row variants would hold one workgroup per CU by LDS alone.
+template <int HD>
+struct Shape;
+template <>
+struct Shape<64> {
+    static constexpr int FWD_KT = 128, FWD_MINB = 3, DQ_KT = 128, DKV_QT = 128, DKV_MINB = 2;
+};
+// (BF_GQA128_*: compile-time overrides for A/B builds of the head-128 tiles, profiles/causal_attention.md)
+#ifndef BF_GQA128_FWD_KT
+#define BF_GQA128_FWD_KT 128
+#define BF_GQA128_FWD_MINB 2
+#endif
+#ifndef BF_GQA128_BWD_T
+#define BF_GQA128_BWD_T 64
+#endif
+template <>
+struct Shape<128> {
+    static constexpr int FWD_KT = BF_GQA128_FWD_KT, FWD_MINB = BF_GQA128_FWD_MINB, DQ_KT = BF_GQA128_BWD_T,
+                         DKV_QT = BF_GQA128_BWD_T, DKV_MINB = 1;
+};
+
+// The tile index is the grid's SLOWEST dimension: the hardware hands consecutive workgroups to the 8 XCDs in turn, so with
+// the tiles fastest (as the BERT kernels order them) every XCD would get the tiles of one position — under a causal mask one
+// XCD all the heaviest — while tiles-slowest issues the heavy tiles of every (head, sequence) first, spread over all XCDs.
+template <typename T, int HD, bool CAUSAL>
+void launch_fwd(const GqaParams& p, hipStream_t stream) {
+    const dim3 grid(p.H, p.B, p.T / TQ);
+    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, Shape<HD>::FWD_MINB>), grid, dim3(256), 0, stream, p);
+}
+
+template <typename T, int HD, bool CAUSAL>
+void launch_bwd(const GqaParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL>), dim3(p.H, p.B, p.T / TQ), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, Shape<HD>::DKV_MINB>), dim3(p.Hkv, p.B, p.T / TQ),
+                       dim3(512), 0, stream, p);
+}
+
+template <typename T, int HD, bool CAUSAL>
+void launch(const GqaParams& p, bool bwd, hipStream_t stream) {
+    if (bwd) launch_bwd<T, HD, CAUSAL>(p, stream);
+    else launch_fwd<T, HD, CAUSAL>(p, stream);
+}
+
+template <typename T>
+void launch(const GqaParams& p, int D, bool causal, bool bwd, hipStream_t stream) {
+    if (D == 64) {
+        if (causal) launch<T, 64, true>(p, bwd, stream);
+        else launch<T, 64, false>(p, bwd, stream);
+    } else {
+        if (causal) launch<T, 128, true>(p, bwd, stream);
+        else launch<T, 128, false>(p, bwd, stream);
+    }
+}
+
+void dispatch(const GqaParams& p, int dtype, int D, bool causal, bool bwd, hipStream_t stream) {
+    if (dtype == BF_DT_BF16) launch<__bf16>(p, D, causal, bwd, stream);
+    else launch<_Float16>(p, D, causal, bwd, stream);
+}
+
+// Validates the shape and fills the parameters' shape part; returns 0 or the BF_FAIL status
+int fill_shape(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int dtype, float scaling) {
+    if (!s) BF_FAIL("%s: shape is NULL", what);
+    if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
+    if (s->head_dim != 64 && s->head_dim != 128) BF_FAIL("%s: head size %d (64 or 128)", what, s->head_dim);
+    if (s->B < 1 || s->H < 1 || s->Hkv < 1 || s->T < TQ || s->T % TQ)
+        BF_FAIL("%s: T=%d must be a positive multiple of %d (B=%d, H=%d, Hkv=%d)", what, s->T, TQ, s->B, s->H, s->Hkv);
+    if (s->H % s->Hkv) BF_FAIL("%s: %d query heads do not divide into %d K/V head groups", what, s->H, s->Hkv);
+    if (s->B > 65535 || s->H > 65535) BF_FAIL("%s: B or H exceeds the grid", what);
+    if (s->causal != 0 && s->causal != 1) BF_FAIL("%s: causal must be 0 or 1", what);
+    for (int i = 0; i < 3; ++i) {
+        const int64_t st[3] = {s->q_stride[i], s->k_stride[i], s->v_stride[i]};
+        for (int t = 0; t < 3; ++t)
+            if (st[t] < 0 || st[t] % 8) BF_FAIL("%s: strides must be non-negative multiples of 8 elements", what);
+    }
+    p.B = s->B;
+    p.T = s->T;
+    p.H = s->H;
+    p.Hkv = s->Hkv;
+    p.group = s->H / s->Hkv;
+    for (int i = 0; i < 3; ++i) {
+        p.qs[i] = s->q_stride[i];
+        p.ks[i] = s->k_stride[i];
+        p.vs[i] = s->v_stride[i];
+    }
+    p.scale = scaling;
+    p.scale_log2e = scaling * LOG2E;
+    return 0;
+}
+
+// the case bf_attention_fwd / bf_attention_bwd take: non-causal, one K/V head per query head, head size 64, q / k / v
+// element (b, t, h, d) at (b T + t) token_stride + 64 h + d with one token stride
+bool bert_case(const bf_attn_gqa_t* s, long long* token_stride) {
+    const long long ts = s->q_stride[2];
+    const int64_t want[3] = {(int64_t)s->T * ts, 64, ts};
+    for (int i = 0; i < 3; ++i)
+        if (s->q_stride[i] != want[i] || s->k_stride[i] != want[i] || s->v_stride[i] != want[i]) return false;
+    *token_stride = ts;
+    return !s->causal && s->H == s->Hkv && s->head_dim == 64 && ts >= (long long)s->H * 64;
+}
+
+}  // namespace
+
+int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
+                                const bf_attn_gqa_t* shape, float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_fwd_gqa";
+    if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
+    GqaParams p = {};
+    if (fill_shape(what, p, shape, dtype, scaling)) return 1;
+    long long ts;
+    if (bert_case(shape, &ts))
+        return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape->B, shape->T, shape->H,
+                                       64, ts, scaling, stream);
+    if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if ((d_mask && ((uintptr_t)d_mask & 15)) || (d_lse && ((uintptr_t)d_lse & 15))) BF_FAIL("%s: mask / lse must be 16-byte aligned", what);
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.mask = d_mask;
+    p.mask_off = d_mask_off;
+    p.out = d_out;
+    p.lse = d_lse;
+    dispatch(p, dtype, shape->head_dim, shape->causal, false, stream);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_bwd_gqa";
+    if (!d_q || !d_k || !d_v || !d_out || !d_dout || !d_lse || !d_delta || !d_dq || !d_dk || !d_dv)
+        BF_FAIL("%s: NULL argument", what);
+    GqaParams p = {};
+    if (fill_shape(what, p, shape, dtype, scaling)) return 1;
+    long long ts;
+    if (bert_case(shape, &ts))
+        return bf_launch_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype,
+                                       shape->B, shape->T, shape->H, 64, ts, scaling, stream);
+    const uintptr_t al = (uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_dout |
+                         (uintptr_t)d_dq | (uintptr_t)d_dk | (uintptr_t)d_dv | (uintptr_t)d_lse | (uintptr_t)d_delta;
+    if (al & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if (d_mask && ((uintptr_t)d_mask & 15)) BF_FAIL("%s: mask must be 16-byte aligned", what);
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.mask = d_mask;
+    p.mask_off = d_mask_off;
+    p.o = d_out;
+    p.dout = d_dout;
+    p.lse = const_cast<float*>(d_lse);
+    p.delta = d_delta;
+    p.dq = d_dq;
+    p.dk = d_dk;
+    p.dv = d_dv;
+    dispatch(p, dtype, shape->head_dim, shape->causal, true, stream);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}

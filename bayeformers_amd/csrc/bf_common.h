@@ -218,6 +218,13 @@ int bf_launch_attention_bwd(const void* d_q, const void* d_k, const void* d_v, c
                             int head_dim, long long token_stride, float scaling, hipStream_t stream,
                             const uint32_t* d_keep_bits = nullptr, float inv_keep = 1.0f, int samples = 0,
                             float* d_cs_partial = nullptr, float* d_colsum = nullptr);
+int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
+                                const bf_attn_gqa_t* shape, float scaling, hipStream_t stream);
+int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                float scaling, hipStream_t stream);
 size_t bf_add_layernorm_bwd_ws_bytes(long long rows, int N);
 int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
                                 const void* d_dy, void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace,

@@ -722,10 +722,15 @@ def embed_layernorm(ids: Tensor, type_ids: Optional[Tensor], pos_ids: Optional[T
     return out
 
 
-def attention_supported(q: Tensor, k: Tensor, v: Tensor) -> bool:
-    """q, k, v as the attention hook gets them: [B, H, T, 64] views of the projections' [B*T, H*64] outputs."""
+def attention_supported(q: Tensor, k: Tensor, v: Tensor, causal: bool = False, kv_heads: Optional[int] = None) -> bool:
+    """q, k, v as the attention hook gets them: [B, H, T, 64] views of the projections' [B*T, H*64] outputs
+    (bf_attention_fwd).  With causal=True or kv_heads given: what bf_attention_fwd_gqa takes instead — q [B, H, T, D],
+    k and v [B, Hkv, T, D] with Hkv (= kv_heads) dividing H, D 64 or 128, T a multiple of 128, each with its own
+    (batch, head, token) strides and a contiguous feature dimension."""
     if not (q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype):
         return False
+    if causal or kv_heads is not None:
+        return _gqa_supported(q, k, v, kv_heads)
     if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
         return False
     B, H, T, D = q.shape
@@ -733,6 +738,88 @@ def attention_supported(q: Tensor, k: Tensor, v: Tensor) -> bool:
         return False
     st = (T * H * D, D, H * D, 1)  # BHTD view of a contiguous [B, T, H, D] tensor
     return all(t.stride() == st and t.data_ptr() % 16 == 0 for t in (q, k, v))
+
+
+def _gqa_supported(q: Tensor, k: Tensor, v: Tensor, kv_heads: Optional[int]) -> bool:
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
+        return False
+    B, H, T, D = q.shape
+    Hkv = k.shape[1] if kv_heads is None else int(kv_heads)
+    if tuple(k.shape) != (B, Hkv, T, D) or Hkv < 1 or H % Hkv:
+        return False
+    if D not in (64, 128) or T < 128 or T % 128 or B > 65535 or H > 65535:
+        return False
+    return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (q, k, v))
+
+
+# launches of bf_attention_fwd_gqa / bf_attention_bwd_gqa from this process (a test can assert that the causal path ran)
+GQA_CALLS = {"fwd": 0, "bwd": 0}
+
+
+def _gqa_shape(q: Tensor, k: Tensor, v: Tensor, causal: bool):
+    B, H, T, D = q.shape
+    s = _C.bf_attn_gqa_t(B, T, H, k.shape[1], D, int(bool(causal)))
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v)):
+        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    return s
+
+
+def attention_forward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float, causal: bool = True,
+                          mask_off: Optional[Tensor] = None, want_lse: bool = False):
+    """Causal and / or grouped-query attention (bf_attention_fwd_gqa): q [B, H, T, D], k / v [B, Hkv, T, D] as described by
+    attention_supported(..., causal=True); key_mask: additive fp32 [B, T] or None.  Returns [B, T, H, D] contiguous (a
+    query with no visible key gives 0) — and, with want_lse, the [B, H, T] fp32 log-sum-exp rows of the backward."""
+    B, H, T, D = q.shape
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device) if want_lse else None
+    shape = _gqa_shape(q, k, v, causal)
+    _C.check(_C.lib().bf_attention_fwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                           key_mask.data_ptr() if key_mask is not None else None,
+                                           mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
+                                           lse.data_ptr() if lse is not None else None, _TORCH2BF[q.dtype],
+                                           ctypes.byref(shape), float(scaling), _stream_ptr()), "bf_attention_fwd_gqa")
+    GQA_CALLS["fwd"] += 1
+    return (out, lse) if want_lse else out
+
+
+def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], mask_off: Optional[Tensor],
+                           out: Tensor, grad_out: Tensor, lse: Tensor, scaling: float, causal: bool = True):
+    """Gradients of attention_forward_gqa (bf_attention_bwd_gqa): (dq [B, T, H, D], dk [B, T, Hkv, D], dv [B, T, Hkv, D]),
+    contiguous; dk / dv summed over the query heads of each group."""
+    B, H, T, D = q.shape
+    Hkv = k.shape[1]
+    go = grad_out if (grad_out.dtype == q.dtype and grad_out.is_contiguous()) else grad_out.to(q.dtype).contiguous()
+    dq = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    dkv = torch.empty((2, B, T, Hkv, D), dtype=q.dtype, device=q.device)
+    delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    shape = _gqa_shape(q, k, v, causal)
+    _C.check(_C.lib().bf_attention_bwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                           key_mask.data_ptr() if key_mask is not None else None,
+                                           mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
+                                           go.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dkv[0].data_ptr(),
+                                           dkv[1].data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(shape), float(scaling),
+                                           _stream_ptr()), "bf_attention_bwd_gqa")
+    GQA_CALLS["bwd"] += 1
+    return dq, dkv[0], dkv[1]
+
+
+class AttentionGqaFn(torch.autograd.Function):
+    """attention_forward_gqa with attention_backward_gqa as its backward (no dropout: decoder configs run attention
+    without it).  Keeps q, k, v, the output and one fp32 row statistic per query."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_mask, mask_off, scaling, causal=True):
+        out, lse = attention_forward_gqa(q, k, v, key_mask, scaling, causal, mask_off, want_lse=True)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.key_mask, ctx.mask_off, ctx.scaling, ctx.causal = key_mask, mask_off, scaling, causal
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = attention_backward_gqa(q, k, v, ctx.key_mask, ctx.mask_off, out, grad_out, lse, ctx.scaling, ctx.causal)
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None
 
 
 def attention_forward(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,

@@ -367,6 +367,34 @@ int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const fl
                      void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
                      void* stream);
 
+/* ---- decoder-only models: causal, grouped-query attention ---------------------------------------------------------
+ * The attention between the Bayesian q/k/v_proj and o_proj layers of the decoder-only models the reference converts
+ * (to_bayesian turns every nn.Linear into a Bayesian layer, /root/reference/bayeformers/convert.py; HF LlamaForCausalLM
+ * and its relatives run their own attention there, /root/reference/bayeformers/nn/layers/linear.py:83-104 around it):
+ *   out[b][t][h][:] = sum over keys j (j <= t when causal) of softmax_j(scaling q[b][t][h] . k[b][j][g] + mask[b][j]) v[b][j][g],
+ *   g = h / (H / Hkv).
+ * Element (b, t, h, d) of q is at b*q_stride[0] + h*q_stride[1] + t*q_stride[2] + d (k and v: head g, their own strides);
+ * the feature dimension is contiguous, every stride a multiple of 8 elements.  head_dim 64 or 128, Hkv divides H,
+ * T a multiple of 128, bf16 or fp16, 16-byte aligned pointers.  d_mask / d_mask_off / d_lse as for bf_attention_fwd;
+ * a query with no visible key outputs 0 and stores lse = +inf (its gradients are then 0).  d_out, d_dout, d_dq:
+ * [B][T][H][head_dim] contiguous; d_dk, d_dv: [B][T][Hkv][head_dim] contiguous, summed over the query heads of a group
+ * inside one workgroup (no atomics: deterministic).  Non-causal, Hkv == H, head_dim 64 with the packed strides of
+ * bf_attention_fwd runs bf_attention_fwd / bf_attention_bwd themselves. */
+typedef struct bf_attn_gqa {
+    int32_t B, T, H, Hkv, head_dim, causal;  /* causal: 0 or 1 */
+    int64_t q_stride[3];                     /* element strides of batch, head, token */
+    int64_t k_stride[3];
+    int64_t v_stride[3];
+} bf_attn_gqa_t;
+int bf_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream);
+/* Backward of bf_attention_fwd_gqa (autograd through the attention of a decoder fine-tuned by Bayes-by-backprop,
+ * /root/reference/examples/bert_glue.py:239 `loss.backward()` in the reference's training loop).  d_delta: [B][H][T] fp32
+ * scratch. */
+int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                         void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream);
+
 /* ---- training mode: HuggingFace dropout inside the fused kernels ------------------------------------------------------
  * The reference trains with the wrapped model in .train() (/root/reference/examples/bert_glue.py:221,227-241): HF's
  * dropout (p = 0.1) acts on the attention probabilities and on every dense output in front of a residual + LayerNorm.
