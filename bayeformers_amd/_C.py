@@ -104,6 +104,8 @@ SYMBOLS = {
                                      ctypes.c_float, ctypes.c_float, _vp, _i, _vp, _vp, _vp]),
     "bf_attention_fwd_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
     "bf_attention_bwd_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
+    "bf_attention_decode_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
+    "bf_attention_decode_workspace_bytes": (_i64, [_vp]),
     "bf_profile_enable": (_i, [_i]),
     "bf_profile_reset": (_i, []),
     "bf_probe_stream_read": (_i, [_vp, _sz, _vp, _vp]),
@@ -129,6 +131,12 @@ class bf_predictive_out_t(ctypes.Structure):
 class bf_attn_gqa_t(ctypes.Structure):
     _fields_ = [("B", ctypes.c_int32), ("T", ctypes.c_int32), ("H", ctypes.c_int32), ("Hkv", ctypes.c_int32),
                 ("head_dim", ctypes.c_int32), ("causal", ctypes.c_int32), ("q_stride", ctypes.c_int64 * 3),
+                ("k_stride", ctypes.c_int64 * 3), ("v_stride", ctypes.c_int64 * 3)]
+
+
+class bf_attn_decode_t(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int32), ("Tq", ctypes.c_int32), ("Tk", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("Hkv", ctypes.c_int32), ("head_dim", ctypes.c_int32), ("q_stride", ctypes.c_int64 * 3),
                 ("k_stride", ctypes.c_int64 * 3), ("v_stride", ctypes.c_int64 * 3)]
 
 

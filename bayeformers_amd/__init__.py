@@ -347,7 +347,7 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     # says with is_causal, else — with no mask — the module's own flag (HF decoders set module.is_causal and pass no mask
     # when nothing is padded); an explicit is_causal wins over the module flag, as in the framework's sdpa_attention_forward
     explicit = kwargs.get("is_causal", None)
-    causal = bool(getattr(attention_mask, "_bf_causal", False)) or (
+    causal = bool(getattr(attention_mask, "_bf_causal", False) or getattr(attention_mask, "_bf_decode", False)) or (
         bool(explicit) if explicit is not None else (attention_mask is None and bool(getattr(module, "is_causal", False))))
     if causal:
         return _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs)
@@ -384,12 +384,23 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
 
 def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):
     """The causal half of _attention_interface: bf_attention_fwd_gqa (bf_attention_bwd_gqa behind it) for equal query and
-    key lengths with no mask or _padding_mask_interface's causal mask; decoding with a KV cache, other masks and
-    attention dropout go to the framework's scaled-dot-product attention."""
+    key lengths with no mask or _padding_mask_interface's causal mask; a decode step against a KV cache (fewer than 17
+    new queries, no gradient, no dropout) on bf_attention_decode_gqa; other masks, longer cached chunks and attention
+    dropout go to the framework's scaled-dot-product attention."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
 
+    if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
+            and ops.attention_decode_supported(query, key, value)
+            and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3])):
+        # no mask: nothing padded (a one-query step sees every cached key); else only the mask _padding_mask_interface built
+        ready = attention_mask is None or bool(getattr(attention_mask, "_bf_decode", False))
+        key_mask = getattr(attention_mask, "_bf_key_mask", None) if attention_mask is not None else None
+        if ready and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])):
+            mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+            scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+            return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off), None
     key_mask = mask_off = None
     usable = (dropout == 0.0 and query.shape[2] == key.shape[2]
               and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1]))
@@ -416,8 +427,30 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     lets the kernel skip the mask (the framework's own function answers that question with `mask.all()` on the host —
     a device synchronisation in every forward, and a different code path under HIP-graph capture).  The 4-D tensor
     returned ([B, 1, 1, T] additive) is what the framework's attention takes when the kernel does not apply.
-    Anything else (4-D masks, extra mask functions, cached keys) goes to the framework's scaled-dot-product mask."""
+    A decoder's causal mask for a step against a KV cache (q_offset = kv_length - q_length, a 2-D padding mask or none)
+    is built on the device too: the [B, 1, Tq, Tk] bool mask the framework's attention takes, carrying the key mask and
+    the causal marker `_bf_decode` for bf_attention_decode_gqa (None for one query and no padding mask, as the framework answers).
+    Anything else (4-D masks, extra mask functions, other offsets) goes to the framework's scaled-dot-product mask."""
     from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
+
+    if (mask_function is causal_mask_function and kv_offset == 0 and q_length is not None and kv_length is not None
+            and 0 < q_length < kv_length and q_offset == kv_length - q_length and not kwargs.get("use_vmap", False)
+            and (attention_mask is None or (attention_mask.dim() == 2 and attention_mask.shape == (batch_size, kv_length)))):
+        if attention_mask is None and q_length == 1:
+            return None  # the new query sees every cached key: module.is_causal routes the call
+        device = attention_mask.device if attention_mask is not None else kwargs.get("device", "cpu")
+        keys = torch.arange(kv_length, device=device)
+        tri = keys[None, :] <= torch.arange(q_offset, kv_length, device=device)[:, None]  # query i sees 0 .. q_offset + i
+        if attention_mask is None:
+            out = tri[None, None, :, :].expand(batch_size, 1, q_length, kv_length)
+            out._bf_key_mask = out._bf_mask_off = None
+        else:
+            visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
+            out = tri[None, None, :, :] & visible[:, None, None, :]
+            out._bf_key_mask = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
+            out._bf_mask_off = visible.all().reshape(1)
+        out._bf_decode = True  # causal, bottom-right aligned (_bf_causal stays the cache-free marker)
+        return out
 
     if (mask_function is causal_mask_function and q_offset == 0 and kv_offset == 0 and q_length == kv_length
             and not kwargs.get("use_vmap", False)

@@ -483,6 +483,17 @@ int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, cons
                                        dtype, shape, scaling, (hipStream_t)stream);
 }
 
+int bf_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                            void* d_out, void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
+                            void* stream) {
+    return bf_launch_attention_decode_gqa(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_workspace, dtype, shape, scaling,
+                                          (hipStream_t)stream);
+}
+
+int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
+    return bf_launch_attention_decode_workspace_bytes(shape);
+}
+
 static bf_dropout_t make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,
                                  const uint32_t* d_call = nullptr) {
     bf_dropout_t d;

@@ -1,0 +1,308 @@
+// bf_attention_decode.hip — causal grouped-query attention of a decode step against a KV cache (inference only): Tq new
+// queries per sequence (1 <= Tq <= 16) against Tk cached keys (Tq <= Tk, any Tk >= 1), for the decoder-only transformers
+// the reference converts (/root/reference/bayeformers/convert.py) when they generate with `past_key_values`.
+//
+//   out[n,i,h,:] = sum_{j <= Tk - Tq + i, key j visible in n} softmax_j(scale q[n,h,i] . k[n,g,j] + mask[n,j]) v[n,g,j,:],
+//   g = h / (H / Hkv).
+//
+// Decode is bound by the read of the cache, so one workgroup reads a K/V head ONCE for the whole head group: the
+// G = H / Hkv query heads x Tq queries of one (sequence, kv head) are the rows of the MFMA tiles (row r = head-in-group *
+// Tq + query), 16 per wave, 64 per 256-thread workgroup (more rows: the grid's z dimension, each chunk reading the head
+// again).  The keys are split so that the grid fills the chip: the split count and boundaries are a function of the
+// shape only (decode_split), and with more than one split a second launch merges the partial (max, sum, output) rows in
+// split order — bitwise the same result on every run, no atomics, no host synchronisation, no allocation (the partials
+// live in the caller's workspace: bf_attention_decode_workspace_bytes).
+// Fragment layouts, LDS images and the online softmax are those of bf_attention_gqa.hip's forward: S^T = K Q^T, then
+// O^T = V^T P^T with P^T straight from the accumulators.  The next key tile is fetched into registers while the current
+// one is computed.  A query with no visible key returns 0.
+#include "bf_attention_tiles.h"
+
+#include <algorithm>
+
+namespace {
+
+constexpr int KT = 64;             // keys per tile
+constexpr int ROWS = 64;           // query rows per workgroup: 4 waves x 16
+constexpr int MIN_SPLIT_KEYS = 128;  // a split walks at least two key tiles
+constexpr long long TARGET_WGS = 1024;  // 256 CUs x 4 resident workgroups
+
+struct DecodeParams {
+    const void* q;
+    const void* k;
+    const void* v;
+    const float* mask;              // [N][Tk] additive over the keys, nullable
+    const unsigned char* mask_off;  // nullable device flag: non-zero = skip the mask
+    void* out;                      // [N][Tq][H][D]
+    float* part_o;                  // [nsplit][N * Hkv][R][D] unnormalised partial outputs (nsplit > 1)
+    float* part_ml;                 // [nsplit][N * Hkv][R][2] their running max (log2 units) and sum
+    long long qs[3], ks[3], vs[3];  // (batch, head, token) element strides
+    int N, Tq, Tk, H, Hkv, group, R, nsplit, split_keys;
+    float scale_log2e;
+};
+
+struct Split {
+    int n, keys;  // splits, keys per split (a multiple of KT; the last split ends at Tk)
+};
+
+Split decode_split(const bf_attn_decode_t* s) {
+    const int R = s->H / s->Hkv * s->Tq;
+    const long long base = (long long)s->N * s->Hkv * ((R + ROWS - 1) / ROWS);
+    const int tiles = (s->Tk + KT - 1) / KT;
+    const long long want = std::max(1LL, (TARGET_WGS + base - 1) / base);
+    const int most = std::max(1, (s->Tk + MIN_SPLIT_KEYS - 1) / MIN_SPLIT_KEYS);
+    const int n0 = (int)std::min<long long>(want, most);
+    const int per = (tiles + n0 - 1) / n0;
+    return Split{(tiles + per - 1) / per, per * KT};
+}
+
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
+    using frag = typename Mfma<T>::frag;
+    using half4 = typename Mfma<T>::half4;
+    constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
+    constexpr int CPR = HD / 8, NLD = KT * CPR / 256;  // 16-byte chunks per key row; per thread and tile
+    constexpr int K_BYTES = KT * Rows<HD>::SWZ, V_BYTES = KT * Rows<HD>::PAD;
+    __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES + KT * 4];
+    char* const ks = smem;
+    char* const vs = smem + K_BYTES;
+    float* const ms = reinterpret_cast<float*>(smem + K_BYTES + V_BYTES);  // this tile's key mask, log2 units
+    const float* const mask = (p.mask && !(p.mask_off && *p.mask_off)) ? p.mask : nullptr;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int li = lane & 15, lg = lane >> 4;
+    const int split = blockIdx.x, nk = blockIdx.y, n = nk / p.Hkv, g = nk % p.Hkv;
+    const int k_lo = split * p.split_keys, k_hi = min(p.Tk, k_lo + p.split_keys);
+    const int r = blockIdx.z * ROWS + wid * 16 + li;  // this lane's query row (its column of S^T and O^T)
+    const bool wave_live = (int)blockIdx.z * ROWS + wid * 16 < p.R, row_ok = r < p.R;
+    const int qi = row_ok ? r % p.Tq : 0, h = g * p.group + (row_ok ? r / p.Tq : 0);
+    const int lim = p.Tk - p.Tq + qi;  // the last key query qi sees
+    const T* kb = reinterpret_cast<const T*>(p.k) + n * p.ks[0] + g * p.ks[1];
+    const T* vb = reinterpret_cast<const T*>(p.v) + n * p.vs[0] + g * p.vs[1];
+
+    frag qf[NDH];
+    const T* qrow = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + qi * p.qs[2];
+#pragma unroll
+    for (int dh = 0; dh < NDH; ++dh) {
+        qf[dh] = frag{};
+        if (row_ok) qf[dh] = *reinterpret_cast<const frag*>(qrow + dh * 32 + lg * 8);
+    }
+
+    f32x4_t o[NDB];
+#pragma unroll
+    for (int j = 0; j < NDB; ++j) o[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    float run_max = -INFINITY, run_sum = 0.f;
+
+    // the next tile travels in registers while the current one is computed; keys past the split read as 0
+    f32x4_t kr[NLD], vr[NLD];
+    float mr = 0.f;
+    auto fetch = [&](int key0) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int c = tid + 256 * i, key = key0 + c / CPR, c8 = c % CPR;
+            kr[i] = vr[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            if (key < k_hi) {
+                kr[i] = *reinterpret_cast<const f32x4_t*>(kb + (long long)key * p.ks[2] + c8 * 8);
+                vr[i] = *reinterpret_cast<const f32x4_t*>(vb + (long long)key * p.vs[2] + c8 * 8);
+            }
+        }
+        if (mask && tid < KT && key0 + tid < k_hi) mr = mask[(long long)n * p.Tk + key0 + tid] * LOG2E;
+    };
+    fetch(k_lo);
+    for (int key0 = k_lo; key0 < k_hi; key0 += KT) {
+        if (key0 != k_lo) __syncthreads();  // every wave is done with the previous tile
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int c = tid + 256 * i, row = c / CPR, c8 = c % CPR;
+            *reinterpret_cast<f32x4_t*>(ks + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = kr[i];
+            *reinterpret_cast<f32x4_t*>(vs + row * Rows<HD>::PAD + (c8 << 4)) = vr[i];
+        }
+        if (mask && tid < KT) ms[tid] = mr;
+        __syncthreads();
+        if (key0 + KT < k_hi) fetch(key0 + KT);
+        if (!wave_live) continue;
+
+        f32x4_t s[NKB];
+#pragma unroll
+        for (int kbk = 0; kbk < NKB; ++kbk) {
+            s[kbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int dh = 0; dh < NDH; ++dh) s[kbk] = Mfma<T>::run(row_frag<T, HD>(ks, kbk, dh, li, lg), qf[dh], s[kbk]);
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kbk = 0; kbk < NKB; ++kbk) {
+            f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
+            if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int key = key0 + kbk * 16 + lg * 4 + j;
+                s[kbk][j] = (key < k_hi && key <= lim) ? fmaf(s[kbk][j], p.scale_log2e, mk[j]) : -INFINITY;
+                mx = fmaxf(mx, s[kbk][j]);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float new_max = fmaxf(run_max, mx);
+        const float ref = new_max == -INFINITY ? 0.f : new_max;  // nothing visible yet: every term is 0
+        const float corr = __builtin_amdgcn_exp2f(run_max - ref);
+        float sum = 0.f;
+#pragma unroll
+        for (int kbk = 0; kbk < NKB; ++kbk)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                s[kbk][j] = __builtin_amdgcn_exp2f(s[kbk][j] - ref);
+                sum += s[kbk][j];
+            }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        run_sum = run_sum * corr + sum;
+        run_max = new_max;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db) o[db] *= corr;
+#pragma unroll
+        for (int c = 0; c < KT / 32; ++c) {
+            const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
+#pragma unroll
+            for (int db = 0; db < NDB; ++db) o[db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[db]);
+        }
+    }
+    if (!row_ok) return;
+
+    if (p.nsplit == 1) {  // one split: the final rows
+        const float inv = run_sum > 0.f ? 1.0f / run_sum : 0.f;
+        T* orow = reinterpret_cast<T*>(p.out) + (((long long)n * p.Tq + qi) * p.H + h) * HD;
+#pragma unroll
+        for (int db = 0; db < NDB; ++db)
+            *reinterpret_cast<half4*>(orow + db * 16 + lg * 4) = __builtin_convertvector(o[db] * inv, half4);
+        return;
+    }
+    const long long prow = ((long long)split * p.N * p.Hkv + nk) * p.R + r;
+#pragma unroll
+    for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4_t*>(p.part_o + prow * HD + db * 16 + lg * 4) = o[db];
+    if (lg == 0) {
+        p.part_ml[2 * prow] = run_max;
+        p.part_ml[2 * prow + 1] = run_sum;
+    }
+}
+
+// one thread per 4 features of an output row [n][i][h]: the splits' partial rows merged in split order
+template <typename T, int HD>
+__global__ __launch_bounds__(256) void decode_merge_kernel(const DecodeParams p) {
+    using half4 = typename Mfma<T>::half4;
+    constexpr int TPR = HD / 4;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x, row = t / TPR;
+    const int c4 = (int)(t % TPR);
+    if (row >= (long long)p.N * p.Tq * p.H) return;
+    const int h = (int)(row % p.H), qi = (int)(row / p.H % p.Tq), n = (int)(row / ((long long)p.H * p.Tq));
+    const int r = (h % p.group) * p.Tq + qi, nk = n * p.Hkv + h / p.group;
+    const long long stride = (long long)p.N * p.Hkv * p.R;  // partial rows per split
+    const long long r0 = (long long)nk * p.R + r;
+    float m = -INFINITY;
+    for (int s = 0; s < p.nsplit; ++s) m = fmaxf(m, p.part_ml[2 * (s * stride + r0)]);
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    float l = 0.f;
+    if (m != -INFINITY) {
+        for (int s = 0; s < p.nsplit; ++s) {
+            const long long pr = s * stride + r0;
+            const float ms = p.part_ml[2 * pr];
+            if (ms == -INFINITY) continue;  // nothing visible in this split
+            const float w = __builtin_amdgcn_exp2f(ms - m);
+            l = fmaf(w, p.part_ml[2 * pr + 1], l);
+            acc += w * *reinterpret_cast<const f32x4_t*>(p.part_o + pr * HD + c4 * 4);
+        }
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    *reinterpret_cast<half4*>(reinterpret_cast<T*>(p.out) + row * HD + c4 * 4) = __builtin_convertvector(acc * inv, half4);
+}
+
+template <typename T, int HD>
+void launch(const DecodeParams& p, hipStream_t stream) {
+    const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
+    decode_kernel<T, HD><<<grid, 256, 0, stream>>>(p);
+    if (p.nsplit > 1) {
+        const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
+        decode_merge_kernel<T, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
+    }
+}
+
+// Validates the shape; returns 0 or the BF_FAIL status
+int check_shape(const char* what, const bf_attn_decode_t* s, int dtype) {
+    if (!s) BF_FAIL("%s: shape is NULL", what);
+    if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
+    if (s->head_dim != 64 && s->head_dim != 128) BF_FAIL("%s: head size %d (64 or 128)", what, s->head_dim);
+    if (s->Tq < 1 || s->Tq > 16) BF_FAIL("%s: Tq=%d new queries (1 .. 16)", what, s->Tq);
+    if (s->Tk < s->Tq) BF_FAIL("%s: Tk=%d cached keys, fewer than Tq=%d", what, s->Tk, s->Tq);
+    if (s->N < 1 || s->H < 1 || s->Hkv < 1) BF_FAIL("%s: N=%d, H=%d, Hkv=%d must be positive", what, s->N, s->H, s->Hkv);
+    if (s->H % s->Hkv) BF_FAIL("%s: %d query heads do not divide into %d K/V head groups", what, s->H, s->Hkv);
+    const long long rows = (long long)(s->H / s->Hkv) * s->Tq;
+    if ((long long)s->N * s->Hkv > 65535 || (rows + ROWS - 1) / ROWS > 65535) BF_FAIL("%s: N * Hkv or H / Hkv * Tq exceeds the grid", what);
+    for (int i = 0; i < 3; ++i) {
+        const int64_t st[3] = {s->q_stride[i], s->k_stride[i], s->v_stride[i]};
+        for (int t = 0; t < 3; ++t)
+            if (st[t] < 0 || st[t] % 8) BF_FAIL("%s: strides must be non-negative multiples of 8 elements", what);
+    }
+    return 0;
+}
+
+int64_t workspace_bytes(const bf_attn_decode_t* s) {
+    const Split sp = decode_split(s);
+    if (sp.n == 1) return 0;
+    const long long rows = (long long)sp.n * s->N * s->Hkv * (s->H / s->Hkv) * s->Tq;
+    return rows * (s->head_dim + 2) * (int64_t)sizeof(float);
+}
+
+}  // namespace
+
+int64_t bf_launch_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
+    if (check_shape("bf_attention_decode_workspace_bytes", shape, BF_DT_BF16)) return -1;
+    return workspace_bytes(shape);
+}
+
+int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                   const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                   const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_decode_gqa";
+    if (check_shape(what, shape, dtype)) return 1;
+    if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
+    if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_workspace) & 15)
+        BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if (d_mask && ((uintptr_t)d_mask & 3)) BF_FAIL("%s: mask must be 4-byte aligned", what);
+    const Split sp = decode_split(shape);
+    if (sp.n > 1 && !d_workspace) BF_FAIL("%s: %d key splits need a workspace of %lld bytes", what, sp.n,
+                                          (long long)workspace_bytes(shape));
+    DecodeParams p = {};
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.mask = d_mask;
+    p.mask_off = d_mask_off;
+    p.out = d_out;
+    p.N = shape->N;
+    p.Tq = shape->Tq;
+    p.Tk = shape->Tk;
+    p.H = shape->H;
+    p.Hkv = shape->Hkv;
+    p.group = shape->H / shape->Hkv;
+    p.R = p.group * shape->Tq;
+    p.nsplit = sp.n;
+    p.split_keys = sp.keys;
+    if (sp.n > 1) {
+        p.part_o = reinterpret_cast<float*>(d_workspace);
+        p.part_ml = p.part_o + (long long)sp.n * p.N * p.Hkv * p.R * shape->head_dim;
+    }
+    for (int i = 0; i < 3; ++i) {
+        p.qs[i] = shape->q_stride[i];
+        p.ks[i] = shape->k_stride[i];
+        p.vs[i] = shape->v_stride[i];
+    }
+    p.scale_log2e = scaling * LOG2E;
+    if (dtype == BF_DT_BF16) {
+        if (shape->head_dim == 64) launch<__bf16, 64>(p, stream);
+        else launch<__bf16, 128>(p, stream);
+    } else {
+        if (shape->head_dim == 64) launch<_Float16, 64>(p, stream);
+        else launch<_Float16, 128>(p, stream);
+    }
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}

@@ -19,35 +19,11 @@
 //     Causal: key tile j visits query tiles from j on; the low key tiles (heavy) come first in the grid.
 // Rows with no visible key (left padding under a causal mask) output 0 and store lse = +inf, so the backward recomputes
 // P = 0 for them and their gradients are 0.
-#include "bf_common.h"
+#include "bf_attention_tiles.h"
 
 namespace {
 
 constexpr int TQ = 128;   // queries per forward / dq workgroup, keys per dk/dv workgroup
-constexpr float LOG2E = 1.4426950408889634f;
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<__bf16> {
-    using frag = bf16x8_t;
-    using half4 = bf16x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <>
-struct Mfma<_Float16> {
-    using frag = f16x8_t;
-    using half4 = f16x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
 
 struct GqaParams {
     const void* q;
@@ -67,52 +43,6 @@ struct GqaParams {
     int B, T, H, Hkv, group;
     float scale, scale_log2e;
 };
-
-// Row stride of the LDS images: swizzled (16-byte chunk ^= row & 7, for direct row-operand reads) and padded (+32 B, for
-// the transpose reads)
-template <int HD>
-struct Rows {
-    static constexpr int SWZ = HD * 2;
-    static constexpr int PAD = HD * 2 + 32;
-};
-
-// stage rows row0 .. row0 + NR - 1 of a [tokens][stride] tensor into the swizzled and / or the padded image
-template <typename T, int HD, int NR, int NT>
-__device__ __forceinline__ void stage(const T* base, long long stride, int row0, char* swz, char* pad, int tid) {
-    constexpr int CPR = HD / 8;  // 16-byte chunks per row
-    static_assert((NR * CPR) % NT == 0, "whole passes");
-#pragma unroll
-    for (int i = 0; i < NR * CPR / NT; ++i) {
-        const int c = tid + NT * i, row = c / CPR, c8 = c % CPR;
-        const f32x4_t x = *reinterpret_cast<const f32x4_t*>(base + (long long)(row0 + row) * stride + c8 * 8);
-        if (swz) *reinterpret_cast<f32x4_t*>(swz + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = x;
-        if (pad) *reinterpret_cast<f32x4_t*>(pad + row * Rows<HD>::PAD + (c8 << 4)) = x;
-    }
-}
-
-// row-operand fragment (16 rows x 32 features, half dh) of block `blk` of a swizzled image: lane (row li, k group lg)
-template <typename T, int HD>
-__device__ __forceinline__ typename Mfma<T>::frag row_frag(const char* swz, int blk, int dh, int li, int lg) {
-    const int row = blk * 16 + li;
-    return *reinterpret_cast<const typename Mfma<T>::frag*>(swz + row * Rows<HD>::SWZ + (((dh * 4 + lg) ^ (row & 7)) << 4));
-}
-
-// transposed fragment: rows = features db*16 + li, k = the 32 image rows {(2c)*16 + 4 lg + 0..3, (2c+1)*16 + 4 lg + 0..3}
-template <typename T, int HD>
-__device__ __forceinline__ typename Mfma<T>::frag tr_frag(const char* pad, int c, int db, int li, int lg) {
-    constexpr int ROW = Rows<HD>::PAD;
-    const char* blk = pad + (lg * 4 + (li >> 2)) * ROW + (db * 16 + (li & 3) * 4) * 2;
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c) * 16 * ROW));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c + 1) * 16 * ROW));
-    const s16x8_t ab = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(typename Mfma<T>::frag, ab);
-}
-
-template <typename T>
-__device__ __forceinline__ typename Mfma<T>::frag pack2(const f32x4_t a, const f32x4_t b) {
-    const f32x8_t v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_convertvector(v, typename Mfma<T>::frag);
-}
 
 // ---------------------------------------------------------------------------------------------------- forward
 template <typename T, int HD, int KT, bool CAUSAL, int MINB>

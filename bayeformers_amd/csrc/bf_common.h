@@ -225,6 +225,10 @@ int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_
                                 const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
                                 float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
                                 float scaling, hipStream_t stream);
+int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                   const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                   const bf_attn_decode_t* shape, float scaling, hipStream_t stream);
+int64_t bf_launch_attention_decode_workspace_bytes(const bf_attn_decode_t* shape);
 size_t bf_add_layernorm_bwd_ws_bytes(long long rows, int N);
 int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
                                 const void* d_dy, void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace,

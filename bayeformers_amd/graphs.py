@@ -223,6 +223,7 @@ def auto_forward(model, args, kwargs) -> Optional[Any]:
     (not an evaluation forward of the kind described in the module docstring, or a signature not seen often enough yet)."""
     if (DISABLED or not getattr(model, "graph_replay", True) or torch.is_grad_enabled() or model.training
             or model._mc_samples != 1 or model._mc_span != (0, 1) or getattr(model, "_mc_harness", 0)
+            or model.__dict__.get("_pinned") is not None  # (pinned_samples: every forward runs on the host reservation)
             or not torch.cuda.is_available()
             or torch.cuda.is_current_stream_capturing()):
         return None

@@ -188,9 +188,13 @@ class Model(Module):
                 plan = self._plan
         if plan is None:
             self._plan = None  # (a plan of an earlier forward that no layer would use now: its arenas are released)
-        # every rank reserves the GLOBAL sample indices of the step and runs its own contiguous slice of them
+        # every rank reserves the GLOBAL sample indices of the step and runs its own contiguous slice of them; inside
+        # pinned_samples() every forward runs on the one reservation made when it was entered
         start, total = self._mc_span
-        base = bfr.reserve_samples(total) + start
+        pinned = self.__dict__.get("_pinned")
+        if pinned is not None and (pinned[1], pinned[2]) != (start, total):
+            raise RuntimeError(f"pinned_samples: entered for sample span {pinned[1:]}, a forward runs with {(start, total)}")
+        base = pinned[0] + start if pinned is not None else bfr.reserve_samples(total) + start
         self._last_base, self._last_seed, self._last_S = base, bfr.STATE.seed, S
         self._last_counter = bfr.counter_snapshot() if bfr.STATE.kl_gradient else None
         ctx = bfr.STATE.ctx = _ForwardContext(base, S, slots, plan, self._lp_buf, shard_start=start, dropping=self.training,
@@ -202,6 +206,15 @@ class Model(Module):
         finally:
             if plan is not None:
                 plan.finish(self._lp_buf)  # one log-prob reduction for all the groups this forward sampled
+            if pinned is not None and self._lp_buf is not None:
+                # the same indices draw the same weights: the log-probs of the block's first forward stand for all of them
+                # (a later forward may reduce them on another kernel, in another summation order)
+                kept = self.__dict__.get("_pinned_lp")
+                if kept is None or kept.shape != self._lp_buf.shape:
+                    with torch.inference_mode(False):
+                        self._pinned_lp = self._lp_buf.clone()
+                else:
+                    self._lp_buf.copy_(kept)
             bfr.STATE.ctx = None
             # what a finished forward keeps is what a checkpointed block's recomputation needs (sample indices, slots,
             # plan, counter): NOT the stacked query/key/value outputs and their inputs — a replay re-keys on data_ptr and
@@ -209,7 +222,8 @@ class Model(Module):
             ctx.shared_out = {}
             if torch.is_grad_enabled() and out is not None:
                 bfr.remember_context(ctx, out)
-            bfr.commit_samples(total)
+            if pinned is None:
+                bfr.commit_samples(total)
 
     @contextlib.contextmanager
     def monte_carlo(self, samples: int, shard=(0, 1), span=None):
@@ -232,6 +246,25 @@ class Model(Module):
         finally:
             self._mc_samples, self._mc_span = prev
             self._mc_harness -= 1
+
+    @contextlib.contextmanager
+    def pinned_samples(self):
+        """Run every forward inside on ONE reservation of Monte-Carlo sample indices: reserved when the block is entered
+        (for the span of the `monte_carlo` setting in force then), committed once when it is left.  Each of the S samples
+        is then one fixed draw of the weights across the forwards — e.g. the steps of a generation that reuse a KV cache
+        — and log_prob_samples() is the same after every forward.  Works with the host counter and with the
+        device-resident one (use_device_counter: the kernels add the counter, which moves once at the end).  Forwards
+        inside are never replayed from a HIP graph.  Outside the block each forward reserves fresh indices, as always."""
+        if self.__dict__.get("_pinned") is not None:
+            raise RuntimeError("pinned_samples: already pinned")
+        start, total = self._mc_span
+        self._pinned = (bfr.reserve_samples(total), start, total)
+        self._pinned_lp = None
+        try:
+            yield self
+        finally:
+            self._pinned = self._pinned_lp = None
+            bfr.commit_samples(total)
 
     def fused_children(self) -> List[KernelLayer]:
         """The kernel-backed children (bnn.Linear, bnn.Embedding) in registration order; their layer_id (Philox

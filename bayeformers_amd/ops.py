@@ -804,6 +804,95 @@ def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[T
     return dq, dkv[0], dkv[1]
 
 
+# launches of bf_attention_decode_gqa from this process (a test can assert that a cached decode step ran on the kernel)
+DECODE_CALLS = {"fwd": 0}
+DECODE_MAX_QUERIES = 16
+
+
+def attention_decode_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bool = True) -> bool:
+    """What bf_attention_decode_gqa takes: q [N, H, Tq, D] (1 <= Tq <= 16), k and v [N, Hkv, Tk, D] with Tq <= Tk, Hkv
+    dividing H, D 64 or 128, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8
+    elements) and a contiguous feature dimension.  check_device=False judges the shapes, dtypes and strides alone (CPU or
+    meta tensors)."""
+    if check_device and not (q.is_cuda and k.is_cuda and v.is_cuda):
+        return False
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        return False
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
+        return False
+    N, H, Tq, D = q.shape
+    Hkv, Tk = k.shape[1], k.shape[2]
+    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in (64, 128):
+        return False
+    if not (1 <= Tq <= DECODE_MAX_QUERIES and Tq <= Tk) or N * Hkv > 65535:
+        return False
+    return all(t.stride(3) == 1 and all(st >= 0 and st % 8 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (q, k, v))
+
+
+def decode_kernel_wins(H: int, Hkv: int, Tq: int, Tk: int, D: int) -> bool:
+    """The dispatch rule of cached decode steps, from the measurement of profiles/decode_attention.md: every measured class
+    runs faster on bf_attention_decode_gqa than on the framework's SDPA except one query per sequence on plain multi-head
+    attention (one query row per workgroup of 64) with head size 128 and a short cache (Tk 512: 0.93x), which stays on SDPA."""
+    return not (H == Hkv and Tq == 1 and D == 128 and Tk <= 512)
+
+
+def _decode_shape(q: Tensor, k: Tensor, v: Tensor):
+    N, H, Tq, D = q.shape
+    s = _C.bf_attn_decode_t(N, Tq, k.shape[2], H, k.shape[1], D)
+    for name, t in (("q_stride", q), ("k_stride", k), ("v_stride", v)):
+        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    return s
+
+
+def attention_decode_workspace_bytes(q: Tensor, k: Tensor, v: Tensor) -> int:
+    """Scratch bytes attention_forward_decode needs at this shape (bf_attention_decode_workspace_bytes)."""
+    n = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(_decode_shape(q, k, v))))
+    if n < 0:
+        _C.check(1, "bf_attention_decode_workspace_bytes")
+    return n
+
+
+def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
+                             mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """Causal attention of Tq new queries against a KV cache (bf_attention_decode_gqa): q [N, H, Tq, D], k / v
+    [N, Hkv, Tk, D] as described by attention_decode_supported; query i sees keys 0 .. Tk - Tq + i.  key_mask: additive
+    fp32 [N, Tk] or None; mask_off: optional 1-element device flag, true = the mask hides nothing.  Returns [N, Tq, H, D]
+    contiguous (a query with no visible key gives 0).  The split partials go to `workspace` (uint8, at least
+    attention_decode_workspace_bytes) or to a fresh tensor of the caching allocator — either way capturable."""
+    _require_device(q, "attention_forward_decode: q")
+    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
+            or k.shape[3] != q.shape[3]:
+        raise _C.BayeFormersAMDError(f"attention_forward_decode: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
+                                     "are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
+    if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
+            or v.device != q.device:
+        raise _C.BayeFormersAMDError("attention_forward_decode: q, k and v must share one dtype and one device")
+    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
+        raise _C.BayeFormersAMDError("attention_forward_decode: the feature dimension of q, k and v must be contiguous")
+    N, H, Tq, D = q.shape
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
+    shape = _decode_shape(q, k, v)
+    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
+    if nbytes < 0:
+        _C.check(1, "bf_attention_decode_workspace_bytes")
+    ws = None
+    if nbytes:
+        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+            raise _C.BayeFormersAMDError(f"attention_forward_decode: the workspace needs {nbytes} device bytes")
+    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
+                                 or not key_mask.is_contiguous()):
+        raise _C.BayeFormersAMDError("attention_forward_decode: key_mask must be contiguous fp32 [N, Tk]")
+    _C.check(_C.lib().bf_attention_decode_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                              key_mask.data_ptr() if key_mask is not None else None,
+                                              mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
+                                              ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype],
+                                              ctypes.byref(shape), float(scaling), _stream_ptr()), "bf_attention_decode_gqa")
+    DECODE_CALLS["fwd"] += 1
+    return out
+
+
 class AttentionGqaFn(torch.autograd.Function):
     """attention_forward_gqa with attention_backward_gqa as its backward (no dropout: decoder configs run attention
     without it).  Keeps q, k, v, the output and one fp32 row statistic per query."""

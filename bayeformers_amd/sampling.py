@@ -729,3 +729,112 @@ class GraphedSampler:
         if self._open:
             self._open = False
             graphs.release_counter()
+
+
+@dataclass
+class Generation:
+    """What `sample_generate` returns; device tensors.  n = max_new_tokens.
+
+        sequences                   [B, T0 + n] int64  the prompt and the generated tokens (pad_token_id past a row's EOS)
+        predictive_entropy          [B, n] fp32  H of the model-average probabilities of each step (total uncertainty)
+        expected_entropy            [B, n] fp32  mean over the samples of H(softmax(l_s))      (aleatoric)
+        mutual_information          [B, n] fp32  max(0, predictive - expected)                 (epistemic)
+        token_prob                  [B, n] fp32  the model-average probability of the token chosen
+        lengths                     [B] int64    tokens generated, the EOS included
+        log_prior                   [S] fp64     per-sample log prior of the pinned weight draws
+        log_variational_posterior   [S] fp64     per-sample log q of the same draws
+    The statistics of a step after a row's EOS are 0."""
+    sequences: Tensor
+    predictive_entropy: Tensor
+    expected_entropy: Tensor
+    mutual_information: Tensor
+    token_prob: Tensor
+    lengths: Tensor
+    log_prior: Tensor
+    log_variational_posterior: Tensor
+
+
+def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor] = None, samples: int = 1,
+                    max_new_tokens: int = 1, do_sample: bool = False, temperature: float = 1.0,
+                    eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
+                    generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None) -> Generation:
+    """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
+    uncertainty of its Monte-Carlo posterior.
+
+    The whole generation runs under `model.monte_carlo(samples)` and `model.pinned_samples()`: each of the S samples is ONE
+    draw of the weights for every token, with its own slice of the KV cache (the sample-major [S*B] batch).  Prefill is one
+    forward over the prompt (input_ids [B, T0], left-padded rows marked by attention_mask [B, T0]); every later step feeds
+    one token per row with `past_key_values`.  The last position's [S, B, V] logits, divided by `temperature`, go through
+    `mc_predictive` (the bf_predictive kernels); the next token is the argmax of the model-average probabilities or, with
+    do_sample, a draw from them (torch.multinomial with `generator`), fed to all S samples.  Rows past eos_token_id emit
+    pad_token_id (default: eos_token_id).  No host synchronisation per step except the all-finished check, and none
+    without eos_token_id.  Single process, eval mode and no gradient only."""
+    samples, max_new_tokens = int(samples), int(max_new_tokens)
+    if samples < 1:
+        raise ValueError(f"sample_generate: samples={samples} (at least 1)")
+    if max_new_tokens < 1:
+        raise ValueError(f"sample_generate: max_new_tokens={max_new_tokens} (at least 1)")
+    if not temperature > 0.0:
+        raise ValueError(f"sample_generate: temperature={temperature} (must be positive)")
+    if group is not None:
+        raise NotImplementedError("sample_generate: S-sharded generation is not supported (single process)")
+    if not isinstance(model, Model):
+        raise TypeError("sample_generate: model must be a bnn.Model (bayeformers_amd.to_bayesian)")
+    if model.training:
+        raise RuntimeError("sample_generate: put the model in eval mode (model.eval())")
+    if torch.is_grad_enabled():
+        raise RuntimeError("sample_generate: call it under torch.no_grad() or torch.inference_mode()")
+    if input_ids.dim() != 2 or input_ids.shape[1] < 1:
+        raise ValueError(f"sample_generate: input_ids must be [B, T0] with T0 >= 1 (got {tuple(input_ids.shape)})")
+    if attention_mask is not None and attention_mask.shape != input_ids.shape:
+        raise ValueError("sample_generate: attention_mask must have the shape of input_ids")
+    from transformers import DynamicCache
+
+    if pad_token_id is None:
+        pad_token_id = eos_token_id if eos_token_id is not None else 0
+    S, n = samples, max_new_tokens
+    B, T0 = input_ids.shape
+    dev = input_ids.device
+    inner = model.model if model.model is not None else model
+    cache = DynamicCache(config=getattr(inner, "config", None))
+    ids = input_ids.repeat(S, 1)
+    mask = attention_mask.to(torch.long).repeat(S, 1) if attention_mask is not None else None
+    # left padding: positions count the visible tokens (what the framework's generate passes)
+    pos = (mask.cumsum(-1) - 1).clamp(min=0) if mask is not None else None
+
+    sequences = torch.full((B, T0 + n), int(pad_token_id), dtype=torch.long, device=dev)
+    sequences[:, :T0] = input_ids
+    stats = torch.zeros((4, B, n), dtype=torch.float32, device=dev)
+    lengths = torch.zeros(B, dtype=torch.long, device=dev)
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    with model.monte_carlo(S), model.pinned_samples():
+        out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
+        lp = model.log_prob_samples().clone()
+        for t in range(n):
+            logits = out.logits[:, -1, :].reshape(S, B, -1)
+            if temperature != 1.0:
+                logits = logits.float() / temperature
+            pred = mc_predictive(logits)
+            if do_sample:
+                tok = torch.multinomial(pred.probs, 1, generator=generator).squeeze(1)
+            else:
+                tok = pred.prediction
+            step = torch.stack([pred.predictive_entropy, pred.expected_entropy, pred.mutual_information,
+                                pred.probs.gather(1, tok[:, None]).squeeze(1)])
+            if eos_token_id is not None:
+                tok = torch.where(finished, torch.full_like(tok, int(pad_token_id)), tok)
+                step = torch.where(finished[None, :], 0.0, step)
+                lengths += (~finished).long()
+                finished = finished | (tok == int(eos_token_id))
+            else:
+                lengths += 1
+            sequences[:, T0 + t] = tok
+            stats[:, :, t] = step
+            if t == n - 1 or (eos_token_id is not None and bool(finished.all())):
+                break
+            ids = tok.repeat(S)[:, None]
+            if mask is not None:
+                mask = torch.cat([mask, mask.new_ones((S * B, 1))], 1)
+                pos = pos[:, -1:] + 1
+            out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
+    return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])

@@ -395,6 +395,32 @@ int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, cons
                          const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
                          void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream);
 
+/* ---- decoding with a KV cache -----------------------------------------------------------------------------------------
+ * Causal grouped-query attention of a generation step (inference only): the Tq new queries of each of N sequences
+ * (1 <= Tq <= 16) against Tk cached keys (Tq <= Tk, any Tk >= 1) — the attention between q/k/v_proj and o_proj of the
+ * wrapped decoder while it generates (the layers to_bayesian converts: /root/reference/bayeformers/__init__.py:19-63,
+ * /root/reference/bayeformers/convert.py; the Monte-Carlo loop it runs under: examples/bert_glue.py:56-73).  Query i of a
+ * sequence sees keys 0 .. Tk - Tq + i.  q element (n, h, i, d) at n q_stride[0] + h q_stride[1] + i q_stride[2] + d, k / v
+ * (n, g, j, d) likewise with g = h / (H / Hkv); head_dim 64 or 128; strides non-negative multiples of 8 elements, 16-byte
+ * aligned pointers.  d_mask: additive fp32 [N][Tk] over the keys or NULL, d_mask_off: NULL or a device byte, non-zero =
+ * the mask hides nothing.  d_out: [N][Tq][H][head_dim] contiguous; a query with no visible key gives 0.
+ * The keys are split into a number of parts that depends on the shape only, and the parts are merged in a fixed order:
+ * bitwise reproducible.  No host synchronisation, no allocation (capturable): d_workspace holds
+ * bf_attention_decode_workspace_bytes(shape) bytes (NULL when that is 0), 16-byte aligned, private to the call until it
+ * completes on `stream`.  Unsupported shapes return 1 with bf_last_error() set. */
+typedef struct bf_attn_decode {
+    int32_t N, Tq, Tk, H, Hkv, head_dim;
+    int64_t q_stride[3]; /* element strides of batch, head, token */
+    int64_t k_stride[3];
+    int64_t v_stride[3];
+} bf_attn_decode_t;
+int bf_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                            void* d_out, void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
+                            void* stream);
+/* Workspace bytes bf_attention_decode_gqa needs for `shape` (0: none); -1 with bf_last_error() set for an unsupported
+ * shape. */
+int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape);
+
 /* ---- training mode: HuggingFace dropout inside the fused kernels ------------------------------------------------------
  * The reference trains with the wrapped model in .train() (/root/reference/examples/bert_glue.py:221,227-241): HF's
  * dropout (p = 0.1) acts on the attention probabilities and on every dense output in front of a residual + LayerNorm.
