@@ -61,6 +61,9 @@ SYMBOLS = {
     "bf_gemm_nt_act": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "bf_gemm_nt_act_pre": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "bf_gemm_nt_layers": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "bf_gemm_nt_skinny": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_gemm_nt_skinny_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "bf_gemm_nt_skinny_max_rows": (_i, []),
     "bf_gemm_nn_layers": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "bf_gemm_nn": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "bf_gemm_tn": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -307,6 +307,18 @@ int bf_gemm_nt_layers(const void* d_x, int x_dtype, int64_t x_sample_stride, con
                              (hipStream_t)stream, act, L);
 }
 
+int bf_gemm_nt_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
+                      const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
+                      size_t workspace_bytes, void* stream) {
+    if ((uintptr_t)d_y & 7) BF_FAIL("bf_gemm_nt_skinny: y must be 8-byte aligned");
+    return bf_launch_gemm_skinny(d_x, x_dtype, x_sample_stride, d_w, w_dtype, d_bias, d_y, y_dtype, S, M, N, K, act,
+                                 d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t bf_gemm_nt_skinny_workspace_bytes(int S, int M, int N, int K) { return bf_gemm_skinny_workspace_impl(S, M, N, K); }
+
+int bf_gemm_nt_skinny_max_rows(void) { return bf_gemm_skinny_max_rows_impl(); }
+
 // workspace layout of bf_linear_fwd: [W_s : S*N*K compute_dtype][b_s : S*N fp32][log-prob partials]
 static void linear_ws_layout(int S, int N, int K, int has_bias, int compute_dtype, size_t* off_w, size_t* off_b,
                              size_t* off_p, size_t* total) {

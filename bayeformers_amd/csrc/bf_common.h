@@ -79,6 +79,12 @@ int bf_launch_reduce_groups(const double* d_partials, const uint32_t* d_rows, in
 int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                       const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, hipStream_t stream,
                       int act = BF_ACT_NONE, int layers = 1, void* d_pre = nullptr);
+// skinny NT GEMM on kept weights (bf_gemm_skinny.hip)
+int bf_launch_gemm_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
+                          const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act,
+                          void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+size_t bf_gemm_skinny_workspace_impl(int S, int M, int N, int K);
+int bf_gemm_skinny_max_rows_impl();
 // out = gelu(in) elementwise (16-bit or fp32 tensors of n elements)
 int bf_launch_gelu(const void* d_in, void* d_out, int dtype, uint64_t n, hipStream_t stream);
 // dpre = dy * gelu'(pre) elementwise on [S][M][N] 16-bit tensors, with the column sums of dpre per sample

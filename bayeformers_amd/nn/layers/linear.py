@@ -262,6 +262,8 @@ class Linear(KernelLayer):
         want_act = self.activation == "gelu"
         need_grad = torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (x2, self.weight.mu, self.weight.rho, mu_b, rho_b))
+        if ctx is not None and ctx.kept is not None and id(self) in ctx.plan.group_of:
+            return self._kept_forward(ctx, x2, S, slot, want_act).view(*input.shape[:-1], self.out_features)
         rows_per_sample = x2.shape[0] // S
         small = rows_per_sample <= ops.fused_small_rows(self.out_features, self.in_features) and self.in_features % 32 == 0 and x2.dtype != torch.float64
         if small != self._small_m:
@@ -289,6 +291,25 @@ class Linear(KernelLayer):
             y = torch.nn.functional.gelu(y)
         self._end(ctx, slot)
         return y.view(*input.shape[:-1], self.out_features)
+
+    def _kept_forward(self, ctx, x2: Tensor, S: int, slot: Tensor, want_act: bool) -> Tensor:
+        """A forward inside Model.pinned_samples(keep_weights=True) (no gradient): the weights were sampled by the block's
+        first forward.  A few rows per sample: bf_gemm_nt_skinny; otherwise the tiled GEMM (or the stacked query/key/value
+        launch), as a planned forward runs it.  Leaves `_small_m` alone: Model._plan is not this block's."""
+        w_s, b_s = ctx.plan.views[id(self)]
+        N, K = self.out_features, self.in_features
+        act = 1 if want_act else 0
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        if ops.skinny_supported(x2, w_s, S, K):
+            y = ops.skinny_linear_forward(x2, w_s, b_s, S, N, K, act)
+        else:
+            y = None
+            if self._shared_input is not None and not want_act:
+                y = self._stacked_forward(ctx, x2, S)
+            if y is None:
+                y = ops.planned_linear_forward(x2, w_s, b_s, S, N, K, act)
+        self._lp_view, self._lp_dirty = slot, True
+        return y
 
     def _stacked_forward(self, ctx, x2: Tensor, S: int, base: int = 0, need_grad: bool = False) -> Optional[Tensor]:
         """Layers that read the same activations (query / key / value): whichever of them runs first multiplies x by

@@ -61,6 +61,7 @@ class _ForwardContext:
         self.drop_counter = bfr.reserve_dropout_counter(needed=dropping)  # device-counter mode: this forward's copy of it
         self.shard_start = int(shard_start)
         self.drop_sites = drop_sites  # the owning model's [next free dropout site number] (random.dropout_site)
+        self.kept = None  # the _KeptWeights of a pinned_samples(keep_weights=True) block (then plan = its plan)
 
     @contextlib.contextmanager
     def replay(self):
@@ -81,6 +82,45 @@ class _ForwardContext:
 
     def slot(self, layer) -> Optional[Tensor]:
         return self._slots.get(id(layer))
+
+
+class _KeptWeights:
+    """The sampled weights of a `pinned_samples(keep_weights=True)` block: every bnn.Linear of the model in ONE SamplePlan with
+    one arena per group (plan.SamplePlan keep=True), sampled by one launch in the block's first forward and read by every
+    later one.  Belongs to the block: Model._plan and its rebuilds never see it."""
+
+    def __init__(self, S: int, cdt: torch.dtype):
+        self.S, self.cdt = S, cdt
+        self.plan: Optional[SamplePlan] = None
+        self.watch = []  # (tensor, data_ptr, _version) of every mu / rho the samples were drawn from
+
+    def prepare(self, model, layers, ctx) -> SamplePlan:
+        """The plan of the block; in its first forward also the one sampling launch over all groups."""
+        S, cdt = ctx.S, bfr.get_compute_dtype()
+        if (S, cdt) != (self.S, self.cdt):
+            raise RuntimeError(f"pinned_samples(keep_weights=True): entered for S={self.S} at {self.cdt}, a forward runs "
+                               f"with S={S} at {cdt}")
+        if torch.is_grad_enabled() or model.training:
+            raise RuntimeError("pinned_samples(keep_weights=True): forwards inside must run in eval mode without gradients")
+        if self.plan is not None:
+            for t, ptr, ver in self.watch:
+                if t.data_ptr() != ptr or t._version != ver:
+                    raise RuntimeError("pinned_samples(keep_weights=True): a posterior mu / rho changed inside the block; "
+                                       "the kept samples no longer match it (leave the block to draw new ones)")
+            return self.plan
+        linears = [(i, l) for i, l in enumerate(layers) if isinstance(l, Linear)]
+        pl = [l for _, l in linears]
+        shared = tuple(sorted({id(l._shared_input): l._shared_input for l in pl
+                               if l._shared_input is not None}.values(), key=lambda t: t[0].layer_id))
+        self.plan = SamplePlan(pl, S, cdt, pl[0].weight.mu.device, index=[i for i, _ in linears], shared=shared, keep=True)
+        self.plan._sample_groups(0, len(self.plan.groups) - 1, ctx.token, bfr.STATE.seed, ctx.sample_base)
+        from .parameters.gaussian import Gaussian
+
+        for l in pl:
+            for g in (l.weight, l.bias):
+                if isinstance(g, Gaussian):
+                    self.watch += [(t, t.data_ptr(), t._version) for t in (g.mu, g.rho)]
+        return self.plan
 
 
 class _KLFn(torch.autograd.Function):
@@ -172,7 +212,10 @@ class Model(Module):
             slots = {id(l): buf[i] for i, l in enumerate(layers)}
         plan = None
         linears = [l for l in layers if isinstance(l, Linear)]
-        if linears and self.cross_layer_sampling and SamplePlan.plannable(linears):
+        kept = self.__dict__.get("_kept")
+        if kept is not None:
+            pass  # the block's own plan (below, once the forward's context exists); Model._plan is left as it is
+        elif linears and self.cross_layer_sampling and SamplePlan.plannable(linears):
             # layers seen with <= 64 rows per sample run the single fused kernel instead (Linear.forward marks them)
             planned = [(i, l) for i, l in enumerate(layers) if isinstance(l, Linear) and not l._small_m]
             if planned:
@@ -186,7 +229,7 @@ class Model(Module):
                     self._plan = SamplePlan(pl, S, cdt, layers[0].weight.mu.device, index=[i for i, _ in planned],
                                             shared=shared)
                 plan = self._plan
-        if plan is None:
+        if plan is None and kept is None:
             self._plan = None  # (a plan of an earlier forward that no layer would use now: its arenas are released)
         # every rank reserves the GLOBAL sample indices of the step and runs its own contiguous slice of them; inside
         # pinned_samples() every forward runs on the one reservation made when it was entered
@@ -201,6 +244,9 @@ class Model(Module):
                                               drop_sites=self.__dict__.setdefault("_drop_sites", [1]))
         out = None
         try:
+            if kept is not None:
+                ctx.kept, ctx.plan = kept, kept.prepare(self, layers, ctx)
+                plan = ctx.plan
             out = super(Model, self).__call__(*args, **kwargs)
             return out
         finally:
@@ -248,23 +294,59 @@ class Model(Module):
             self._mc_harness -= 1
 
     @contextlib.contextmanager
-    def pinned_samples(self):
+    def pinned_samples(self, keep_weights: bool = False, max_bytes: Optional[int] = None):
         """Run every forward inside on ONE reservation of Monte-Carlo sample indices: reserved when the block is entered
         (for the span of the `monte_carlo` setting in force then), committed once when it is left.  Each of the S samples
         is then one fixed draw of the weights across the forwards — e.g. the steps of a generation that reuse a KV cache
         — and log_prob_samples() is the same after every forward.  Works with the host counter and with the
         device-resident one (use_device_counter: the kernels add the counter, which moves once at the end).  Forwards
-        inside are never replayed from a HIP graph.  Outside the block each forward reserves fresh indices, as always."""
+        inside are never replayed from a HIP graph.  Outside the block each forward reserves fresh indices, as always.
+
+        keep_weights=True (eval mode, no gradient): the block's first forward samples the S weight draws of EVERY bnn.Linear in
+        one launch and keeps them in device memory until the block is left; later forwards sample nothing.  Their layers with at
+        most ops.SKINNY_ROWS rows per sample (decode steps) run bf_gemm_nt_skinny on the kept 16-bit weights, the others the
+        tiled GEMM (fp32 compute: the fp32 GEMM).  The draws and log-probs are the bits the cross-layer plan gives.  Costs
+        plan.kept_weight_bytes(model, S, compute dtype) bytes — S * P * 2 in bf16 for P Linear weights — checked before
+        anything is allocated against max_bytes (default plan.ARENA_BYTES): above it, ValueError.  A forward after a
+        posterior mu / rho was changed inside the block raises.  bnn.Embedding layers keep their own path."""
         if self.__dict__.get("_pinned") is not None:
             raise RuntimeError("pinned_samples: already pinned")
+        kept = None
+        if keep_weights:
+            kept = self._keep_weights_check(max_bytes)
+        elif max_bytes is not None:
+            raise ValueError("pinned_samples: max_bytes is the budget of keep_weights=True")
         start, total = self._mc_span
         self._pinned = (bfr.reserve_samples(total), start, total)
         self._pinned_lp = None
+        self._kept = kept
         try:
             yield self
         finally:
-            self._pinned = self._pinned_lp = None
+            self._pinned = self._pinned_lp = self._kept = None  # (the kept samples' arenas go with the last reference)
             bfr.commit_samples(total)
+
+    def _keep_weights_check(self, max_bytes: Optional[int]) -> "_KeptWeights":
+        """Everything pinned_samples(keep_weights=True) refuses, checked before anything is reserved or allocated."""
+        from .. import plan as bplan
+
+        if torch.is_grad_enabled():
+            raise RuntimeError("pinned_samples(keep_weights=True) is inference only: enter it under torch.no_grad()")
+        if self.training:
+            raise RuntimeError("pinned_samples(keep_weights=True) is inference only: put the model in eval mode (model.eval())")
+        S, cdt = self._mc_samples, bfr.get_compute_dtype()
+        limit = bplan.ARENA_BYTES if max_bytes is None else int(max_bytes)
+        need = bplan.kept_weight_bytes(self, S, cdt)
+        if need > limit:
+            raise ValueError(f"pinned_samples(keep_weights=True): the kept samples need {need} bytes (S={S}, {cdt}), "
+                             f"above max_bytes={limit}")
+        linears = [l for l in self.fused_children() if isinstance(l, Linear)]
+        if not linears:
+            raise ValueError("pinned_samples(keep_weights=True): the model has no Bayesian Linear layer")
+        if not SamplePlan.plannable(linears):
+            raise ValueError("pinned_samples(keep_weights=True) needs every Bayesian Linear on one ROCm device, with built-in "
+                             "priors and the global compute dtype (SamplePlan.plannable)")
+        return _KeptWeights(S, cdt)
 
     def fused_children(self) -> List[KernelLayer]:
         """The kernel-backed children (bnn.Linear, bnn.Embedding) in registration order; their layer_id (Philox

@@ -441,6 +441,53 @@ def planned_linear_forward(x: Tensor, w_s: Tensor, b_s: Optional[Tensor], S: int
     return gemm_nt(x, w_s, b_s, S, M, N, K, M * K, x.dtype, act).view(S * M, N)
 
 
+# Rows per sample up to which a layer of a keep_weights block (nn.Model.pinned_samples) runs bf_gemm_nt_skinny rather than the
+# tiled GEMM (bf_gemm_nt_act): the kernel takes up to bf_gemm_nt_skinny_max_rows() = 64, but at 64 rows the tiled GEMM is faster on
+# the wide layers (32000 x 1024: 43 against 92 us at S 4); at 16 rows the skinny kernel wins or ties every layer of the DESIGN 4.5
+# decoder but the head (46 against 41 us) — the measured crossover (profiles/kept_weights_decode.md).
+SKINNY_ROWS = 16
+SKINNY_CALLS = [0]  # launches of bf_gemm_nt_skinny through skinny_linear_forward (tests, diagnostics)
+
+
+def skinny_supported(x: Tensor, w_s: Tensor, S: int, K: int) -> bool:
+    """Does skinny_linear_forward take x ([S*M, K]) with these kept weights?  16-bit x of the weights' dtype, K % 32 == 0,
+    1 <= M <= SKINNY_ROWS, 16-byte aligned operands."""
+    if w_s.dtype not in (torch.bfloat16, torch.float16) or x.dtype != w_s.dtype or K % 32 or S > 65535:
+        return False
+    rows = x.shape[0]
+    if rows % S or not 1 <= rows // S <= min(SKINNY_ROWS, _C.lib().bf_gemm_nt_skinny_max_rows()):
+        return False
+    return x.is_contiguous() and (x.data_ptr() | w_s.data_ptr()) % 16 == 0
+
+
+def skinny_linear_forward(x: Tensor, w_s: Tensor, b_s: Optional[Tensor], S: int, N: int, K: int, act: int = 0,
+                          x_sample_stride: Optional[int] = None, out: Optional[Tensor] = None) -> Tensor:
+    """y[s] = act(x[s] W_s^T + b_s) for a few rows per sample on weights already in memory (bf_gemm_nt_skinny).  x: [S*M, K]
+    (or any storage with `x_sample_stride` elements between samples), w_s: [S, N, K] 16-bit, b_s: [S, N] fp32 or None;
+    returns [S*M, N] of x's dtype.  The split-K scratch comes from the stream's workspace."""
+    _require_device(x, "input")
+    lib = _C.lib()
+    if x_sample_stride is None:
+        if not x.is_contiguous():
+            x = x.contiguous()
+        rows = x.numel() // K
+        if rows % S:
+            raise _C.BayeFormersAMDError(f"input rows ({rows}) are not a multiple of the sample count S={S}")
+        M = rows // S
+        x_sample_stride = M * K
+    else:
+        M = x.shape[-2]
+    y = out if out is not None else torch.empty((S * M, N), dtype=x.dtype, device=x.device)
+    need = lib.bf_gemm_nt_skinny_workspace_bytes(S, M, N, K)
+    ws = workspace(x.device, need) if need else None
+    _C.check(lib.bf_gemm_nt_skinny(x.data_ptr(), _TORCH2BF[x.dtype], int(x_sample_stride), w_s.data_ptr(), _TORCH2BF[w_s.dtype],
+                                   b_s.data_ptr() if b_s is not None else None, y.data_ptr(), _TORCH2BF[y.dtype], S, M, N, K,
+                                   int(act), ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                   _stream_ptr()), "bf_gemm_nt_skinny")
+    SKINNY_CALLS[0] += 1
+    return y
+
+
 COLSUMS_FOLDED = [0]  # bias gradients whose column sums came with the output gradient (tests, diagnostics)
 
 # Column sums a gradient's PRODUCER left for its consumer (attention_backward -> linear_backward of query / key / value).

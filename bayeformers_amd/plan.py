@@ -48,12 +48,14 @@ class SamplePlan:
     def __reduce__(self):
         return (_no_plan, ())
 
-    def __init__(self, layers, S: int, cdt: torch.dtype, device: torch.device, index=None, shared=()):
+    def __init__(self, layers, S: int, cdt: torch.dtype, device: torch.device, index=None, shared=(), keep=False):
         """layers: the planned bnn.Linear modules; index[i] = row of layers[i] in the model's [L, S, 2] log-prob
         buffer (layers that take the single-kernel small-M path are left out, so rows may have gaps).
         shared: tuples of layers that read the same activations (query/key/value): when such a tuple is a run of
         consecutive planned layers of one shape its sampled weights are laid out back to back ([L][S][N][K], then
-        [L][S][N] biases) so that ONE bf_gemm_nt_layers launch can multiply them all (self.stacked)."""
+        [L][S][N] biases) so that ONE bf_gemm_nt_layers launch can multiply them all (self.stacked).
+        keep: one arena of its own size per group, no ring: every group stays resident once sampled (the sampled weights
+        kept across the forwards of Model.pinned_samples(keep_weights=True)); the grouping is the same."""
         from .nn.parameters.base import NoneParameter
 
         self.S, self.cdt, self.device = S, cdt, device
@@ -126,7 +128,10 @@ class SamplePlan:
             group_bytes.append(off)
         arena_bytes = max(group_bytes)
         # ring of arenas: group g lives in arena g % R; a launch samples as many consecutive groups as the ring holds
-        self.arenas = [torch.empty(arena_bytes, dtype=torch.uint8, device=device) for _ in range(max(1, min(len(groups), ARENA_BYTES // max(arena_bytes, 1))))]
+        if keep:
+            self.arenas = [torch.empty(b, dtype=torch.uint8, device=device) for b in group_bytes]
+        else:
+            self.arenas = [torch.empty(arena_bytes, dtype=torch.uint8, device=device) for _ in range(max(1, min(len(groups), ARENA_BYTES // max(arena_bytes, 1))))]
         self.arena_owner = [None] * len(self.arenas)
 
         self.pending = set()  # groups sampled in the running forward whose block partials are not reduced yet
@@ -287,3 +292,25 @@ class SamplePlan:
                          "bf_reduce_logprob")
             run = (span[0], span[1], span[4]) if span is not None else None
         self.pending.clear()
+
+
+def kept_weight_bytes(model, S: int, dtype) -> int:
+    """Device bytes Model.pinned_samples(keep_weights=True) keeps for `S` samples at compute dtype `dtype` (torch.float32,
+    torch.bfloat16 or torch.float16): S * sum(N * K) * element size over the model's Bayesian Linear layers, plus S * N fp32 per
+    bias.  (The arenas round each slice up to 256 bytes.)  Needs no GPU."""
+    from .nn.layers.linear import Linear
+    from .nn.parameters.base import NoneParameter
+
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"kept_weight_bytes: dtype {dtype} (float32, bfloat16 or float16)")
+    S = int(S)
+    if S < 1:
+        raise ValueError(f"kept_weight_bytes: S={S} (at least 1)")
+    esz = 4 if dtype == torch.float32 else 2
+    total = 0
+    for l in model.fused_children():
+        if isinstance(l, Linear):
+            total += S * l.out_features * l.in_features * esz
+            if not isinstance(l.bias, NoneParameter):
+                total += S * l.out_features * 4
+    return total

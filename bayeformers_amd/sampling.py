@@ -757,7 +757,8 @@ class Generation:
 def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor] = None, samples: int = 1,
                     max_new_tokens: int = 1, do_sample: bool = False, temperature: float = 1.0,
                     eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
-                    generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None) -> Generation:
+                    generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None,
+                    keep_weights: bool = False, max_bytes: Optional[int] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -768,7 +769,11 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     `mc_predictive` (the bf_predictive kernels); the next token is the argmax of the model-average probabilities or, with
     do_sample, a draw from them (torch.multinomial with `generator`), fed to all S samples.  Rows past eos_token_id emit
     pad_token_id (default: eos_token_id).  No host synchronisation per step except the all-finished check, and none
-    without eos_token_id.  Single process, eval mode and no gradient only."""
+    without eos_token_id.  Single process, eval mode and no gradient only.
+
+    keep_weights / max_bytes go to `model.pinned_samples`: with keep_weights=True the prefill samples every Bayesian Linear's
+    S weight draws once and the decode steps run on them (bf_gemm_nt_skinny) instead of drawing them again per token, at the
+    cost of plan.kept_weight_bytes(model, S, compute dtype) bytes of device memory; the result is the same Generation."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -807,7 +812,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     stats = torch.zeros((4, B, n), dtype=torch.float32, device=dev)
     lengths = torch.zeros(B, dtype=torch.long, device=dev)
     finished = torch.zeros(B, dtype=torch.bool, device=dev)
-    with model.monte_carlo(S), model.pinned_samples():
+    with model.monte_carlo(S), model.pinned_samples(keep_weights=keep_weights, max_bytes=max_bytes):
         out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
         lp = model.log_prob_samples().clone()
         for t in range(n):

@@ -173,6 +173,23 @@ int bf_gemm_nt_layers(const void* d_x, int x_dtype, int64_t x_sample_stride, con
                       const float* d_bias, void* d_y, int y_dtype, int L, int S, int M, int N, int K, int act,
                       void* stream);
 
+/* bf_gemm_nt_act for a few rows per sample on weights already in memory (F.linear, layers/linear.py:104):
+ *   y[s] = act(x[s] w[s]^T + bias[s]),  1 <= M <= bf_gemm_nt_skinny_max_rows() rows per sample, any N, K % 32 == 0,
+ *   S <= 65535.  x, w and y of one 16-bit dtype (BF_DT_BF16 | BF_DT_F16), fp32 accumulation; w [S][N][K] as the sampling
+ *   plan lays it out (a layer's slab of a stacked run included); bias [S][N] fp32 or NULL; x sample stride >= M*K elements;
+ *   x, w, the x sample stride and the workspace 16-byte aligned, y 8-byte aligned.
+ * The decode step of Model.pinned_samples(keep_weights=True): a stream over the weights (bf_gemm_nt_act's tiled kernels leave
+ * most of the chip idle at these shapes).  When the grid of feature blocks x samples is small and K large, K is split over
+ * workgroups and a second launch sums the fp32 partials in a fixed order: bitwise reproducible.  No host synchronisation, no
+ * allocation (capturable): d_workspace holds bf_gemm_nt_skinny_workspace_bytes(S, M, N, K) bytes (NULL when that is 0),
+ * private to the call until it completes on `stream`.  Unsupported arguments return 1 with bf_last_error() set. */
+int bf_gemm_nt_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
+                      const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
+                      size_t workspace_bytes, void* stream);
+size_t bf_gemm_nt_skinny_workspace_bytes(int S, int M, int N, int K);
+/* Rows per sample the skinny kernel takes (64). */
+int bf_gemm_nt_skinny_max_rows(void);
+
 /* Weight-gradient GEMM of the backward pass (autograd of F.linear, layers/linear.py:104), per batch entry b:
  *   out[b][n][k] = sum_m a[b][m][n] * bm[b][m][k]        (dW = dy^T x; a = dy [Mc][N], bm = x [Mc][K])
  * Both operands are read as they lie (contraction-major), products accumulate in fp32, out is fp32 [batch][N][K].

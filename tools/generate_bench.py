@@ -1,0 +1,205 @@
+"""Kept sampled weights for generation: the skinny decode GEMM against what decode runs today, and sample_generate tokens/s.
+
+    python tools/generate_bench.py kernels [--out K.json] [--only N,K,S,M]
+    python tools/generate_bench.py e2e [--out E.json] [--runs 3] [--new-tokens 256]
+    python tools/generate_bench.py trace --mode keep|draw [--steps 32]      (run under rocprofv3 --kernel-trace)
+    python tools/generate_bench.py analyze <kernel_trace.csv> [--steps 32]
+
+kernels: per layer shape of the DESIGN 4.5 decoder (N x K), S and M rows per sample, bf16: bf_gemm_nt_skinny on kept weights,
+fused_small (bf_linear_fwd: sampling + GEMM + log-probs, what a decode step runs without keep_weights) and bf_gemm_nt_act on the
+same kept weights.  Time per call = device events around 200 back-to-back calls after 20 warm-up calls, median of 5 windows
+(launch gaps included).  Weight bandwidth = S*N*K*2 bytes / time, against 6.29 TB/s.
+e2e: sample_generate on the DESIGN 4.5 decoder (8 layers, hidden 1024, 16 / 4 heads, FFN 2816, vocab 32000), S 4, B 4, prompt
+512, bf16, fuse_attention; keep_weights off and on alternated in one process, `runs` each.
+trace: a prefill-only generation, a 2 s pause, then a generation of `new-tokens`; analyze splits a kernel trace of it at the
+pause and attributes (second - first) to the decode steps: GPU time per kernel class and the host gaps between kernels.
+"""
+import argparse
+import csv
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM = 6.29e12
+SHAPES = [(1024, 1024), (256, 1024), (2816, 1024), (1024, 2816), (32000, 1024)]
+
+
+def _time(fn, iters=200, warm=20, reps=5):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3 / iters)
+    return statistics.median(ts)
+
+
+def kernels(only=None):
+    import bayeformers_amd as bf
+    import bayeformers_amd.nn as bnn
+    from bayeformers_amd import ops
+
+    bf.set_compute_dtype("bf16")
+    rows = []
+    configs = [(N, K, S, M) for N, K in SHAPES for S in (4, 10) for M in (1, 4, 16, 64)]
+    if only is not None:
+        configs = [only]
+    for N, K, S, M in configs:
+        torch.manual_seed(0)
+        layer = bnn.Linear(K, N, bias=False).cuda()
+        w = torch.randn(S, N, K, device="cuda", dtype=torch.bfloat16)
+        x = torch.randn(S * M, K, device="cuda", dtype=torch.bfloat16)
+        lp = torch.empty((S, 2), dtype=torch.float64, device="cuda")
+        wbytes = S * N * K * 2
+        t_skinny = _time(lambda: ops.skinny_linear_forward(x, w, None, S, N, K))
+        t_gemm = _time(lambda: ops.gemm_nt(x, w, None, S, M, N, K, M * K, torch.bfloat16))
+        assert M <= ops.fused_small_rows(N, K)
+        t_fused = _time(lambda: ops.linear_forward(layer, x, S, 0x5EED, 0, lp))
+        rows.append({"N": N, "K": K, "S": S, "M": M, "weight_MB": round(wbytes / 1e6, 2), "skinny_us": round(t_skinny, 2),
+                     "fused_small_us": round(t_fused, 2), "gemm_nt_act_us": round(t_gemm, 2),
+                     "skinny_hbm_frac": round(wbytes / (t_skinny * 1e-6) / HBM, 3),
+                     "gemm_nt_act_hbm_frac": round(wbytes / (t_gemm * 1e-6) / HBM, 3)})
+        print(json.dumps(rows[-1]), flush=True)
+        del w, x, layer
+    return rows
+
+
+def _decoder():
+    from transformers import LlamaConfig, LlamaForCausalLM
+
+    import bayeformers_amd as bf
+
+    cfg = LlamaConfig(hidden_size=1024, num_attention_heads=16, num_key_value_heads=4, num_hidden_layers=8,
+                      intermediate_size=2816, vocab_size=32000, max_position_embeddings=1024, tie_word_embeddings=False,
+                      attention_dropout=0.0, attn_implementation="sdpa")
+    torch.manual_seed(0)
+    bmodel = bf.to_bayesian(LlamaForCausalLM(cfg).eval(), delta=0.05, freeze=True).eval().cuda()
+    freqs = {n: b.detach().clone() for n, b in bmodel.named_buffers() if "inv_freq" in n}
+    bmodel = bmodel.to(torch.bfloat16)
+    for n, b in freqs.items():
+        setattr(bmodel.get_submodule(n.rsplit(".", 1)[0]), n.rsplit(".", 1)[1], b)
+    assert bf.fuse_attention(bmodel)
+    bf.set_compute_dtype("bf16")
+    return bmodel
+
+
+def e2e(runs, new_tokens):
+    import bayeformers_amd as bf
+    from bayeformers_amd.sampling import sample_generate
+
+    bmodel = _decoder()
+    ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    res = {"keep_weights": [], "draw_per_step": [], "kept_bytes": bf.kept_weight_bytes(bmodel, 4, torch.bfloat16)}
+    seqs = {}
+    with torch.no_grad():
+        for keep in (False, True):  # warm-up
+            sample_generate(bmodel, ids, samples=4, max_new_tokens=8, keep_weights=keep)
+        for _ in range(runs):
+            for keep in (False, True):
+                bf.manual_seed(0x5EED)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gen = sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                res["keep_weights" if keep else "draw_per_step"].append(round(4 * new_tokens / dt, 1))
+                seqs[keep] = gen.sequences
+                print(json.dumps({"keep_weights": keep, "seconds": round(dt, 3), "tokens_per_s": round(4 * new_tokens / dt, 1)}),
+                      flush=True)
+    res["same_tokens"] = bool(torch.equal(seqs[False], seqs[True]))
+    for k in ("keep_weights", "draw_per_step"):
+        v = res[k]
+        res[k + "_summary"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    return res
+
+
+def trace(mode, new_tokens):
+    from bayeformers_amd.sampling import sample_generate
+
+    bmodel = _decoder()
+    ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    keep = mode == "keep"
+    with torch.no_grad():
+        sample_generate(bmodel, ids, samples=4, max_new_tokens=4, keep_weights=keep)  # warm-up
+        torch.cuda.synchronize()
+        time.sleep(2.0)
+        sample_generate(bmodel, ids, samples=4, max_new_tokens=1, keep_weights=keep)  # prefill only
+        torch.cuda.synchronize()
+        time.sleep(2.0)
+        sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep)
+        torch.cuda.synchronize()
+
+
+def _klass(name):
+    for key, k in (("gemm_skinny", "skinny GEMM (Bayesian layers)"), ("fused_small", "fused_small (Bayesian layers)"),
+                   ("sample", "sampling (Bayesian layers)"), ("reduce_logprob", "sampling (Bayesian layers)"),
+                   ("gemm", "tiled GEMM (Bayesian layers)"), ("attention", "attention"), ("predictive", "predictive statistics")):
+        if key in name:
+            return k
+    return "other kernels"
+
+
+def analyze(path, steps):
+    with open(path) as f:
+        ks = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(f)))
+    # the last two gaps of over 1.5 s between kernels are the pauses: warm-up | prefill | prefill + decode steps
+    a, b = [i for i in range(1, len(ks)) if ks[i][0] - ks[i - 1][1] > 1.5e9][-2:]
+    parts = [ks[a:b], ks[b:]]
+
+    def summary(part):
+        busy, by = 0, {}
+        for s, e, n in part:
+            busy += e - s
+            by[_klass(n)] = by.get(_klass(n), 0) + e - s
+        return part[-1][1] - part[0][0], busy, by
+
+    (w1, b1, by1), (w2, b2, by2) = summary(parts[0]), summary(parts[1])
+    out = {"decode_steps": steps, "step_wall_us": round((w2 - w1) / steps / 1e3, 1),
+           "step_kernel_us": round((b2 - b1) / steps / 1e3, 1)}
+    out["step_host_gap_us"] = round(out["step_wall_us"] - out["step_kernel_us"], 1)
+    out["per_class_us"] = {k: round((by2.get(k, 0) - by1.get(k, 0)) / steps / 1e3, 1) for k in sorted(set(by1) | set(by2))}
+    out["kernels_per_step"] = round((len(parts[1]) - len(parts[0])) / steps, 1)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("what", choices=["kernels", "e2e", "trace", "analyze"])
+    ap.add_argument("path", nargs="?")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--new-tokens", type=int, default=256)
+    ap.add_argument("--mode", choices=["keep", "draw"], default="keep")
+    ap.add_argument("--steps", type=int, default=32)
+    a = ap.parse_args()
+    if a.what == "analyze":
+        res = analyze(a.path, a.steps)
+    else:
+        assert torch.cuda.is_available(), "this benchmark measures the GPU"
+        if a.what == "kernels":
+            res = kernels(tuple(int(v) for v in a.only.split(",")) if a.only else None)
+        elif a.what == "e2e":
+            res = e2e(a.runs, a.new_tokens)
+        else:
+            trace(a.mode, a.steps + 1)
+            return
+    print(json.dumps(res, indent=1))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
