@@ -386,12 +386,25 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
 def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):
     """The causal half of _attention_interface: bf_attention_fwd_gqa (bf_attention_bwd_gqa behind it) for equal query and
     key lengths with no mask or _padding_mask_interface's causal mask; a decode step against a KV cache (fewer than 17
-    new queries, no gradient, no dropout) on bf_attention_decode_gqa; other masks, longer cached chunks and attention
+    new queries, no gradient, no dropout) on bf_attention_decode_gqa, or on bf_attention_decode_gqa_len when the cache has
+    a fixed capacity (the mask carries the filled length `_bf_kv_len`); other masks, longer cached chunks and attention
     dropout go to the framework's scaled-dot-product attention."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
 
+    kv_len = getattr(attention_mask, "_bf_kv_len", None) if attention_mask is not None else None
+    if kv_len is not None:  # a step against a fixed-capacity cache: _padding_mask_interface's mask carries the fill
+        key_mask = getattr(attention_mask, "_bf_key_mask", None)
+        if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
+                and ops.attention_decode_supported(query, key, value)
+                and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3])
+                and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2]))):
+            scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+            return ops.attention_forward_decode_len(query, key, value, kv_len, key_mask, scale,
+                                                    getattr(attention_mask, "_bf_mask_off", None)), None
+        # (the bool mask hides the keys past the fill: the framework's attention over the whole capacity is exact)
+        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
             and ops.attention_decode_supported(query, key, value)
             and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3])):
@@ -431,8 +444,35 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     A decoder's causal mask for a step against a KV cache (q_offset = kv_length - q_length, a 2-D padding mask or none)
     is built on the device too: the [B, 1, Tq, Tk] bool mask the framework's attention takes, carrying the key mask and
     the causal marker `_bf_decode` for bf_attention_decode_gqa (None for one query and no padding mask, as the framework answers).
+    A step against a fixed-capacity cache (q_offset a device tensor: the fill of a transformers StaticCache, kv_length its
+    capacity) gets the [B, 1, Tq, capacity] bool mask built on the device (causal from q_offset, the keys past the fill
+    hidden) with the key mask and a snapshot of the fill after this step, `_bf_kv_len`, for bf_attention_decode_gqa_len.
     Anything else (4-D masks, extra mask functions, other offsets) goes to the framework's scaled-dot-product mask."""
     from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
+
+    if (mask_function is causal_mask_function and isinstance(q_offset, torch.Tensor) and kv_offset == 0
+            and q_length is not None and kv_length is not None and 0 < q_length <= kv_length
+            and not kwargs.get("use_vmap", False)
+            and (attention_mask is None or (attention_mask.dim() == 2 and attention_mask.shape == (batch_size, kv_length)))):
+        # a fixed-capacity cache (transformers' StaticLayer: q_offset is its fill count, a device tensor, and kv_length its
+        # capacity).  Tested before the comparisons below: on a tensor they synchronise with the host (or fail a capture).
+        # Query i sees keys 0 .. q_offset + i, which hides the keys past the fill; the snapshot kv_len is the fill after
+        # this forward's update (the cache bumps its counter in place during the forward)
+        device = q_offset.device
+        kv_len = (q_offset.reshape(()) + q_length).reshape(1)
+        keys = torch.arange(kv_length, device=device)
+        tri = keys[None, :] <= (q_offset.reshape(()) + torch.arange(q_length, device=device))[:, None]
+        if attention_mask is None:
+            out = tri[None, None, :, :].expand(batch_size, 1, q_length, kv_length)
+            out._bf_key_mask = out._bf_mask_off = None
+        else:
+            visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
+            out = tri[None, None, :, :] & visible[:, None, None, :]
+            out._bf_key_mask = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
+            out._bf_mask_off = visible.all().reshape(1)
+        out._bf_decode = True
+        out._bf_kv_len = kv_len
+        return out
 
     if (mask_function is causal_mask_function and kv_offset == 0 and q_length is not None and kv_length is not None
             and 0 < q_length < kv_length and q_offset == kv_length - q_length and not kwargs.get("use_vmap", False)

@@ -506,6 +506,24 @@ int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
     return bf_launch_attention_decode_workspace_bytes(shape);
 }
 
+int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                int dtype, const bf_attn_decode_t* shape, float scaling, void* stream) {
+    return bf_launch_attention_decode_gqa_len(d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape,
+                                              scaling, (hipStream_t)stream);
+}
+
+int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
+                     const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
+                     int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
+                     uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
+                     int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed, void* stream) {
+    return bf_launch_generate_step(d_probs, d_predictive_entropy, d_expected_entropy, d_mutual_information, B, V, S,
+                                   d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished, d_lengths,
+                                   d_next_ids, d_positions, eos_token_id, pad_token_id, do_sample, d_seed,
+                                   (hipStream_t)stream);
+}
+
 static bf_dropout_t make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,
                                  const uint32_t* d_call = nullptr) {
     bf_dropout_t d;

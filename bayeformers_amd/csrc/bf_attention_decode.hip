@@ -15,6 +15,11 @@
 // Fragment layouts, LDS images and the online softmax are those of bf_attention_gqa.hip's forward: S^T = K Q^T, then
 // O^T = V^T P^T with P^T straight from the accumulators.  The next key tile is fetched into registers while the current
 // one is computed.  A query with no visible key returns 0.
+//
+// bf_attention_decode_gqa_len runs the same kernels over a fixed-capacity cache (a static cache that one captured graph
+// serves at every step): Tk is the capacity, the filled length L comes from a device scalar.  The grid and the workspace
+// follow the capacity; the split boundaries follow the keys-per-split rule applied to L, computed in the kernel (splits
+// past L write an empty partial the merge skips), so at L == Tk the launch is bitwise bf_attention_decode_gqa's.
 #include "bf_attention_tiles.h"
 
 #include <algorithm>
@@ -36,7 +41,9 @@ struct DecodeParams {
     float* part_o;                  // [nsplit][N * Hkv][R][D] unnormalised partial outputs (nsplit > 1)
     float* part_ml;                 // [nsplit][N * Hkv][R][2] their running max (log2 units) and sum
     long long qs[3], ks[3], vs[3];  // (batch, head, token) element strides
+    const int64_t* kv_len;          // nullable device scalar: the filled keys L (Tk is then the capacity)
     int N, Tq, Tk, H, Hkv, group, R, nsplit, split_keys;
+    long long want;                 // the split count the grid asks for (decode_split), the kernel's rule for L
     float scale_log2e;
 };
 
@@ -44,14 +51,23 @@ struct Split {
     int n, keys;  // splits, keys per split (a multiple of KT; the last split ends at Tk)
 };
 
-Split decode_split(const bf_attn_decode_t* s) {
+long long split_want(const bf_attn_decode_t* s) {
     const int R = s->H / s->Hkv * s->Tq;
     const long long base = (long long)s->N * s->Hkv * ((R + ROWS - 1) / ROWS);
+    return std::max(1LL, (TARGET_WGS + base - 1) / base);
+}
+
+// key tiles per split for `keys` keys when the grid asks for `want` splits (at least two tiles a split)
+__host__ __device__ inline int split_tiles(int keys, long long want) {
+    const int tiles = (keys + KT - 1) / KT;
+    const int most = (keys + MIN_SPLIT_KEYS - 1) / MIN_SPLIT_KEYS;
+    const int n0 = (int)(want < most ? want : (most > 1 ? most : 1));
+    return (tiles + n0 - 1) / n0;
+}
+
+Split decode_split(const bf_attn_decode_t* s) {
     const int tiles = (s->Tk + KT - 1) / KT;
-    const long long want = std::max(1LL, (TARGET_WGS + base - 1) / base);
-    const int most = std::max(1, (s->Tk + MIN_SPLIT_KEYS - 1) / MIN_SPLIT_KEYS);
-    const int n0 = (int)std::min<long long>(want, most);
-    const int per = (tiles + n0 - 1) / n0;
+    const int per = split_tiles(s->Tk, split_want(s));
     return Split{(tiles + per - 1) / per, per * KT};
 }
 
@@ -71,11 +87,18 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int split = blockIdx.x, nk = blockIdx.y, n = nk / p.Hkv, g = nk % p.Hkv;
-    const int k_lo = split * p.split_keys, k_hi = min(p.Tk, k_lo + p.split_keys);
+    int L = p.Tk, split_keys = p.split_keys;
+    if (p.kv_len) {  // a fixed-capacity cache filled to L: L's own split rule, within the grid's nsplit splits
+        const int64_t len = *p.kv_len;
+        L = len < 0 ? 0 : (len > p.Tk ? p.Tk : (int)len);
+        const int tiles = (L + KT - 1) / KT;
+        split_keys = max(max(split_tiles(L, p.want), (tiles + p.nsplit - 1) / p.nsplit), 1) * KT;
+    }
+    const int k_lo = split * split_keys, k_hi = min(L, k_lo + split_keys);
     const int r = blockIdx.z * ROWS + wid * 16 + li;  // this lane's query row (its column of S^T and O^T)
     const bool wave_live = (int)blockIdx.z * ROWS + wid * 16 < p.R, row_ok = r < p.R;
     const int qi = row_ok ? r % p.Tq : 0, h = g * p.group + (row_ok ? r / p.Tq : 0);
-    const int lim = p.Tk - p.Tq + qi;  // the last key query qi sees
+    const int lim = L - p.Tq + qi;  // the last key query qi sees
     const T* kb = reinterpret_cast<const T*>(p.k) + n * p.ks[0] + g * p.ks[1];
     const T* vb = reinterpret_cast<const T*>(p.v) + n * p.vs[0] + g * p.vs[1];
 
@@ -258,10 +281,11 @@ int64_t bf_launch_attention_decode_workspace_bytes(const bf_attn_decode_t* shape
     return workspace_bytes(shape);
 }
 
-int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                   const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
-                                   const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
-    const char* what = "bf_attention_decode_gqa";
+namespace {
+
+int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+           const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
+           const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
     if (check_shape(what, shape, dtype)) return 1;
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
     if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_workspace) & 15)
@@ -286,6 +310,8 @@ int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void*
     p.R = p.group * shape->Tq;
     p.nsplit = sp.n;
     p.split_keys = sp.keys;
+    p.kv_len = d_kv_len;
+    p.want = split_want(shape);
     if (sp.n > 1) {
         p.part_o = reinterpret_cast<float*>(d_workspace);
         p.part_ml = p.part_o + (long long)sp.n * p.N * p.Hkv * p.R * shape->head_dim;
@@ -305,4 +331,22 @@ int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void*
     }
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                   const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                   const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
+    return decode("bf_attention_decode_gqa", d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape,
+                  scaling, stream);
+}
+
+int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
+                                       void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
+                                       hipStream_t stream) {
+    const char* what = "bf_attention_decode_gqa_len";
+    if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, scaling, stream);
 }

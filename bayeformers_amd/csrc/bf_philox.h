@@ -96,6 +96,15 @@ static inline void bf_normal4_host(uint64_t group, uint32_t sample, uint32_t str
 // step's Monte-Carlo samples: a kernel that sees the slabs of samples [s0, s0 + S_local) numbers its groups from
 // first_group = s0 * (groups per sample) — masks are a function of the global sample, like epsilon.
 #define BF_DROPOUT_STREAM 0x80000000u
+
+// ---- generation contract --------------------------------------------------------------------------------------------
+// A sampled token of sample_generate's static-cache path (bf_generate_step) is an inverse-CDF draw of ONE uniform per
+// (prompt row, step):
+//   (x0..x3) = Philox4x32-7(counter = {lo32(row), step, BF_GENERATE_STREAM, hi32(row)}, key = {lo32(seed), hi32(seed)})
+//   u = bf_u32_to_unit(x0)  in (0, 1]
+// The stream (bit 30 set, bit 31 clear) collides neither with the weight streams 2 * layer_id + {0, 1} nor with the
+// dropout streams.  `seed` is the generation's own 64-bit seed (drawn once per call), not the weight seed.
+#define BF_GENERATE_STREAM 0x40000000u
 BF_HD uint32_t bf_dropout_thresh(float p) {
     const float t = p * 65536.0f + 0.5f;
     return t <= 0.f ? 0u : (t >= 65535.f ? 65535u : (uint32_t)t);

@@ -851,8 +851,9 @@ def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[T
     return dq, dkv[0], dkv[1]
 
 
-# launches of bf_attention_decode_gqa from this process (a test can assert that a cached decode step ran on the kernel)
-DECODE_CALLS = {"fwd": 0}
+# launches of bf_attention_decode_gqa from this process (a test can assert that a cached decode step ran on the kernel);
+# "len": of bf_attention_decode_gqa_len (a step against a fixed-capacity cache, attention_forward_decode_len)
+DECODE_CALLS = {"fwd": 0, "len": 0}
 DECODE_MAX_QUERIES = 16
 
 
@@ -938,6 +939,103 @@ def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional
                                               ctypes.byref(shape), float(scaling), _stream_ptr()), "bf_attention_decode_gqa")
     DECODE_CALLS["fwd"] += 1
     return out
+
+
+def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
+                                 scaling: float, mask_off: Optional[Tensor] = None,
+                                 workspace: Optional[Tensor] = None) -> Tensor:
+    """attention_forward_decode over a fixed-capacity cache (bf_attention_decode_gqa_len): k / v [N, Hkv, capacity, D] of
+    which the first L = kv_len keys are filled, kv_len a one-element int64 device tensor read by the kernel (keys past it
+    are never read).  Query i sees keys 0 .. L - Tq + i; key_mask is [N, capacity].  One launch serves every L, so a
+    captured call replays correctly while the cache fills; at L == capacity it is bitwise attention_forward_decode."""
+    _require_device(q, "attention_forward_decode_len: q")
+    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
+            or k.shape[3] != q.shape[3]:
+        raise _C.BayeFormersAMDError(f"attention_forward_decode_len: q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                                     f"v {tuple(v.shape)} are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
+    if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
+            or v.device != q.device:
+        raise _C.BayeFormersAMDError("attention_forward_decode_len: q, k and v must share one dtype and one device")
+    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
+        raise _C.BayeFormersAMDError("attention_forward_decode_len: the feature dimension of q, k and v must be contiguous")
+    if kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device:
+        raise _C.BayeFormersAMDError("attention_forward_decode_len: kv_len must be one int64 on the device of q")
+    N, H, Tq, D = q.shape
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
+    shape = _decode_shape(q, k, v)
+    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
+    if nbytes < 0:
+        _C.check(1, "bf_attention_decode_workspace_bytes")
+    ws = None
+    if nbytes:
+        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+            raise _C.BayeFormersAMDError(f"attention_forward_decode_len: the workspace needs {nbytes} device bytes")
+    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
+                                 or not key_mask.is_contiguous()):
+        raise _C.BayeFormersAMDError("attention_forward_decode_len: key_mask must be contiguous fp32 [N, Tk]")
+    _C.check(_C.lib().bf_attention_decode_gqa_len(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                                  key_mask.data_ptr() if key_mask is not None else None,
+                                                  mask_off.data_ptr() if mask_off is not None else None,
+                                                  kv_len.data_ptr(), out.data_ptr(),
+                                                  ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype],
+                                                  ctypes.byref(shape), float(scaling), _stream_ptr()),
+             "bf_attention_decode_gqa_len")
+    DECODE_CALLS["len"] += 1
+    return out
+
+
+GENERATE_CALLS = [0]  # launches of bf_generate_step through generate_step (tests, diagnostics)
+
+
+def generate_step(probs: Tensor, predictive_entropy: Tensor, expected_entropy: Tensor, mutual_information: Tensor,
+                  samples: int, state: Tensor, sequences: Tensor, T0: int, stats: Tensor, finished: Optional[Tensor],
+                  lengths: Tensor, next_ids: Tensor, positions: Optional[Tensor], eos_token_id: Optional[int],
+                  pad_token_id: int, seed: Optional[Tensor] = None) -> None:
+    """One generation step's epilogue in one launch (bf_generate_step), at the step state[0]: the token of each of the B
+    rows of probs [B, V] (fp32: the lowest-index argmax, or with `seed` — a one-element int64 device tensor — an
+    inverse-CDF draw of a Philox uniform), written into sequences [B, T0 + n] at T0 + step, the four statistics
+    (predictive_entropy, expected_entropy, mutual_information [B], the token's probability) into stats [4, B, n] at step
+    (zero for rows finished before it), finished [B] bool and lengths [B] int64 updated as sample_generate's loop does
+    with eos_token_id (None: every row counts the token), the token into next_ids [samples * B] (sample-major) and
+    positions [samples * B] (or None) advanced by one; state [2] int64 {step, 0} advances by one.  No host
+    synchronisation: capturable."""
+    _require_device(probs, "generate_step: probs")
+    if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise _C.BayeFormersAMDError("generate_step: probs must be contiguous fp32 [B, V]")
+    B, V = probs.shape
+    n = stats.shape[-1] if stats.dim() == 3 else 0
+    dev = probs.device
+
+    def need(t, what, dtype, shape):
+        if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise _C.BayeFormersAMDError(f"generate_step: {what} must be contiguous {dtype} {list(shape)} on {dev}")
+
+    for t, what in ((predictive_entropy, "predictive_entropy"), (expected_entropy, "expected_entropy"),
+                    (mutual_information, "mutual_information")):
+        need(t, what, torch.float32, (B,))
+    need(stats, "stats", torch.float32, (4, B, n))
+    need(state, "state", torch.int64, (2,))
+    need(lengths, "lengths", torch.int64, (B,))
+    need(next_ids, "next_ids", torch.int64, (int(samples) * B,))
+    if positions is not None:
+        need(positions, "positions", torch.int64, (int(samples) * B,))
+    if sequences.dim() != 2 or sequences.shape[0] != B or sequences.stride(1) != 1 or sequences.dtype != torch.int64 \
+            or sequences.device != dev:
+        raise _C.BayeFormersAMDError("generate_step: sequences must be int64 [B, T0 + n] with contiguous rows")
+    if eos_token_id is not None:
+        need(finished, "finished", torch.bool, (B,))
+    if seed is not None:
+        need(seed, "seed", torch.int64, (1,))
+    _C.check(_C.lib().bf_generate_step(probs.data_ptr(), predictive_entropy.data_ptr(), expected_entropy.data_ptr(),
+                                       mutual_information.data_ptr(), B, V, int(samples), state.data_ptr(), n,
+                                       sequences.data_ptr(), sequences.stride(0), int(T0), stats.data_ptr(),
+                                       finished.data_ptr() if finished is not None else None, lengths.data_ptr(),
+                                       next_ids.data_ptr(), positions.data_ptr() if positions is not None else None,
+                                       int(eos_token_id) if eos_token_id is not None else -1, int(pad_token_id),
+                                       1 if seed is not None else 0, seed.data_ptr() if seed is not None else None,
+                                       _stream_ptr()), "bf_generate_step")
+    GENERATE_CALLS[0] += 1
 
 
 class AttentionGqaFn(torch.autograd.Function):

@@ -758,7 +758,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     max_new_tokens: int = 1, do_sample: bool = False, temperature: float = 1.0,
                     eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None,
-                    keep_weights: bool = False, max_bytes: Optional[int] = None) -> Generation:
+                    keep_weights: bool = False, max_bytes: Optional[int] = None, static_cache: bool = False,
+                    graph: bool = False) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -773,7 +774,18 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
 
     keep_weights / max_bytes go to `model.pinned_samples`: with keep_weights=True the prefill samples every Bayesian Linear's
     S weight draws once and the decode steps run on them (bf_gemm_nt_skinny) instead of drawing them again per token, at the
-    cost of plan.kept_weight_bytes(model, S, compute dtype) bytes of device memory; the result is the same Generation."""
+    cost of plan.kept_weight_bytes(model, S, compute dtype) bytes of device memory; the result is the same Generation.
+
+    static_cache=True decodes on a transformers StaticCache of capacity T0 + max_new_tokens - 1, filled from the (unchanged)
+    prefill: every step has the same shapes, the attention runs on bf_attention_decode_gqa_len (the fill is a device
+    scalar), the mask is preallocated and the positions and ids are updated in place, and the per-step bookkeeping is one
+    bf_generate_step launch.  do_sample then draws by an inverse CDF from a Philox uniform per (row, step) keyed by a seed
+    drawn once per call from `generator` (or torch's default generator): the same generator state gives the same text,
+    but not the text of the default path's torch.multinomial.  graph=True (implies static_cache) runs one decode step
+    eagerly, captures the next one in a HIP graph and replays it for the rest; the Generation is bitwise the one
+    static_cache=True returns.  With eos_token_id the all-finished check runs every 8 replays (rows past EOS emit pad with
+    zero statistics either way).  Both need a model routed by fuse_attention, a single process and no sliding-window
+    layers."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -781,6 +793,9 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         raise ValueError(f"sample_generate: max_new_tokens={max_new_tokens} (at least 1)")
     if not temperature > 0.0:
         raise ValueError(f"sample_generate: temperature={temperature} (must be positive)")
+    static_cache = bool(static_cache) or bool(graph)
+    if static_cache and group is not None:
+        raise ValueError("sample_generate: static_cache / graph generation runs in a single process (group must be None)")
     if group is not None:
         raise NotImplementedError("sample_generate: S-sharded generation is not supported (single process)")
     if not isinstance(model, Model):
@@ -797,6 +812,9 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
 
     if pad_token_id is None:
         pad_token_id = eos_token_id if eos_token_id is not None else 0
+    if static_cache:
+        return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
+                                eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph))
     S, n = samples, max_new_tokens
     B, T0 = input_ids.shape
     dev = input_ids.device
@@ -842,4 +860,110 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                 mask = torch.cat([mask, mask.new_ones((S * B, 1))], 1)
                 pos = pos[:, -1:] + 1
             out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
+    return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])
+
+
+_FINISHED_EVERY = 8  # graph replays between two all-finished checks (host synchronisations) of sample_generate(graph=True)
+
+
+def _static_cache(model: Model, capacity: int):
+    """A transformers StaticCache of `capacity` tokens for the wrapped decoder, or the reason it cannot serve."""
+    from transformers import StaticCache
+    from transformers.cache_utils import StaticLayer
+
+    from . import _ATTENTION_NAME
+
+    inner = model.model if model.model is not None else model
+    config = getattr(inner, "config", None)
+    if config is None or getattr(config, "_attn_implementation", None) != _ATTENTION_NAME:
+        raise RuntimeError("sample_generate: static_cache / graph need the model's attention routed through the HIP kernels "
+                           "— call bayeformers_amd.fuse_attention(model) first")
+    cache = StaticCache(config=config, max_cache_len=int(capacity))
+    if any(type(layer) is not StaticLayer or getattr(layer, "is_sliding", False) for layer in cache.layers):
+        raise ValueError("sample_generate: static_cache / graph take full-attention decoders only (this config has "
+                         "sliding-window or other non-static cache layers)")
+    return cache
+
+
+def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, do_sample: bool,
+                     temperature: float, eos_token_id: Optional[int], pad_token_id: int,
+                     generator: Optional[torch.Generator], keep_weights: bool, max_bytes: Optional[int],
+                     graph: bool) -> Generation:
+    """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
+    static one), then decode steps of one shape whose bookkeeping is bf_generate_step."""
+    from transformers import DynamicCache
+
+    from . import ops
+
+    B, T0 = input_ids.shape
+    dev = input_ids.device
+    static = _static_cache(model, T0 + n - 1)
+    inner = model.model if model.model is not None else model
+    seed = None
+    if do_sample:  # the generation's own Philox key: one draw from the caller's generator per call
+        gdev = generator.device if generator is not None else torch.device("cpu")
+        seed = torch.randint(0, 2 ** 63 - 1, (1,), generator=generator, device=gdev, dtype=torch.int64).to(dev)
+    ids = input_ids.repeat(S, 1)
+    mask = attention_mask.to(torch.long).repeat(S, 1) if attention_mask is not None else None
+    pos = (mask.cumsum(-1) - 1).clamp(min=0) if mask is not None else None
+
+    sequences = torch.full((B, T0 + n), int(pad_token_id), dtype=torch.long, device=dev)
+    sequences[:, :T0] = input_ids
+    stats = torch.zeros((4, B, n), dtype=torch.float32, device=dev)
+    lengths = torch.zeros(B, dtype=torch.long, device=dev)
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    state = torch.zeros(2, dtype=torch.long, device=dev)  # {step, the epilogue's arrival count}
+    # the step's inputs, written in place: the ids by the epilogue, the positions advanced by it; the mask covers the whole
+    # capacity at once (keys past the fill are hidden by the causal mask built from the cache's fill)
+    next_ids = torch.empty((S * B, 1), dtype=torch.long, device=dev)
+    if mask is not None:
+        positions = pos[:, -1:].clone()
+        full_mask = torch.cat([mask, mask.new_ones((S * B, n - 1))], 1)
+    else:
+        positions = torch.full((S * B, 1), T0 - 1, dtype=torch.long, device=dev)
+        full_mask = None
+
+    def epilogue(out):
+        logits = out.logits[:, -1, :].reshape(S, B, -1)
+        if temperature != 1.0:
+            logits = logits.float() / temperature
+        pred = mc_predictive(logits)
+        ops.generate_step(pred.probs, pred.predictive_entropy, pred.expected_entropy, pred.mutual_information, S, state,
+                          sequences, T0, stats, finished, lengths, next_ids.view(-1), positions.view(-1), eos_token_id,
+                          pad_token_id, seed)
+
+    def decode():
+        epilogue(model(input_ids=next_ids, attention_mask=full_mask, position_ids=positions, past_key_values=static,
+                       use_cache=True))
+
+    def all_finished():
+        return eos_token_id is not None and bool(finished.all())
+
+    with model.monte_carlo(S), model.pinned_samples(keep_weights=keep_weights, max_bytes=max_bytes):
+        dynamic = DynamicCache(config=getattr(inner, "config", None))
+        out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=dynamic, use_cache=True)
+        lp = model.log_prob_samples().clone()
+        for i, layer in enumerate(dynamic.layers):  # the prompt's keys and values fill the static cache's first T0 slots
+            static.update(layer.keys, layer.values, i)
+        del dynamic
+        epilogue(out)
+        del out
+        t = 1
+        if n > 1 and not all_finished():
+            decode()  # eagerly: plans, workspaces and the kept weights' launches are set up outside any capture
+            t = 2
+        if graph and t < n and not all_finished():
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                decode()
+            replays = 0
+            while t < n:
+                g.replay()
+                t, replays = t + 1, replays + 1
+                if replays % _FINISHED_EVERY == 0 and all_finished():
+                    break
+            del g
+        while t < n and not all_finished():
+            decode()
+            t += 1
     return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])

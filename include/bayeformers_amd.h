@@ -437,6 +437,30 @@ int bf_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, c
 /* Workspace bytes bf_attention_decode_gqa needs for `shape` (0: none); -1 with bf_last_error() set for an unsupported
  * shape. */
 int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape);
+/* bf_attention_decode_gqa over a fixed-capacity cache (a static KV cache, one captured launch for every step): shape->Tk
+ * is the CAPACITY and *d_kv_len (a device int64, 8-byte aligned) the filled length L, read by the kernel.  Keys j >= L are
+ * never read (they may hold anything); query i sees keys 0 .. L - Tq + i; d_mask stays [N][capacity].  The grid and the
+ * workspace (bf_attention_decode_workspace_bytes(shape)) depend on the shape only; the key split follows L.  At L == Tk
+ * the output is bitwise bf_attention_decode_gqa's; it is a function of (shape, L) only. */
+int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                int dtype, const bf_attn_decode_t* shape, float scaling, void* stream);
+
+/* ---- one generation step's epilogue -------------------------------------------------------------------------------
+ * What sample_generate does between the predictive statistics of a step and the next decode forward, in one launch (one
+ * workgroup per prompt row; no host synchronisation, capturable).  d_state: int64[2] {step, 0} — the step counter t
+ * (advanced by one per launch) and the launch's arrival count (left at 0).  Reads the model-average probabilities
+ * d_probs [B][V] and the three entropies [B] (bf_mc_predictive_finish); the token of row b is the lowest-index argmax
+ * (do_sample = 0), or with do_sample the inverse-CDF draw of one Philox uniform (BF_GENERATE_STREAM, bf_philox.h) keyed by
+ * *d_seed.  With eos_token_id >= 0 a row already finished emits pad_token_id and zero statistics and d_finished / d_lengths
+ * follow it; without, every row counts the token.  Writes d_sequences[b * seq_stride + T0 + t], d_stats [4][B][max_new_tokens]
+ * (predictive entropy, expected entropy, mutual information, the token's probability) at t, the token into d_next_ids
+ * [S * B] (sample-major) and adds 1 to d_positions [S * B] (nullable).  A launch at t >= max_new_tokens writes nothing. */
+int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
+                     const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
+                     int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
+                     uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
+                     int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed, void* stream);
 
 /* ---- training mode: HuggingFace dropout inside the fused kernels ------------------------------------------------------
  * The reference trains with the wrapped model in .train() (/root/reference/examples/bert_glue.py:221,227-241): HF's

@@ -1,8 +1,8 @@
 """Kept sampled weights for generation: the skinny decode GEMM against what decode runs today, and sample_generate tokens/s.
 
     python tools/generate_bench.py kernels [--out K.json] [--only N,K,S,M]
-    python tools/generate_bench.py e2e [--out E.json] [--runs 3] [--new-tokens 256]
-    python tools/generate_bench.py trace --mode keep|draw [--steps 32]      (run under rocprofv3 --kernel-trace)
+    python tools/generate_bench.py e2e [--out E.json] [--runs 3] [--new-tokens 256] [--mode dynamic|static|graph ...]
+    python tools/generate_bench.py trace --mode keep|draw [--mode dynamic|static|graph] [--steps 32]   (under rocprofv3 --kernel-trace)
     python tools/generate_bench.py analyze <kernel_trace.csv> [--steps 32]
 
 kernels: per layer shape of the DESIGN 4.5 decoder (N x K), S and M rows per sample, bf16: bf_gemm_nt_skinny on kept weights,
@@ -10,7 +10,9 @@ fused_small (bf_linear_fwd: sampling + GEMM + log-probs, what a decode step runs
 same kept weights.  Time per call = device events around 200 back-to-back calls after 20 warm-up calls, median of 5 windows
 (launch gaps included).  Weight bandwidth = S*N*K*2 bytes / time, against 6.29 TB/s.
 e2e: sample_generate on the DESIGN 4.5 decoder (8 layers, hidden 1024, 16 / 4 heads, FFN 2816, vocab 32000), S 4, B 4, prompt
-512, bf16, fuse_attention; keep_weights off and on alternated in one process, `runs` each.
+512, bf16, fuse_attention; keep_weights off and on alternated in one process, `runs` each, and for each of them the decode
+paths named by --mode (default all three, alternated): dynamic (the default DynamicCache loop), static
+(static_cache=True) and graph (graph=True).
 trace: a prefill-only generation, a 2 s pause, then a generation of `new-tokens`; analyze splits a kernel trace of it at the
 pause and attributes (second - first) to the decode steps: GPU time per kernel class and the host gaps between kernels.
 """
@@ -94,50 +96,59 @@ def _decoder():
     return bmodel
 
 
-def e2e(runs, new_tokens):
+PATHS = {"dynamic": {}, "static": {"static_cache": True}, "graph": {"graph": True}}
+
+
+def e2e(runs, new_tokens, paths=("dynamic", "static", "graph")):
     import bayeformers_amd as bf
     from bayeformers_amd.sampling import sample_generate
 
     bmodel = _decoder()
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    res = {"keep_weights": [], "draw_per_step": [], "kept_bytes": bf.kept_weight_bytes(bmodel, 4, torch.bfloat16)}
+    name = lambda keep, path: ("keep_weights" if keep else "draw_per_step") + ("" if path == "dynamic" else "_" + path)
+    res = {name(k, p): [] for k in (False, True) for p in paths}
+    res["kept_bytes"] = bf.kept_weight_bytes(bmodel, 4, torch.bfloat16)
     seqs = {}
     with torch.no_grad():
         for keep in (False, True):  # warm-up
-            sample_generate(bmodel, ids, samples=4, max_new_tokens=8, keep_weights=keep)
+            for path in paths:
+                sample_generate(bmodel, ids, samples=4, max_new_tokens=8, keep_weights=keep, **PATHS[path])
         for _ in range(runs):
             for keep in (False, True):
-                bf.manual_seed(0x5EED)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                gen = sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep)
-                torch.cuda.synchronize()
-                dt = time.perf_counter() - t0
-                res["keep_weights" if keep else "draw_per_step"].append(round(4 * new_tokens / dt, 1))
-                seqs[keep] = gen.sequences
-                print(json.dumps({"keep_weights": keep, "seconds": round(dt, 3), "tokens_per_s": round(4 * new_tokens / dt, 1)}),
-                      flush=True)
-    res["same_tokens"] = bool(torch.equal(seqs[False], seqs[True]))
-    for k in ("keep_weights", "draw_per_step"):
+                for path in paths:
+                    bf.manual_seed(0x5EED)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    gen = sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep,
+                                          **PATHS[path])
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    res[name(keep, path)].append(round(4 * new_tokens / dt, 1))
+                    seqs[keep, path] = gen.sequences
+                    print(json.dumps({"keep_weights": keep, "path": path, "seconds": round(dt, 3),
+                                      "tokens_per_s": round(4 * new_tokens / dt, 1)}), flush=True)
+    first = next(iter(seqs.values()))
+    res["same_tokens"] = all(bool(torch.equal(first, v)) for v in seqs.values())
+    for k in [k for k in res if isinstance(res[k], list)]:
         v = res[k]
         res[k + "_summary"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
     return res
 
 
-def trace(mode, new_tokens):
+def trace(mode, new_tokens, path="dynamic"):
     from bayeformers_amd.sampling import sample_generate
 
     bmodel = _decoder()
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    keep = mode == "keep"
+    kw = dict(keep_weights=mode == "keep", **PATHS[path])
     with torch.no_grad():
-        sample_generate(bmodel, ids, samples=4, max_new_tokens=4, keep_weights=keep)  # warm-up
+        sample_generate(bmodel, ids, samples=4, max_new_tokens=4, **kw)  # warm-up
         torch.cuda.synchronize()
         time.sleep(2.0)
-        sample_generate(bmodel, ids, samples=4, max_new_tokens=1, keep_weights=keep)  # prefill only
+        sample_generate(bmodel, ids, samples=4, max_new_tokens=1, **kw)  # prefill only
         torch.cuda.synchronize()
         time.sleep(2.0)
-        sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep)
+        sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, **kw)
         torch.cuda.synchronize()
 
 
@@ -181,7 +192,8 @@ def main():
     ap.add_argument("--only", default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--new-tokens", type=int, default=256)
-    ap.add_argument("--mode", choices=["keep", "draw"], default="keep")
+    # keep | draw: the weights (trace); dynamic | static | graph: the decode path (e2e: the ones to alternate; trace: one)
+    ap.add_argument("--mode", choices=["keep", "draw", "dynamic", "static", "graph"], action="append", default=None)
     ap.add_argument("--steps", type=int, default=32)
     a = ap.parse_args()
     if a.what == "analyze":
@@ -190,10 +202,12 @@ def main():
         assert torch.cuda.is_available(), "this benchmark measures the GPU"
         if a.what == "kernels":
             res = kernels(tuple(int(v) for v in a.only.split(",")) if a.only else None)
-        elif a.what == "e2e":
-            res = e2e(a.runs, a.new_tokens)
+        modes = a.mode or []
+        paths = [m for m in modes if m in PATHS] or None
+        if a.what == "e2e":
+            res = e2e(a.runs, a.new_tokens, *([paths] if paths else []))
         else:
-            trace(a.mode, a.steps + 1)
+            trace("draw" if "draw" in modes else "keep", a.steps + 1, (paths or ["dynamic"])[-1])
             return
     print(json.dumps(res, indent=1))
     if a.out:
