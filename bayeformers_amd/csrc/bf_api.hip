@@ -524,6 +524,11 @@ int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, co
                                    (hipStream_t)stream);
 }
 
+int bf_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
+                      float min_p, void* stream) {
+    return bf_launch_probs_truncate(d_probs, d_out, R, V, top_k, top_p, min_p, (hipStream_t)stream);
+}
+
 static bf_dropout_t make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,
                                  const uint32_t* d_call = nullptr) {
     bf_dropout_t d;

@@ -246,6 +246,8 @@ int bf_launch_generate_step(const float* d_probs, const float* d_predictive_entr
                             uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
                             int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed,
                             hipStream_t stream);
+int bf_launch_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
+                             float min_p, hipStream_t stream);
 size_t bf_add_layernorm_bwd_ws_bytes(long long rows, int N);
 int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
                                 const void* d_dy, void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace,

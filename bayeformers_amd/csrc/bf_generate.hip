@@ -246,3 +246,247 @@ int bf_launch_generate_step(const float* d_probs, const float* d_predictive_entr
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
+
+// ---- bf_probs_truncate: top-k / top-p / min-p on the model-average rows ---------------------------------------------
+// One 1024-thread workgroup per row; no state between launches and no grid-wide synchronisation.  Every criterion is a
+// threshold on the value, found by a radix select over the key of a probability: its fp32 bit pattern (which orders
+// non-negative floats), 0 for p <= 0.  A select takes three digit passes over the row (key bits 30..20, 19..9, 8..0), each
+// a histogram in LDS of the elements whose higher digits match the prefix chosen so far: counts (top-k) or the fixed-point
+// mass q = floor(p * 2^(40 - E)) (top-p), all integer adds, so no sum depends on the order threads arrive in.  The first
+// pass also takes the row's largest key and its non-finite check and counts the top-k's first digit; the last pass
+// writes the row.  After the first, the row is re-read from L2.
+namespace {
+
+constexpr int TR_THREADS = 1024, TR_WAVES = TR_THREADS / 64, TR_BINS = 2048;
+constexpr int TR_SHIFT[3] = {20, 9, 0}, TR_WIDTH[3] = {11, 11, 9};
+
+struct TruncParams {
+    const float* probs;
+    float* out;
+    int64_t V, top_k;
+    float top_p, min_p;
+};
+
+__device__ __forceinline__ uint32_t prob_key(float p) {
+    const uint32_t u = __float_as_uint(p);
+    return (u >> 31) ? 0u : u;  // negative values and -0 are 0, like +0
+}
+
+// f(index, value, valid) for every element of the row; every thread runs the same number of iterations (the tail is
+// `valid = false`), so whole waves reach the wave-wide votes inside f
+template <bool VEC, typename F>
+__device__ __forceinline__ void for_row(const float* row, int V, F&& f) {
+    if constexpr (VEC) {
+        const int n4 = V >> 2, iters = (n4 + TR_THREADS - 1) / TR_THREADS;
+        for (int it = 0; it < iters; ++it) {
+            const int i = it * TR_THREADS + (int)threadIdx.x;
+            const bool ok = i < n4;
+            const float4 v = ok ? reinterpret_cast<const float4*>(row)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            f(4 * i, v.x, ok);
+            f(4 * i + 1, v.y, ok);
+            f(4 * i + 2, v.z, ok);
+            f(4 * i + 3, v.w, ok);
+        }
+    } else {
+        const int iters = (V + TR_THREADS - 1) / TR_THREADS;
+        for (int it = 0; it < iters; ++it) {
+            const int i = it * TR_THREADS + (int)threadIdx.x;
+            const bool ok = i < V;
+            f(i, ok ? row[i] : 0.0f, ok);
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k);
+    return v;
+}
+
+// adds (1, or q) at bin (-1: nothing).  A wave whose lanes all hit one bin (flat or quantised rows) adds once.
+template <bool MASS>
+__device__ __forceinline__ void hist_add(int bin, unsigned long long q, uint32_t* cnt, unsigned long long* mass) {
+    const int b0 = __builtin_amdgcn_readfirstlane(bin);
+    if (__all(bin == b0)) {
+        if (b0 < 0) return;
+        if constexpr (MASS) {
+            q = wave_sum_u64(q);
+            if ((threadIdx.x & 63) == 0) atomicAdd(&mass[b0], q);
+        } else {
+            if ((threadIdx.x & 63) == 0) atomicAdd(&cnt[b0], 64u);
+        }
+    } else if (bin >= 0) {
+        if constexpr (MASS) atomicAdd(&mass[bin], q);
+        else atomicAdd(&cnt[bin], 1u);
+    }
+}
+
+// The bin of `hist` [nbins] where the running sum from the top bin down first reaches need(total): *s_bin, and the sum of
+// the bins above it *s_above (total = the sum of every bin).  Thread t holds bins 2t, 2t + 1; a suffix scan over threads.
+template <typename T, typename Need>
+__device__ __forceinline__ void find_bin(const T* hist, int nbins, Need need_of, T* s_wave, int* s_bin, T* s_above) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lo = min(2 * tid, nbins), hi = min(2 * tid + 2, nbins);
+    T s = 0;
+    for (int i = lo; i < hi; ++i) s += hist[i];
+    T incl = s;  // sum over this wave's lanes >= lane (a fixed order)
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_down(incl, d);
+        if (lane + d < 64) incl += o;
+    }
+    if (lane == 0) s_wave[wave] = incl;
+    __syncthreads();
+    T above = incl - s, total = 0;
+    for (int w = 0; w < TR_WAVES; ++w) {
+        total += s_wave[w];
+        if (w > wave) above += s_wave[w];
+    }
+    const T need = need_of(total);
+    for (int i = hi - 1; i >= lo; --i) {
+        if (above < need && above + hist[i] >= need) *s_bin = i, *s_above = above;
+        above += hist[i];
+    }
+    __syncthreads();
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(TR_THREADS) void probs_truncate_kernel(const TruncParams p) {
+    __shared__ uint32_t cnt[TR_BINS];
+    __shared__ unsigned long long mass[TR_BINS];
+    __shared__ uint32_t s_wave_u[TR_WAVES];
+    __shared__ unsigned long long s_wave_q[TR_WAVES];
+    __shared__ uint32_t s_max[TR_WAVES], s_bad[TR_WAVES];
+    __shared__ int s_bin;
+    __shared__ uint32_t s_above_u;
+    __shared__ unsigned long long s_above_q;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int V = (int)p.V;
+    const float* row = p.probs + (int64_t)blockIdx.x * V;
+    float* out = p.out + (int64_t)blockIdx.x * V;
+    const bool topk = p.top_k > 0 && p.top_k < p.V, topp = p.top_p < 1.0f, minp = p.min_p > 0.0f;
+
+    // pass 1: the largest key, a NaN / infinity anywhere, the top-k's first-digit counts
+    if (topk)
+        for (int i = tid; i < TR_BINS; i += TR_THREADS) cnt[i] = 0;
+    __syncthreads();
+    uint32_t kmax = 0, bad = 0;
+    for_row<VEC>(row, V, [&](int, float v, bool ok) {
+        const uint32_t u = __float_as_uint(v), key = prob_key(v);
+        bad |= ok && (u & 0x7f800000u) == 0x7f800000u;
+        kmax = max(kmax, key);
+        if (topk) hist_add<false>(ok && key > 0 ? (int)(key >> TR_SHIFT[0]) : -1, 0, cnt, mass);
+    });
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor(kmax, k)), bad |= (uint32_t)__shfl_xor(bad, k);
+    if (lane == 0) s_max[wave] = kmax, s_bad[wave] = bad;
+    __syncthreads();
+    for (int w = 0; w < TR_WAVES; ++w) kmax = max(kmax, s_max[w]), bad |= s_bad[w];
+    if (bad || kmax == 0) {  // copied through (the whole workgroup takes this branch)
+        if (out != row)
+            for_row<false>(row, V, [&](int i, float v, bool ok) {
+                if (ok) out[i] = v;
+            });
+        return;
+    }
+
+    uint32_t thr = 1;  // keep key >= thr (p > 0)
+    if (topk) {  // the top_k-th largest key: three digits of counts
+        uint32_t prefix = 0, need = (uint32_t)p.top_k;
+        bool all = false;
+        for (int lvl = 0; lvl < 3 && !all; ++lvl) {
+            if (lvl > 0) {
+                for (int i = tid; i < TR_BINS; i += TR_THREADS) cnt[i] = 0;
+                __syncthreads();
+                const int up = TR_SHIFT[lvl] + TR_WIDTH[lvl], sh = TR_SHIFT[lvl], m = (1 << TR_WIDTH[lvl]) - 1;
+                for_row<VEC>(row, V, [&](int, float v, bool ok) {
+                    const uint32_t key = prob_key(v);
+                    hist_add<false>(ok && key > 0 && (key >> up) == prefix ? (int)((key >> sh) & m) : -1, 0, cnt, mass);
+                });
+                __syncthreads();
+            }
+            uint32_t total0 = 0;
+            find_bin(cnt, 1 << TR_WIDTH[lvl], [&](uint32_t total) {
+                total0 = total;
+                return min(need, total);
+            }, s_wave_u, &s_bin, &s_above_u);
+            if (lvl == 0 && need >= total0) all = true;  // k >= the positive entries: every one of them
+            need -= s_above_u;
+            prefix = (prefix << TR_WIDTH[lvl]) | (uint32_t)s_bin;
+        }
+        if (!all) thr = prefix;
+    }
+    if (topp) {  // the largest key t with mass(key >= t) >= top_p * mass(key >= thr): three digits of fixed-point mass
+        int e2;
+        const float fr = frexpf(__uint_as_float(kmax), &e2);
+        const int sexp = 40 - (fr == 0.5f ? e2 - 1 : e2);  // max p * 2^sexp in (2^39, 2^40]
+        const uint32_t lo = thr;
+        uint32_t prefix = 0;
+        unsigned long long need = 0;
+        for (int lvl = 0; lvl < 3; ++lvl) {
+            for (int i = tid; i < TR_BINS; i += TR_THREADS) mass[i] = 0;
+            __syncthreads();
+            const int up = TR_SHIFT[lvl] + TR_WIDTH[lvl], sh = TR_SHIFT[lvl], m = (1 << TR_WIDTH[lvl]) - 1;
+            for_row<VEC>(row, V, [&](int, float v, bool ok) {
+                const uint32_t key = prob_key(v);
+                const bool in = ok && key >= lo && (key >> up) == prefix;
+                hist_add<true>(in ? (int)((key >> sh) & m) : -1,
+                               in ? (unsigned long long)ldexpf(v, sexp) : 0ull, cnt, mass);
+            });
+            __syncthreads();
+            find_bin(mass, 1 << TR_WIDTH[lvl], [&](unsigned long long total) {
+                if (lvl == 0) {
+                    need = (unsigned long long)ceil((double)p.top_p * (double)total);
+                    need = need < 1 ? 1 : (need > total ? total : need);
+                }
+                return need;
+            }, s_wave_q, &s_bin, &s_above_q);
+            need -= s_above_q;
+            prefix = (prefix << TR_WIDTH[lvl]) | (uint32_t)s_bin;
+        }
+        thr = max(thr, prefix);
+    }
+    if (minp) thr = max(thr, prob_key(__fmul_rn(p.min_p, __uint_as_float(kmax))));
+    thr = min(thr, kmax);  // the argmax always stays
+
+    if constexpr (VEC) {
+        const int n4 = V >> 2;
+        for (int i = tid; i < n4; i += TR_THREADS) {
+            float4 v = reinterpret_cast<const float4*>(row)[i];
+            v.x = prob_key(v.x) >= thr ? v.x : 0.0f;
+            v.y = prob_key(v.y) >= thr ? v.y : 0.0f;
+            v.z = prob_key(v.z) >= thr ? v.z : 0.0f;
+            v.w = prob_key(v.w) >= thr ? v.w : 0.0f;
+            reinterpret_cast<float4*>(out)[i] = v;
+        }
+    } else {
+        for (int i = tid; i < V; i += TR_THREADS) {
+            const float v = row[i];
+            out[i] = prob_key(v) >= thr ? v : 0.0f;
+        }
+    }
+}
+
+}  // namespace
+
+int bf_launch_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
+                             float min_p, hipStream_t stream) {
+    const char* what = "bf_probs_truncate";
+    if (R < 1 || R > 65535 || V < 1 || V > (int64_t)MAX_TILES * TILE)
+        BF_FAIL("%s: R=%lld must be in [1, 65535] and V=%lld in [1, %d]", what, (long long)R, (long long)V,
+                MAX_TILES * TILE);
+    if (!d_probs || !d_out) BF_FAIL("%s: NULL argument", what);
+    if (!(top_p > 0.0f)) BF_FAIL("%s: top_p=%g must be positive (>= 1: off)", what, (double)top_p);
+    if (!(min_p <= 1.0f)) BF_FAIL("%s: min_p=%g must be at most 1 (<= 0: off)", what, (double)min_p);
+    const uintptr_t a = (uintptr_t)d_probs, b = (uintptr_t)d_out, n = (uintptr_t)(R * V) * sizeof(float);
+    if (a != b && a < b + n && b < a + n) BF_FAIL("%s: d_out overlaps d_probs without being it", what);
+    if ((a | b) & 3) BF_FAIL("%s: rows must be 4-byte aligned", what);
+    TruncParams p = {d_probs, d_out, V, top_k, top_p, min_p};
+    if (V % 4 == 0 && ((a | b) & 15) == 0)
+        probs_truncate_kernel<true><<<(unsigned)R, TR_THREADS, 0, stream>>>(p);
+    else
+        probs_truncate_kernel<false><<<(unsigned)R, TR_THREADS, 0, stream>>>(p);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}

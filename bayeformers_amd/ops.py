@@ -1038,6 +1038,33 @@ def generate_step(probs: Tensor, predictive_entropy: Tensor, expected_entropy: T
     GENERATE_CALLS[0] += 1
 
 
+TRUNCATE_CALLS = [0]  # launches of bf_probs_truncate through truncate_probs (tests, diagnostics)
+TRUNCATE_MAX_V = 524288
+
+
+def truncate_probs(probs: Tensor, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                   min_p: Optional[float] = None, out: Optional[Tensor] = None) -> Tensor:
+    """probs [R, V] (contiguous fp32 on the device) truncated for sampling in one launch (bf_probs_truncate): HF's order,
+    top-k, then top-p on the renormalised top-k set, then min-p; kept entries are bitwise the input, the others 0 (the
+    contract, its tie rule and its fixed-point mass: include/bayeformers_amd.h).  None turns a criterion off.  Writes
+    `out` (same shape; may be probs itself) or a new tensor, and returns it.  No host synchronisation: capturable."""
+    _require_device(probs, "truncate_probs: probs")
+    if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise _C.BayeFormersAMDError("truncate_probs: probs must be contiguous fp32 [R, V]")
+    R, V = probs.shape
+    if V > TRUNCATE_MAX_V:
+        raise _C.BayeFormersAMDError(f"truncate_probs: V={V} exceeds {TRUNCATE_MAX_V}")
+    if out is None:
+        out = torch.empty_like(probs)
+    elif out.shape != probs.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != probs.device:
+        raise _C.BayeFormersAMDError(f"truncate_probs: out must be contiguous fp32 {list(probs.shape)} on {probs.device}")
+    _C.check(_C.lib().bf_probs_truncate(probs.data_ptr(), out.data_ptr(), R, V, int(top_k) if top_k is not None else 0,
+                                        float(top_p) if top_p is not None else 1.0,
+                                        float(min_p) if min_p is not None else 0.0, _stream_ptr()), "bf_probs_truncate")
+    TRUNCATE_CALLS[0] += 1
+    return out
+
+
 class AttentionGqaFn(torch.autograd.Function):
     """attention_forward_gqa with attention_backward_gqa as its backward (no dropout: decoder configs run attention
     without it).  Keeps q, k, v, the output and one fp32 row statistic per query."""

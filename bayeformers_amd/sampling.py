@@ -11,6 +11,7 @@ over the ranks of a torch.distributed group: rank r runs the global sample indic
 all-reduce (RCCL over xGMI on MI355X) of the packed [sum of outputs | sum log_prior | sum lvp] buffer finishes the
 step.  The message is KB-sized, i.e. latency-bound: one collective per step, on the compute stream.
 """
+import numbers
 from dataclasses import dataclass, fields
 from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
@@ -759,7 +760,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None,
                     keep_weights: bool = False, max_bytes: Optional[int] = None, static_cache: bool = False,
-                    graph: bool = False) -> Generation:
+                    graph: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                    min_p: Optional[float] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -768,7 +770,13 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     forward over the prompt (input_ids [B, T0], left-padded rows marked by attention_mask [B, T0]); every later step feeds
     one token per row with `past_key_values`.  The last position's [S, B, V] logits, divided by `temperature`, go through
     `mc_predictive` (the bf_predictive kernels); the next token is the argmax of the model-average probabilities or, with
-    do_sample, a draw from them (torch.multinomial with `generator`), fed to all S samples.  Rows past eos_token_id emit
+    do_sample, a draw from them (torch.multinomial with `generator`), fed to all S samples.  With do_sample, top_k /
+    top_p / min_p truncate the model-average row before the draw as HF's warpers do, in HF's order (top-k, top-p on the
+    renormalised top-k set, min-p): one bf_probs_truncate launch per step (ops.truncate_probs; its contract and tie rule
+    are in include/bayeformers_amd.h), on the one row all S samples share; the draw is from the renormalised kept set.
+    top_k must be an int >= 1, top_p in (0, 1], min_p in [0, 1]; None, top_k >= V, top_p = 1 and min_p = 0 launch
+    nothing.  The statistics keep their meaning: the entropies, the MI and token_prob are those of the unfiltered,
+    temperature-scaled predictive (a kept probability is bitwise the unfiltered one).  Rows past eos_token_id emit
     pad_token_id (default: eos_token_id).  No host synchronisation per step except the all-finished check, and none
     without eos_token_id.  Single process, eval mode and no gradient only.
 
@@ -793,6 +801,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         raise ValueError(f"sample_generate: max_new_tokens={max_new_tokens} (at least 1)")
     if not temperature > 0.0:
         raise ValueError(f"sample_generate: temperature={temperature} (must be positive)")
+    truncation = _truncation(top_k, top_p, min_p, do_sample)
     static_cache = bool(static_cache) or bool(graph)
     if static_cache and group is not None:
         raise ValueError("sample_generate: static_cache / graph generation runs in a single process (group must be None)")
@@ -814,7 +823,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         pad_token_id = eos_token_id if eos_token_id is not None else 0
     if static_cache:
         return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
-                                eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph))
+                                eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph),
+                                truncation)
     S, n = samples, max_new_tokens
     B, T0 = input_ids.shape
     dev = input_ids.device
@@ -839,7 +849,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                 logits = logits.float() / temperature
             pred = mc_predictive(logits)
             if do_sample:
-                tok = torch.multinomial(pred.probs, 1, generator=generator).squeeze(1)
+                tok = torch.multinomial(_truncated(pred.probs, truncation), 1, generator=generator).squeeze(1)
             else:
                 tok = pred.prediction
             step = torch.stack([pred.predictive_entropy, pred.expected_entropy, pred.mutual_information,
@@ -861,6 +871,37 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                 pos = pos[:, -1:] + 1
             out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
     return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])
+
+
+def _truncation(top_k, top_p, min_p, do_sample: bool) -> Optional[Tuple[Optional[int], Optional[float], Optional[float]]]:
+    """sample_generate's checked (top_k, top_p, min_p), the no-op settings as None; None when all are no-ops."""
+    if (top_k is not None or top_p is not None or min_p is not None) and not do_sample:
+        raise ValueError("sample_generate: top_k / top_p / min_p truncate a draw: they need do_sample=True")
+    if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or top_k < 1):
+        raise ValueError(f"sample_generate: top_k={top_k!r} (an int >= 1)")
+    if top_p is not None and not (isinstance(top_p, numbers.Real) and 0.0 < top_p <= 1.0):
+        raise ValueError(f"sample_generate: top_p={top_p!r} (must be in (0, 1])")
+    if min_p is not None and not (isinstance(min_p, numbers.Real) and 0.0 <= min_p <= 1.0):
+        raise ValueError(f"sample_generate: min_p={min_p!r} (must be in [0, 1])")
+    k = int(top_k) if top_k is not None else None
+    p = float(top_p) if top_p is not None and top_p < 1.0 else None
+    m = float(min_p) if min_p is not None and min_p > 0.0 else None
+    return (k, p, m) if (k, p, m) != (None, None, None) else None
+
+
+def _truncated(probs: Tensor, truncation) -> Tensor:
+    """The model-average rows [B, V] a draw samples from: truncated by one bf_probs_truncate launch, or as they are
+    when every criterion is a no-op (top_k >= V included)."""
+    if truncation is None:
+        return probs
+    top_k, top_p, min_p = truncation
+    if top_k is not None and top_k >= probs.shape[-1]:
+        top_k = None
+    if (top_k, top_p, min_p) == (None, None, None):
+        return probs
+    from . import ops
+
+    return ops.truncate_probs(probs, top_k, top_p, min_p)
 
 
 _FINISHED_EVERY = 8  # graph replays between two all-finished checks (host synchronisations) of sample_generate(graph=True)
@@ -888,9 +929,10 @@ def _static_cache(model: Model, capacity: int):
 def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, do_sample: bool,
                      temperature: float, eos_token_id: Optional[int], pad_token_id: int,
                      generator: Optional[torch.Generator], keep_weights: bool, max_bytes: Optional[int],
-                     graph: bool) -> Generation:
+                     graph: bool, truncation=None) -> Generation:
     """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
-    static one), then decode steps of one shape whose bookkeeping is bf_generate_step."""
+    static one), then decode steps of one shape whose bookkeeping is bf_generate_step (after bf_probs_truncate with a
+    truncation: the step's inverse-CDF draw over the filtered, unnormalised row samples the renormalised kept set)."""
     from transformers import DynamicCache
 
     from . import ops
@@ -928,7 +970,7 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
         if temperature != 1.0:
             logits = logits.float() / temperature
         pred = mc_predictive(logits)
-        ops.generate_step(pred.probs, pred.predictive_entropy, pred.expected_entropy, pred.mutual_information, S, state,
+        ops.generate_step(_truncated(pred.probs, truncation), pred.predictive_entropy, pred.expected_entropy, pred.mutual_information, S, state,
                           sequences, T0, stats, finished, lengths, next_ids.view(-1), positions.view(-1), eos_token_id,
                           pad_token_id, seed)
 

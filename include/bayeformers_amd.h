@@ -462,6 +462,28 @@ int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, co
                      uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
                      int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed, void* stream);
 
+/* ---- truncated sampling: top-k, top-p, min-p --------------------------------------------------------------------------
+ * Truncate R rows of V fp32 probabilities (sample_generate's model-average rows) for sampling: HF's order, top-k, then
+ * top-p on the renormalised top-k set, then min-p.  d_out[r, j] = d_probs[r, j] (bit for bit) for kept j, 0 otherwise;
+ * d_out may alias d_probs.  top_k <= 0 or >= V: off; top_p >= 1: off; min_p <= 0: off.  Capturable, deterministic.
+ *   The kept set depends on the values only, through thresholds.  With p_(k) the k-th largest value of the row:
+ *     top-k keeps p >= p_(k), ties included (as HF's TopKLogitsWarper);
+ *     top-p keeps, inside the top-k set K, p >= t: t is the largest value with mass(p >= t) >= top_p * mass(K), in
+ *       the fixed-point mass below — every token tied at t stays (HF's sort may drop some of them: a deviation);
+ *     min-p keeps p >= m, m = min_p * max p as one fp32 product;
+ *   j is kept when it passes all three and p_j > 0.  Every entry equal to max p is kept whatever the criteria, so a
+ *   greedy choice is always in the kept set.
+ *   Mass, exact in integers: q_j = floor(p_j * 2^(40 - E)) in uint64, E the smallest integer with max p <= 2^E (E = 0
+ *   for a row whose largest probability is in (1/2, 1]); mass(A) = sum of q_j over A (at most V * 2^40).  t is the
+ *   largest value with mass(p >= t) >= need, need = ceil(fl64(top_p) * fl64(mass(K))) in double arithmetic (fl64: the
+ *   round-to-nearest double), at least 1.
+ *   A row holding a NaN or an infinity, or no positive entry, is copied through unchanged.
+ *   1 <= R <= 65535, 1 <= V <= 524288; top_p must be positive, min_p at most 1 (NaN refused); d_out either is d_probs
+ *   or does not overlap it.  One workgroup per row, integer histograms in LDS: no result depends on the order in
+ *   which threads arrive. */
+int bf_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
+                      float min_p, void* stream);
+
 /* ---- training mode: HuggingFace dropout inside the fused kernels ------------------------------------------------------
  * The reference trains with the wrapped model in .train() (/root/reference/examples/bert_glue.py:221,227-241): HF's
  * dropout (p = 0.1) acts on the attention probabilities and on every dense output in front of a residual + LayerNorm.

@@ -2,6 +2,7 @@
 
     python tools/generate_bench.py kernels [--out K.json] [--only N,K,S,M]
     python tools/generate_bench.py e2e [--out E.json] [--runs 3] [--new-tokens 256] [--mode dynamic|static|graph ...]
+                                       [--top-k K] [--top-p P] [--min-p M]
     python tools/generate_bench.py trace --mode keep|draw [--mode dynamic|static|graph] [--steps 32]   (under rocprofv3 --kernel-trace)
     python tools/generate_bench.py analyze <kernel_trace.csv> [--steps 32]
 
@@ -12,7 +13,8 @@ same kept weights.  Time per call = device events around 200 back-to-back calls 
 e2e: sample_generate on the DESIGN 4.5 decoder (8 layers, hidden 1024, 16 / 4 heads, FFN 2816, vocab 32000), S 4, B 4, prompt
 512, bf16, fuse_attention; keep_weights off and on alternated in one process, `runs` each, and for each of them the decode
 paths named by --mode (default all three, alternated): dynamic (the default DynamicCache loop), static
-(static_cache=True) and graph (graph=True).
+(static_cache=True) and graph (graph=True).  With --top-k / --top-p / --min-p every decode path runs do_sample=True twice,
+alternated: without the truncation (`..._sample`) and with it (`..._truncated`).
 trace: a prefill-only generation, a 2 s pause, then a generation of `new-tokens`; analyze splits a kernel trace of it at the
 pause and attributes (second - first) to the decode steps: GPU time per kernel class and the host gaps between kernels.
 """
@@ -99,34 +101,40 @@ def _decoder():
 PATHS = {"dynamic": {}, "static": {"static_cache": True}, "graph": {"graph": True}}
 
 
-def e2e(runs, new_tokens, paths=("dynamic", "static", "graph")):
+def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None):
     import bayeformers_amd as bf
     from bayeformers_amd.sampling import sample_generate
 
     bmodel = _decoder()
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    name = lambda keep, path: ("keep_weights" if keep else "draw_per_step") + ("" if path == "dynamic" else "_" + path)
-    res = {name(k, p): [] for k in (False, True) for p in paths}
+    variants = {"": {}} if not truncation else {"_sample": dict(do_sample=True),
+                                                "_truncated": dict(do_sample=True, **truncation)}
+    name = lambda keep, path, v="": (("keep_weights" if keep else "draw_per_step") + ("" if path == "dynamic" else "_" + path)
+                                     + v)
+    res = {name(k, p, v): [] for k in (False, True) for p in paths for v in variants}
     res["kept_bytes"] = bf.kept_weight_bytes(bmodel, 4, torch.bfloat16)
     seqs = {}
     with torch.no_grad():
         for keep in (False, True):  # warm-up
             for path in paths:
-                sample_generate(bmodel, ids, samples=4, max_new_tokens=8, keep_weights=keep, **PATHS[path])
+                for v, kw in variants.items():
+                    sample_generate(bmodel, ids, samples=4, max_new_tokens=8, keep_weights=keep, **PATHS[path], **kw)
         for _ in range(runs):
             for keep in (False, True):
                 for path in paths:
-                    bf.manual_seed(0x5EED)
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    gen = sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep,
-                                          **PATHS[path])
-                    torch.cuda.synchronize()
-                    dt = time.perf_counter() - t0
-                    res[name(keep, path)].append(round(4 * new_tokens / dt, 1))
-                    seqs[keep, path] = gen.sequences
-                    print(json.dumps({"keep_weights": keep, "path": path, "seconds": round(dt, 3),
-                                      "tokens_per_s": round(4 * new_tokens / dt, 1)}), flush=True)
+                    for v, kw in variants.items():
+                        bf.manual_seed(0x5EED)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        gen = sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep,
+                                              generator=torch.Generator(device="cuda").manual_seed(3) if kw else None,
+                                              **PATHS[path], **kw)
+                        torch.cuda.synchronize()
+                        dt = time.perf_counter() - t0
+                        res[name(keep, path, v)].append(round(4 * new_tokens / dt, 1))
+                        seqs[keep, path, v] = gen.sequences
+                        print(json.dumps({"keep_weights": keep, "path": path + v, "seconds": round(dt, 3),
+                                          "tokens_per_s": round(4 * new_tokens / dt, 1)}), flush=True)
     first = next(iter(seqs.values()))
     res["same_tokens"] = all(bool(torch.equal(first, v)) for v in seqs.values())
     for k in [k for k in res if isinstance(res[k], list)]:
@@ -195,6 +203,9 @@ def main():
     # keep | draw: the weights (trace); dynamic | static | graph: the decode path (e2e: the ones to alternate; trace: one)
     ap.add_argument("--mode", choices=["keep", "draw", "dynamic", "static", "graph"], action="append", default=None)
     ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--top-k", type=int, default=None)
+    ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--min-p", type=float, default=None)
     a = ap.parse_args()
     if a.what == "analyze":
         res = analyze(a.path, a.steps)
@@ -205,7 +216,8 @@ def main():
         modes = a.mode or []
         paths = [m for m in modes if m in PATHS] or None
         if a.what == "e2e":
-            res = e2e(a.runs, a.new_tokens, *([paths] if paths else []))
+            truncation = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p), ("min_p", a.min_p)) if v is not None}
+            res = e2e(a.runs, a.new_tokens, paths or ("dynamic", "static", "graph"), truncation)
         else:
             trace("draw" if "draw" in modes else "keep", a.steps + 1, (paths or ["dynamic"])[-1])
             return
