@@ -346,7 +346,7 @@ def test_bench_serial_workload_reports_the_replayed_reference_loop():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "bert_base_serial", "--steps", "3", "--warmup", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["config"]["hip_graph"] == "bnn.Model.__call__ replay" and "SERIAL" in d["config"]["workload"]

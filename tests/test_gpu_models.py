@@ -994,7 +994,7 @@ def test_bench_line_carries_the_contract_keys():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "linear768", "--steps", "3", "--warmup", "1",
-                        "--no-traffic"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--full", "--no-traffic"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1011,6 +1011,28 @@ def test_bench_line_carries_the_contract_keys():
         assert k in d["cpu_baseline"], k
     assert d["cpu_baseline"]["kind"] == "port" and d["value"] > 0
     assert "HSA_ENABLE_IPC_MODE_LEGACY" in d["config"]["env"]
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full bench.py prints the same keys, but leaves the legs the headline does not need unmeasured: `roofline` and
+    `cpu_baseline` are null."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "linear768", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "MC-samples/sec (fwd+ELBO)" and d["unit"] == "MC-samples/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+    assert d["value"] == pytest.approx(10 * 3 / (3 * d["ms_per_step"] * 1e-3), rel=1e-2)
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["config"]["hip_graph"] is True and d["config"]["allreduce_ms_per_step"] is None
 
 
 def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
@@ -1055,7 +1077,7 @@ def test_bench_bert_line_accounts_for_the_sampling_launch_and_the_positions(dtyp
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "bert_base", "--dtype", dtype, "--steps", "2",
-                        "--warmup", "1", "--no-traffic", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--warmup", "1", "--full", "--no-traffic", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     roof = d["roofline"]

@@ -218,7 +218,7 @@ def _bench_line(args, env_extra):
     env = dict(os.environ, **env_extra)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--no-traffic", "--no-cpu-baseline"], env=env,
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--full", "--no-traffic", "--no-cpu-baseline"], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     return json.loads(out.stdout.strip().splitlines()[-1])

@@ -14,14 +14,14 @@ print('$1', 'samples/s', d['value'], 'ms/step', d['ms_per_step'], 'frac', r.get(
 for round in 1 2 3; do
   for v in base ea2 ea4 at1 at3; do
     lib=$L/libbayeformers_amd.so; [ $v != base ] && lib=$L/libbayeformers_amd_$v.so
-    BF_LIB_PATH=$lib python3 bench.py --steps 300 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v" >> $OUT/gemm_variants_in_step.txt
+    BF_LIB_PATH=$lib python3 bench.py --full --steps 300 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v" >> $OUT/gemm_variants_in_step.txt
   done
 done
 for round in 1 2 3; do
   for S in 1 2; do
     for v in base pair; do
       lib=$L/libbayeformers_amd.so; [ $v != base ] && lib=$L/libbayeformers_amd_$v.so
-      BF_LIB_PATH=$lib python3 bench.py --samples $S --steps 400 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round S=$S $v" >> $OUT/sampling_pair_small_shards.txt
+      BF_LIB_PATH=$lib python3 bench.py --full --samples $S --steps 400 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round S=$S $v" >> $OUT/sampling_pair_small_shards.txt
     done
   done
 done

@@ -8,7 +8,7 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; s=r.ge
 print('$1', 'samples/s', d['value'], 'ms/step', d['ms_per_step'], 'frac', r.get('frac'), 'with_sampling', r.get('frac_with_sampling'), 'gemm_ms', r.get('gemm_ms_per_step'), 'elbo', d['config'].get('last_elbo'))"; }
 for round in 1 2 3 4; do
   for v in 1 0; do
-    BF_AB_OLD_SNAPSHOT=$v python3 bench.py --steps 200 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round old_snapshot=$v" >> $OUT/counter_copy_ab.txt
+    BF_AB_OLD_SNAPSHOT=$v python3 bench.py --full --steps 200 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round old_snapshot=$v" >> $OUT/counter_copy_ab.txt
   done
 done
 cat $OUT/counter_copy_ab.txt

@@ -19,8 +19,8 @@ print('$1', 'samples/s', d['value'], 'ms/step', d['ms_per_step'], 'frac', r.get(
 for round in 1 2 3; do
   for v in old base; do
     lib=$L/libbayeformers_amd.so; [ $v = old ] && lib=$L/libbayeformers_amd_attnold.so
-    BF_LIB_PATH=$lib python3 bench.py --steps 200 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v bert_base" >> $OUT/attn_ab.txt
-    BF_LIB_PATH=$lib python3 bench.py --workload bert_large_qa --steps 40 --warmup 3 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v bert_large_qa" >> $OUT/attn_ab.txt
+    BF_LIB_PATH=$lib python3 bench.py --full --steps 200 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v bert_base" >> $OUT/attn_ab.txt
+    BF_LIB_PATH=$lib python3 bench.py --full --workload bert_large_qa --steps 40 --warmup 3 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v bert_large_qa" >> $OUT/attn_ab.txt
   done
 done
 cat $OUT/attn_ab.txt

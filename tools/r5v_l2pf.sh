@@ -9,7 +9,7 @@ print('$1', 'samples/s', d['value'], 'ms/step', d['ms_per_step'], 'frac', r.get(
 for round in 1 2 3; do
   for v in base l2pf1 l2pf2 l2pf3; do
     lib=$L/libbayeformers_amd.so; [ $v != base ] && lib=$L/libbayeformers_amd_$v.so
-    BF_LIB_PATH=$lib python3 bench.py --steps 200 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v" >> $OUT/l2pf.txt
+    BF_LIB_PATH=$lib python3 bench.py --full --steps 200 --warmup 5 --no-traffic --no-cpu-baseline 2>/dev/null | line "round$round $v" >> $OUT/l2pf.txt
   done
 done
 cat $OUT/l2pf.txt

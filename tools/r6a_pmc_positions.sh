@@ -6,7 +6,7 @@ TAG=${1:-r6a}; shift
 OUT=$PWD/gpurun_out/$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for a in "$@"; do export "$a"; done
-ARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --graph off"
+ARGS="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-traffic --graph off"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE \
     --output-format csv -d $OUT/sq -o t -- python3 $ARGS > $OUT/bench_sq.json 2> $OUT/sq.err
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_REQ_sum \

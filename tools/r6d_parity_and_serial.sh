@@ -7,9 +7,9 @@ tail -3 $OUT/pytest_new_parity.txt
 grep "^\[c" $OUT/pytest_new_parity.txt
 python3 -m pytest tests -m gpu -q > $OUT/pytest_gpu.txt 2>&1
 tail -5 $OUT/pytest_gpu.txt
-python3 bench.py --workload bert_base_serial --steps 20 --warmup 3 > $OUT/bench_bert_base_serial.json 2> $OUT/serial.err
-BF_NO_AUTO_GRAPH=1 python3 bench.py --workload bert_base_serial --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_bert_base_serial_eager.json 2>> $OUT/serial.err
-python3 bench.py --no-cpu-baseline --no-traffic --steps 50 > $OUT/bench_bert_base.json 2>> $OUT/serial.err
+python3 bench.py --full --workload bert_base_serial --steps 20 --warmup 3 > $OUT/bench_bert_base_serial.json 2> $OUT/serial.err
+BF_NO_AUTO_GRAPH=1 python3 bench.py --full --workload bert_base_serial --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_bert_base_serial_eager.json 2>> $OUT/serial.err
+python3 bench.py --full --no-cpu-baseline --no-traffic --steps 50 > $OUT/bench_bert_base.json 2>> $OUT/serial.err
 for f in bench_bert_base_serial bench_bert_base_serial_eager bench_bert_base; do python3 -c "
 import json
 d=json.loads(open('$OUT/$f.json').read().strip().splitlines()[-1]); r=d['roofline']
