@@ -112,7 +112,11 @@ SYMBOLS = {
     "bf_attention_decode_gqa_len": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
     "bf_generate_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                               _i64, _i, _vp, _vp]),
+    "bf_generate_step_stat_probs": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
+                                         _vp, _vp, _i64, _i64, _i, _vp, _vp]),
     "bf_probs_truncate": (_i, [_vp, _vp, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, _vp]),
+    "bf_logits_process": (_i, [_vp, _i, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, ctypes.c_float, _i64,
+                               _i64, _i64, ctypes.c_float, _vp]),
     "bf_profile_enable": (_i, [_i]),
     "bf_profile_reset": (_i, []),
     "bf_probe_stream_read": (_i, [_vp, _sz, _vp, _vp]),

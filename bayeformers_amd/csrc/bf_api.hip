@@ -518,15 +518,37 @@ int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, co
                      int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
                      uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
                      int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed, void* stream) {
-    return bf_launch_generate_step(d_probs, d_predictive_entropy, d_expected_entropy, d_mutual_information, B, V, S,
-                                   d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished, d_lengths,
+    return bf_launch_generate_step(d_probs, nullptr, d_predictive_entropy, d_expected_entropy, d_mutual_information, B, V,
+                                   S, d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished, d_lengths,
                                    d_next_ids, d_positions, eos_token_id, pad_token_id, do_sample, d_seed,
+                                   (hipStream_t)stream);
+}
+
+int bf_generate_step_stat_probs(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
+                                const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
+                                int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences,
+                                int64_t seq_stride, int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths,
+                                int64_t* d_next_ids, int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id,
+                                int do_sample, const uint64_t* d_seed, void* stream) {
+    if (!d_stat_probs) BF_FAIL("bf_generate_step_stat_probs: NULL argument");
+    return bf_launch_generate_step(d_probs, d_stat_probs, d_predictive_entropy, d_expected_entropy, d_mutual_information,
+                                   B, V, S, d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished,
+                                   d_lengths, d_next_ids, d_positions, eos_token_id, pad_token_id, do_sample, d_seed,
                                    (hipStream_t)stream);
 }
 
 int bf_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
                       float min_p, void* stream) {
     return bf_launch_probs_truncate(d_probs, d_out, R, V, top_k, top_p, min_p, (hipStream_t)stream);
+}
+
+int bf_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
+                      const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0, const int64_t* d_step,
+                      int64_t step, float repetition_penalty, int64_t no_repeat_ngram_size, int64_t min_new_tokens,
+                      int64_t eos_token_id, float temperature, void* stream) {
+    return bf_launch_logits_process(d_logits, dtype, R, V, row_stride, d_out, d_sequences, B, seq_stride, T0, d_step, step,
+                                    repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, temperature,
+                                    (hipStream_t)stream);
 }
 
 static bf_dropout_t make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,

@@ -240,14 +240,19 @@ int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const v
                                        void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
                                        hipStream_t stream);
 // one generation step's epilogue (bf_generate.hip)
-int bf_launch_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
-                            const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
-                            int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
-                            uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
-                            int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed,
-                            hipStream_t stream);
+int bf_launch_generate_step(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
+                            const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
+                            int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride,
+                            int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids,
+                            int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id, int do_sample,
+                            const uint64_t* d_seed, hipStream_t stream);
 int bf_launch_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
                              float min_p, hipStream_t stream);
+int bf_launch_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
+                             const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0,
+                             const int64_t* d_step, int64_t step, float repetition_penalty,
+                             int64_t no_repeat_ngram_size, int64_t min_new_tokens, int64_t eos_token_id,
+                             float temperature, hipStream_t stream);
 size_t bf_add_layernorm_bwd_ws_bytes(long long rows, int N);
 int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
                                 const void* d_dy, void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace,

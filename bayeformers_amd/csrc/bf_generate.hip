@@ -20,6 +20,7 @@ constexpr int MAX_TILES = 512;  // V <= 524288
 
 struct GenParams {
     const float* probs;
+    const float* stat_probs;  // the row the token's probability statistic is read from (probs when NULL)
     const float* pe;
     const float* ee;
     const float* mi;
@@ -56,6 +57,7 @@ __global__ __launch_bounds__(THREADS) void generate_step_kernel(const GenParams 
     const int64_t step = *p.state;
     if (step >= p.n) return;  // past the last step: nothing to write (and the counter stays)
     const float* row = p.probs + b * V;
+    const float* stat_row = p.stat_probs ? p.stat_probs + b * V : row;
     const int tiles = (int)((V + TILE - 1) / TILE);
 
     // pass 1: argmax (first index of the largest value; NaN never wins) and the per-tile wave sums
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(THREADS) void generate_step_kernel(const GenParams 
     const int64_t tok = done ? p.pad : s_tok;
     if (tid == 0) {
         const int64_t B = p.B, n = p.n;
-        const float st[4] = {p.pe[b], p.ee[b], p.mi[b], row[s_tok]};
+        const float st[4] = {p.pe[b], p.ee[b], p.mi[b], stat_row[s_tok]};
         for (int i = 0; i < 4; ++i) p.stats[(i * B + b) * n + step] = done ? 0.0f : st[i];
         p.seq[b * p.seq_stride + p.T0 + step] = tok;
         if (p.eos >= 0) {
@@ -198,12 +200,12 @@ __global__ __launch_bounds__(THREADS) void generate_step_kernel(const GenParams 
 
 }  // namespace
 
-int bf_launch_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
-                            const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
-                            int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
-                            uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
-                            int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed,
-                            hipStream_t stream) {
+int bf_launch_generate_step(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
+                            const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
+                            int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride,
+                            int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids,
+                            int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id, int do_sample,
+                            const uint64_t* d_seed, hipStream_t stream) {
     const char* what = "bf_generate_step";
     if (B < 1 || B > 0x7fffffff || V < 1 || S < 1 || max_new_tokens < 1)
         BF_FAIL("%s: B=%lld, V=%lld, S=%d, max_new_tokens=%lld must be positive", what, (long long)B, (long long)V, S,
@@ -222,6 +224,7 @@ int bf_launch_generate_step(const float* d_probs, const float* d_predictive_entr
         BF_FAIL("%s: int64 arguments must be 8-byte aligned", what);
     GenParams p = {};
     p.probs = d_probs;
+    p.stat_probs = d_stat_probs;
     p.pe = d_predictive_entropy;
     p.ee = d_expected_entropy;
     p.mi = d_mutual_information;
@@ -487,6 +490,176 @@ int bf_launch_probs_truncate(const float* d_probs, float* d_out, int64_t R, int6
         probs_truncate_kernel<true><<<(unsigned)R, TR_THREADS, 0, stream>>>(p);
     else
         probs_truncate_kernel<false><<<(unsigned)R, TR_THREADS, 0, stream>>>(p);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- bf_logits_process: repetition penalty, no-repeat n-grams, min_new_tokens, temperature --------------------------
+// A grid of (2048-column chunk, batch row b).  Each workgroup first scans row b's L tokens (from L2) into two LDS bitmaps
+// over its chunk: "seen" (the token occurs) and "banned" (the token completes a window whose first n - 1 tokens equal the
+// row's last n - 1).  The bits are set with LDS atomicOr, which does not depend on the order threads arrive in.  Then it
+// streams its chunk of the S sample rows of b (rows s * B + b): thread t owns columns 8t .. 8t + 7 of the chunk, read as
+// one 16-byte load per bf16 / fp16 row (two for fp32) and written as two float4.
+namespace {
+
+constexpr int LP_THREADS = 256, LP_PER = 8, LP_CHUNK = LP_THREADS * LP_PER, LP_WORDS = LP_CHUNK / 32;
+constexpr int LP_MAX_NGRAM = 64;
+constexpr int64_t LP_MAX_V = 524288;
+
+struct ProcParams {
+    const void* logits;
+    float* out;
+    const int64_t* seq;
+    const int64_t* d_step;
+    int64_t row_stride, seq_stride, T0, step, eos, m;
+    int V, B, S, n;
+    float theta, T;
+};
+
+__device__ __forceinline__ float lp_f32(float v) { return v; }
+__device__ __forceinline__ float lp_f32(__bf16 v) { return (float)v; }
+__device__ __forceinline__ float lp_f32(_Float16 v) { return (float)v; }
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(LP_THREADS) void logits_process_kernel(const ProcParams p) {
+    __shared__ uint32_t seen[LP_WORDS], banned[LP_WORDS];
+    __shared__ int64_t prefix[LP_MAX_NGRAM];
+
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.y, c0 = (int64_t)blockIdx.x * LP_CHUNK, V = p.V;
+    const int64_t step = p.d_step ? *p.d_step : p.step;
+    const int64_t L = min(max(p.T0 + step, (int64_t)0), p.seq_stride);  // the history: seq[0, L)
+    const int64_t* seq = p.seq + b * p.seq_stride;
+    const bool pen = p.theta != 1.0f;
+    const int n = L >= p.n ? p.n : 0;  // no complete n-gram yet: nothing to ban
+    if (tid < LP_WORDS) seen[tid] = 0u, banned[tid] = 0u;
+    for (int j = tid; j < n - 1; j += LP_THREADS) prefix[j] = seq[L - n + 1 + j];
+    __syncthreads();
+    if (pen || n > 0) {
+        for (int64_t i = tid; i < L; i += LP_THREADS) {
+            const int64_t id = seq[i];
+            if (id < c0 || id >= c0 + LP_CHUNK || id >= V) continue;  // c0 >= 0: ids < 0 are out too
+            const int c = (int)(id - c0);
+            const uint32_t bit = 1u << (c & 31);
+            if (pen) atomicOr(&seen[c >> 5], bit);
+            if (n > 0 && i >= n - 1) {  // the window seq[i - n + 1 .. i] ends with id: banned if it starts with the prefix
+                bool match = true;
+                for (int j = 0; j < n - 1 && match; ++j) match = seq[i - n + 1 + j] == prefix[j];
+                if (match) atomicOr(&banned[c >> 5], bit);
+            }
+        }
+    }
+    __syncthreads();
+
+    const int64_t col = c0 + LP_PER * tid;
+    if (col >= V) return;
+    const int sh = LP_PER * (tid & 3);
+    const uint32_t sb = (seen[tid >> 2] >> sh) & 0xffu;
+    uint32_t bb = (banned[tid >> 2] >> sh) & 0xffu;
+    if (step < p.m && p.eos >= col && p.eos < col + LP_PER) bb |= 1u << (int)(p.eos - col);  // eos < V: host-checked
+    const bool full = col + LP_PER <= V;
+    for (int s = 0; s < p.S; ++s) {
+        const int64_t r = (int64_t)s * p.B + b;
+        const T* row = reinterpret_cast<const T*>(p.logits) + r * p.row_stride + col;
+        float* out = p.out + r * V + col;
+        float v[LP_PER];
+        if (VEC && full) {
+            if constexpr (sizeof(T) == 2) {
+                const uint4 u = *reinterpret_cast<const uint4*>(row);
+                const T* h = reinterpret_cast<const T*>(&u);
+#pragma unroll
+                for (int e = 0; e < LP_PER; ++e) v[e] = lp_f32(h[e]);
+            } else {
+                const float4 a = reinterpret_cast<const float4*>(row)[0], c = reinterpret_cast<const float4*>(row)[1];
+                v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = c.x, v[5] = c.y, v[6] = c.z, v[7] = c.w;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < LP_PER; ++e) v[e] = col + e < V ? lp_f32(row[e]) : 0.0f;
+        }
+#pragma unroll
+        for (int e = 0; e < LP_PER; ++e) {
+            float x = v[e];
+            if ((sb >> e) & 1u) x = x < 0.0f ? __fmul_rn(x, p.theta) : __fdiv_rn(x, p.theta);
+            if ((bb >> e) & 1u) x = -INFINITY;
+            v[e] = p.T != 1.0f ? __fdiv_rn(x, p.T) : x;
+        }
+        if (VEC && full) {
+            reinterpret_cast<float4*>(out)[0] = make_float4(v[0], v[1], v[2], v[3]);
+            reinterpret_cast<float4*>(out)[1] = make_float4(v[4], v[5], v[6], v[7]);
+        } else {
+#pragma unroll
+            for (int e = 0; e < LP_PER; ++e)
+                if (col + e < V) out[e] = v[e];
+        }
+    }
+}
+
+template <typename T>
+void launch_logits_process(const ProcParams& p, bool vec, dim3 grid, hipStream_t stream) {
+    if (vec)
+        logits_process_kernel<T, true><<<grid, LP_THREADS, 0, stream>>>(p);
+    else
+        logits_process_kernel<T, false><<<grid, LP_THREADS, 0, stream>>>(p);
+}
+
+}  // namespace
+
+int bf_launch_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
+                             const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0,
+                             const int64_t* d_step, int64_t step, float repetition_penalty,
+                             int64_t no_repeat_ngram_size, int64_t min_new_tokens, int64_t eos_token_id,
+                             float temperature, hipStream_t stream) {
+    const char* what = "bf_logits_process";
+    if (dtype != BF_DT_F32 && dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype=%d is not a BF_DT_*", what, dtype);
+    if (B < 1 || B > 65535 || R < B || R % B != 0 || R / B > 0x7fffffff)
+        BF_FAIL("%s: R=%lld must be a positive multiple of B=%lld (B in [1, 65535])", what, (long long)R, (long long)B);
+    if (V < 1 || V > LP_MAX_V) BF_FAIL("%s: V=%lld must be in [1, %lld]", what, (long long)V, (long long)LP_MAX_V);
+    if (row_stride < V) BF_FAIL("%s: row_stride=%lld is shorter than V=%lld", what, (long long)row_stride, (long long)V);
+    if (T0 < 0 || seq_stride < 1 || (!d_step && (step < 0 || T0 + step > seq_stride)))
+        BF_FAIL("%s: a sequence row of %lld tokens does not hold T0=%lld + step=%lld", what, (long long)seq_stride,
+                (long long)T0, (long long)step);
+    if (!d_logits || !d_out || !d_sequences) BF_FAIL("%s: NULL argument", what);
+    if (!(repetition_penalty > 0.0f) || !isfinite(repetition_penalty))
+        BF_FAIL("%s: repetition_penalty=%g must be finite and positive", what, (double)repetition_penalty);
+    if (no_repeat_ngram_size < 0 || no_repeat_ngram_size > LP_MAX_NGRAM)
+        BF_FAIL("%s: no_repeat_ngram_size=%lld must be in [0, %d]", what, (long long)no_repeat_ngram_size, LP_MAX_NGRAM);
+    if (min_new_tokens < 0) BF_FAIL("%s: min_new_tokens=%lld must be non-negative", what, (long long)min_new_tokens);
+    if (min_new_tokens > 0 && (eos_token_id < 0 || eos_token_id >= V))
+        BF_FAIL("%s: min_new_tokens needs an eos_token_id in [0, V) (got %lld)", what, (long long)eos_token_id);
+    if (!(temperature > 0.0f) || !isfinite(temperature))
+        BF_FAIL("%s: temperature=%g must be finite and positive", what, (double)temperature);
+    const size_t esz = bf_dtype_size(dtype);
+    const uintptr_t a = (uintptr_t)d_logits, o = (uintptr_t)d_out;
+    if ((a & (esz - 1)) || (o & 3)) BF_FAIL("%s: logits must be aligned to their element and d_out to 4 bytes", what);
+    if (((uintptr_t)d_sequences | (uintptr_t)d_step) & 7) BF_FAIL("%s: int64 arguments must be 8-byte aligned", what);
+    const uintptr_t in_end = a + (uintptr_t)((R - 1) * row_stride + V) * esz, out_end = o + (uintptr_t)(R * V) * 4;
+    if (a < out_end && o < in_end) BF_FAIL("%s: d_out overlaps the logits", what);
+    ProcParams p = {};
+    p.logits = d_logits;
+    p.out = d_out;
+    p.seq = d_sequences;
+    p.d_step = d_step;
+    p.row_stride = row_stride;
+    p.seq_stride = seq_stride;
+    p.T0 = T0;
+    p.step = step;
+    p.eos = min_new_tokens > 0 ? eos_token_id : -1;
+    p.m = min_new_tokens;
+    p.V = (int)V;
+    p.B = (int)B;
+    p.S = (int)(R / B);
+    p.n = (int)no_repeat_ngram_size;
+    p.theta = repetition_penalty;
+    p.T = temperature;
+    const bool vec = (a & 15) == 0 && ((uintptr_t)row_stride * esz & 15) == 0 && (o & 15) == 0 && V % 4 == 0;
+    const dim3 grid((unsigned)((V + LP_CHUNK - 1) / LP_CHUNK), (unsigned)B);
+    if (dtype == BF_DT_F32)
+        launch_logits_process<float>(p, vec, grid, stream);
+    else if (dtype == BF_DT_BF16)
+        launch_logits_process<__bf16>(p, vec, grid, stream);
+    else
+        launch_logits_process<_Float16>(p, vec, grid, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }

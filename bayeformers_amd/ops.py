@@ -6,7 +6,7 @@ are not on a ROCm device raise.
 """
 import ctypes
 import os
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 from torch import Tensor
@@ -991,15 +991,17 @@ GENERATE_CALLS = [0]  # launches of bf_generate_step through generate_step (test
 def generate_step(probs: Tensor, predictive_entropy: Tensor, expected_entropy: Tensor, mutual_information: Tensor,
                   samples: int, state: Tensor, sequences: Tensor, T0: int, stats: Tensor, finished: Optional[Tensor],
                   lengths: Tensor, next_ids: Tensor, positions: Optional[Tensor], eos_token_id: Optional[int],
-                  pad_token_id: int, seed: Optional[Tensor] = None) -> None:
+                  pad_token_id: int, seed: Optional[Tensor] = None, stat_probs: Optional[Tensor] = None) -> None:
     """One generation step's epilogue in one launch (bf_generate_step), at the step state[0]: the token of each of the B
     rows of probs [B, V] (fp32: the lowest-index argmax, or with `seed` — a one-element int64 device tensor — an
     inverse-CDF draw of a Philox uniform), written into sequences [B, T0 + n] at T0 + step, the four statistics
     (predictive_entropy, expected_entropy, mutual_information [B], the token's probability) into stats [4, B, n] at step
     (zero for rows finished before it), finished [B] bool and lengths [B] int64 updated as sample_generate's loop does
     with eos_token_id (None: every row counts the token), the token into next_ids [samples * B] (sample-major) and
-    positions [samples * B] (or None) advanced by one; state [2] int64 {step, 0} advances by one.  No host
-    synchronisation: capturable."""
+    positions [samples * B] (or None) advanced by one; state [2] int64 {step, 0} advances by one.  With stat_probs
+    ([B, V] like probs; bf_generate_step_stat_probs) the token's probability statistic is read from it instead of from
+    probs: the token is chosen from processed rows, its probability is the unprocessed one.  No host synchronisation:
+    capturable."""
     _require_device(probs, "generate_step: probs")
     if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_contiguous():
         raise _C.BayeFormersAMDError("generate_step: probs must be contiguous fp32 [B, V]")
@@ -1027,14 +1029,18 @@ def generate_step(probs: Tensor, predictive_entropy: Tensor, expected_entropy: T
         need(finished, "finished", torch.bool, (B,))
     if seed is not None:
         need(seed, "seed", torch.int64, (1,))
-    _C.check(_C.lib().bf_generate_step(probs.data_ptr(), predictive_entropy.data_ptr(), expected_entropy.data_ptr(),
-                                       mutual_information.data_ptr(), B, V, int(samples), state.data_ptr(), n,
-                                       sequences.data_ptr(), sequences.stride(0), int(T0), stats.data_ptr(),
-                                       finished.data_ptr() if finished is not None else None, lengths.data_ptr(),
-                                       next_ids.data_ptr(), positions.data_ptr() if positions is not None else None,
-                                       int(eos_token_id) if eos_token_id is not None else -1, int(pad_token_id),
-                                       1 if seed is not None else 0, seed.data_ptr() if seed is not None else None,
-                                       _stream_ptr()), "bf_generate_step")
+    args = (predictive_entropy.data_ptr(), expected_entropy.data_ptr(), mutual_information.data_ptr(), B, V, int(samples),
+            state.data_ptr(), n, sequences.data_ptr(), sequences.stride(0), int(T0), stats.data_ptr(),
+            finished.data_ptr() if finished is not None else None, lengths.data_ptr(), next_ids.data_ptr(),
+            positions.data_ptr() if positions is not None else None,
+            int(eos_token_id) if eos_token_id is not None else -1, int(pad_token_id), 1 if seed is not None else 0,
+            seed.data_ptr() if seed is not None else None, _stream_ptr())
+    if stat_probs is None:
+        _C.check(_C.lib().bf_generate_step(probs.data_ptr(), *args), "bf_generate_step")
+    else:
+        need(stat_probs, "stat_probs", torch.float32, (B, V))
+        _C.check(_C.lib().bf_generate_step_stat_probs(probs.data_ptr(), stat_probs.data_ptr(), *args),
+                 "bf_generate_step_stat_probs")
     GENERATE_CALLS[0] += 1
 
 
@@ -1062,6 +1068,56 @@ def truncate_probs(probs: Tensor, top_k: Optional[int] = None, top_p: Optional[f
                                         float(top_p) if top_p is not None else 1.0,
                                         float(min_p) if min_p is not None else 0.0, _stream_ptr()), "bf_probs_truncate")
     TRUNCATE_CALLS[0] += 1
+    return out
+
+
+PROCESS_CALLS = [0]  # launches of bf_logits_process through process_logits (tests, diagnostics)
+PROCESS_MAX_V = 524288
+PROCESS_MAX_NGRAM = 64
+
+
+def process_logits(logits: Tensor, sequences: Tensor, T0: int, step: Union[int, Tensor], samples: int,
+                   repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None,
+                   min_new_tokens: Optional[int] = None, eos_token_id: Optional[int] = None, temperature: float = 1.0,
+                   out: Optional[Tensor] = None) -> Tensor:
+    """HF's logits processors, then the temperature, in one launch (bf_logits_process): the repetition penalty, the
+    no-repeat n-gram ban, the min_new_tokens eos ban and / temperature, bitwise transformers' chain on the fp32 upcast
+    (the contract: include/bayeformers_amd.h).  logits [samples * B, V] (bf16, fp16 or fp32, sample-major, unit column
+    stride, any row stride: the prefill's out.logits[:, -1, :] is read in place); sequences [B, seq_stride] int64, the
+    history of row b being sequences[b, :T0 + step]; step an int, or a device int64 tensor whose first element is read by
+    the kernel (sample_generate's step counter: a captured launch follows the replays).  None turns a processor off.
+    Writes `out` (contiguous fp32 [samples * B, V]) or a new tensor, and returns it.  No host synchronisation:
+    capturable."""
+    _require_device(logits, "process_logits: logits")
+    if logits.dim() != 2 or logits.dtype not in _TORCH2BF or logits.stride(1) != 1 or logits.shape[1] < 1:
+        raise _C.BayeFormersAMDError("process_logits: logits must be bf16, fp16 or fp32 [R, V] with unit column stride")
+    R, V = logits.shape
+    if V > PROCESS_MAX_V:
+        raise _C.BayeFormersAMDError(f"process_logits: V={V} exceeds {PROCESS_MAX_V}")
+    if sequences.dim() != 2 or sequences.dtype != torch.int64 or sequences.stride(1) != 1 \
+            or sequences.device != logits.device:
+        raise _C.BayeFormersAMDError(f"process_logits: sequences must be int64 [B, T] with contiguous rows on "
+                                     f"{logits.device}")
+    B = sequences.shape[0]
+    if R != int(samples) * B:
+        raise _C.BayeFormersAMDError(f"process_logits: logits has {R} rows, not samples * B = {int(samples) * B}")
+    if isinstance(step, Tensor):
+        if step.dtype != torch.int64 or step.numel() < 1 or step.device != logits.device:
+            raise _C.BayeFormersAMDError(f"process_logits: a device step must be an int64 tensor on {logits.device}")
+        d_step, host_step = step.data_ptr(), 0
+    else:
+        d_step, host_step = None, int(step)
+    if out is None:
+        out = torch.empty((R, V), dtype=torch.float32, device=logits.device)
+    elif out.shape != (R, V) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != logits.device:
+        raise _C.BayeFormersAMDError(f"process_logits: out must be contiguous fp32 [{R}, {V}] on {logits.device}")
+    _C.check(_C.lib().bf_logits_process(logits.data_ptr(), _TORCH2BF[logits.dtype], R, V, logits.stride(0),
+                                        out.data_ptr(), sequences.data_ptr(), B, sequences.stride(0), int(T0), d_step,
+                                        host_step, float(repetition_penalty) if repetition_penalty is not None else 1.0,
+                                        int(no_repeat_ngram_size or 0), int(min_new_tokens or 0),
+                                        int(eos_token_id) if eos_token_id is not None else -1, float(temperature),
+                                        _stream_ptr()), "bf_logits_process")
+    PROCESS_CALLS[0] += 1
     return out
 
 

@@ -11,6 +11,7 @@ over the ranks of a torch.distributed group: rank r runs the global sample indic
 all-reduce (RCCL over xGMI on MI355X) of the packed [sum of outputs | sum log_prior | sum lvp] buffer finishes the
 step.  The message is KB-sized, i.e. latency-bound: one collective per step, on the compute stream.
 """
+import math
 import numbers
 from dataclasses import dataclass, fields
 from typing import Any, Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
@@ -761,7 +762,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None,
                     keep_weights: bool = False, max_bytes: Optional[int] = None, static_cache: bool = False,
                     graph: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                    min_p: Optional[float] = None) -> Generation:
+                    min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
+                    no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -776,7 +778,19 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     are in include/bayeformers_amd.h), on the one row all S samples share; the draw is from the renormalised kept set.
     top_k must be an int >= 1, top_p in (0, 1], min_p in [0, 1]; None, top_k >= V, top_p = 1 and min_p = 0 launch
     nothing.  The statistics keep their meaning: the entropies, the MI and token_prob are those of the unfiltered,
-    temperature-scaled predictive (a kept probability is bitwise the unfiltered one).  Rows past eos_token_id emit
+    temperature-scaled predictive (a kept probability is bitwise the unfiltered one).
+
+    repetition_penalty, no_repeat_ngram_size and min_new_tokens are HF's logits processors, in HF's order and bitwise
+    HF's chain on the fp32 upcast of each sample's logits (then / temperature): every token already in the row's
+    sequence (prompt, padding and pads of finished rows included) is penalised once, l < 0 ? l * θ : l / θ; a token that
+    would repeat an n-gram of the sequence is banned; eos_token_id is banned while fewer than min_new_tokens tokens were
+    generated.  They act on the S sample rows of a batch row alike, in greedy decoding as in sampling (before top_k /
+    top_p / min_p): one bf_logits_process launch per step (ops.process_logits; contract in include/bayeformers_amd.h)
+    and a second `mc_predictive` on the processed logits, whose model-average row chooses the token.  The statistics and
+    token_prob stay those of the unprocessed, temperature-scaled predictive.  repetition_penalty must be finite and
+    positive, no_repeat_ngram_size an int in [0, 64], min_new_tokens an int >= 0 and, when positive, needs
+    eos_token_id.  None, repetition_penalty = 1, no_repeat_ngram_size = 0 and min_new_tokens = 0 (or a step at or past
+    min_new_tokens) launch nothing: the Generation is bitwise the one without them.  Rows past eos_token_id emit
     pad_token_id (default: eos_token_id).  No host synchronisation per step except the all-finished check, and none
     without eos_token_id.  Single process, eval mode and no gradient only.
 
@@ -802,6 +816,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     if not temperature > 0.0:
         raise ValueError(f"sample_generate: temperature={temperature} (must be positive)")
     truncation = _truncation(top_k, top_p, min_p, do_sample)
+    processors = _processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id)
     static_cache = bool(static_cache) or bool(graph)
     if static_cache and group is not None:
         raise ValueError("sample_generate: static_cache / graph generation runs in a single process (group must be None)")
@@ -824,7 +839,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     if static_cache:
         return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
                                 eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph),
-                                truncation)
+                                truncation, processors)
     S, n = samples, max_new_tokens
     B, T0 = input_ids.shape
     dev = input_ids.device
@@ -848,10 +863,11 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
             if temperature != 1.0:
                 logits = logits.float() / temperature
             pred = mc_predictive(logits)
+            choice = _processed(out, pred, processors, t, sequences, T0, S, eos_token_id, temperature)
             if do_sample:
-                tok = torch.multinomial(_truncated(pred.probs, truncation), 1, generator=generator).squeeze(1)
+                tok = torch.multinomial(_truncated(choice.probs, truncation), 1, generator=generator).squeeze(1)
             else:
-                tok = pred.prediction
+                tok = choice.prediction
             step = torch.stack([pred.predictive_entropy, pred.expected_entropy, pred.mutual_information,
                                 pred.probs.gather(1, tok[:, None]).squeeze(1)])
             if eos_token_id is not None:
@@ -887,6 +903,48 @@ def _truncation(top_k, top_p, min_p, do_sample: bool) -> Optional[Tuple[Optional
     p = float(top_p) if top_p is not None and top_p < 1.0 else None
     m = float(min_p) if min_p is not None and min_p > 0.0 else None
     return (k, p, m) if (k, p, m) != (None, None, None) else None
+
+
+_MAX_NGRAM = 64  # bf_logits_process's cap on no_repeat_ngram_size
+
+
+def _processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens,
+                eos_token_id) -> Optional[Tuple[float, int, int]]:
+    """sample_generate's checked (repetition_penalty, no_repeat_ngram_size, min_new_tokens), the no-op settings as
+    (1.0, 0, 0); None when all are no-ops."""
+    theta = repetition_penalty
+    if theta is not None and (isinstance(theta, bool) or not isinstance(theta, numbers.Real) or
+                              not math.isfinite(theta) or not theta > 0.0):
+        raise ValueError(f"sample_generate: repetition_penalty={theta!r} (must be finite and positive)")
+    for name, v, hi in (("no_repeat_ngram_size", no_repeat_ngram_size, _MAX_NGRAM), ("min_new_tokens", min_new_tokens, None)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0 or
+                              (hi is not None and v > hi)):
+            raise ValueError(f"sample_generate: {name}={v!r} (an int >= 0{f' and <= {hi}' if hi else ''})")
+    if min_new_tokens and eos_token_id is None:
+        raise ValueError("sample_generate: min_new_tokens bans eos_token_id: it needs an eos_token_id")
+    p = (float(theta) if theta is not None else 1.0, int(no_repeat_ngram_size or 0), int(min_new_tokens or 0))
+    return p if p != (1.0, 0, 0) else None
+
+
+def _processing_at(processors, t: int) -> bool:
+    """Whether step t launches the processors: a penalty or an n-gram ban acts at every step, the eos ban before
+    min_new_tokens only."""
+    return processors is not None and (processors[0] != 1.0 or processors[1] > 0 or t < processors[2])
+
+
+def _processed(out, pred: "Predictive", processors, t, sequences: Tensor, T0: int, S: int, eos_token_id,
+               temperature: float, step: Optional[Tensor] = None) -> "Predictive":
+    """The predictive a step's token is chosen from: `pred` itself when no processor acts at step t, else the predictive
+    of the last position's logits processed by one bf_logits_process launch (at the device step `step` when given)."""
+    if not _processing_at(processors, t):
+        return pred
+    from . import ops
+
+    theta, ngram, m = processors
+    raw = out.logits[:, -1, :]
+    processed = ops.process_logits(raw, sequences, T0, step if step is not None else t, S, theta, ngram, m,
+                                   eos_token_id, temperature)
+    return mc_predictive(processed.view(S, sequences.shape[0], -1))
 
 
 def _truncated(probs: Tensor, truncation) -> Tensor:
@@ -929,10 +987,12 @@ def _static_cache(model: Model, capacity: int):
 def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, do_sample: bool,
                      temperature: float, eos_token_id: Optional[int], pad_token_id: int,
                      generator: Optional[torch.Generator], keep_weights: bool, max_bytes: Optional[int],
-                     graph: bool, truncation=None) -> Generation:
+                     graph: bool, truncation=None, processors=None) -> Generation:
     """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
     static one), then decode steps of one shape whose bookkeeping is bf_generate_step (after bf_probs_truncate with a
-    truncation: the step's inverse-CDF draw over the filtered, unnormalised row samples the renormalised kept set)."""
+    truncation: the step's inverse-CDF draw over the filtered, unnormalised row samples the renormalised kept set; with
+    logits processors, bf_logits_process at the device step and a second mc_predictive choose the token, and
+    bf_generate_step_stat_probs reads its probability from the unprocessed row)."""
     from transformers import DynamicCache
 
     from . import ops
@@ -965,18 +1025,19 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
         positions = torch.full((S * B, 1), T0 - 1, dtype=torch.long, device=dev)
         full_mask = None
 
-    def epilogue(out):
+    def epilogue(out, t):
         logits = out.logits[:, -1, :].reshape(S, B, -1)
         if temperature != 1.0:
             logits = logits.float() / temperature
         pred = mc_predictive(logits)
-        ops.generate_step(_truncated(pred.probs, truncation), pred.predictive_entropy, pred.expected_entropy, pred.mutual_information, S, state,
+        choice = _processed(out, pred, processors, t, sequences, T0, S, eos_token_id, temperature, step=state)
+        ops.generate_step(_truncated(choice.probs, truncation), pred.predictive_entropy, pred.expected_entropy, pred.mutual_information, S, state,
                           sequences, T0, stats, finished, lengths, next_ids.view(-1), positions.view(-1), eos_token_id,
-                          pad_token_id, seed)
+                          pad_token_id, seed, stat_probs=pred.probs if choice is not pred else None)
 
-    def decode():
+    def decode(t):
         epilogue(model(input_ids=next_ids, attention_mask=full_mask, position_ids=positions, past_key_values=static,
-                       use_cache=True))
+                       use_cache=True), t)
 
     def all_finished():
         return eos_token_id is not None and bool(finished.all())
@@ -988,16 +1049,21 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
         for i, layer in enumerate(dynamic.layers):  # the prompt's keys and values fill the static cache's first T0 slots
             static.update(layer.keys, layer.values, i)
         del dynamic
-        epilogue(out)
+        epilogue(out, 0)
         del out
         t = 1
         if n > 1 and not all_finished():
-            decode()  # eagerly: plans, workspaces and the kept weights' launches are set up outside any capture
+            decode(1)  # eagerly: plans, workspaces and the kept weights' launches are set up outside any capture
             t = 2
+        # min_new_tokens alone: eager steps until its eos ban lifts, so the captured step has the launches of every replay
+        settled = processors[2] if processors is not None and processors[:2] == (1.0, 0) else 0
+        while graph and t < min(n, settled) and not all_finished():
+            decode(t)
+            t += 1
         if graph and t < n and not all_finished():
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                decode()
+                decode(t)
             replays = 0
             while t < n:
                 g.replay()
@@ -1006,6 +1072,6 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
                     break
             del g
         while t < n and not all_finished():
-            decode()
+            decode(t)
             t += 1
     return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])

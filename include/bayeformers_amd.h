@@ -484,6 +484,47 @@ int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, co
 int bf_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
                       float min_p, void* stream);
 
+/* ---- logits processors: repetition penalty, no-repeat n-grams, min_new_tokens, temperature ------------------------------
+ * transformers' processor chain of generate(), restated exactly, then its temperature warper, on R = S * B rows of V
+ * logits (sample-major: row r belongs to batch row b = r mod B) in one launch:
+ *     d_out[r, j] = f(x) / temperature,  x = the fp32 value of d_logits[r * row_stride + j] (dtype BF_DT_*),
+ *   where, with L = T0 + t the length of the history h = d_sequences[b * seq_stride + 0 .. L - 1] of row b:
+ *     1. RepetitionPenaltyLogitsProcessor(repetition_penalty = θ): if j occurs in h (once or more often)
+ *        x = x < 0 ? x * θ : x / θ;
+ *     2. NoRepeatNGramLogitsProcessor(no_repeat_ngram_size = n): if n >= 1 and L >= n, x = -inf when j ends a window
+ *        h[i .. i + n - 1] (0 <= i <= L - n) whose first n - 1 tokens equal h[L - n + 1 .. L - 1] (n = 1: every j in h);
+ *     3. MinNewTokensLengthLogitsProcessor(min_new_tokens = m, eos_token_id): x = -inf at j = eos_token_id if t < m;
+ *     4. TemperatureLogitsWarper: the result divided by temperature (a -inf stays -inf).
+ *   Each product and quotient is one correctly rounded fp32 operation (IEEE, no reciprocal): bitwise transformers' chain
+ *   on the fp32 upcast of the logits, as generate() processes them.  θ = 1, n = 0 and m = 0 turn a processor off;
+ *   temperature = 1 leaves the values as they are.  All S rows of a batch row get the same processing; the history is
+ *   what generate() passes as input_ids (the prompt's left padding and the pad tokens of finished rows included).
+ *   Token ids of h outside [0, V) are ignored: they are never penalised or banned (a window still compares them as
+ *   values).  A row in which every token is banned stays all -inf (only with a tiny V; bf_mc_predictive then gives it
+ *   zero probabilities and bf_generate_step takes token 0).
+ *   t is *d_step when d_step is not NULL (an int64 on the device: bf_generate_step's d_state, so one captured launch
+ *   follows a graph-replayed generation), else `step`; L is capped at seq_stride.
+ *   1 <= B <= 65535, R a multiple of B, 1 <= V <= 524288, row_stride >= V (elements), T0 >= 0, seq_stride >= 1 and,
+ *   with a host step, 0 <= step and T0 + step <= seq_stride; θ and temperature finite and positive; 0 <= n <= 64;
+ *   m >= 0, and m > 0 needs eos_token_id in [0, V).  d_out: contiguous fp32 [R][V], 4-byte aligned, not overlapping the
+ *   logits; the logits aligned to their element size, d_sequences and d_step to 8 bytes.  A grid of (2048-column chunk,
+ *   b); the bans and the seen set are LDS bitmaps set by atomic OR: deterministic, no host synchronisation,
+ *   capturable. */
+int bf_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
+                      const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0, const int64_t* d_step,
+                      int64_t step, float repetition_penalty, int64_t no_repeat_ngram_size, int64_t min_new_tokens,
+                      int64_t eos_token_id, float temperature, void* stream);
+
+/* bf_generate_step with the token's probability statistic (d_stats[3]) read from d_stat_probs [B][V] instead of d_probs:
+ * the token is chosen from d_probs (processed, perhaps truncated rows), the statistic is the probability of that token
+ * under d_stat_probs (the unprocessed model average).  Everything else is bf_generate_step's. */
+int bf_generate_step_stat_probs(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
+                                const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
+                                int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences,
+                                int64_t seq_stride, int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths,
+                                int64_t* d_next_ids, int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id,
+                                int do_sample, const uint64_t* d_seed, void* stream);
+
 /* ---- training mode: HuggingFace dropout inside the fused kernels ------------------------------------------------------
  * The reference trains with the wrapped model in .train() (/root/reference/examples/bert_glue.py:221,227-241): HF's
  * dropout (p = 0.1) acts on the attention probabilities and on every dense output in front of a residual + LayerNorm.

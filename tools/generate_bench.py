@@ -3,7 +3,9 @@
     python tools/generate_bench.py kernels [--out K.json] [--only N,K,S,M]
     python tools/generate_bench.py e2e [--out E.json] [--runs 3] [--new-tokens 256] [--mode dynamic|static|graph ...]
                                        [--top-k K] [--top-p P] [--min-p M]
-    python tools/generate_bench.py trace --mode keep|draw [--mode dynamic|static|graph] [--steps 32]   (under rocprofv3 --kernel-trace)
+                                       [--repetition-penalty R] [--no-repeat-ngram N] [--min-new-tokens M --eos-token-id E]
+    python tools/generate_bench.py trace --mode keep|draw [--mode dynamic|static|graph] [--steps 32] [the processors]
+                                                                                         (under rocprofv3 --kernel-trace)
     python tools/generate_bench.py analyze <kernel_trace.csv> [--steps 32]
 
 kernels: per layer shape of the DESIGN 4.5 decoder (N x K), S and M rows per sample, bf16: bf_gemm_nt_skinny on kept weights,
@@ -14,7 +16,9 @@ e2e: sample_generate on the DESIGN 4.5 decoder (8 layers, hidden 1024, 16 / 4 he
 512, bf16, fuse_attention; keep_weights off and on alternated in one process, `runs` each, and for each of them the decode
 paths named by --mode (default all three, alternated): dynamic (the default DynamicCache loop), static
 (static_cache=True) and graph (graph=True).  With --top-k / --top-p / --min-p every decode path runs do_sample=True twice,
-alternated: without the truncation (`..._sample`) and with it (`..._truncated`).
+alternated: without the truncation (`..._sample`) and with it (`..._truncated`).  With --repetition-penalty /
+--no-repeat-ngram / --min-new-tokens every decode path runs twice, alternated: without the logits processors (`..._plain`)
+and with them (`..._processed`), both with the truncation when one is given.
 trace: a prefill-only generation, a 2 s pause, then a generation of `new-tokens`; analyze splits a kernel trace of it at the
 pause and attributes (second - first) to the decode steps: GPU time per kernel class and the host gaps between kernels.
 """
@@ -101,7 +105,7 @@ def _decoder():
 PATHS = {"dynamic": {}, "static": {"static_cache": True}, "graph": {"graph": True}}
 
 
-def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None):
+def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None, processors=None):
     import bayeformers_amd as bf
     from bayeformers_amd.sampling import sample_generate
 
@@ -109,6 +113,9 @@ def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None)
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     variants = {"": {}} if not truncation else {"_sample": dict(do_sample=True),
                                                 "_truncated": dict(do_sample=True, **truncation)}
+    if processors:
+        base = variants["_truncated"] if truncation else {}
+        variants = {"_plain": base, "_processed": dict(base, **processors)}
     name = lambda keep, path, v="": (("keep_weights" if keep else "draw_per_step") + ("" if path == "dynamic" else "_" + path)
                                      + v)
     res = {name(k, p, v): [] for k in (False, True) for p in paths for v in variants}
@@ -127,7 +134,8 @@ def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None)
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
                         gen = sample_generate(bmodel, ids, samples=4, max_new_tokens=new_tokens, keep_weights=keep,
-                                              generator=torch.Generator(device="cuda").manual_seed(3) if kw else None,
+                                              generator=torch.Generator(device="cuda").manual_seed(3)
+                                              if kw.get("do_sample") else None,
                                               **PATHS[path], **kw)
                         torch.cuda.synchronize()
                         dt = time.perf_counter() - t0
@@ -143,12 +151,12 @@ def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None)
     return res
 
 
-def trace(mode, new_tokens, path="dynamic"):
+def trace(mode, new_tokens, path="dynamic", processors=None):
     from bayeformers_amd.sampling import sample_generate
 
     bmodel = _decoder()
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
-    kw = dict(keep_weights=mode == "keep", **PATHS[path])
+    kw = dict(keep_weights=mode == "keep", **PATHS[path], **(processors or {}))
     with torch.no_grad():
         sample_generate(bmodel, ids, samples=4, max_new_tokens=4, **kw)  # warm-up
         torch.cuda.synchronize()
@@ -206,7 +214,14 @@ def main():
     ap.add_argument("--top-k", type=int, default=None)
     ap.add_argument("--top-p", type=float, default=None)
     ap.add_argument("--min-p", type=float, default=None)
+    ap.add_argument("--repetition-penalty", type=float, default=None)
+    ap.add_argument("--no-repeat-ngram", type=int, default=None)
+    ap.add_argument("--min-new-tokens", type=int, default=None)
+    ap.add_argument("--eos-token-id", type=int, default=None)
     a = ap.parse_args()
+    processors = {k: v for k, v in (("repetition_penalty", a.repetition_penalty), ("no_repeat_ngram_size", a.no_repeat_ngram),
+                                    ("min_new_tokens", a.min_new_tokens), ("eos_token_id", a.eos_token_id))
+                  if v is not None}
     if a.what == "analyze":
         res = analyze(a.path, a.steps)
     else:
@@ -217,9 +232,9 @@ def main():
         paths = [m for m in modes if m in PATHS] or None
         if a.what == "e2e":
             truncation = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p), ("min_p", a.min_p)) if v is not None}
-            res = e2e(a.runs, a.new_tokens, paths or ("dynamic", "static", "graph"), truncation)
+            res = e2e(a.runs, a.new_tokens, paths or ("dynamic", "static", "graph"), truncation, processors)
         else:
-            trace("draw" if "draw" in modes else "keep", a.steps + 1, (paths or ["dynamic"])[-1])
+            trace("draw" if "draw" in modes else "keep", a.steps + 1, (paths or ["dynamic"])[-1], processors)
             return
     print(json.dumps(res, indent=1))
     if a.out:
