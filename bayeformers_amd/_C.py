@@ -110,6 +110,12 @@ SYMBOLS = {
     "bf_attention_decode_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
     "bf_attention_decode_workspace_bytes": (_i64, [_vp]),
     "bf_attention_decode_gqa_len": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
+    # the sliding-window siblings: the same arguments plus int32 window before scaling
+    "bf_attention_fwd_gqa_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp]),
+    "bf_attention_bwd_gqa_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i,
+                                         ctypes.c_float, _vp]),
+    "bf_attention_decode_gqa_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp]),
+    "bf_attention_decode_gqa_len_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp]),
     "bf_generate_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                               _i64, _i, _vp, _vp]),
     "bf_generate_step_stat_probs": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp,

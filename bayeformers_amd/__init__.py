@@ -348,7 +348,8 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     # says with is_causal, else — with no mask — the module's own flag (HF decoders set module.is_causal and pass no mask
     # when nothing is padded); an explicit is_causal wins over the module flag, as in the framework's sdpa_attention_forward
     explicit = kwargs.get("is_causal", None)
-    causal = bool(getattr(attention_mask, "_bf_causal", False) or getattr(attention_mask, "_bf_decode", False)) or (
+    causal = bool(getattr(attention_mask, "_bf_causal", False) or getattr(attention_mask, "_bf_decode", False)
+                  or getattr(attention_mask, "_bf_window", None) is not None) or (
         bool(explicit) if explicit is not None else (attention_mask is None and bool(getattr(module, "is_causal", False))))
     if causal:
         return _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs)
@@ -388,37 +389,49 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     key lengths with no mask or _padding_mask_interface's causal mask; a decode step against a KV cache (fewer than 17
     new queries, no gradient, no dropout) on bf_attention_decode_gqa, or on bf_attention_decode_gqa_len when the cache has
     a fixed capacity (the mask carries the filled length `_bf_kv_len`); other masks, longer cached chunks and attention
-    dropout go to the framework's scaled-dot-product attention."""
+    dropout go to the framework's scaled-dot-product attention.  A sliding-window mask (`_bf_window`) takes the window
+    siblings of the same entries, unless the module's own `sliding_window` argument disagrees with it or the call carries
+    attention sinks (`s_aux`) or logit soft-capping (`softcap`), which the kernels do not apply: those go to the framework."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
 
+    window = getattr(attention_mask, "_bf_window", None) if attention_mask is not None else None
+    if window is not None and (("sliding_window" in kwargs and kwargs["sliding_window"] != window)
+                               or kwargs.get("s_aux", None) is not None or kwargs.get("softcap", None) is not None):
+        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     kv_len = getattr(attention_mask, "_bf_kv_len", None) if attention_mask is not None else None
+    # the keys a decode step reads: all Tk, or with a window the ~W + Tq - 1 some query sees (decode_kernel_wins' Tk)
+    read = key.shape[2] if window is None else min(key.shape[2], window + query.shape[2] - 1)
     if kv_len is not None:  # a step against a fixed-capacity cache: _padding_mask_interface's mask carries the fill
         key_mask = getattr(attention_mask, "_bf_key_mask", None)
         if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
                 and ops.attention_decode_supported(query, key, value)
-                and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3])
+                and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], read, query.shape[3])
                 and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2]))):
             scale = scaling if scaling is not None else query.shape[-1] ** -0.5
             return ops.attention_forward_decode_len(query, key, value, kv_len, key_mask, scale,
-                                                    getattr(attention_mask, "_bf_mask_off", None)), None
+                                                    getattr(attention_mask, "_bf_mask_off", None), window=window), None
         # (the bool mask hides the keys past the fill: the framework's attention over the whole capacity is exact)
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
             and ops.attention_decode_supported(query, key, value)
-            and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3])):
+            and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], read, query.shape[3])):
         # no mask: nothing padded (a one-query step sees every cached key); else only the mask _padding_mask_interface built
         ready = attention_mask is None or bool(getattr(attention_mask, "_bf_decode", False))
         key_mask = getattr(attention_mask, "_bf_key_mask", None) if attention_mask is not None else None
         if ready and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])):
             mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
             scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-            return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off), None
+            return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off, window=window), None
     key_mask = mask_off = None
     usable = (dropout == 0.0 and query.shape[2] == key.shape[2]
               and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1]))
-    if usable and attention_mask is not None:
+    if usable and window is not None:  # the sliding mask of the cache-free sequence (key mask None: nothing padded)
+        key_mask = getattr(attention_mask, "_bf_key_mask", None)
+        usable = key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])
+        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+    elif usable and attention_mask is not None:
         key_mask = getattr(attention_mask, "_bf_key_mask", None)
         usable = getattr(attention_mask, "_bf_causal", False) and key_mask is not None and \
             tuple(key_mask.shape) == (query.shape[0], key.shape[2])
@@ -428,9 +441,96 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
             attention_mask = attention_mask.to(query.dtype)
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+    if window is not None:
+        if need_grad:
+            return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True, window), None
+        return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off, window=window), None
     if need_grad:
         return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True), None
     return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off), None
+
+
+def _sliding_window_of(mask_function):
+    """W when mask_function is exactly transformers' sliding_window_causal_mask_function(W) — and_masks over the two
+    functions (sliding_window_overlay(W)'s inner function, causal_mask_function) and nothing else — else None."""
+    from transformers import masking_utils as mu
+
+    def cell(fn, name):
+        code = getattr(fn, "__code__", None)
+        if code is None or name not in code.co_freevars or fn.__closure__ is None:
+            return None
+        return fn.__closure__[code.co_freevars.index(name)].cell_contents
+
+    if getattr(mask_function, "__code__", None) is not mu.and_masks(mu.causal_mask_function).__code__:
+        return None
+    fns = cell(mask_function, "mask_functions")
+    if not isinstance(fns, tuple) or len(fns) != 2 or fns[1] is not mu.causal_mask_function:
+        return None
+    if getattr(fns[0], "__code__", None) is not mu.sliding_window_overlay(1).__code__:
+        return None
+    w = cell(fns[0], "sliding_window")
+    return w if isinstance(w, int) and not isinstance(w, bool) and w >= 1 else None
+
+
+def _sliding_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, attention_mask, **kwargs):
+    """The three sliding-window causal masks _padding_mask_interface builds on the device (NotImplemented: not one of
+    them; None: sdpa_mask's answer when the window hides nothing and nothing is padded).
+    Query i (index q_offset + i) sees key j (index kv_offset + j) iff q_offset + i - window < kv_offset + j <= q_offset + i
+    and the key is not padding — sdpa_mask's [B, 1, Tq, Tk] bool mask, carrying `_bf_window` and the key mask."""
+    local_size = kwargs.get("local_size", None)
+    if kwargs.get("use_vmap", False) or (local_size is not None and local_size != window) or q_length is None \
+            or kv_length is None or not 0 < q_length <= kv_length:
+        return NotImplemented
+    if isinstance(q_offset, torch.Tensor):  # a fixed-capacity cache (see the causal case below): q_offset is its fill
+        if kv_offset != 0 or not (attention_mask is None or (attention_mask.dim() == 2
+                                                              and attention_mask.shape == (batch_size, kv_length))):
+            return NotImplemented
+        device = q_offset.device
+        keys = torch.arange(kv_length, device=device)
+        last = q_offset.reshape(()) + torch.arange(q_length, device=device)  # each query's own index
+        tri = (keys[None, :] <= last[:, None]) & (keys[None, :] > last[:, None] - window)
+        visible = None if attention_mask is None else (attention_mask if attention_mask.dtype == torch.bool
+                                                       else attention_mask != 0)
+        out = _with_keys(tri, visible, batch_size, q_length, kv_length)
+        out._bf_decode = True
+        out._bf_kv_len = (q_offset.reshape(()) + q_length).reshape(1)
+        out._bf_window = window
+        return out
+    if not (isinstance(q_offset, int) and isinstance(kv_offset, int) and kv_offset >= 0
+            and q_offset - kv_offset == kv_length - q_length):
+        return NotImplemented
+    if attention_mask is not None and not (attention_mask.dim() == 2
+                                           and attention_mask.shape == (batch_size, kv_offset + kv_length)):
+        return NotImplemented
+    if attention_mask is None and kwargs.get("allow_is_causal_skip", True) and kv_length < window \
+            and (q_length == 1 or q_length == kv_length):
+        return None  # as sdpa_mask answers: the window hides nothing, module.is_causal routes the call
+    device = attention_mask.device if attention_mask is not None else kwargs.get("device", "cpu")
+    keys = torch.arange(kv_offset, kv_offset + kv_length, device=device)
+    last = torch.arange(q_offset, q_offset + q_length, device=device)
+    tri = (keys[None, :] <= last[:, None]) & (keys[None, :] > last[:, None] - window)
+    visible = None
+    if attention_mask is not None:
+        visible = attention_mask[:, kv_offset:kv_offset + kv_length]
+        visible = visible if visible.dtype == torch.bool else visible != 0
+    out = _with_keys(tri, visible, batch_size, q_length, kv_length)
+    if q_length < kv_length:
+        out._bf_decode = True  # a step against a cache (bottom-right aligned)
+    out._bf_window = window
+    return out
+
+
+def _with_keys(tri, visible, batch_size, q_length, kv_length):
+    """tri [Tq, Tk] & the padding key mask visible [B, Tk] (None: nothing padded) as [B, 1, Tq, Tk], carrying the
+    additive fp32 key mask and the device flag "nothing is hidden" (both None without padding)."""
+    if visible is None:
+        out = tri[None, None, :, :].expand(batch_size, 1, q_length, kv_length)
+        out._bf_key_mask = out._bf_mask_off = None
+        return out
+    out = tri[None, None, :, :] & visible[:, None, None, :]
+    out._bf_key_mask = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
+    out._bf_mask_off = visible.all().reshape(1)
+    return out
 
 
 def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=0, kv_offset=0, mask_function=None,
@@ -447,8 +547,18 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     A step against a fixed-capacity cache (q_offset a device tensor: the fill of a transformers StaticCache, kv_length its
     capacity) gets the [B, 1, Tq, capacity] bool mask built on the device (causal from q_offset, the keys past the fill
     hidden) with the key mask and a snapshot of the fill after this step, `_bf_kv_len`, for bf_attention_decode_gqa_len.
+    A sliding-window causal mask (exactly transformers' sliding_window_causal_mask_function(W)) is built the same three
+    ways — the cache-free sequence, a step against a cache (a DynamicSlidingWindowLayer's kv_offset > 0 included: its
+    key mask is the 2-D mask's slice at kv_offset) and a fixed-capacity cache — and carries `_bf_window = W` for the
+    window entries; it is never None when the window hides something.
     Anything else (4-D masks, extra mask functions, other offsets) goes to the framework's scaled-dot-product mask."""
     from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
+
+    window = _sliding_window_of(mask_function) if mask_function is not causal_mask_function else None
+    if window is not None:
+        out = _sliding_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, attention_mask, **kwargs)
+        if out is not NotImplemented:
+            return out
 
     if (mask_function is causal_mask_function and isinstance(q_offset, torch.Tensor) and kv_offset == 0
             and q_length is not None and kv_length is not None and 0 < q_length <= kv_length

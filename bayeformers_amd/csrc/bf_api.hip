@@ -513,6 +513,36 @@ int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_
                                               scaling, (hipStream_t)stream);
 }
 
+int bf_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape,
+                                int32_t window, float scaling, void* stream) {
+    return bf_launch_attention_fwd_gqa_window(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, scaling,
+                                              (hipStream_t)stream);
+}
+
+int bf_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                int32_t window, float scaling, void* stream) {
+    return bf_launch_attention_bwd_gqa_window(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk,
+                                              d_dv, dtype, shape, window, scaling, (hipStream_t)stream);
+}
+
+int bf_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                   const uint8_t* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                   const bf_attn_decode_t* shape, int32_t window, float scaling, void* stream) {
+    return bf_launch_attention_decode_gqa_window(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_workspace, dtype, shape, window,
+                                                 scaling, (hipStream_t)stream);
+}
+
+int bf_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                       int dtype, const bf_attn_decode_t* shape, int32_t window, float scaling,
+                                       void* stream) {
+    return bf_launch_attention_decode_gqa_len_window(d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype,
+                                                     shape, window, scaling, (hipStream_t)stream);
+}
+
 int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
                      const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
                      int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,

@@ -43,6 +43,7 @@ struct DecodeParams {
     long long qs[3], ks[3], vs[3];  // (batch, head, token) element strides
     const int64_t* kv_len;          // nullable device scalar: the filled keys L (Tk is then the capacity)
     int N, Tq, Tk, H, Hkv, group, R, nsplit, split_keys;
+    int window;                     // LOCAL: query i (index L - Tq + i) sees keys L - Tq + i - window + 1 .. L - Tq + i
     long long want;                 // the split count the grid asks for (decode_split), the kernel's rule for L
     float scale_log2e;
 };
@@ -71,7 +72,7 @@ Split decode_split(const bf_attn_decode_t* s) {
     return Split{(tiles + per - 1) / per, per * KT};
 }
 
-template <typename T, int HD>
+template <typename T, int HD, bool LOCAL>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -88,13 +89,17 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
     const int li = lane & 15, lg = lane >> 4;
     const int split = blockIdx.x, nk = blockIdx.y, n = nk / p.Hkv, g = nk % p.Hkv;
     int L = p.Tk, split_keys = p.split_keys;
-    if (p.kv_len) {  // a fixed-capacity cache filled to L: L's own split rule, within the grid's nsplit splits
+    if (p.kv_len) {  // a fixed-capacity cache filled to L
         const int64_t len = *p.kv_len;
         L = len < 0 ? 0 : (len > p.Tk ? p.Tk : (int)len);
-        const int tiles = (L + KT - 1) / KT;
-        split_keys = max(max(split_tiles(L, p.want), (tiles + p.nsplit - 1) / p.nsplit), 1) * KT;
     }
-    const int k_lo = split * split_keys, k_hi = min(L, k_lo + split_keys);
+    // LOCAL: the keys some query sees start at lo (the first query's window); the splits are laid over [lo, L)
+    const int lo = LOCAL ? max(0, L - p.Tq - p.window + 1) : 0;
+    if (p.kv_len) {  // the range's own split rule, within the grid's nsplit splits
+        const int tiles = (L - lo + KT - 1) / KT;
+        split_keys = max(max(split_tiles(L - lo, p.want), (tiles + p.nsplit - 1) / p.nsplit), 1) * KT;
+    }
+    const int k_lo = lo + split * split_keys, k_hi = min(L, k_lo + split_keys);
     const int r = blockIdx.z * ROWS + wid * 16 + li;  // this lane's query row (its column of S^T and O^T)
     const bool wave_live = (int)blockIdx.z * ROWS + wid * 16 < p.R, row_ok = r < p.R;
     const int qi = row_ok ? r % p.Tq : 0, h = g * p.group + (row_ok ? r / p.Tq : 0);
@@ -159,7 +164,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int key = key0 + kbk * 16 + lg * 4 + j;
-                s[kbk][j] = (key < k_hi && key <= lim) ? fmaf(s[kbk][j], p.scale_log2e, mk[j]) : -INFINITY;
+                const bool seen = key < k_hi && key <= lim && (!LOCAL || key > lim - p.window);
+                s[kbk][j] = seen ? fmaf(s[kbk][j], p.scale_log2e, mk[j]) : -INFINITY;
                 mx = fmaxf(mx, s[kbk][j]);
             }
         }
@@ -241,7 +247,8 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(const DecodeParams p)
 template <typename T, int HD>
 void launch(const DecodeParams& p, hipStream_t stream) {
     const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
-    decode_kernel<T, HD><<<grid, 256, 0, stream>>>(p);
+    if (p.window) decode_kernel<T, HD, true><<<grid, 256, 0, stream>>>(p);
+    else decode_kernel<T, HD, false><<<grid, 256, 0, stream>>>(p);
     if (p.nsplit > 1) {
         const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
         decode_merge_kernel<T, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
@@ -283,9 +290,11 @@ int64_t bf_launch_attention_decode_workspace_bytes(const bf_attn_decode_t* shape
 
 namespace {
 
+// window 0: the plain entries; >= 1: the sliding-window ones
 int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
            const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
-           const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
+           const bf_attn_decode_t* shape, int window, float scaling, hipStream_t stream) {
+    if (window < 0) BF_FAIL("%s: window=%d must be at least 1", what, window);
     if (check_shape(what, shape, dtype)) return 1;
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
     if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_workspace) & 15)
@@ -312,6 +321,16 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
     p.split_keys = sp.keys;
     p.kv_len = d_kv_len;
     p.want = split_want(shape);
+    p.window = window < shape->Tk ? window : shape->Tk;  // (a wider window hides nothing)
+    if (window && !d_kv_len) {
+        // the keys [lo, Tk) some query sees, split by the shape's rule within the workspace's sp.n splits (the kernel's
+        // rule for a fixed-capacity cache at L = Tk); at lo == 0 these are the plain entry's splits
+        const int lo = std::max(0, shape->Tk - shape->Tq - p.window + 1), keys = shape->Tk - lo;
+        const int tiles = (keys + KT - 1) / KT;
+        const int per = std::max(std::max(split_tiles(keys, p.want), (tiles + sp.n - 1) / sp.n), 1);
+        p.nsplit = (tiles + per - 1) / per;
+        p.split_keys = per * KT;
+    }
     if (sp.n > 1) {
         p.part_o = reinterpret_cast<float*>(d_workspace);
         p.part_ml = p.part_o + (long long)sp.n * p.N * p.Hkv * p.R * shape->head_dim;
@@ -338,8 +357,17 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
 int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
                                    const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
                                    const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
-    return decode("bf_attention_decode_gqa", d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape,
+    return decode("bf_attention_decode_gqa", d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, 0,
                   scaling, stream);
+}
+
+int bf_launch_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                          const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                          const bf_attn_decode_t* shape, int window, float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_decode_gqa_window";
+    if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, window, scaling,
+                  stream);
 }
 
 int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
@@ -348,5 +376,16 @@ int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const v
                                        hipStream_t stream) {
     const char* what = "bf_attention_decode_gqa_len";
     if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
-    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, scaling, stream);
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, 0, scaling, stream);
+}
+
+int bf_launch_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                              const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
+                                              void* d_workspace, int dtype, const bf_attn_decode_t* shape, int window,
+                                              float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_decode_gqa_len_window";
+    if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, scaling,
+                  stream);
 }

@@ -41,11 +41,12 @@ struct GqaParams {
     void* dv;
     long long qs[3], ks[3], vs[3];  // (batch, head, token) element strides
     int B, T, H, Hkv, group;
+    int window;                     // LOCAL: query i sees keys i - window + 1 .. i (1 <= window <= T)
     float scale, scale_log2e;
 };
 
 // ---------------------------------------------------------------------------------------------------- forward
-template <typename T, int HD, int KT, bool CAUSAL, int MINB>
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, int MINB>
 __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -80,8 +81,9 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
     float run_max[2] = {-INFINITY, -INFINITY}, run_sum[2] = {0.f, 0.f};
 
     const int kend = CAUSAL ? (qt + 1) * TQ : p.T;
-    for (int key0 = 0; key0 < kend; key0 += KT) {
-        if (key0) __syncthreads();
+    const int kbeg = LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;  // the tile of the tile's first window key
+    for (int key0 = kbeg; key0 < kend; key0 += KT) {
+        if (key0 != kbeg) __syncthreads();
         stage<T, HD, KT, 256>(kb, p.ks[2], key0, ks, nullptr, tid);
         stage<T, HD, KT, 256>(vb, p.vs[2], key0, nullptr, vs, tid);
         if (mask && tid < KT / 4)
@@ -93,6 +95,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
         for (int qi = 0; qi < 2; ++qi) {
             const int qr0 = q0 + qi * 16;  // the block's first query
             if (CAUSAL && key0 > qr0 + 15) continue;  // the tile lies wholly above the diagonal for these 16 queries
+            if (LOCAL && key0 + KT - 1 < qr0 - p.window + 1) continue;  // ... or wholly before their windows
             f32x4_t s[NKB];
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -101,6 +104,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
                 for (int dh = 0; dh < NDH; ++dh) s[kbk] = Mfma<T>::run(row_frag<T, HD>(ks, kbk, dh, li, lg), qf[qi][dh], s[kbk]);
             }
             const bool diag = CAUSAL && key0 + KT - 1 > qr0;
+            const bool edge = LOCAL && key0 < qr0 + 16 - p.window;  // the tile crosses a window's lower edge
             float mx = -INFINITY;
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -110,6 +114,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
                 for (int j = 0; j < 4; ++j) {
                     s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) s[kbk][j] = -INFINITY;
+                    if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) s[kbk][j] = -INFINITY;
                     mx = fmaxf(mx, s[kbk][j]);
                 }
             }
@@ -156,7 +161,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
-template <typename T, int HD, int KT, bool CAUSAL>
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL>
 __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -209,8 +214,9 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
         for (int j = 0; j < NDB; ++j) dq[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int kend = CAUSAL ? (qt + 1) * TQ : p.T;
-    for (int key0 = 0; key0 < kend; key0 += KT) {
-        if (key0) __syncthreads();
+    const int kbeg = LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;
+    for (int key0 = kbeg; key0 < kend; key0 += KT) {
+        if (key0 != kbeg) __syncthreads();
         stage<T, HD, KT, 256>(kb, p.ks[2], key0, ks, kp, tid);
         stage<T, HD, KT, 256>(vb, p.vs[2], key0, vs, nullptr, tid);
         if (mask && tid < KT / 4)
@@ -221,6 +227,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
         for (int qi = 0; qi < 2; ++qi) {
             const int qr0 = q0 + qi * 16;
             if (CAUSAL && key0 > qr0 + 15) continue;
+            if (LOCAL && key0 + KT - 1 < qr0 - p.window + 1) continue;
             f32x4_t s[NKB], dp[NKB];
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -232,6 +239,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
                 }
             }
             const bool diag = CAUSAL && key0 + KT - 1 > qr0;
+            const bool edge = LOCAL && key0 < qr0 + 16 - p.window;
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
                 f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
@@ -240,6 +248,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
                 for (int j = 0; j < 4; ++j) {
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
+                    if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
                     s[kbk][j] = pr * (dp[kbk][j] - delta[qi]);  // dS^T
                 }
             }
@@ -262,7 +271,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dK, dV
-template <typename T, int HD, int QT, bool CAUSAL, int MINB>
+template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, int MINB>
 __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -298,13 +307,15 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
     for (int j = 0; j < NDB; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int qbeg = CAUSAL ? kt * TQ : 0;
+    // LOCAL: up to the query tile of the last query that sees the tile's last key
+    const int qend = LOCAL ? min(p.T, (kt * TQ + TQ - 1 + p.window - 1) / QT * QT + QT) : p.T;
     bool first = true;
     for (int h = g * p.group; h < (g + 1) * p.group; ++h) {  // the group's query heads, in order: a fixed summation order
         const T* qb = reinterpret_cast<const T*>(p.q) + b * p.qs[0] + h * p.qs[1];
         const T* dob = reinterpret_cast<const T*>(p.dout) + (long long)b * p.T * ostride + (long long)h * HD;
         const float* lse_g = p.lse + ((long long)b * p.H + h) * p.T;
         const float* del_g = p.delta + ((long long)b * p.H + h) * p.T;
-        for (int q0 = qbeg; q0 < p.T; q0 += QT) {
+        for (int q0 = qbeg; q0 < qend; q0 += QT) {
             if (!first) __syncthreads();
             first = false;
             stage<T, HD, QT, 512>(qb, p.qs[2], q0, qs, qp, tid);
@@ -315,6 +326,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
             }
             __syncthreads();
             if (CAUSAL && q0 + QT - 1 < wkey0) continue;  // every query of the tile precedes the wave's keys
+            if (LOCAL && q0 > wkey0 + 15 + p.window - 1) continue;  // ... or lies past all their windows
             f32x4_t s[NQB], dp[NQB];
 #pragma unroll
             for (int qbk = 0; qbk < NQB; ++qbk) {
@@ -326,6 +338,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
                 }
             }
             const bool diag = CAUSAL && q0 < wkey0 + 15;
+            const bool edge = LOCAL && q0 + QT - 1 > wkey0 + p.window - 1;  // some query lies past a key's window
 #pragma unroll
             for (int qbk = 0; qbk < NQB; ++qbk) {
                 const f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(lse_s + qbk * 16 + lg * 4);
@@ -334,6 +347,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
                 for (int j = 0; j < 4; ++j) {
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
                     if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
+                    if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
                     s[qbk][j] = pr;                          // P
                     dp[qbk][j] = pr * (dp[qbk][j] - d4[j]);  // dS
                 }
@@ -386,39 +400,44 @@ struct Shape<128> {
 // The tile index is the grid's SLOWEST dimension: the hardware hands consecutive workgroups to the 8 XCDs in turn, so with
 // the tiles fastest (as the BERT kernels order them) every XCD would get the tiles of one position — under a causal mask one
 // XCD all the heaviest — while tiles-slowest issues the heavy tiles of every (head, sequence) first, spread over all XCDs.
-template <typename T, int HD, bool CAUSAL>
+template <typename T, int HD, bool CAUSAL, bool LOCAL>
 void launch_fwd(const GqaParams& p, hipStream_t stream) {
     const dim3 grid(p.H, p.B, p.T / TQ);
-    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, Shape<HD>::FWD_MINB>), grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, Shape<HD>::FWD_MINB>), grid, dim3(256), 0, stream,
+                       p);
 }
 
-template <typename T, int HD, bool CAUSAL>
+template <typename T, int HD, bool CAUSAL, bool LOCAL>
 void launch_bwd(const GqaParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL>), dim3(p.H, p.B, p.T / TQ), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, Shape<HD>::DKV_MINB>), dim3(p.Hkv, p.B, p.T / TQ),
-                       dim3(512), 0, stream, p);
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL>), dim3(p.H, p.B, p.T / TQ), dim3(256), 0,
+                       stream, p);
+    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, Shape<HD>::DKV_MINB>),
+                       dim3(p.Hkv, p.B, p.T / TQ), dim3(512), 0, stream, p);
 }
 
-template <typename T, int HD, bool CAUSAL>
+template <typename T, int HD, bool CAUSAL, bool LOCAL = false>
 void launch(const GqaParams& p, bool bwd, hipStream_t stream) {
-    if (bwd) launch_bwd<T, HD, CAUSAL>(p, stream);
-    else launch_fwd<T, HD, CAUSAL>(p, stream);
+    if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL>(p, stream);
+    else launch_fwd<T, HD, CAUSAL, LOCAL>(p, stream);
 }
 
+// local: the sliding-window instantiations (causal only); the others are the kernels the plain entries always ran
 template <typename T>
-void launch(const GqaParams& p, int D, bool causal, bool bwd, hipStream_t stream) {
+void launch(const GqaParams& p, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
     if (D == 64) {
-        if (causal) launch<T, 64, true>(p, bwd, stream);
+        if (local) launch<T, 64, true, true>(p, bwd, stream);
+        else if (causal) launch<T, 64, true>(p, bwd, stream);
         else launch<T, 64, false>(p, bwd, stream);
     } else {
-        if (causal) launch<T, 128, true>(p, bwd, stream);
+        if (local) launch<T, 128, true, true>(p, bwd, stream);
+        else if (causal) launch<T, 128, true>(p, bwd, stream);
         else launch<T, 128, false>(p, bwd, stream);
     }
 }
 
-void dispatch(const GqaParams& p, int dtype, int D, bool causal, bool bwd, hipStream_t stream) {
-    if (dtype == BF_DT_BF16) launch<__bf16>(p, D, causal, bwd, stream);
-    else launch<_Float16>(p, D, causal, bwd, stream);
+void dispatch(const GqaParams& p, int dtype, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
+    if (dtype == BF_DT_BF16) launch<__bf16>(p, D, causal, local, bwd, stream);
+    else launch<_Float16>(p, D, causal, local, bwd, stream);
 }
 
 // Validates the shape and fills the parameters' shape part; returns 0 or the BF_FAIL status
@@ -462,17 +481,24 @@ bool bert_case(const bf_attn_gqa_t* s, long long* token_stride) {
     return !s->causal && s->H == s->Hkv && s->head_dim == 64 && ts >= (long long)s->H * 64;
 }
 
-}  // namespace
+// The window entries' extra arguments: causal shapes only, window >= 1 (clamped to T: a wider window hides nothing)
+int fill_window(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int window) {
+    if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    if (s->causal != 1) BF_FAIL("%s: a sliding window needs a causal shape (causal=%d)", what, s->causal);
+    p.window = window < p.T ? window : p.T;
+    return 0;
+}
 
-int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
-                                const bf_attn_gqa_t* shape, float scaling, hipStream_t stream) {
-    const char* what = "bf_attention_fwd_gqa";
+// window 0: the plain entries; >= 1: the sliding-window ones
+int fwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+            const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, int window,
+            float scaling, hipStream_t stream) {
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
     GqaParams p = {};
     if (fill_shape(what, p, shape, dtype, scaling)) return 1;
+    if (window && fill_window(what, p, shape, window)) return 1;
     long long ts;
-    if (bert_case(shape, &ts))
+    if (!window && bert_case(shape, &ts))
         return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape->B, shape->T, shape->H,
                                        64, ts, scaling, stream);
     if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
@@ -484,22 +510,22 @@ int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_
     p.mask_off = d_mask_off;
     p.out = d_out;
     p.lse = d_lse;
-    dispatch(p, dtype, shape->head_dim, shape->causal, false, stream);
+    dispatch(p, dtype, shape->head_dim, shape->causal, window > 0, false, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
-                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
-                                float scaling, hipStream_t stream) {
-    const char* what = "bf_attention_bwd_gqa";
+int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+            const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse, float* d_delta,
+            void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape, int window, float scaling,
+            hipStream_t stream) {
     if (!d_q || !d_k || !d_v || !d_out || !d_dout || !d_lse || !d_delta || !d_dq || !d_dk || !d_dv)
         BF_FAIL("%s: NULL argument", what);
     GqaParams p = {};
     if (fill_shape(what, p, shape, dtype, scaling)) return 1;
+    if (window && fill_window(what, p, shape, window)) return 1;
     long long ts;
-    if (bert_case(shape, &ts))
+    if (!window && bert_case(shape, &ts))
         return bf_launch_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype,
                                        shape->B, shape->T, shape->H, 64, ts, scaling, stream);
     const uintptr_t al = (uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_dout |
@@ -518,7 +544,41 @@ int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_
     p.dq = d_dq;
     p.dk = d_dk;
     p.dv = d_dv;
-    dispatch(p, dtype, shape->head_dim, shape->causal, true, stream);
+    dispatch(p, dtype, shape->head_dim, shape->causal, window > 0, true, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+}  // namespace
+
+int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
+                                const bf_attn_gqa_t* shape, float scaling, hipStream_t stream) {
+    return fwd_gqa("bf_attention_fwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, 0, scaling, stream);
+}
+
+int bf_launch_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
+                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_fwd_gqa_window";
+    if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    return fwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, scaling, stream);
+}
+
+int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                float scaling, hipStream_t stream) {
+    return bwd_gqa("bf_attention_bwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv,
+                   dtype, shape, 0, scaling, stream);
+}
+
+int bf_launch_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const unsigned char* d_mask_off, const void* d_out, const void* d_dout,
+                                       const float* d_lse, float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype,
+                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream) {
+    const char* what = "bf_attention_bwd_gqa_window";
+    if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    return bwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, shape,
+                   window, scaling, stream);
 }

@@ -239,6 +239,21 @@ int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const v
                                        const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
                                        void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
                                        hipStream_t stream);
+// the sliding-window siblings of the four above (window >= 1, causal shapes)
+int bf_launch_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
+                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream);
+int bf_launch_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const unsigned char* d_mask_off, const void* d_out, const void* d_dout,
+                                       const float* d_lse, float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype,
+                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream);
+int bf_launch_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                          const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                          const bf_attn_decode_t* shape, int window, float scaling, hipStream_t stream);
+int bf_launch_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                              const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
+                                              void* d_workspace, int dtype, const bf_attn_decode_t* shape, int window,
+                                              float scaling, hipStream_t stream);
 // one generation step's epilogue (bf_generate.hip)
 int bf_launch_generate_step(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
                             const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,

@@ -800,8 +800,9 @@ def _gqa_supported(q: Tensor, k: Tensor, v: Tensor, kv_heads: Optional[int]) -> 
                for t in (q, k, v))
 
 
-# launches of bf_attention_fwd_gqa / bf_attention_bwd_gqa from this process (a test can assert that the causal path ran)
-GQA_CALLS = {"fwd": 0, "bwd": 0}
+# launches of bf_attention_fwd_gqa / bf_attention_bwd_gqa from this process (a test can assert that the causal path ran);
+# "fwd_window" / "bwd_window": of their sliding-window siblings bf_attention_fwd_gqa_window / bf_attention_bwd_gqa_window
+GQA_CALLS = {"fwd": 0, "bwd": 0, "fwd_window": 0, "bwd_window": 0}
 
 
 def _gqa_shape(q: Tensor, k: Tensor, v: Tensor, causal: bool):
@@ -813,27 +814,35 @@ def _gqa_shape(q: Tensor, k: Tensor, v: Tensor, causal: bool):
 
 
 def attention_forward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float, causal: bool = True,
-                          mask_off: Optional[Tensor] = None, want_lse: bool = False):
+                          mask_off: Optional[Tensor] = None, want_lse: bool = False, window: Optional[int] = None):
     """Causal and / or grouped-query attention (bf_attention_fwd_gqa): q [B, H, T, D], k / v [B, Hkv, T, D] as described by
     attention_supported(..., causal=True); key_mask: additive fp32 [B, T] or None.  Returns [B, T, H, D] contiguous (a
-    query with no visible key gives 0) — and, with want_lse, the [B, H, T] fp32 log-sum-exp rows of the backward."""
+    query with no visible key gives 0) — and, with want_lse, the [B, H, T] fp32 log-sum-exp rows of the backward.
+    window: a sliding window of that many keys (bf_attention_fwd_gqa_window; causal only): query i sees keys
+    i - window + 1 .. i."""
     B, H, T, D = q.shape
     out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device) if want_lse else None
     shape = _gqa_shape(q, k, v, causal)
-    _C.check(_C.lib().bf_attention_fwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                           key_mask.data_ptr() if key_mask is not None else None,
-                                           mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
-                                           lse.data_ptr() if lse is not None else None, _TORCH2BF[q.dtype],
-                                           ctypes.byref(shape), float(scaling), _stream_ptr()), "bf_attention_fwd_gqa")
-    GQA_CALLS["fwd"] += 1
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+            mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
+            lse.data_ptr() if lse is not None else None, _TORCH2BF[q.dtype], ctypes.byref(shape))
+    if window is None:
+        _C.check(_C.lib().bf_attention_fwd_gqa(*args, float(scaling), _stream_ptr()), "bf_attention_fwd_gqa")
+        GQA_CALLS["fwd"] += 1
+    else:
+        _C.check(_C.lib().bf_attention_fwd_gqa_window(*args, int(window), float(scaling), _stream_ptr()),
+                 "bf_attention_fwd_gqa_window")
+        GQA_CALLS["fwd_window"] += 1
     return (out, lse) if want_lse else out
 
 
 def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], mask_off: Optional[Tensor],
-                           out: Tensor, grad_out: Tensor, lse: Tensor, scaling: float, causal: bool = True):
-    """Gradients of attention_forward_gqa (bf_attention_bwd_gqa): (dq [B, T, H, D], dk [B, T, Hkv, D], dv [B, T, Hkv, D]),
-    contiguous; dk / dv summed over the query heads of each group."""
+                           out: Tensor, grad_out: Tensor, lse: Tensor, scaling: float, causal: bool = True,
+                           window: Optional[int] = None):
+    """Gradients of attention_forward_gqa (bf_attention_bwd_gqa, or bf_attention_bwd_gqa_window with a window):
+    (dq [B, T, H, D], dk [B, T, Hkv, D], dv [B, T, Hkv, D]), contiguous; dk / dv summed over the query heads of each
+    group."""
     B, H, T, D = q.shape
     Hkv = k.shape[1]
     go = grad_out if (grad_out.dtype == q.dtype and grad_out.is_contiguous()) else grad_out.to(q.dtype).contiguous()
@@ -841,19 +850,23 @@ def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[T
     dkv = torch.empty((2, B, T, Hkv, D), dtype=q.dtype, device=q.device)
     delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
     shape = _gqa_shape(q, k, v, causal)
-    _C.check(_C.lib().bf_attention_bwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                           key_mask.data_ptr() if key_mask is not None else None,
-                                           mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
-                                           go.data_ptr(), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), dkv[0].data_ptr(),
-                                           dkv[1].data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(shape), float(scaling),
-                                           _stream_ptr()), "bf_attention_bwd_gqa")
-    GQA_CALLS["bwd"] += 1
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+            mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), go.data_ptr(), lse.data_ptr(),
+            delta.data_ptr(), dq.data_ptr(), dkv[0].data_ptr(), dkv[1].data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(shape))
+    if window is None:
+        _C.check(_C.lib().bf_attention_bwd_gqa(*args, float(scaling), _stream_ptr()), "bf_attention_bwd_gqa")
+        GQA_CALLS["bwd"] += 1
+    else:
+        _C.check(_C.lib().bf_attention_bwd_gqa_window(*args, int(window), float(scaling), _stream_ptr()),
+                 "bf_attention_bwd_gqa_window")
+        GQA_CALLS["bwd_window"] += 1
     return dq, dkv[0], dkv[1]
 
 
 # launches of bf_attention_decode_gqa from this process (a test can assert that a cached decode step ran on the kernel);
-# "len": of bf_attention_decode_gqa_len (a step against a fixed-capacity cache, attention_forward_decode_len)
-DECODE_CALLS = {"fwd": 0, "len": 0}
+# "len": of bf_attention_decode_gqa_len (a step against a fixed-capacity cache, attention_forward_decode_len);
+# "window" / "len_window": of their sliding-window siblings
+DECODE_CALLS = {"fwd": 0, "len": 0, "window": 0, "len_window": 0}
 DECODE_MAX_QUERIES = 16
 
 
@@ -902,12 +915,15 @@ def attention_decode_workspace_bytes(q: Tensor, k: Tensor, v: Tensor) -> int:
 
 
 def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
-                             mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+                             mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+                             window: Optional[int] = None) -> Tensor:
     """Causal attention of Tq new queries against a KV cache (bf_attention_decode_gqa): q [N, H, Tq, D], k / v
     [N, Hkv, Tk, D] as described by attention_decode_supported; query i sees keys 0 .. Tk - Tq + i.  key_mask: additive
     fp32 [N, Tk] or None; mask_off: optional 1-element device flag, true = the mask hides nothing.  Returns [N, Tq, H, D]
     contiguous (a query with no visible key gives 0).  The split partials go to `workspace` (uint8, at least
-    attention_decode_workspace_bytes) or to a fresh tensor of the caching allocator — either way capturable."""
+    attention_decode_workspace_bytes) or to a fresh tensor of the caching allocator — either way capturable.  window: a
+    sliding window of that many keys (bf_attention_decode_gqa_window): query i sees keys Tk - Tq + i - window + 1 ..
+    Tk - Tq + i; the workspace is the same."""
     _require_device(q, "attention_forward_decode: q")
     if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
             or k.shape[3] != q.shape[3]:
@@ -932,22 +948,28 @@ def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional
     if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
                                  or not key_mask.is_contiguous()):
         raise _C.BayeFormersAMDError("attention_forward_decode: key_mask must be contiguous fp32 [N, Tk]")
-    _C.check(_C.lib().bf_attention_decode_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                              key_mask.data_ptr() if key_mask is not None else None,
-                                              mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
-                                              ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype],
-                                              ctypes.byref(shape), float(scaling), _stream_ptr()), "bf_attention_decode_gqa")
-    DECODE_CALLS["fwd"] += 1
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+            mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), ws.data_ptr() if ws is not None else None,
+            _TORCH2BF[q.dtype], ctypes.byref(shape))
+    if window is None:
+        _C.check(_C.lib().bf_attention_decode_gqa(*args, float(scaling), _stream_ptr()), "bf_attention_decode_gqa")
+        DECODE_CALLS["fwd"] += 1
+    else:
+        _C.check(_C.lib().bf_attention_decode_gqa_window(*args, int(window), float(scaling), _stream_ptr()),
+                 "bf_attention_decode_gqa_window")
+        DECODE_CALLS["window"] += 1
     return out
 
 
 def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
                                  scaling: float, mask_off: Optional[Tensor] = None,
-                                 workspace: Optional[Tensor] = None) -> Tensor:
+                                 workspace: Optional[Tensor] = None, window: Optional[int] = None) -> Tensor:
     """attention_forward_decode over a fixed-capacity cache (bf_attention_decode_gqa_len): k / v [N, Hkv, capacity, D] of
     which the first L = kv_len keys are filled, kv_len a one-element int64 device tensor read by the kernel (keys past it
     are never read).  Query i sees keys 0 .. L - Tq + i; key_mask is [N, capacity].  One launch serves every L, so a
-    captured call replays correctly while the cache fills; at L == capacity it is bitwise attention_forward_decode."""
+    captured call replays correctly while the cache fills; at L == capacity it is bitwise attention_forward_decode.
+    window: a sliding window of that many keys (bf_attention_decode_gqa_len_window): query i sees keys
+    L - Tq + i - window + 1 .. L - Tq + i, and the key split is laid over the keys some query sees."""
     _require_device(q, "attention_forward_decode_len: q")
     if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
             or k.shape[3] != q.shape[3]:
@@ -974,14 +996,16 @@ def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor
     if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
                                  or not key_mask.is_contiguous()):
         raise _C.BayeFormersAMDError("attention_forward_decode_len: key_mask must be contiguous fp32 [N, Tk]")
-    _C.check(_C.lib().bf_attention_decode_gqa_len(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                                  key_mask.data_ptr() if key_mask is not None else None,
-                                                  mask_off.data_ptr() if mask_off is not None else None,
-                                                  kv_len.data_ptr(), out.data_ptr(),
-                                                  ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype],
-                                                  ctypes.byref(shape), float(scaling), _stream_ptr()),
-             "bf_attention_decode_gqa_len")
-    DECODE_CALLS["len"] += 1
+    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+            mask_off.data_ptr() if mask_off is not None else None, kv_len.data_ptr(), out.data_ptr(),
+            ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype], ctypes.byref(shape))
+    if window is None:
+        _C.check(_C.lib().bf_attention_decode_gqa_len(*args, float(scaling), _stream_ptr()), "bf_attention_decode_gqa_len")
+        DECODE_CALLS["len"] += 1
+    else:
+        _C.check(_C.lib().bf_attention_decode_gqa_len_window(*args, int(window), float(scaling), _stream_ptr()),
+                 "bf_attention_decode_gqa_len_window")
+        DECODE_CALLS["len_window"] += 1
     return out
 
 
@@ -1126,17 +1150,18 @@ class AttentionGqaFn(torch.autograd.Function):
     without it).  Keeps q, k, v, the output and one fp32 row statistic per query."""
 
     @staticmethod
-    def forward(ctx, q, k, v, key_mask, mask_off, scaling, causal=True):
-        out, lse = attention_forward_gqa(q, k, v, key_mask, scaling, causal, mask_off, want_lse=True)
+    def forward(ctx, q, k, v, key_mask, mask_off, scaling, causal=True, window=None):
+        out, lse = attention_forward_gqa(q, k, v, key_mask, scaling, causal, mask_off, want_lse=True, window=window)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.key_mask, ctx.mask_off, ctx.scaling, ctx.causal = key_mask, mask_off, scaling, causal
+        ctx.key_mask, ctx.mask_off, ctx.scaling, ctx.causal, ctx.window = key_mask, mask_off, scaling, causal, window
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         q, k, v, out, lse = ctx.saved_tensors
-        dq, dk, dv = attention_backward_gqa(q, k, v, ctx.key_mask, ctx.mask_off, out, grad_out, lse, ctx.scaling, ctx.causal)
-        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None
+        dq, dk, dv = attention_backward_gqa(q, k, v, ctx.key_mask, ctx.mask_off, out, grad_out, lse, ctx.scaling, ctx.causal,
+                                            ctx.window)
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None
 
 
 def attention_forward(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,

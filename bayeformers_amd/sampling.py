@@ -807,7 +807,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     eagerly, captures the next one in a HIP graph and replays it for the rest; the Generation is bitwise the one
     static_cache=True returns.  With eos_token_id the all-finished check runs every 8 replays (rows past EOS emit pad with
     zero statistics either way).  Both need a model routed by fuse_attention, a single process and no sliding-window
-    layers."""
+    layers — except in Mistral, Qwen2 and Qwen3 models, whose sliding layers get full-capacity static layers (capacity
+    slots each, not W) and decode on bf_attention_decode_gqa_len_window."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -965,8 +966,18 @@ def _truncated(probs: Tensor, truncation) -> Tensor:
 _FINISHED_EVERY = 8  # graph replays between two all-finished checks (host synchronisations) of sample_generate(graph=True)
 
 
+# Model families whose attention modules are known to apply the config's sliding window (they hand it to the attention
+# function, which the window kernels then apply over a full-capacity cache): a family joins together with a test of its
+# static / graph generation.  Others with sliding layers — a Llama config that carries layer_types, whose attention
+# ignores them — stay refused.
+_SLIDING_STATIC_FAMILIES = ("mistral", "qwen2", "qwen3")
+
+
 def _static_cache(model: Model, capacity: int):
-    """A transformers StaticCache of `capacity` tokens for the wrapped decoder, or the reason it cannot serve."""
+    """A transformers StaticCache of `capacity` tokens for the wrapped decoder, or the reason it cannot serve.  For the
+    families of _SLIDING_STATIC_FAMILIES the sliding-window layers get plain full-capacity StaticLayers too (transformers'
+    StaticSlidingWindowLayer branches on a host count and rolls its buffer, so one captured graph could not serve every
+    step): the mask carries the window and the decode kernel applies it.  Such a layer holds `capacity` slots, not W."""
     from transformers import StaticCache
     from transformers.cache_utils import StaticLayer
 
@@ -978,6 +989,9 @@ def _static_cache(model: Model, capacity: int):
         raise RuntimeError("sample_generate: static_cache / graph need the model's attention routed through the HIP kernels "
                            "— call bayeformers_amd.fuse_attention(model) first")
     cache = StaticCache(config=config, max_cache_len=int(capacity))
+    if getattr(config, "model_type", None) in _SLIDING_STATIC_FAMILIES:
+        cache.layers = [StaticLayer(max_cache_len=int(capacity)) if getattr(layer, "is_sliding", False) else layer
+                        for layer in cache.layers]
     if any(type(layer) is not StaticLayer or getattr(layer, "is_sliding", False) for layer in cache.layers):
         raise ValueError("sample_generate: static_cache / graph take full-attention decoders only (this config has "
                          "sliding-window or other non-static cache layers)")
@@ -994,6 +1008,7 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
     logits processors, bf_logits_process at the device step and a second mc_predictive choose the token, and
     bf_generate_step_stat_probs reads its probability from the unprocessed row)."""
     from transformers import DynamicCache
+    from transformers.cache_utils import DynamicLayer
 
     from . import ops
 
@@ -1044,6 +1059,8 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
 
     with model.monte_carlo(S), model.pinned_samples(keep_weights=keep_weights, max_bytes=max_bytes):
         dynamic = DynamicCache(config=getattr(inner, "config", None))
+        # (a sliding layer of the prefill keeps every key: they go to their own slots of the full-capacity static layer)
+        dynamic.layers = [DynamicLayer() if getattr(layer, "is_sliding", False) else layer for layer in dynamic.layers]
         out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=dynamic, use_cache=True)
         lp = model.log_prob_samples().clone()
         for i, layer in enumerate(dynamic.layers):  # the prompt's keys and values fill the static cache's first T0 slots

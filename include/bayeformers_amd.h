@@ -446,6 +446,31 @@ int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_
                                 const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
                                 int dtype, const bf_attn_decode_t* shape, float scaling, void* stream);
 
+/* ---- sliding-window attention (Mistral, Qwen2/Qwen3 with use_sliding_window, ...) ---------------------------------
+ * The four causal entries above with a window of `window` keys: key j is visible to query i iff j <= i and
+ * i - j < window (HF's sliding_window_overlay: kv_idx > q_idx - window).  Indices are cache slots, left-padding slots
+ * included; in decode, query i of Tq has index Tk - Tq + i (L - Tq + i for the _len form).  Everything else — the
+ * arguments, the padding key mask, "a query with no visible key outputs 0 (lse = +inf)", the workspace
+ * (bf_attention_decode_workspace_bytes(shape), the same for every window) — is the plain entry's.  window is any int
+ * >= 1, not necessarily a tile multiple; window < 1 and a shape with causal == 0 are refused (1, bf_last_error() set).
+ * The key loops start at the first tile a window reaches, so a prefill costs O(T window) rather than O(T^2 / 2) and a
+ * decode step reads min(window + Tq - 1, L) keys; the decode split is laid over those keys.
+ * With window >= T (prefill) or window >= Tk / L (decode) the result is bitwise the plain entry's. */
+int bf_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape,
+                                int32_t window, float scaling, void* stream);
+int bf_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                int32_t window, float scaling, void* stream);
+int bf_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                   const uint8_t* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                   const bf_attn_decode_t* shape, int32_t window, float scaling, void* stream);
+int bf_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                       int dtype, const bf_attn_decode_t* shape, int32_t window, float scaling,
+                                       void* stream);
+
 /* ---- one generation step's epilogue -------------------------------------------------------------------------------
  * What sample_generate does between the predictive statistics of a step and the next decode forward, in one launch (one
  * workgroup per prompt row; no host synchronisation, capturable).  d_state: int64[2] {step, 0} — the step counter t
