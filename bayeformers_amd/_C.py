@@ -6,7 +6,7 @@ import ctypes
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("BF_LIB_PATH") or os.path.join(_HERE, "lib", "libbayeformers_amd.so")  # BF_LIB_PATH: developer A/B of kernel variants
+LIB_PATH = os.environ.get("BF_LIB_PATH") or os.path.join(_HERE, "lib", "libbayeformers_amd.so")  # BF_LIB_PATH: load another build of the library
 
 BF_DT_F32, BF_DT_BF16, BF_DT_F16 = 0, 1, 2
 BF_PRIOR_MIXTURE, BF_PRIOR_GAUSSIAN, BF_PRIOR_NONE = 0, 1, 2
@@ -167,12 +167,6 @@ BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
 ABI_VERSION = 6  # bf_version() of the library these bindings describe (include/bayeformers_amd.h: BF_VERSION_*)
 
-# developer-build entry points (csrc/bf_dev_api.h): bound when the loaded library has them (BF_LIB_PATH=..._dev.so)
-DEV_SYMBOLS = {
-    "bf_linear_fwd_ws_workspace_bytes": (_sz, [_i, _i]),
-    "bf_linear_fwd_ws": (_i, [_vp, _i, _i64, _tp, _tp, _vp, _i, _i, _i, _i, _i, _i, _u64, _u32, _i, _vp, _vp, _sz, _vp]),
-}
-
 _lib = None
 
 
@@ -193,11 +187,6 @@ def lib():
             fn = getattr(l, name)  # AttributeError here = header/library drift
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in DEV_SYMBOLS.items():
-            fn = getattr(l, name, None)
-            if fn is not None:
-                fn.restype = res
-                fn.argtypes = args
         if l.bf_version() != ABI_VERSION:  # a stale .so called through newer signatures corrupts the stack: refuse it
             raise BayeFormersAMDError(
                 f"{LIB_PATH} is version {l.bf_version()}, these bindings expect {ABI_VERSION}: rebuild it with "

@@ -15,8 +15,6 @@
 //   * O^T = V^T P^T accumulates in fp32; longer sequences walk the key tiles with the usual running max / sum rescale;
 //   * a lane owns 4 consecutive features of one query at the end: 8-byte stores into the [B, T, H, 64] output.
 // Algorithmic HBM bytes: (3 reads + 1 write) * B*T*H*64 * 2 B.
-#include <stdlib.h>
-
 #include "bf_common.h"
 #include "bf_philox.h"
 
@@ -71,7 +69,6 @@ struct AttnParams {
     long long tok_stride;  // elements between consecutive tokens of q / k / v (H * 64 for packed heads)
     int B, T, H;
     float scale_log2e;  // scaling * log2(e)
-    int ablate;         // developer ablation bits (BF_ATTN_ABLATE): 1 = no output stores, 2 = K/V staged once from tile 0
     // DROP instantiation (training, HF attention_probs_dropout): the probabilities are dropped AFTER the softmax
     // normalisation (the row sums keep every term) with the Philox keep-mask of bf_philox.h.  A dropout group is the 8
     // probabilities of one P^T fragment: query q, keys tile * 128 + (2c + e) * 16 + 4 lg + j (e = 0, 1; j = 0..3) ->
@@ -121,9 +118,6 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 
     for (int key0 = 0; key0 < p.T; key0 += TKEY) {
         if (key0) __syncthreads();  // the previous tile's fragment reads are done
-#ifdef BF_DEV
-        if (!((p.ablate & 2) && (blockIdx.x | blockIdx.y | blockIdx.z)))
-#endif
         // stage K ([key][d], chunk ^= key & 7) and V ([key][d], 160-byte rows), 16 bytes per lane
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -228,9 +222,6 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 
     // lane (query li, group lg) holds features db*16 + 4*lg + 0..3 of its query: 8-byte stores
     T* ob = reinterpret_cast<T*>(p.out) + ((long long)b * p.T * p.H + h) * HD;
-#ifdef BF_DEV
-    if (!(p.ablate & 1) || run_sum[0] == 12345.f)
-#endif
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
         const float inv = run_sum[qi] > 0.f ? (DROP ? p.drop.inv_keep : 1.0f) / run_sum[qi] : 0.f;
@@ -273,14 +264,6 @@ int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, c
     p.T = T;
     p.H = H;
     p.scale_log2e = scaling * 1.4426950408889634f;
-#ifdef BF_DEV
-    {
-        const char* e = getenv("BF_ATTN_ABLATE");
-        p.ablate = e ? atoi(e) : 0;
-    }
-#else
-    p.ablate = 0;
-#endif
     const dim3 grid(T / TQ, H, B);
     p.keep_bits = nullptr;
     p.drop = bf_dropout_t{0, 0, 0, 0, 0, 1.0f, 0, 0, nullptr};

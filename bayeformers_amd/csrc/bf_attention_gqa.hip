@@ -383,18 +383,10 @@ template <>
 struct Shape<64> {
     static constexpr int FWD_KT = 128, FWD_MINB = 3, DQ_KT = 128, DKV_QT = 128, DKV_MINB = 2;
 };
-// (BF_GQA128_*: compile-time overrides for A/B builds of the head-128 tiles, profiles/causal_attention.md)
-#ifndef BF_GQA128_FWD_KT
-#define BF_GQA128_FWD_KT 128
-#define BF_GQA128_FWD_MINB 2
-#endif
-#ifndef BF_GQA128_BWD_T
-#define BF_GQA128_BWD_T 64
-#endif
+// (the head-128 alternatives were measured: profiles/causal_attention.md)
 template <>
 struct Shape<128> {
-    static constexpr int FWD_KT = BF_GQA128_FWD_KT, FWD_MINB = BF_GQA128_FWD_MINB, DQ_KT = BF_GQA128_BWD_T,
-                         DKV_QT = BF_GQA128_BWD_T, DKV_MINB = 1;
+    static constexpr int FWD_KT = 128, FWD_MINB = 2, DQ_KT = 64, DKV_QT = 64, DKV_MINB = 1;
 };
 
 // The tile index is the grid's SLOWEST dimension: the hardware hands consecutive workgroups to the 8 XCDs in turn, so with

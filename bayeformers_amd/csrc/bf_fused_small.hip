@@ -308,7 +308,7 @@ void mixture_consts(const bf_prior_t& pr, float& a1, float& b1, float& a2, float
 // (profiles/r4b_mid_m_crossover.txt, r4c_mlp_fused_threshold_ab.txt): up to 64 rows it wins or ties at every layer size
 // (one launch instead of three), from 65 to 128 rows only for layers of at most 512 x 512 weights (BASELINE configs[0]'s
 // hidden layers) — wider layers re-read x once per 16 output features and fall behind the tiled GEMM.
-// bf_set_fused_small_max_rows() caps both (tools/crossover_bench.py, BF_FUSED_SMALL_MAX_ROWS).
+// bf_set_fused_small_max_rows() caps both (tools/crossover_bench.py).
 static int g_fused_small_max_rows = 128;
 extern "C" int bf_fused_small_max_rows(void) { return g_fused_small_max_rows; }
 extern "C" int bf_set_fused_small_max_rows(int rows) {

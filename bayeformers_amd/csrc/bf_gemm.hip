@@ -19,16 +19,6 @@
 
 namespace {
 
-// Kernel choice: 2 = the scheduled 256-wide persistent kernel (bf_gemm256.hip).  Developer builds (-DBF_DEV, tools/)
-// can override it with BF_GEMM_VARIANT: 0 = force the generic kernel, 1 = the round-1 fixed-tile kernel (A/B baseline).
-int gemm_variant() {
-#ifdef BF_DEV
-    const char* v = getenv("BF_GEMM_VARIANT");
-    if (v) return atoi(v);
-#endif
-    return 2;
-}
-
 template <typename T>
 struct Mfma16;
 template <>
@@ -287,7 +277,7 @@ int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, con
     if (d_pre) {
         // pre-activation wanted next to act(y) (the forward of a training step): one launch with two outputs when the
         // 256-wide kernel takes the shape, else the GEMM into d_pre followed by the elementwise activation
-        const bool fast = layers == 1 && gemm_variant() != 0 && w_dtype != BF_DT_F32 && (long long)M * N >= 128 * 128 &&
+        const bool fast = layers == 1 && w_dtype != BF_DT_F32 && (long long)M * N >= 128 * 128 &&
                           ((uintptr_t)d_bias & 15) == 0 && ((uintptr_t)d_pre & 15) == 0 &&
                           bf_gemm256_supported(x_dtype, w_dtype, y_dtype, S, M, N, K, d_x, d_w, x_sample_stride);
         if (!fast || act == BF_ACT_NONE) {
@@ -304,7 +294,7 @@ int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, con
     }
     if (layers > 1) {
         // L layers sharing x: one launch of the 256x256 kernel when it applies, else one launch per layer
-        const bool fast = gemm_variant() != 0 && (long long)M * N >= 128 * 128 &&
+        const bool fast = (long long)M * N >= 128 * 128 &&
                           ((uintptr_t)d_bias & 15) == 0 && (long long)layers * S <= 65535 &&
                           (w_dtype == BF_DT_F32
                                ? x_dtype == BF_DT_F32 && y_dtype == BF_DT_F32 && getenv("BF_F32_GENERIC") == nullptr &&
@@ -354,14 +344,9 @@ int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, con
         return 0;
     }
     // large aligned problems: the 256x256x64 LDS-DMA kernel; everything else: the generic 128x128x32 kernel
-    const int variant = gemm_variant();
-    if (variant != 0 && (long long)M * N >= 128 * 128 && ((uintptr_t)d_bias & 15) == 0 &&
-        bf_gemm256_supported(x_dtype, w_dtype, y_dtype, layers * S, M, N, K, d_x, d_w, x_sample_stride)) {
-#ifdef BF_DEV
-        if (variant == 1) return bf_launch_gemm256_r1(p, w_dtype, y_dtype, stream);
-#endif
+    if ((long long)M * N >= 128 * 128 && ((uintptr_t)d_bias & 15) == 0 &&
+        bf_gemm256_supported(x_dtype, w_dtype, y_dtype, layers * S, M, N, K, d_x, d_w, x_sample_stride))
         return bf_launch_gemm256(p, w_dtype, y_dtype, stream);
-    }
     p.tiles_m = (M + BM - 1) / BM;
     p.tiles_n = (N + BN - 1) / BN;
     const size_t xs = bf_dtype_size(x_dtype);

@@ -36,13 +36,6 @@
 
 #include "bf_gemm256_dev.h"
 
-#ifndef BF_NT_FORM
-#define BF_NT_FORM 2
-#endif
-#ifndef BF_NN_FORM
-#define BF_NN_FORM 1
-#endif
-
 namespace {
 
 
@@ -213,10 +206,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
     // RING: this wave's pieces (the first `cnt` of four) of its group's unit `half` (0 / 1) of k-step kt of tile t, into
     // buffer buf
     auto issue_unit = [&](const Src& t, int kt, int buf, int half, int cnt) {
-#ifdef BF_DEV
-        if (p.flags & 1) return;     // ablation: no DMA in the k-loop (tools/r6g_tn_probe.sh)
-        if (p.flags & 64) kt = 0;    // ablation: every k-step re-reads k-step 0 (operands L2-hot)
-#endif
         char* dst = smem + buf * STAGE_BYTES + (wm == 0 ? 0 : X_BYTES) + half * 16384 + wn * 1024;
         const T* b = t.ob;
         if constexpr (SEG) {
@@ -478,19 +467,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
                 kstep_ring(nk - 1, std::true_type{}, std::false_type{});
             } else {
             for (int kt = 0; kt + 1 < nk; ++kt)
-                kstep([&] {
-#ifdef BF_DEV
-                    if (p.flags & 1) return;
-                    stage(cur, (p.flags & 64) ? 0 : kt + 1, (g & 1) ^ 1, hc);
-#else
-                    stage(cur, kt + 1, (g & 1) ^ 1, hc);
-#endif
-                }, std::false_type{}, round > 0 && kt == 0);
+                kstep([&] { stage(cur, kt + 1, (g & 1) ^ 1, hc); }, std::false_type{}, round > 0 && kt == 0);
             // last k-step: its DMA slot fetches k-step 0 of this workgroup's next tile
             kstep([&] {
-#ifdef BF_DEV
-                if (p.flags & 1) return;
-#endif
                 if (has_next) {
                     Src nxt;
                     int s2, m2, n2, h2;
@@ -502,24 +481,16 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
             // the last consumed buffer is (g-1)&1; buffer g&1 already holds k-step 0 of the next tile.  Group 0 is one
             // slot ahead here and stays ahead through its epilogue
             YT* y = reinterpret_cast<YT*>(p.y) + (long long)s * M * N;
-            int m_end = min(M, m0 + h * UNIT);
-#ifdef BF_DEV
-            if (p.flags & 16) m_end = 0;
-            const bool skip = (p.flags & 8) != 0;
-#else
-            constexpr bool skip = false;
-#endif
+            const int m_end = min(M, m0 + h * UNIT);
             YT* y2 = p.y2 ? reinterpret_cast<YT*>(p.y2) + (long long)s * M * N : nullptr;
             // every fragment read of buffer (g - 1) & 1 is complete: group 0 passed its last barrier together with the
             // end of group 1's last LDS slot, group 1 comes from its last MFMA slot
-            if (!skip) {
-                if constexpr (RING)
-                    epilogue_wave<YT, H, sizeof(YT) == 2 ? 2 : 1>(smem + 2 * STAGE_BYTES + wid * 4096, acc, y, y2, m0, m_end, n0, N, wm, wn, lane,
-                                            p.act);
-                else
-                    epilogue_wave<YT, H>(smem + ((g - 1) & 1) * STAGE_BYTES + wid * 8192, acc, y, y2, m0, m_end, n0, N, wm,
-                                         wn, lane, p.act);
-            }
+            if constexpr (RING)
+                epilogue_wave<YT, H, sizeof(YT) == 2 ? 2 : 1>(smem + 2 * STAGE_BYTES + wid * 4096, acc, y, y2, m0, m_end, n0, N, wm, wn, lane,
+                                        p.act);
+            else
+                epilogue_wave<YT, H>(smem + ((g - 1) & 1) * STAGE_BYTES + wid * 8192, acc, y, y2, m0, m_end, n0, N, wm,
+                                     wn, lane, p.act);
         };
         switch (h) {
             case 8: body(std::integral_constant<int, 8>{}); break;
@@ -901,30 +872,15 @@ extern "C" size_t bf_gemm_schedule_policy(int S, int L, int M, int N, int n_cu, 
 
 int bf_launch_gemm256(const GemmParams& p0, int w_dtype, int y_dtype, hipStream_t stream) {
     GemmParams p = p0;
-    int policy = BF_SCHED_POLICY;
-#ifdef BF_DEV
-    const char* ab = getenv("BF_GEMM_ABLATE");
-    p.flags = ab ? atoi(ab) : 0;
-    const char* pol = getenv("BF_GEMM_SCHED");
-    if (pol) policy = atoi(pol);
-#else
-    p.flags = 0;
-#endif
     if (p.layers < 1) p.layers = 1;
     p.tiles_m = (p.M + TM - 1) / TM;
     p.tiles_n = (p.N + TN - 1) / TN;
     Sched sc;
-    if (get_schedule(p.S, p.layers, p.tiles_n, p.M, policy, stream, sc)) return 1;
+    if (get_schedule(p.S, p.layers, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
     p.sched = sc.d_table;
     p.sched_rounds = sc.rounds;
-    // forward form: the five-slot ring (bf_gemm256_r5.hip) where it applies.  BF_NT_FORM: 0 = burst kernel, non-zero = ring
-    // (developer builds: BF_GEMM_NT_FORM overrides)
-    int form = BF_NT_FORM;
-#ifdef BF_DEV
-    const char* fe = getenv("BF_GEMM_NT_FORM");
-    if (fe) form = atoi(fe);
-#endif
-    if (form && bf_gemm256_r5_supported(p, w_dtype, y_dtype)) return bf_launch_gemm256_r5(p, w_dtype, stream, sc.grid);
+    // forward form: the five-slot ring (bf_gemm256_r5.hip) where it applies, the burst kernel for the other shapes
+    if (bf_gemm256_r5_supported(p, w_dtype, y_dtype)) return bf_launch_gemm256_r5(p, w_dtype, stream, sc.grid);
     if (w_dtype == BF_DT_BF16) return launch256<__bf16>(p, y_dtype, stream, sc.grid);
     return launch256<_Float16>(p, y_dtype, stream, sc.grid);
 }
@@ -956,23 +912,14 @@ int bf_launch_gemm256_tn(const void* d_a, const void* d_b, float* d_out, int dty
     p.K = Mc;
     p.act = BF_ACT_NONE;
     p.layers = 1;
-    p.flags = 0;
-#ifdef BF_DEV
-    if (const char* ab = getenv("BF_GEMM_ABLATE")) p.flags = atoi(ab);
-#endif
     p.tiles_m = (p.M + TM - 1) / TM;
     p.tiles_n = (p.N + TN - 1) / TN;
     Sched sc;
     if (get_schedule(p.S, 1, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
     p.sched = sc.d_table;
     p.sched_rounds = sc.rounds;
-#ifdef BF_DEV
-    // developer builds, BF_GEMM_TN_FORM=1: the TN form on the five-slot ring (bf_gemm256_r5.hip, TRX) — built and measured in
-    // round 6 (profiles/r6h_tn_ring5_ab.txt): bit-identical, 0-1.4 % per launch, nothing in the training step; the product
-    // keeps the two-buffer unit ring of this file
-    if (const char* fe = getenv("BF_GEMM_TN_FORM"))
-        if (atoi(fe) && bf_gemm256_r5_tn_supported(p)) return bf_launch_gemm256_r5_tn(p, dtype, stream, sc.grid);
-#endif
+    // the two-buffer unit ring of this file: the TN form on the five-slot ring measured bit-identical and 0-1.4 % per
+    // launch in round 6, nothing in the training step
     if (dtype == BF_DT_BF16) return launch256_tn<__bf16>(p, stream, sc.grid);
     return launch256_tn<_Float16>(p, stream, sc.grid);
 }
@@ -1018,20 +965,14 @@ int bf_launch_gemm256_nn(const void* d_x, const void* d_w, void* d_y, int dtype,
     p.w_seg_stride = (long long)S * Nl * Kl;
     p.act = BF_ACT_NONE;
     p.layers = 1;
-    p.flags = 0;
     p.tiles_m = (p.M + TM - 1) / TM;
     p.tiles_n = (p.N + TN - 1) / TN;
     Sched sc;
     if (get_schedule(p.S, 1, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
     p.sched = sc.d_table;
     p.sched_rounds = sc.rounds;
-    // the five-slot ring (bf_gemm256_r5.hip) where it applies; BF_NN_FORM 0 = burst kernel (developer builds: BF_GEMM_NN_FORM)
-    int form = BF_NN_FORM;
-#ifdef BF_DEV
-    const char* fe = getenv("BF_GEMM_NN_FORM");
-    if (fe) form = atoi(fe);
-#endif
-    if (form && bf_gemm256_r5_supported(p, dtype, dtype)) return bf_launch_gemm256_r5_nn(p, dtype, stream, sc.grid);
+    // the five-slot ring (bf_gemm256_r5.hip) where it applies, the burst kernel for the other shapes
+    if (bf_gemm256_r5_supported(p, dtype, dtype)) return bf_launch_gemm256_r5_nn(p, dtype, stream, sc.grid);
     if (dtype == BF_DT_BF16) return launch256_nn<__bf16>(p, stream, sc.grid);
     return launch256_nn<_Float16>(p, stream, sc.grid);
 }

@@ -54,16 +54,12 @@ struct FragOf { using type = typename Mfma16<T>::frag; };
 template <>
 struct FragOf<float> { using type = f32x4_t; };
 
-// TRX (round 6): the x unit contraction-major too ([64 contraction rows][256] tile of 512-byte rows, swizzled and read through
-// ds_read_b64_tr_b16 like a TRW unit) with fp32 outputs — the TN form dW[s] = dy[s]^T x[s] of the backward pass, which ran on
-// the two-buffer unit ring of bf_gemm256.hip (1 k-step ahead, 32 KiB of LDS reserved for its epilogue) until round 6.
 // AG (round 6, NN form): the epilogue multiplies the stored rows by act'(p.gpre) (bf_gemm_nn_actgrad) — an instantiation of its
 // own, so that the plain input-gradient launches are the kernel they were.
-template <typename T, typename YT, bool TRW = false, bool SEG = false, bool TRX = false, bool AG = false>
+template <typename T, typename YT, bool TRW = false, bool SEG = false, bool AG = false>
 __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams p) {
-    static_assert(!AG || (TRW && !TRX && !SEG && sizeof(YT) == 2), "the activation-gradient epilogue: NN form, 16-bit outputs");
-    static_assert(sizeof(T) == 2 || (!TRW && !SEG && !TRX && sizeof(YT) == 4), "fp32 operands: forward form, fp32 outputs");
-    static_assert(!TRX || (TRW && !SEG), "contraction-major x: the TN form (both operands contraction-major, no segments)");
+    static_assert(!AG || (TRW && !SEG && sizeof(YT) == 2), "the activation-gradient epilogue: NN form, 16-bit outputs");
+    static_assert(sizeof(T) == 2 || (!TRW && !SEG && sizeof(YT) == 4), "fp32 operands: forward form, fp32 outputs");
     using frag = typename FragOf<T>::type;
     constexpr unsigned ES = sizeof(T);            // bytes per operand element
     constexpr int TKE = ROW_BYTES / (int)ES;      // k-values per k-step: 64 (16-bit) or 32 (fp32)
@@ -119,25 +115,13 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
     auto setup_x = [&](const int4 d) {
         const int m0 = __builtin_amdgcn_readfirstlane(d.w);
         xb = reinterpret_cast<const T*>(p.x) + (long long)__builtin_amdgcn_readfirstlane(d.y) * p.x_sstride;
-        if constexpr (TRX) {  // as the W unit of the TRW form, over the M (= 512-byte row) direction of x
-            int ln = lane;
-            asm volatile("" : "+v"(ln));
-            const int tr_r = wid * 2 + (ln >> 5);
-            const int tr_c = (ln & 31) ^ (((tr_r & 3) | ((tr_r >> 1) & 4)) << 1);
-            xo = ((unsigned)tr_r * (unsigned)M + (unsigned)min(m0 + tr_c * 8, M - 8)) * 2u;
-            x_bytes = 0x7FFFFFFF;
-        } else {
-            int prow, kc8;
-            piece_lane(prow, kc8);
-            xo = ((unsigned)(m0 + wid * 8 + prow) * (unsigned)K + kc8) * ES;
-            x_bytes = (unsigned)M * (unsigned)K * ES;
-        }
+        int prow, kc8;
+        piece_lane(prow, kc8);
+        xo = ((unsigned)(m0 + wid * 8 + prow) * (unsigned)K + kc8) * ES;
+        x_bytes = (unsigned)M * (unsigned)K * ES;
     };
     // one 1 KiB piece: `base` (a buffer of `bytes`) + per-lane byte offset `off` + wave-uniform byte offset `soff` -> LDS `dst`
     auto piece = [&](const T* base, unsigned bytes, unsigned off, int soff, char* dst) {
-#ifdef BF_DEV
-        if (p.flags & 1) return;  // ablation: no DMA in the k-loop
-#endif
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, (int)bytes, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)dst, 16, (int)off, soff, 0, 0);
     };
@@ -154,22 +138,14 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
     // this wave's pieces of unit X(kt) / W(kt) into ring slot `slot`; only the 4 h pieces of the tile's rows of x are
     // fetched (h4 = 4 h: an integral_constant inside a tile's k-loop, so a full-height tile issues without branches)
     auto issue_x = [&](int kt, int slot, auto h4) {
-#ifdef BF_DEV
-        if (p.flags & 64) kt = 0;  // ablation: every k-step re-reads k-step 0 (operands L2-hot)
-#endif
         char* base = smem + slot * SLOT_BYTES + wid * 1024;
         const int seg = segment(kt);
         const T* xs = SEG ? xb + (long long)seg * p.x_seg_stride : xb;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if constexpr (TRX) piece(xs, x_bytes, xo, (kt * TK + i * 16) * M * 2, base + i * 8192);
-            else if (i * 8 + 7 < h4 || i * 8 + wid < h4) piece(xs, x_bytes, xo + i * rowblk, kt * (TK * 2), base + i * 8192);
-        }
+        for (int i = 0; i < 4; ++i)
+            if (i * 8 + 7 < h4 || i * 8 + wid < h4) piece(xs, x_bytes, xo + i * rowblk, kt * (TK * 2), base + i * 8192);
     };
     auto issue_w = [&](int kt, int slot) {
-#ifdef BF_DEV
-        if (p.flags & 64) kt = 0;
-#endif
         char* base = smem + slot * SLOT_BYTES + wid * 1024;
         const int seg = segment(kt);
         const T* ws = SEG ? wb + (long long)seg * p.w_seg_stride : wb;
@@ -198,8 +174,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
     // the block's 32-byte granule; granule' = granule ^ key(row).  Fragment block i of the wave: one XOR away.
     const int tr_rl = ((lane & 15) >> 2) | (((lane >> 4) & 1) << 2);
     const unsigned tr_w0 = lds0 + ((lane >> 4) * 8 + ((lane & 15) >> 2)) * 512 + (lane & 3) * 8 + (((wn * 4) ^ tr_rl) << 5);
-    // contraction-major x unit: wave group wm owns the 16-row blocks wm, wm + 2, ... of the tile = granules wm + 2 j
-    const unsigned tr_x0 = lds0 + ((lane >> 4) * 8 + ((lane & 15) >> 2)) * 512 + (lane & 3) * 8 + ((wm ^ tr_rl) << 5);
     auto tr_read = [&](unsigned a0, int blk, auto half) -> frag {
         const unsigned a = a0 ^ (unsigned)(blk << 5);
         constexpr int off = decltype(half)::value * 32 * 512;
@@ -259,15 +233,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
                         wf[decltype(ic)::value] = lds_read(aw, std::integral_constant<int, decltype(ic)::value * 16 * ROW_BYTES>{});
                     });
                 }
-                if constexpr (TRX) {
-                    const unsigned atx = tr_x0 + slot_x * SLOT_BYTES;
-#pragma unroll
-                    for (int j = 0; j < H; ++j) xf[j] = tr_read(atx, 2 * j, half);
-                } else {
-                    static_for<0, H>([&](auto jc) {
-                        xf[decltype(jc)::value] = lds_read(ax, std::integral_constant<int, decltype(jc)::value * 32 * ROW_BYTES>{});
-                    });
-                }
+                static_for<0, H>([&](auto jc) {
+                    xf[decltype(jc)::value] = lds_read(ax, std::integral_constant<int, decltype(jc)::value * 32 * ROW_BYTES>{});
+                });
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             };
             auto mfmas = [&] {
@@ -334,11 +302,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
             };
 
             if (wm == 1) __builtin_amdgcn_s_barrier();  // G1 runs one slot behind G0
-#ifdef BF_DEV
-            init_acc<H>(acc, (p.bias && !(p.flags & 2)) ? p.bias + (long long)s * N : nullptr, n0, N, wn, lane);
-#else
             init_acc<H>(acc, p.bias ? p.bias + (long long)s * N : nullptr, n0, N, wn, lane);
-#endif
 
             for (int kt = 0; kt + 2 < nk; ++kt) kstep(kt, std::integral_constant<int, 0>{});
             if (has_next) setup_w(dn);  // every W unit of this tile is issued
@@ -356,12 +320,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
             if (sc >= NSLOT) sc -= NSLOT;
             YT* y = reinterpret_cast<YT*>(p.y) + (long long)s * M * N;
             YT* y2 = p.y2 ? reinterpret_cast<YT*>(p.y2) + (long long)s * M * N : nullptr;
-            int m_end = min(M, m0 + h * UNIT);
+            const int m_end = min(M, m0 + h * UNIT);
             char* scratch = smem + sc * SLOT_BYTES + wid * 4096;
-#ifdef BF_DEV
-            if (p.flags & 16) m_end = 0;  // ablation: no global stores
-            if (p.flags & 8) return;      // ablation: no epilogue
-#endif
             const YT* gpre = AG ? reinterpret_cast<const YT*>(p.gpre) + (long long)s * M * N : nullptr;
             epilogue_wave<YT, H, sizeof(YT) == 2 ? 2 : 1>(scratch, acc, y, y2, m0, m_end, n0, N, wm, wn, lane, p.act, gpre);
         };
@@ -383,9 +343,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
     }
 }
 
-template <typename T, typename YT, bool TRW, bool SEG, bool TRX = false, bool AG = false>
+template <typename T, typename YT, bool TRW, bool SEG, bool AG = false>
 int launch_r5(const GemmParams& p, hipStream_t stream, int grid) {
-    hipLaunchKernelGGL((gemm256_ring5_kernel<T, YT, TRW, SEG, TRX, AG>), dim3(grid), dim3(512), 0, stream, p);
+    hipLaunchKernelGGL((gemm256_ring5_kernel<T, YT, TRW, SEG, AG>), dim3(grid), dim3(512), 0, stream, p);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -424,7 +384,6 @@ bool bf_gemm256_f32_supported(int S, int M, int N, int K, const void* d_x, const
 
 int bf_launch_gemm256_f32(const GemmParams& p0, hipStream_t stream) {
     GemmParams p = p0;
-    p.flags = 0;
     if (p.layers < 1) p.layers = 1;
     p.tiles_m = (p.M + TM - 1) / TM;
     p.tiles_n = (p.N + TN - 1) / TN;
@@ -435,27 +394,12 @@ int bf_launch_gemm256_f32(const GemmParams& p0, hipStream_t stream) {
     return launch_r5<float, float, false, false>(p, stream, sc.grid);
 }
 
-#ifdef BF_DEV
-// TN form (both operands contraction-major, fp32 out): out[b][n][k] = sum_m a[b][m][n] * bmat[b][m][k] — the weight gradient.
-// Developer builds only: measured against the unit ring of bf_gemm256.hip (profiles/r6h_tn_ring5_ab.txt), not faster.
-bool bf_gemm256_r5_tn_supported(const GemmParams& p) {
-    if (p.K < 2 * TK || p.M % 8 || p.N % 8) return false;
-    // (a sample's operand is addressed by 32-bit byte offsets through a buffer descriptor)
-    return (long long)(p.K + 64) * p.M < (1ll << 30) && (long long)(p.K + 64) * p.N < (1ll << 30);
-}
-
-int bf_launch_gemm256_r5_tn(const GemmParams& p, int dtype, hipStream_t stream, int grid) {
-    if (dtype == BF_DT_BF16) return launch_r5<__bf16, float, true, false, true>(p, stream, grid);
-    return launch_r5<_Float16, float, true, false, true>(p, stream, grid);
-}
-#endif
-
 // NN form (x K-contiguous, W contraction-major as sampled, 16-bit out): y[s][m][k] = sum_n x[s][m][n] w[s][n][k]
 int bf_launch_gemm256_r5_nn(const GemmParams& p, int dtype, hipStream_t stream, int grid) {
     const bool seg = p.segs > 1;
     if (p.gpre) {  // the activation-gradient epilogue (one layer, no segments: checked by the caller)
-        if (dtype == BF_DT_BF16) return launch_r5<__bf16, __bf16, true, false, false, true>(p, stream, grid);
-        return launch_r5<_Float16, _Float16, true, false, false, true>(p, stream, grid);
+        if (dtype == BF_DT_BF16) return launch_r5<__bf16, __bf16, true, false, true>(p, stream, grid);
+        return launch_r5<_Float16, _Float16, true, false, true>(p, stream, grid);
     }
     if (dtype == BF_DT_BF16)
         return seg ? launch_r5<__bf16, __bf16, true, true>(p, stream, grid) : launch_r5<__bf16, __bf16, true, false>(p, stream, grid);

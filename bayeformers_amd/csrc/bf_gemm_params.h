@@ -26,11 +26,6 @@ struct GemmParams {
     // input gradient of `segs` layers that read the same activations, dx = sum_l dy_l W_l, in one launch
     int segs;
     long long x_seg_stride, w_seg_stride;
-    int flags;  // developer ablation bits, honoured by -DBF_DEV builds only (tools/): 1 = no DMA in the k-loop,
-                // 8 = no epilogue, 16 = no global stores, 64 = every k-step's DMA re-reads k-step 0 (operands L2-hot);
-                // ring kernel: 32 = the first two k-steps of a tile wait with vmcnt(24) (not held up by the previous tile's
-                // stores), bits 8..11 = k: the workgroups of an XCD start k * 64 cycles apart, 4096 = one barrier per k-step from a
-                // tile's second k-step on, 8192 = no s_setprio around the MFMA slots
 };
 
 // fast 256-wide LDS-DMA kernel (bf_gemm256.hip)
@@ -52,7 +47,3 @@ int bf_launch_gemm256_nn(const void* d_x, const void* d_w, void* d_y, int dtype,
                          hipStream_t stream, int segs = 1, const void* d_gpre = nullptr, int act = 0);
 bool bf_gemm256_nn_actgrad_supported(int dtype, int S, int M, int Nl, int Kl, const void* d_x, const void* d_w, const void* d_y,
                                      const void* d_gpre);
-#ifdef BF_DEV
-// round-1 kernel (fixed 256x256 tiles, arithmetic tile order), kept in developer builds as the A/B baseline
-int bf_launch_gemm256_r1(const GemmParams& p, int w_dtype, int y_dtype, hipStream_t stream);
-#endif

@@ -5,7 +5,6 @@ step of the Monte-Carlo forward path runs in the HIP kernels of csrc/.  There is
 are not on a ROCm device raise.
 """
 import ctypes
-import os
 from typing import Optional, Union
 
 import torch
@@ -48,20 +47,10 @@ def philox_normal_host(n: int, seed: int, sample: int, stream_id: int, offset: i
     return out
 
 
-_FUSED_ROWS_SET = False
-
-
 def fused_small_rows(N: int, K: int) -> int:
     """Rows per sample up to which bf_linear_fwd runs an N x K layer as ONE fused kernel (bf_fused_small_rows_for: the
-    measured crossover; BF_FUSED_SMALL_MAX_ROWS caps it for developer A/B runs)."""
-    global _FUSED_ROWS_SET
-    lib = _C.lib()
-    if not _FUSED_ROWS_SET:
-        _FUSED_ROWS_SET = True
-        v = os.environ.get("BF_FUSED_SMALL_MAX_ROWS")
-        if v is not None:
-            _C.check(lib.bf_set_fused_small_max_rows(int(v)), "bf_set_fused_small_max_rows")
-    return lib.bf_fused_small_rows_for(int(N), int(K))
+    measured crossover, capped by bf_set_fused_small_max_rows)."""
+    return _C.lib().bf_fused_small_rows_for(int(N), int(K))
 
 
 def philox_normal(n: int, S: int, seed: int, sample_base: int, stream_id: int, device="cuda") -> Tensor:
@@ -70,9 +59,6 @@ def philox_normal(n: int, S: int, seed: int, sample_base: int, stream_id: int, d
     _C.check(_C.lib().bf_philox_normal(out.data_ptr(), int(n), int(S), int(seed), int(sample_base) & 0xFFFFFFFF,
                                        int(stream_id), _stream_ptr()), "bf_philox_normal")
     return out
-
-
-_NO_ALIAS = os.environ.get("BF_NO_PRIOR_ALIAS") is not None  # developer A/B: always read the prior's mu / rho
 
 
 def prior_alias(gaussian, prior) -> Optional[float]:
@@ -87,7 +73,7 @@ def prior_alias(gaussian, prior) -> Optional[float]:
     log-prior and bump the library's stale counter when it fails; `stale_priors_seen()` notices that at the next forward
     and `invalidate_caches(model)` drops every cached verdict."""
     mu, pmu, prho = gaussian.mu, prior.mu, prior.rho
-    if _NO_ALIAS or mu.requires_grad or pmu.shape != mu.shape or prho.shape != mu.shape or pmu.dtype != torch.float32:
+    if mu.requires_grad or pmu.shape != mu.shape or prho.shape != mu.shape or pmu.dtype != torch.float32:
         return None
     state = (mu.data_ptr(), mu._version, pmu.data_ptr(), pmu._version, prho.data_ptr(), prho._version, bfr.STATE.stale_epoch)
     hit = getattr(prior, "_bf_alias", None)
@@ -367,36 +353,6 @@ def linear_forward(layer, x: Tensor, S: int, seed: int, sample_base: int, lp_out
                                ctypes.byref(plan.b) if has_bias else None, y.data_ptr(), _TORCH2BF[x.dtype],
                                _TORCH2BF[cdt], S, M, N, K, seed, sample_base & 0xFFFFFFFF, lp_out.data_ptr(),
                                ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_linear_fwd")
-    return y
-
-
-def linear_forward_ws(layer, x: Tensor, S: int, seed: int, sample_base: int, lp_out: Tensor, row_shares: int = 0) -> Tensor:
-    """Linear.forward for S samples in ONE launch, weight-stationary (bf_linear_fwd_ws): the measured alternative to
-    sampling launch + GEMM for large M (LABBOOK.md 4.3).  Same arguments and results as linear_forward; 16-bit x only."""
-    from .nn.parameters.base import NoneParameter
-
-    if not hasattr(_C.lib(), "bf_linear_fwd_ws"):
-        raise _C.BayeFormersAMDError("bf_linear_fwd_ws is a developer-build entry point: python -m bayeformers_amd.build --dev, "
-                                     "then BF_LIB_PATH=bayeformers_amd/lib/libbayeformers_amd_dev.so")
-    _require_device(x, "input")
-    K, N = layer.in_features, layer.out_features
-    x = x if x.is_contiguous() else x.contiguous()
-    M = x.numel() // K // S
-    cdt = layer.compute_dtype or bfr.get_compute_dtype()
-    has_bias = not isinstance(layer.bias, NoneParameter)
-    w, b = _C.bf_tensor_t(), _C.bf_tensor_t()
-    ok = fill_tensor(w, layer.weight, layer.weight_prior, 2 * layer.layer_id)
-    if has_bias:
-        ok = fill_tensor(b, layer.bias, layer.bias_prior, 2 * layer.layer_id + 1) and ok
-    if not ok:
-        raise _C.BayeFormersAMDError("linear_forward_ws: user-defined priors are not supported")
-    lib = _C.lib()
-    y = torch.empty((S * M, N), dtype=x.dtype, device=x.device)
-    ws = workspace(x.device, lib.bf_linear_fwd_ws_workspace_bytes(S, N))
-    _C.check(lib.bf_linear_fwd_ws(x.data_ptr(), _TORCH2BF[x.dtype], M * K, ctypes.byref(w),
-                                  ctypes.byref(b) if has_bias else None, y.data_ptr(), _TORCH2BF[x.dtype],
-                                  _TORCH2BF[cdt], S, M, N, K, seed, sample_base & 0xFFFFFFFF, int(row_shares),
-                                  lp_out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_linear_fwd_ws")
     return y
 
 
@@ -1322,8 +1278,8 @@ def add_layernorm_backward(x: Tensor, residual: Optional[Tensor], gamma: Tensor,
     return dz.view(x.shape), dgamma, dbeta
 
 
-_NO_COLSUM_FOLD = os.environ.get("BF_NO_COLSUM_FOLD") is not None  # developer A/B: every bias gradient's column sums by a pass of its own
-_NO_TWIN = os.environ.get("BF_NO_LN_TWIN") is not None  # developer A/B: let autograd add the two consumers' gradients
+_NO_COLSUM_FOLD = False  # tests' reference path: every bias gradient's column sums by a pass of its own
+_NO_TWIN = False  # tests' reference path: let autograd add the two consumers' gradients
 
 
 class AddLayerNormFn(torch.autograd.Function):

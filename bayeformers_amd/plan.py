@@ -251,8 +251,6 @@ class SamplePlan:
             mask = 0
             for k in self.entry_kinds[self.first_entry_of_layer[l0]:self.first_entry_of_layer[l1]]:
                 mask |= 1 << k
-            if os.environ.get("BF_NO_UNIFORM_TABLE") is not None:
-                mask = 0  # developer A/B: always the kernel that takes every prior kind
             self._kinds_of[(first, last)] = mask
         _C.check(_C.lib().bf_sample_logprob_table(self.blob.data_ptr(), self.n_entries, b0, b1, self.S, seed,
                                                   sample_base & 0xFFFFFFFF, self.partials.data_ptr(), mask,

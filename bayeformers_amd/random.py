@@ -7,8 +7,6 @@ and the next unused Monte-Carlo sample index.  Every forward of a bnn.Model (or 
 consecutive sample indices; all layers inside one forward share them, which is what makes results independent
 of kernel tiling, of S-batching and of how samples are sharded over GPUs.
 """
-import os
-
 import torch
 
 DEFAULT_SEED = 0x5EED
@@ -275,17 +273,12 @@ def set_kl_gradient(enable: bool = True) -> None:
     STATE.kl_gradient = bool(enable)
 
 
-_AB_OLD_SNAPSHOT = os.environ.get("BF_AB_OLD_SNAPSHOT", "0") == "1"
-
-
 def counter_snapshot(needed: bool = True):
     """In device-counter mode: a copy of the counter as the forward saw it (backward regenerates the same eps).
     `needed` False — no gradient will be asked of this forward — gives None: the copy is a 4 us kernel, and every
     Bayesian layer of a BERT-base forward used to launch one.  Inside a bnn.Model forward the layers share ONE copy for
     as long as nothing moved the counter (commit_samples / manual_seed count their moves in STATE.counter_moves)."""
     counter = STATE.device_counter
-    if _AB_OLD_SNAPSHOT:  # tools/r5r_ab.sh: one copy per call, as before round 5
-        return counter.clone() if counter is not None else None
     if counter is None or not needed:
         return None
     fwd = STATE.ctx

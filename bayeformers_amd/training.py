@@ -27,7 +27,7 @@ from .nn.model import Model
 from .sampling import elbo, sample_bayesian
 
 
-_NO_DEFERRED = __import__("os").environ.get("BF_NO_DEFERRED_PGRAD") is not None  # developer A/B: per-layer weight reductions
+_NO_DEFERRED = False  # tests' reference path: per-layer weight reductions
 
 _BUCKETS_OF: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # optimizer -> the buckets training_step built for it
 

@@ -251,10 +251,10 @@ int bf_linear_fwd(const void* d_x, int x_dtype, int64_t x_sample_stride, const b
                   uint64_t seed, uint32_t sample_base, double* d_logprob_out, void* d_workspace,
                   size_t workspace_bytes, void* stream);
 
-/* (The weight-stationary single-launch variant for LARGE M, bf_linear_fwd_ws, is a DEVELOPER-build entry point since
- * round 4 — csrc/bf_dev_api.h, library libbayeformers_amd_dev.so: measured 2.1-3.3x slower than sampling launch + tiled
- * GEMM at M = 4096 and slower than both alternatives at every M from 32 to 2048 (profiles/r4b_mid_m_crossover.txt), it
- * is dispatched nowhere, so the product library does not carry it.) */
+/* (A weight-stationary single-launch variant for LARGE M was built in round 4 and measured 2.1-3.3x slower than
+ * sampling launch + tiled GEMM at M = 4096 and slower than both alternatives at every M from 32 to 2048
+ * (profiles/r4b_mid_m_crossover.txt).  It was dispatched nowhere and has been removed; its source is in git history
+ * up to commit 6892a82.) */
 
 /* Backward of bf_linear_fwd, reproducing the reference's autograd graph: gradients flow through
  * F.linear(input, mu + eps*softplus(rho), ...) (layers/linear.py:97,104, gaussian.py:100-101) with eps a constant and

@@ -1,14 +1,13 @@
-"""Mid-M crossover of the three ways to run one bnn.Linear forward:
+"""Mid-M crossover of the two ways to run one bnn.Linear forward:
 
     A  sampling launch + tiled GEMM          (bf_linear_fwd above the fused threshold: what large M runs)
     B  the single fused kernel               (bf_fused_small: epsilon in registers -> MFMA operand; M <= 128)
-    C  the weight-stationary fused launch    (bf_linear_fwd_ws: a strip of sampled weights resident in LDS)
 
     python tools/crossover_bench.py  >  profiles/r4*_mid_m_crossover.txt
 
 Sweeps M in {32, 64, 96, 128, 256, 512, 1024, 2048} x (N, K) in {512^2, 768^2, 3072x768} at S = 5 and 10, bf16, mixture and
-MOPED priors.  Microseconds per call from HIP events around back-to-back calls, interleaved rounds, median.  All three
-give the same outputs (checked)."""
+MOPED priors.  Microseconds per call from HIP events around back-to-back calls, interleaved rounds, median.  Both give
+the same outputs (checked)."""
 import os
 import sys
 
@@ -63,8 +62,6 @@ def main():
                             _C.check(lib.bf_set_fused_small_max_rows(0), "set")
                             return y
                         runs["B fused-small"] = fused
-                    for sh in (1, 2):
-                        runs[f"C ws x{sh}"] = (lambda sh=sh: ops.linear_forward_ws(layer, x, S, seed, base, lp, sh))
                     for name, fn in runs.items():
                         y = fn()
                         torch.cuda.synchronize()

@@ -38,7 +38,6 @@ def overlapped():
     gemm()
     torch.cuda.current_stream().wait_event(done)
 
-print("variant", os.environ.get("BF_GEMM_VARIANT", "default"))
 print("gemm only   %.1f us" % timeit(gemm))
 print("sample only %.1f us" % timeit(sample))
 print("serial      %.1f us" % timeit(serial))

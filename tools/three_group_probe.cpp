@@ -5,7 +5,7 @@
 // partner's load slot); a third wave per SIMD would make that min(1, 3 M / (L + M)).  The probe keeps what decides that —
 // the fragment reads, the MFMAs, the barriers and (optionally) LDS-DMA pieces from an L2-resident buffer — and drops the
 // rest (no tiles, no epilogue, garbage operands).
-//   make -C tools bin/three_group_probe && tools/bin/three_group_probe
+//   hipcc -O3 --offload-arch=gfx950 tools/three_group_probe.cpp -o tools/three_group_probe && ./tools/three_group_probe
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
