@@ -251,6 +251,7 @@ int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, c
     if (B > 65535 || H > 65535) BF_FAIL("bf_attention_fwd: B or H exceeds the grid");
     if (token_stride < (long long)H * HD || token_stride % 8) BF_FAIL("bf_attention_fwd: bad token stride %lld", token_stride);
     if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) BF_FAIL("bf_attention_fwd: pointers must be 16-byte aligned");
+    if (d_mask && ((uintptr_t)d_mask & 15)) BF_FAIL("bf_attention_fwd: mask must be 16-byte aligned");  // read 16 bytes at a time
     AttnParams p;
     p.q = d_q;
     p.k = d_k;
