@@ -64,6 +64,8 @@ SYMBOLS = {
     "bf_gemm_nt_skinny": (_i, [_vp, _i, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "bf_gemm_nt_skinny_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "bf_gemm_nt_skinny_max_rows": (_i, []),
+    "bf_gemm_nt_rows": (_i, [_vp, _i, _i64, _i64, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_gemm_nt_rows_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "bf_gemm_nn_layers": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "bf_gemm_nn": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "bf_gemm_tn": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -86,12 +88,14 @@ SYMBOLS = {
     "bf_embedding_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, _i64, _i, _u64, _u32, _u32, _vp]),
     "bf_embedding_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _u64, _u32, _u32, _vp]),
     "bf_attention_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, ctypes.c_float, _vp]),
+    "bf_attention_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, _i, ctypes.c_float, _vp]),
     "bf_attention_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64,
                               ctypes.c_float, _vp]),
     "bf_add_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i]),
     "bf_add_layernorm_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i64, _i, ctypes.c_float, _vp]),
     "bf_embed_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _i, _i, _i64, _i64, _i64, _i64, ctypes.c_float, _vp]),
     "bf_add_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i64, _i, ctypes.c_float, _vp]),
+    "bf_add_layernorm_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i, _i64, _i, ctypes.c_float, _vp]),
     "bf_dropout_keep_host": (_i, [_vp, _u64, _u64, ctypes.c_float, _u64, _u32, _u32]),
     "bf_attention_fwd_dropout": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i64, ctypes.c_float,
                                       ctypes.c_float, _u64, _u32, _u32, _u64, _vp, _vp, _vp]),

@@ -6,6 +6,8 @@
 
 `to_bayesian` mirrors /root/reference/bayeformers/__init__.py:19-63.
 """
+import os
+import threading
 import types
 from copy import deepcopy
 from typing import Optional
@@ -635,11 +637,197 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     return out
 
 
+_POOLED_LAST_LAYER = [True]
+_POOLED_ACTIVE = threading.local()  # .layers: ids of the last layers whose head said "narrow" for the call running on this thread
+
+
+def pooled_last_layer(enable: bool = True) -> None:
+    """Switch the narrow last encoder layer of pooled-head models (installed by `fuse_attention`) on or off for this
+    process; BF_NO_POOLED_LAST_LAYER in the environment switches it off too.  Off: the layer runs on every row.  The switch
+    is part of what a captured forward bakes in (graphs.baked_state): a forward replayed from a HIP graph is captured again
+    at its next call after a flip."""
+    _POOLED_LAST_LAYER[0] = bool(enable)
+
+
+def pooled_last_layer_enabled() -> bool:
+    return _POOLED_LAST_LAYER[0] and os.environ.get("BF_NO_POOLED_LAST_LAYER") is None
+
+
+def _pooled_active(layer) -> bool:
+    return id(layer) in getattr(_POOLED_ACTIVE, "layers", ())
+
+
+def _hooked(module: torch.nn.Module) -> bool:
+    """Does a hook watch `module`?  transformers' own output-capturing hooks do not count: it leaves them on the layers for
+    good after the first call that asked for hidden states or attentions, and they do nothing in a call that asks for
+    neither (such a call keeps the full path by its arguments).  They are told by the module their closure was defined in,
+    `transformers.utils.output_capturing` — checked against transformers 5.15; should a release move it, the hooks count as
+    anybody's and the full layer runs from the first call that asked for hidden states on: slower, never wrong."""
+    fwd = [h for h in module._forward_hooks.values()
+           if getattr(h, "__module__", None) != "transformers.utils.output_capturing"]
+    return bool(fwd or module._forward_pre_hooks or module._backward_hooks or module._backward_pre_hooks)
+
+
+def _pooled_head_forward(self, *args, **kwargs):
+    """forward of a BertForSequenceClassification: decides, per call, whether the last encoder layer may compute the
+    [CLS] rows alone (the head reads pooler(hidden[:, 0]) and nothing else of that layer), tells the layer, and runs the
+    module's own forward.  Everything the narrow layer cannot honour keeps the full path: hidden states or attentions
+    asked for (arguments or config), gradients recorded, training mode, a hook on the encoder, the pooler or any module of
+    the last layer, a fusion that is not installed."""
+    import torch.nn.modules.module as tmod
+
+    bert = self.bert
+    last = bert.encoder.layer[-1]
+    cfg = self.config
+    # (any module in training mode: nn.Dropout modules switched back on in an eval() model — Monte-Carlo dropout — drop inside
+    # the full layer's kernels, which the narrow layer does not do)
+    narrow = (pooled_last_layer_enabled()
+              and not torch.is_grad_enabled() and not self.training and not bert.training
+              and not any(m.training for m in last.modules()) and not any(m.training for m in bert.pooler.modules())
+              and bert.pooler is not None
+              and not kwargs.get("output_hidden_states") and not kwargs.get("output_attentions")
+              and not getattr(cfg, "output_hidden_states", False) and not getattr(cfg, "output_attentions", False)
+              and not getattr(cfg, "is_decoder", False) and not getattr(cfg, "add_cross_attention", False)
+              and not (tmod._global_forward_hooks or tmod._global_forward_pre_hooks or tmod._global_backward_hooks
+                       or tmod._global_backward_pre_hooks)
+              and not _hooked(bert.encoder) and not _hooked(bert.encoder.layer)
+              and not any(_hooked(m) for m in bert.pooler.modules()) and not any(_hooked(m) for m in last.modules())
+              and _pooled_fusions_installed(last))
+    if not narrow:
+        return self._bf_plain_forward(*args, **kwargs)
+    before = getattr(_POOLED_ACTIVE, "layers", frozenset())
+    _POOLED_ACTIVE.layers = before | {id(last)}  # (per thread: two threads on one model do not see each other's verdict)
+    try:
+        return self._bf_plain_forward(*args, **kwargs)
+    finally:
+        _POOLED_ACTIVE.layers = before
+
+
+def _pooled_fusions_installed(last) -> bool:
+    """residual+LayerNorm, query/key/value and attention fusions on the last layer, and the GELU in the up-projection."""
+    so, out, sa = last.attention.output, last.output, last.attention.self
+
+    def ln_fused(m):
+        f = m.__dict__.get("forward")
+        return isinstance(f, types.MethodType) and f.__func__ is _dense_residual_norm_forward
+
+    dense = (so.dense, last.intermediate.dense, out.dense)
+    return (ln_fused(so) and ln_fused(out) and all(isinstance(l, nn.Linear) for l in dense)
+            and all(l.activation is None for l in (so.dense, out.dense))
+            and last.intermediate.dense.activation == "gelu"
+            and isinstance(last.intermediate.intermediate_act_fn, _FusedIntoDense)
+            and all(isinstance(getattr(sa, n, None), nn.Linear) and getattr(sa, n)._shared_input is not None
+                    for n in ("query", "key", "value"))
+            and getattr(sa.config, "_attn_implementation", None) == _ATTENTION_NAME
+            and last.chunk_size_feed_forward == 0)
+
+
+def _pooled_last_layer_forward(self, hidden_states, attention_mask=None, encoder_hidden_states=None,
+                               encoder_attention_mask=None, past_key_values=None, **kwargs):
+    """forward of the LAST BertLayer under a pooled head (`_pooled_head_forward` said so for this call): everything behind
+    the key / value projections is computed for the [CLS] row of each sequence alone — one query row per (sequence, head)
+    against all keys and values (bf_attention_fwd_rows), the three dense layers on B rows per sample (bf_gemm_nt_rows) on
+    the weights the sampling plan drew anyway, the two residual+LayerNorm passes on those rows (bf_add_layernorm_rows reads
+    the residual where it lies).  Returns [S*B, 1, hidden]: the pooler's hidden[:, 0] is that row.  Per row the arithmetic
+    is the full layer's, except that the dense layers sum over k in the streaming kernel's order.  Whatever this form does
+    not take — no sampling plan, another dtype, cached keys, an attention mask with per-query structure — runs the
+    module's own forward on every row."""
+    from . import ops
+
+    def full():
+        return self._bf_plain_layer_forward(hidden_states, attention_mask, encoder_hidden_states,
+                                            encoder_attention_mask=encoder_attention_mask, past_key_values=past_key_values,
+                                            **kwargs)
+
+    if not _pooled_active(self):
+        return full()
+    ctx = bfr.STATE.ctx
+    plan = ctx.plan if ctx is not None else None
+    sa, so, up, down = self.attention.self, self.attention.output, self.intermediate.dense, self.output
+    dense = (so.dense, up, down.dense)
+    h = hidden_states
+    if (plan is None or ctx.kept is not None or encoder_hidden_states is not None or past_key_values is not None
+            or torch.is_grad_enabled() or any(m.training for m in self.modules()) or h.dim() != 3 or not h.is_cuda or not h.is_contiguous()
+            or h.dtype not in (torch.bfloat16, torch.float16) or plan.cdt != h.dtype
+            or h.shape[0] % ctx.S or any(id(l) not in plan.group_of or l._small_m for l in dense)
+            or any(l.in_features % 32 or l.out_features % 8 for l in dense)
+            # a layer so small that the full layer runs the single small-M kernel outside the sampling plan keeps doing so
+            # (the plan holds exactly the layers it would hold without this rewrite)
+            or any(h.shape[0] * h.shape[1] // ctx.S <= ops.fused_small_rows(l.out_features, l.in_features) for l in dense)
+            or not ops.layernorm_supported(h[:, :1], None, so.LayerNorm)
+            or not ops.layernorm_supported(h[:, :1], None, down.LayerNorm)):
+        return full()
+    Bt, T, Hd = h.shape
+    S = ctx.S
+    M = Bt // S
+    H, D = sa.num_attention_heads, sa.attention_head_size
+    q = sa.query(h).view(Bt, T, H, D).transpose(1, 2)  # (one stacked launch serves the three)
+    k = sa.key(h).view(Bt, T, H, D).transpose(1, 2)
+    v = sa.value(h).view(Bt, T, H, D).transpose(1, 2)
+    key_mask = mask_off = None
+    rows_attention = ops.attention_supported(q, k, v)
+    if rows_attention and attention_mask is not None:
+        ready = getattr(attention_mask, "_bf_key_mask", None)
+        if ready is not None and ready.shape == (Bt, T):
+            key_mask, mask_off = ready, attention_mask._bf_mask_off
+        else:
+            rows_attention = False
+    if rows_attention:
+        a = ops.attention_forward_rows(q, k, v, key_mask, sa.scaling, mask_off, q_rows=1).view(Bt, Hd)
+        a_row_stride = Hd
+    else:
+        # the attention this length or mask needs, on every query; its [CLS] rows are read where they lie
+        from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+
+        fn = ALL_ATTENTION_FUNCTIONS.get_interface(sa.config._attn_implementation, None)
+        a, _ = fn(sa, q, k, v, attention_mask, dropout=0.0, scaling=sa.scaling, **kwargs)
+        a = a.reshape(Bt, T, Hd)
+        a = a if a.is_contiguous() else a.contiguous()
+        a_row_stride = T * Hd
+
+    def rows_linear(layer, x, row_stride, act=0):
+        w_s, b_s = plan.ensure(layer, ctx.token, bfr.STATE.seed, ctx.sample_base, ctx.lp_buf)
+        y = ops.gemm_nt_rows(x, w_s, b_s, S, M, layer.out_features, layer.in_features, M * row_stride, row_stride, act)
+        layer._lp_view, layer._lp_dirty = ctx.slot(layer), True
+        return y
+
+    ln1, ln2 = so.LayerNorm, down.LayerNorm
+    y = rows_linear(so.dense, a, a_row_stride)
+    y = ops.add_layernorm_rows(y, h, T * Hd, ln1.weight, ln1.bias, ln1.eps)  # residual: the [CLS] rows of the layer's input
+    z = rows_linear(up, y, Hd, 1)
+    z = rows_linear(down.dense, z, up.out_features)
+    z = ops.add_layernorm(z, y, ln2.weight, ln2.bias, ln2.eps)
+    return z.view(Bt, 1, Hd)
+
+
+def _install_pooled_last_layer(inner: torch.nn.Module) -> bool:
+    """A BertForSequenceClassification (BertModel with a pooler under a head that reads pooler_output alone): its forward and
+    its last encoder layer's get the per-call narrow path.  Any other model is left as it is."""
+    for head in inner.modules():
+        bert = getattr(head, "bert", None)
+        if (type(head).__name__ != "BertForSequenceClassification" or type(bert).__name__ != "BertModel"
+                or getattr(bert, "pooler", None) is None or hasattr(head, "_bf_plain_forward")):
+            continue
+        layers = getattr(getattr(bert, "encoder", None), "layer", None)
+        if not layers or type(layers[-1]).__name__ != "BertLayer":
+            continue
+        last = layers[-1]
+        last._bf_plain_layer_forward = last.forward
+        last.forward = types.MethodType(_pooled_last_layer_forward, last)
+        head._bf_plain_forward = head.forward
+        head.forward = types.MethodType(_pooled_head_forward, head)
+        return True
+    return False
+
+
 def fuse_attention(model: torch.nn.Module) -> bool:
     """Route the wrapped HuggingFace model's attention through bf_attention_fwd: registers an attention function in
     transformers' AttentionInterface (mask format: the scaled-dot-product one) and selects it in the model's config.
     The function falls back to the framework's attention for anything it does not take.  Returns False (and changes
-    nothing) when the model has no HuggingFace config or transformers lacks the interface."""
+    nothing) when the model has no HuggingFace config or transformers lacks the interface.
+    A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation
+    forwards that ask for neither hidden states nor attentions, everything behind the last layer's key / value
+    projections runs on the [CLS] rows alone (`pooled_last_layer(False)` or BF_NO_POOLED_LAST_LAYER: on every row)."""
     try:
         from transformers import AttentionInterface
         from transformers.masking_utils import AttentionMaskInterface, sdpa_mask
@@ -655,4 +843,5 @@ def fuse_attention(model: torch.nn.Module) -> bool:
         c = getattr(m, "config", None)
         if c is not None and hasattr(c, "_attn_implementation"):
             c._attn_implementation = _ATTENTION_NAME
+    _install_pooled_last_layer(inner)
     return True

@@ -303,6 +303,23 @@ int bf_gemm_nt_layers(const void* d_x, int x_dtype, int64_t x_sample_stride, con
                              (hipStream_t)stream, act, L);
 }
 
+int bf_gemm_nt_rows(const void* d_x, int x_dtype, int64_t x_sample_stride, int64_t x_row_stride, const void* d_w, int w_dtype,
+                    const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
+                    size_t workspace_bytes, void* stream) {
+    if (act != BF_ACT_NONE && act != BF_ACT_GELU) BF_FAIL("bf_gemm_nt_rows: unknown activation %d", act);
+    if (x_row_stride < K) BF_FAIL("bf_gemm_nt_rows: x row stride %lld < K=%d", (long long)x_row_stride, K);
+    if (M < 1 || x_sample_stride < (int64_t)(M - 1) * x_row_stride + K)
+        BF_FAIL("bf_gemm_nt_rows: x sample stride %lld does not hold M=%d rows", (long long)x_sample_stride, M);
+    ProfScope prof(BF_PROF_GEMM, 2.0 * S * M * (double)N * K, (hipStream_t)stream);
+    return bf_launch_gemm_nt(d_x, x_dtype, x_sample_stride, d_w, w_dtype, d_bias, d_y, y_dtype, S, M, N, K,
+                             (hipStream_t)stream, act, 1, nullptr, x_row_stride, d_workspace, workspace_bytes);
+}
+
+size_t bf_gemm_nt_rows_workspace_bytes(int dtype, int S, int M, int N, int K) {
+    if (S < 1 || M < 1 || N < 1 || K < 1) return 0;
+    return bf_gemm_nt_rows_workspace_impl(dtype, S, M, N, K);
+}
+
 int bf_gemm_nt_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                       const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
                       size_t workspace_bytes, void* stream) {
@@ -422,6 +439,15 @@ int bf_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamm
                                    (hipStream_t)stream);
 }
 
+int bf_add_layernorm_rows(const void* d_x, const void* d_residual, int64_t residual_row_stride, const void* d_gamma,
+                          const void* d_beta, int param_dtype, void* d_out, int dtype, int64_t rows, int N, float eps,
+                          void* stream) {
+    if (!d_residual) BF_FAIL("bf_add_layernorm_rows: d_residual is NULL");
+    if (residual_row_stride < N) BF_FAIL("bf_add_layernorm_rows: residual row stride %lld < N=%d", (long long)residual_row_stride, N);
+    return bf_launch_add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps,
+                                   (hipStream_t)stream, nullptr, residual_row_stride);
+}
+
 int bf_embed_layernorm(const int64_t* d_ids, const int64_t* d_type_ids, const int64_t* d_pos_ids, const void* d_word,
                        const void* d_type, const void* d_pos, const void* d_gamma, const void* d_beta, int param_dtype,
                        void* d_out, int dtype, int64_t rows, int N, int seq_len, int64_t pos_rows, int64_t word_rows,
@@ -436,6 +462,14 @@ int bf_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const fl
                      float scaling, void* stream) {
     return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim,
                                    token_stride, scaling, (hipStream_t)stream);
+}
+
+int bf_attention_fwd_rows(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                          void* d_out, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, int q_rows,
+                          float scaling, void* stream) {
+    if (q_rows < 1 || q_rows > 16) BF_FAIL("bf_attention_fwd_rows: q_rows=%d (1 .. 16)", q_rows);
+    return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, nullptr, dtype, B, T, H, head_dim,
+                                   token_stride, scaling, (hipStream_t)stream, nullptr, nullptr, q_rows);
 }
 
 int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,

@@ -78,13 +78,20 @@ struct AttnParams {
     // would have to evaluate eight Philox blocks per group of eight to regenerate them.
     bf_dropout_t drop;
     uint32_t* keep_bits;  // [B][H][T][T / 32]
+    // ROWS instantiation: only queries 0 .. q_rows - 1 (<= 16) of each (sequence, head) are computed, against all T keys;
+    // out is the compact [B][q_rows][H][64]
+    int q_rows;
 };
 
 // 3 workgroups per CU, for the DROP instantiation too: at 3 it spills 12 registers (168 VGPRs + 48 B of scratch), at 2 it does
 // not (178 VGPRs); measured back to back, same box: 69.9 vs 72.0 us at the BERT-base shape, 278 vs 304 us at 160 x 16 heads x
 // 384 tokens — the third workgroup is worth more than the spills cost.
-template <typename T, bool DROP = false>
+// ROWS: the first q_rows <= 16 queries only — the block (wave 0, qi 0) of the full kernel that owns them, run as it is (the
+// lanes past q_rows repeat the last row and store nothing), so those rows come out bit for bit as the full kernel's; the other
+// three waves only stage the key / value tiles, which is what the launch costs.
+template <typename T, bool DROP = false, bool ROWS = false>
 __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams p) {
+    static_assert(!(DROP && ROWS), "the query-subset form is an inference kernel");
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES + TKEY * 4];
@@ -107,7 +114,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
     for (int qb_i = 0; qb_i < 2; ++qb_i)
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh)
-            qf[qb_i][dh] = *reinterpret_cast<const frag*>(qb + (long long)(q0 + qb_i * 16 + li) * p.tok_stride + dh * 32 + lg * 8);
+            qf[qb_i][dh] = *reinterpret_cast<const frag*>(
+                qb + (long long)(ROWS ? min(li, p.q_rows - 1) : q0 + qb_i * 16 + li) * p.tok_stride + dh * 32 + lg * 8);
 
     f32x4_t o[2][4];
 #pragma unroll
@@ -135,6 +143,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
         // One block of 16 queries at a time (keeps the live scores at 32 registers, 4 waves per SIMD fit).
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi) {
+            if (ROWS && (qi || wid)) continue;  // (wave-uniform)
             // S^T[key][query]: lane (query li, group lg) holds keys kb*16 + 4*lg + 0..3 of each 16-key block
             f32x4_t s[8];
 #pragma unroll
@@ -221,6 +230,17 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
     }
 
     // lane (query li, group lg) holds features db*16 + 4*lg + 0..3 of its query: 8-byte stores
+    if constexpr (ROWS) {
+        if (wid || li >= p.q_rows) return;
+        T* orow = reinterpret_cast<T*>(p.out) + (((long long)b * p.q_rows + li) * p.H + h) * HD;
+        const float inv = run_sum[0] > 0.f ? 1.0f / run_sum[0] : 0.f;
+#pragma unroll
+        for (int db = 0; db < 4; ++db) {
+            const f32x4_t r = o[0][db] * inv;
+            attn_st8(reinterpret_cast<half4*>(orow + db * 16 + lg * 4), __builtin_convertvector(r, half4));
+        }
+        return;
+    }
     T* ob = reinterpret_cast<T*>(p.out) + ((long long)b * p.T * p.H + h) * HD;
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
@@ -243,7 +263,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
                             const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype, int B, int T, int H,
                             int head_dim, long long token_stride, float scaling, hipStream_t stream,
-                            const bf_dropout_t* drop, uint32_t* d_keep_bits) {
+                            const bf_dropout_t* drop, uint32_t* d_keep_bits, int q_rows) {
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("bf_attention_fwd: NULL argument");
     if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("bf_attention_fwd: dtype must be bf16 or fp16");
     if (head_dim != HD) BF_FAIL("bf_attention_fwd: head size %d (only %d)", head_dim, HD);
@@ -268,6 +288,16 @@ int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, c
     const dim3 grid(T / TQ, H, B);
     p.keep_bits = nullptr;
     p.drop = bf_dropout_t{0, 0, 0, 0, 0, 1.0f, 0, 0, nullptr};
+    p.q_rows = q_rows;
+    if (q_rows) {
+        if (q_rows < 1 || q_rows > 16) BF_FAIL("bf_attention_fwd_rows: q_rows=%d (1 .. 16)", q_rows);
+        if (d_lse || (drop && drop->thresh)) BF_FAIL("bf_attention_fwd_rows: inference only (no log-sum-exp rows, no dropout)");
+        const dim3 rgrid(1, H, B);
+        if (dtype == BF_DT_BF16) hipLaunchKernelGGL((attention_fwd_kernel<__bf16, false, true>), rgrid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((attention_fwd_kernel<_Float16, false, true>), rgrid, dim3(256), 0, stream, p);
+        BF_HIP_CHECK(hipGetLastError());
+        return 0;
+    }
     if (drop && drop->thresh) {
         if (d_keep_bits && ((uintptr_t)d_keep_bits & 3)) BF_FAIL("bf_attention_fwd: keep bits must be 4-byte aligned");
         p.drop = *drop;

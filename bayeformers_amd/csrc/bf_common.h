@@ -78,12 +78,20 @@ int bf_launch_reduce_groups(const double* d_partials, const uint32_t* d_rows, in
                             hipStream_t stream);
 int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                       const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, hipStream_t stream,
-                      int act = BF_ACT_NONE, int layers = 1, void* d_pre = nullptr);
+                      int act = BF_ACT_NONE, int layers = 1, void* d_pre = nullptr, int64_t x_row_stride = 0,
+                      void* d_workspace = nullptr, size_t workspace_bytes = 0);
+// x_row_stride: elements between consecutive rows of x (0 = K, rows back to back).  A call that names one (bf_gemm_nt_rows)
+// runs the weight-streaming kernel of bf_gemm_skinny.hip when bf_gemm_skinny_refuses() is NULL (d_workspace: its split-K
+// scratch, bf_gemm_nt_rows_workspace_impl bytes — missing or too small is an error), else the generic 128 x 128 kernel.
+size_t bf_gemm_nt_rows_workspace_impl(int dtype, int S, int M, int N, int K);
 // skinny NT GEMM on kept weights (bf_gemm_skinny.hip)
 int bf_launch_gemm_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                           const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act,
-                          void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+                          void* d_workspace, size_t workspace_bytes, hipStream_t stream, int64_t x_row_stride = 0);
 size_t bf_gemm_skinny_workspace_impl(int S, int M, int N, int K);
+// NULL when the skinny kernel takes these dtypes, this shape and these operand / stride alignments, else the reason
+const char* bf_gemm_skinny_refuses(int x_dtype, int w_dtype, int y_dtype, int S, int M, int N, int K,
+                                   int64_t x_sample_stride, int64_t x_row_stride, const void* d_x, const void* d_w);
 int bf_gemm_skinny_max_rows_impl();
 // out = gelu(in) elementwise (16-bit or fp32 tensors of n elements)
 int bf_launch_gelu(const void* d_in, void* d_out, int dtype, uint64_t n, hipStream_t stream);
@@ -202,7 +210,7 @@ int bf_launch_embedding_bwd(const long long* d_ids, const void* d_grad, int grad
 struct bf_dropout_t;  // bf_philox.h
 int bf_launch_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta,
                             int param_dtype, void* d_out, int dtype, long long rows, int N, float eps,
-                            hipStream_t stream, const bf_dropout_t* drop = nullptr);
+                            hipStream_t stream, const bf_dropout_t* drop = nullptr, long long residual_row_stride = 0);
 int bf_launch_embed_layernorm(const long long* d_ids, const long long* d_type_ids, const long long* d_pos_ids,
                               const void* d_word, const void* d_type, const void* d_pos, const void* d_gamma,
                               const void* d_beta, int param_dtype, void* d_out, int dtype, long long rows, int N,
@@ -211,7 +219,7 @@ int bf_launch_embed_layernorm(const long long* d_ids, const long long* d_type_id
 int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
                             const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype, int B, int T, int H,
                             int head_dim, long long token_stride, float scaling, hipStream_t stream,
-                            const bf_dropout_t* drop = nullptr, uint32_t* d_keep_bits = nullptr);
+                            const bf_dropout_t* drop = nullptr, uint32_t* d_keep_bits = nullptr, int q_rows = 0);
 int bf_launch_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
                             const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
                             float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, int B, int T, int H,

@@ -101,8 +101,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmParams p) {
 
     // loader mapping: two 8-element chunks per operand per thread
     const int lr = tid >> 2, lk = (tid & 3) * 8;
-    const XT* xrow0 = x + (long long)min(m0 + lr, M - 1) * K;
-    const XT* xrow1 = x + (long long)min(m0 + lr + 64, M - 1) * K;
+    const XT* xrow0 = x + (long long)min(m0 + lr, M - 1) * p.x_rstride;
+    const XT* xrow1 = x + (long long)min(m0 + lr + 64, M - 1) * p.x_rstride;
     const T* wrow0 = w + (long long)min(n0 + lr, N - 1) * K;
     const T* wrow1 = w + (long long)min(n0 + lr + 64, N - 1) * K;
 
@@ -272,7 +272,20 @@ int launch_16_xy(const GemmParams& p, int x_dtype, int y_dtype, int t_dtype, boo
 
 int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                       const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, hipStream_t stream,
-                      int act, int layers, void* d_pre) {
+                      int act, int layers, void* d_pre, int64_t x_row_stride, void* d_workspace,
+                      size_t workspace_bytes) {
+    if (x_row_stride) {
+        // rows of x that do not lie back to back (the [CLS] rows of a [S][B*L][K] activation): M is small by construction, so
+        // the launch is a stream over W_s — the skinny kernel — and whatever that refuses runs the generic tiled kernel below
+        if (layers != 1 || d_pre) BF_FAIL("bf_gemm_nt: a row stride goes with one layer and one output");
+        if (x_row_stride < K || x_sample_stride < 0) BF_FAIL("bf_gemm_nt: x row stride %lld < K=%d", (long long)x_row_stride, K);
+        if (w_dtype == BF_DT_F32) BF_FAIL("bf_gemm_nt: a row stride needs 16-bit weights");
+        // the kernel is chosen by dtype, shape and operand alignment alone (the one predicate the skinny launcher itself checks);
+        // a shape that is the streaming kernel's but comes without its workspace fails there, it does not run the slow kernel
+        if (!bf_gemm_skinny_refuses(x_dtype, w_dtype, y_dtype, S, M, N, K, x_sample_stride, x_row_stride, d_x, d_w))
+            return bf_launch_gemm_skinny(d_x, x_dtype, x_sample_stride, d_w, w_dtype, d_bias, d_y, y_dtype, S, M, N, K, act,
+                                         d_workspace, workspace_bytes, stream, x_row_stride);
+    }
     if (layers < 1) BF_FAIL("bf_gemm_nt: layers must be >= 1 (got %d)", layers);
     if (d_pre) {
         // pre-activation wanted next to act(y) (the forward of a training step): one launch with two outputs when the
@@ -328,6 +341,7 @@ int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, con
     p.K = K;
     p.act = act;
     p.layers = layers;
+    p.x_rstride = x_row_stride ? x_row_stride : K;
     if (w_dtype == BF_DT_F32) {
         if (x_dtype != BF_DT_F32 || y_dtype != BF_DT_F32) BF_FAIL("bf_gemm_nt: fp32 weights need fp32 x and y");
         // large aligned problems: the 256-wide ring kernel on v_mfma_f32_16x16x4_f32 (BF_F32_GENERIC: developer A/B)
@@ -344,14 +358,14 @@ int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, con
         return 0;
     }
     // large aligned problems: the 256x256x64 LDS-DMA kernel; everything else: the generic 128x128x32 kernel
-    if ((long long)M * N >= 128 * 128 && ((uintptr_t)d_bias & 15) == 0 &&
+    if (!x_row_stride && (long long)M * N >= 128 * 128 && ((uintptr_t)d_bias & 15) == 0 &&
         bf_gemm256_supported(x_dtype, w_dtype, y_dtype, layers * S, M, N, K, d_x, d_w, x_sample_stride))
         return bf_launch_gemm256(p, w_dtype, y_dtype, stream);
     p.tiles_m = (M + BM - 1) / BM;
     p.tiles_n = (N + BN - 1) / BN;
     const size_t xs = bf_dtype_size(x_dtype);
     const bool aligned = (K % 8) == 0 && ((uintptr_t)d_x % 16) == 0 && ((uintptr_t)d_w % 16) == 0 &&
-                         ((size_t)x_sample_stride * xs) % 16 == 0;
+                         ((size_t)x_sample_stride * xs) % 16 == 0 && ((size_t)p.x_rstride * xs) % 16 == 0;
     if (w_dtype == BF_DT_BF16) return launch_16_xy<__bf16>(p, x_dtype, y_dtype, BF_DT_BF16, aligned, stream);
     if (w_dtype == BF_DT_F16) return launch_16_xy<_Float16>(p, x_dtype, y_dtype, BF_DT_F16, aligned, stream);
     BF_FAIL("bf_gemm_nt: bad w dtype %d", w_dtype);

@@ -26,6 +26,8 @@ struct GemmParams {
     // input gradient of `segs` layers that read the same activations, dx = sum_l dy_l W_l, in one launch
     int segs;
     long long x_seg_stride, w_seg_stride;
+    // generic 128 x 128 kernel only: elements between consecutive rows of x (the launcher sets K for rows back to back)
+    long long x_rstride;
 };
 
 // fast 256-wide LDS-DMA kernel (bf_gemm256.hip)

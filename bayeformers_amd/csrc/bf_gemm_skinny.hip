@@ -25,6 +25,7 @@ constexpr int kMaxRows = 64;
 struct SkinnyParams {
     const void* x;
     long long x_sstride;
+    long long x_rstride;  // elements between consecutive rows of x (K for rows back to back)
     const void* w;
     const float* bias;
     void* y;
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const SkinnyParams
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
         const int m = min(mb * 16 + (lane & 15), M - 1);
-        xrow[mb] = reinterpret_cast<const T*>(p.x) + (long long)s * p.x_sstride + (long long)m * K + kq;
+        xrow[mb] = reinterpret_cast<const T*>(p.x) + (long long)s * p.x_sstride + (long long)m * p.x_rstride + kq;
     }
 
     f32x4_t acc[NB][MB];
@@ -249,22 +250,40 @@ size_t bf_gemm_skinny_workspace_impl(int S, int M, int N, int K) {
     return sp > 1 ? (size_t)sp * S * M * N * sizeof(float) : 0;
 }
 
+const char* bf_gemm_skinny_refuses(int x_dtype, int w_dtype, int y_dtype, int S, int M, int N, int K,
+                                   int64_t x_sample_stride, int64_t x_row_stride, const void* d_x, const void* d_w) {
+    if (w_dtype != BF_DT_BF16 && w_dtype != BF_DT_F16) return "weights must be bf16 or fp16";
+    if (x_dtype != w_dtype || y_dtype != x_dtype) return "x and y must have the weights' dtype";
+    if (S < 1 || S > 65535 || M < 1 || M > kMaxRows || N < 1 || K < 32 || K % 32 != 0)
+        return "unsupported shape (1 <= S <= 65535, 1 <= M <= 64, K % 32 == 0)";
+    if (((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)(x_sample_stride * 2) | (uintptr_t)(x_row_stride * 2)) & 15)
+        return "x, w and the x sample and row strides must be 16-byte aligned";
+    return nullptr;
+}
+
+size_t bf_gemm_nt_rows_workspace_impl(int dtype, int S, int M, int N, int K) {
+    // (whatever the streaming kernel refuses by shape runs the tiled kernel: no scratch)
+    if (bf_gemm_skinny_refuses(dtype, dtype, dtype, S, M, N, K, 0, 0, nullptr, nullptr)) return 0;
+    return bf_gemm_skinny_workspace_impl(S, M, N, K);
+}
+
 int bf_launch_gemm_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                           const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act,
-                          void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+                          void* d_workspace, size_t workspace_bytes, hipStream_t stream, int64_t x_row_stride) {
     if (!d_x || !d_w || !d_y) BF_FAIL("bf_gemm_nt_skinny: NULL operand");
-    if (w_dtype != BF_DT_BF16 && w_dtype != BF_DT_F16) BF_FAIL("bf_gemm_nt_skinny: weights must be bf16 or fp16");
-    if (x_dtype != w_dtype || y_dtype != x_dtype) BF_FAIL("bf_gemm_nt_skinny: x and y must have the weights' dtype");
     if (act != BF_ACT_NONE && act != BF_ACT_GELU) BF_FAIL("bf_gemm_nt_skinny: unknown activation %d", act);
-    if (S < 1 || S > 65535 || M < 1 || M > kMaxRows || N < 1 || K < 32 || K % 32 != 0)
-        BF_FAIL("bf_gemm_nt_skinny: unsupported shape S=%d M=%d N=%d K=%d (1 <= S <= 65535, 1 <= M <= %d, K %% 32 == 0)", S, M,
-                N, K, kMaxRows);
-    if (x_sample_stride < (int64_t)M * K) BF_FAIL("bf_gemm_nt_skinny: x sample stride %lld < M*K", (long long)x_sample_stride);
-    if (((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)(x_sample_stride * 2)) & 15)
-        BF_FAIL("bf_gemm_nt_skinny: x, w and the x sample stride must be 16-byte aligned");
+    if (!x_row_stride) x_row_stride = K;
+    if (const char* why = bf_gemm_skinny_refuses(x_dtype, w_dtype, y_dtype, S, M, N, K, x_sample_stride, x_row_stride, d_x, d_w))
+        BF_FAIL("bf_gemm_nt_skinny: %s (S=%d M=%d N=%d K=%d, x sample stride %lld, row stride %lld)", why, S, M, N, K,
+                (long long)x_sample_stride, (long long)x_row_stride);
+    if (x_row_stride < K) BF_FAIL("bf_gemm_nt_skinny: x row stride %lld < K", (long long)x_row_stride);
+    if (x_sample_stride < (int64_t)(M - 1) * x_row_stride + K)
+        BF_FAIL("bf_gemm_nt_skinny: x sample stride %lld < the rows of a sample", (long long)x_sample_stride);
+    if ((uintptr_t)d_y & 7) BF_FAIL("bf_gemm_nt_skinny: y must be 8-byte aligned");
     SkinnyParams p{};
     p.x = d_x;
     p.x_sstride = x_sample_stride;
+    p.x_rstride = x_row_stride;
     p.w = d_w;
     p.bias = d_bias;
     p.y = d_y;

@@ -71,13 +71,13 @@ __device__ __forceinline__ void drop8(const bf_dropout_t& d, long long row, int 
 template <typename T, typename GT, int VPL, bool DROP = false>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void add_layernorm_kernel(
     const T* __restrict__ x, const T* __restrict__ res, const GT* __restrict__ gamma, const GT* __restrict__ beta,
-    T* __restrict__ out, long long rows, int N, float eps, const bf_dropout_t drop) {
+    T* __restrict__ out, long long rows, int N, float eps, const bf_dropout_t drop, long long res_stride) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int nvec = N >> 3;
     const T* xr = x + row * N;
-    const T* rr = res ? res + row * N : nullptr;
+    const T* rr = res ? res + row * res_stride : nullptr;
     float v[VPL][8];
     float sum = 0.f;
 #pragma unroll
@@ -131,14 +131,14 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void add_layernorm_kernel(
 template <typename T, typename GT, int V, bool DROP = false>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void add_layernorm_half_kernel(
     const T* __restrict__ x, const T* __restrict__ res, const GT* __restrict__ gamma, const GT* __restrict__ beta,
-    T* __restrict__ out, long long rows, int N, float eps, const bf_dropout_t drop) {
+    T* __restrict__ out, long long rows, int N, float eps, const bf_dropout_t drop, long long res_stride) {
     const int lane = threadIdx.x & 63, hl = lane & 31;
     const long long row_raw = ((long long)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6)) * 2 + (lane >> 5);
     if (row_raw - (lane >> 5) >= rows) return;           // the whole wave is past the end
     const bool live = row_raw < rows;
     const long long row = live ? row_raw : rows - 1;      // the idle half of the last wave reads a valid row
     const T* xr = x + row * N;
-    const T* rr = res ? res + row * N : nullptr;
+    const T* rr = res ? res + row * res_stride : nullptr;
     float v[V][8];
     float sum = 0.f;
 #pragma unroll
@@ -353,7 +353,7 @@ int launch_bwd_vpl(const void* x, const void* res, const void* gamma, const void
 
 template <typename T, typename GT>
 int launch_vpl(const void* x, const void* res, const void* gamma, const void* beta, void* out, long long rows, int N,
-               float eps, hipStream_t stream, const bf_dropout_t* drop) {
+               float eps, hipStream_t stream, const bf_dropout_t* drop, long long rs) {
     const int nvec = N >> 3;
     const bf_dropout_t d = drop ? *drop : bf_dropout_t{0, 0, 0, 0, 0, 1.0f, 0, 0, nullptr};
     if (nvec % 32 == 0 && nvec <= 128) {  // N = 256, 512, 768, 1024: half a wave per row
@@ -362,10 +362,10 @@ int launch_vpl(const void* x, const void* res, const void* gamma, const void* be
     do {                                                                                                                \
         if (d.thresh)                                                                                                   \
             hipLaunchKernelGGL((add_layernorm_half_kernel<T, GT, V, true>), hgrid, hblock, 0, stream, (const T*)x,      \
-                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d);             \
+                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d, rs);             \
         else                                                                                                            \
             hipLaunchKernelGGL((add_layernorm_half_kernel<T, GT, V, false>), hgrid, hblock, 0, stream, (const T*)x,     \
-                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d);             \
+                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d, rs);             \
     } while (0)
         switch (nvec / 32) {
             case 1: BF_LNH_LAUNCH(1); break;
@@ -382,10 +382,10 @@ int launch_vpl(const void* x, const void* res, const void* gamma, const void* be
     do {                                                                                                               \
         if (d.thresh)                                                                                                  \
             hipLaunchKernelGGL((add_layernorm_kernel<T, GT, VPL, true>), grid, block, 0, stream, (const T*)x,          \
-                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d);            \
+                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d, rs);            \
         else                                                                                                           \
             hipLaunchKernelGGL((add_layernorm_kernel<T, GT, VPL, false>), grid, block, 0, stream, (const T*)x,         \
-                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d);            \
+                               (const T*)res, (const GT*)gamma, (const GT*)beta, (T*)out, rows, N, eps, d, rs);            \
     } while (0)
     if (nvec <= 64) BF_LN_LAUNCH(1);
     else if (nvec <= 128) BF_LN_LAUNCH(2);
@@ -399,9 +399,9 @@ int launch_vpl(const void* x, const void* res, const void* gamma, const void* be
 
 template <typename T>
 int launch_gt(const void* x, const void* res, const void* gamma, const void* beta, int param_dtype, int dtype,
-              void* out, long long rows, int N, float eps, hipStream_t stream, const bf_dropout_t* drop) {
-    if (param_dtype == BF_DT_F32) return launch_vpl<T, float>(x, res, gamma, beta, out, rows, N, eps, stream, drop);
-    if (param_dtype == dtype) return launch_vpl<T, T>(x, res, gamma, beta, out, rows, N, eps, stream, drop);
+              void* out, long long rows, int N, float eps, hipStream_t stream, const bf_dropout_t* drop, long long rs) {
+    if (param_dtype == BF_DT_F32) return launch_vpl<T, float>(x, res, gamma, beta, out, rows, N, eps, stream, drop, rs);
+    if (param_dtype == dtype) return launch_vpl<T, T>(x, res, gamma, beta, out, rows, N, eps, stream, drop, rs);
     BF_FAIL("bf_add_layernorm: gamma/beta must be fp32 or have the activation dtype");
 }
 
@@ -500,8 +500,11 @@ int launch_embed(const long long* ids, const long long* type_ids, const long lon
 
 int bf_launch_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta,
                             int param_dtype, void* d_out, int dtype, long long rows, int N, float eps,
-                            hipStream_t stream, const bf_dropout_t* drop) {
+                            hipStream_t stream, const bf_dropout_t* drop, long long residual_row_stride) {
     if (rows < 0 || N <= 0) BF_FAIL("bf_add_layernorm: bad shape rows=%lld N=%d", rows, N);
+    // residual rows that do not lie back to back (the [CLS] rows of a [B*L, N] activation); x and out are always compact
+    const long long rs = residual_row_stride ? residual_row_stride : N;
+    if (rs < N || rs % 8) BF_FAIL("bf_add_layernorm: residual row stride %lld must be a multiple of 8 and at least N=%d", rs, N);
     if (rows == 0) return 0;
     if (!d_x || !d_gamma || !d_beta || !d_out) BF_FAIL("bf_add_layernorm: null pointer");
     if (N % 8 || N > 8192) BF_FAIL("bf_add_layernorm: N=%d must be a multiple of 8 and at most 8192", N);
@@ -509,9 +512,9 @@ int bf_launch_add_layernorm(const void* d_x, const void* d_residual, const void*
     const uintptr_t al = (uintptr_t)d_x | (uintptr_t)d_residual | (uintptr_t)d_gamma | (uintptr_t)d_beta | (uintptr_t)d_out;
     if (al & 15) BF_FAIL("bf_add_layernorm: pointers must be 16-byte aligned");
     switch (dtype) {
-        case BF_DT_BF16: return launch_gt<__bf16>(d_x, d_residual, d_gamma, d_beta, param_dtype, dtype, d_out, rows, N, eps, stream, drop);
-        case BF_DT_F16: return launch_gt<_Float16>(d_x, d_residual, d_gamma, d_beta, param_dtype, dtype, d_out, rows, N, eps, stream, drop);
-        case BF_DT_F32: return launch_gt<float>(d_x, d_residual, d_gamma, d_beta, param_dtype, dtype, d_out, rows, N, eps, stream, drop);
+        case BF_DT_BF16: return launch_gt<__bf16>(d_x, d_residual, d_gamma, d_beta, param_dtype, dtype, d_out, rows, N, eps, stream, drop, rs);
+        case BF_DT_F16: return launch_gt<_Float16>(d_x, d_residual, d_gamma, d_beta, param_dtype, dtype, d_out, rows, N, eps, stream, drop, rs);
+        case BF_DT_F32: return launch_gt<float>(d_x, d_residual, d_gamma, d_beta, param_dtype, dtype, d_out, rows, N, eps, stream, drop, rs);
     }
     BF_FAIL("bf_add_layernorm: unknown dtype %d", dtype);
 }

@@ -444,6 +444,31 @@ def skinny_linear_forward(x: Tensor, w_s: Tensor, b_s: Optional[Tensor], S: int,
     return y
 
 
+# launches of the row-subset entries from this process (tests, diagnostics): bf_gemm_nt_rows, bf_attention_fwd_rows,
+# bf_add_layernorm_rows — what the last encoder layer under a pooled head runs (bayeformers_amd._pooled_last_layer_forward)
+ROWS_CALLS = {"gemm": 0, "attention": 0, "layernorm": 0}
+
+
+def gemm_nt_rows(x: Tensor, w_s: Tensor, b_s: Optional[Tensor], S: int, M: int, N: int, K: int, x_sample_stride: int,
+                 x_row_stride: int, act: int = 0, out: Optional[Tensor] = None) -> Tensor:
+    """y[s] = act(x[s] W_s^T + b_s) for M rows per sample that lie `x_row_stride` elements apart (bf_gemm_nt_rows): row m
+    of sample s starts at x.data_ptr() + (s * x_sample_stride + m * x_row_stride) elements — the [CLS] rows of a
+    [S*B, L, K] activation at x_row_stride = L*K, read where they are.  w_s: [S, N, K] 16-bit, b_s: [S, N] fp32 or None;
+    returns the compact [S*M, N] of x's dtype.  A tiled-GEMM launch for bf_profile_*; the split-K scratch comes from the
+    stream's workspace."""
+    _require_device(x, "input")
+    lib = _C.lib()
+    y = out if out is not None else torch.empty((S * M, N), dtype=x.dtype, device=x.device)
+    need = lib.bf_gemm_nt_rows_workspace_bytes(_TORCH2BF[w_s.dtype], S, M, N, K)
+    ws = workspace(x.device, need) if need else None
+    _C.check(lib.bf_gemm_nt_rows(x.data_ptr(), _TORCH2BF[x.dtype], int(x_sample_stride), int(x_row_stride), w_s.data_ptr(),
+                                 _TORCH2BF[w_s.dtype], b_s.data_ptr() if b_s is not None else None, y.data_ptr(),
+                                 _TORCH2BF[y.dtype], S, M, N, K, int(act), ws.data_ptr() if ws is not None else None,
+                                 ws.numel() if ws is not None else 0, _stream_ptr()), "bf_gemm_nt_rows")
+    ROWS_CALLS["gemm"] += 1
+    return y
+
+
 COLSUMS_FOLDED = [0]  # bias gradients whose column sums came with the output gradient (tests, diagnostics)
 
 # Column sums a gradient's PRODUCER left for its consumer (attention_backward -> linear_backward of query / key / value).
@@ -698,6 +723,25 @@ def add_layernorm(x: Tensor, residual: Optional[Tensor], gamma: Tensor, beta: Te
                                        beta.data_ptr(), _TORCH2BF[gamma.dtype], out.data_ptr(), _TORCH2BF[x.dtype],
                                        x2.shape[0], N, float(eps), _stream_ptr()), "bf_add_layernorm")
     return out.view(x.shape)
+
+
+def add_layernorm_rows(x: Tensor, residual: Tensor, residual_row_stride: int, gamma: Tensor, beta: Tensor,
+                       eps: float) -> Tensor:
+    """LayerNorm(x + residual) with residual rows `residual_row_stride` elements apart (bf_add_layernorm_rows): x is the
+    compact [rows, N], row r of the residual starts at residual.data_ptr() + r * residual_row_stride elements.  Returns the
+    compact [rows, N]; per row the arithmetic of add_layernorm."""
+    _require_device(x, "add_layernorm_rows input")
+    rows, N = x.shape
+    if not x.is_contiguous() or residual.dtype != x.dtype:
+        raise _C.BayeFormersAMDError("add_layernorm_rows: x must be contiguous [rows, N] and the residual of its dtype")
+    if gamma.dtype != beta.dtype or gamma.dtype not in (torch.float32, x.dtype):
+        raise _C.BayeFormersAMDError("add_layernorm_rows: gamma/beta must be float32 or have the input's dtype")
+    out = torch.empty_like(x)
+    _C.check(_C.lib().bf_add_layernorm_rows(x.data_ptr(), residual.data_ptr(), int(residual_row_stride), gamma.data_ptr(),
+                                            beta.data_ptr(), _TORCH2BF[gamma.dtype], out.data_ptr(), _TORCH2BF[x.dtype],
+                                            rows, N, float(eps), _stream_ptr()), "bf_add_layernorm_rows")
+    ROWS_CALLS["layernorm"] += 1
+    return out
 
 
 def embed_layernorm(ids: Tensor, type_ids: Optional[Tensor], pos_ids: Optional[Tensor], word: Tensor, type_table: Tensor,
@@ -1151,6 +1195,27 @@ def attention_forward(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor
                                        _TORCH2BF[q.dtype], B, T, H, D, H * D, float(scaling), _stream_ptr()),
              "bf_attention_fwd")
     return (out, lse) if want_lse else out
+
+
+ATTENTION_MAX_Q_ROWS = 16
+
+
+def attention_forward_rows(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
+                           mask_off: Optional[Tensor] = None, q_rows: int = 1) -> Tensor:
+    """attention_forward for the first `q_rows` (1 .. 16) queries of every (sequence, head) against all T keys and values
+    (bf_attention_fwd_rows).  q, k, v, key_mask, mask_off as attention_forward takes them; returns the compact
+    [B, q_rows, H, 64], bit for bit rows 0 .. q_rows - 1 of attention_forward's output."""
+    B, H, T, D = q.shape
+    if not 1 <= int(q_rows) <= ATTENTION_MAX_Q_ROWS:
+        raise _C.BayeFormersAMDError(f"attention_forward_rows: q_rows={q_rows} (1 .. {ATTENTION_MAX_Q_ROWS})")
+    out = torch.empty((B, int(q_rows), H, D), dtype=q.dtype, device=q.device)
+    _C.check(_C.lib().bf_attention_fwd_rows(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                            key_mask.data_ptr() if key_mask is not None else None,
+                                            mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
+                                            _TORCH2BF[q.dtype], B, T, H, D, H * D, int(q_rows), float(scaling),
+                                            _stream_ptr()), "bf_attention_fwd_rows")
+    ROWS_CALLS["attention"] += 1
+    return out
 
 
 def attention_backward(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], mask_off: Optional[Tensor],

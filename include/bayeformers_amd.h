@@ -31,7 +31,9 @@ extern "C" {
                                read from (re-checked by the kernels), bf_stale_counter; bf_linear_bwd takes d_dy_colsum,
                                bf_attention_bwd_colsum; the dropout entries take first_group; 6: the dropout entries take d_call
                                (device-resident part of the call number), bf_gemm_schedule_policy / _fetch_rows,
-                               bf_profile_read_launches */
+                               bf_profile_read_launches; still 6 (additions only, no signature changed): bf_gemm_nt_rows,
+                               bf_gemm_nt_rows_workspace_bytes, bf_attention_fwd_rows, bf_add_layernorm_rows — a library
+                               without them fails to bind by the missing symbol */
 
 /* element types of activations / sampled weights */
 enum { BF_DT_F32 = 0, BF_DT_BF16 = 1, BF_DT_F16 = 2 };
@@ -190,6 +192,22 @@ size_t bf_gemm_nt_skinny_workspace_bytes(int S, int M, int N, int K);
 /* Rows per sample the skinny kernel takes (64). */
 int bf_gemm_nt_skinny_max_rows(void);
 
+/* bf_gemm_nt_act on a few rows per sample that do not lie back to back (F.linear, layers/linear.py:104, on the rows a caller
+ * keeps): row m of sample s is at d_x + s * x_sample_stride + m * x_row_stride elements (x_row_stride >= K) — e.g. the [CLS]
+ * rows of a [S][B*L][K] activation at x_row_stride = L*K, read in place, no gather copy.  y [S][M][N] is compact.  Counted as
+ * a tiled-GEMM launch by bf_profile_*.  16-bit operands of one dtype with M <= bf_gemm_nt_skinny_max_rows(), K % 32 == 0,
+ * strides that are multiples of 8 elements and 16-byte aligned x / w (8-byte y) stream the weights through
+ * bf_gemm_nt_skinny's kernel (fp32 accumulation, each output's k split over four waves — and over workgroups when
+ * bf_gemm_nt_rows_workspace_bytes() > 0 — and summed in a fixed order: bitwise reproducible, but not the tiled kernel's
+ * summation order); every other 16-bit shape (M above that, K % 32 != 0, mixed dtypes) runs the generic tiled kernel on the
+ * strided rows, which is slow at small M.  fp32 weights are refused.
+ * d_workspace: bf_gemm_nt_rows_workspace_bytes(w_dtype, S, M, N, K) bytes, 16-byte aligned (NULL when that is 0), private to
+ * the call until it completes on `stream`; a streaming-kernel shape without it is an error (status 1), not a slower launch.  No host synchronisation, no allocation: capturable. */
+int bf_gemm_nt_rows(const void* d_x, int x_dtype, int64_t x_sample_stride, int64_t x_row_stride, const void* d_w, int w_dtype,
+                    const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
+                    size_t workspace_bytes, void* stream);
+size_t bf_gemm_nt_rows_workspace_bytes(int dtype, int S, int M, int N, int K);
+
 /* Weight-gradient GEMM of the backward pass (autograd of F.linear, layers/linear.py:104), per batch entry b:
  *   out[b][n][k] = sum_m a[b][m][n] * bm[b][m][k]        (dW = dy^T x; a = dy [Mc][N], bm = x [Mc][K])
  * Both operands are read as they lie (contraction-major), products accumulate in fp32, out is fp32 [batch][N][K].
@@ -338,6 +356,13 @@ int bf_embedding_bwd(const int64_t* d_ids, const void* d_grad, int grad_dtype, c
 int bf_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, int param_dtype,
                      void* d_out, int dtype, int64_t rows, int N, float eps, void* stream);
 
+/* bf_add_layernorm with residual rows that do not lie back to back: residual row r is at d_residual +
+ * r * residual_row_stride elements (a multiple of 8, >= N) — the [CLS] rows of the [B*L, N] input of a layer whose output
+ * only feeds a pooled head.  x and out are compact [rows, N]; the arithmetic per row is bf_add_layernorm's. */
+int bf_add_layernorm_rows(const void* d_x, const void* d_residual, int64_t residual_row_stride, const void* d_gamma,
+                          const void* d_beta, int param_dtype, void* d_out, int dtype, int64_t rows, int N, float eps,
+                          void* stream);
+
 /* The embedding block that feeds the first Bayesian layers of a converted transformer (HF BertEmbeddings, called
  * ahead of bnn.Linear.forward, bayeformers/nn/layers/linear.py:83-104), in one pass:
  *   out[r] = LayerNorm(word[ids[r]] + type[type_ids ? type_ids[r] : 0] + pos[pos_ids ? pos_ids[r % pos_rows] : r % seq_len])
@@ -371,6 +396,14 @@ int bf_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_
 int bf_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
                      void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, int64_t token_stride,
                      float scaling, void* stream);
+
+/* bf_attention_fwd for the first q_rows (1 .. 16) queries of every (sequence, head) against all T keys and values — what a
+ * layer computes whose output is read at the leading ([CLS]) position only.  d_out: the compact [B][q_rows][H][head_dim].
+ * Same arguments and limits as bf_attention_fwd otherwise (no d_lse: inference only); the rows are bit for bit the
+ * corresponding rows of bf_attention_fwd. */
+int bf_attention_fwd_rows(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                          void* d_out, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, int q_rows,
+                          float scaling, void* stream);
 
 /* Backward of bf_attention_fwd (autograd through the attention block in the training loop,
  * /root/reference/examples/bert_glue.py:239): given the forward's inputs, its output, the gradient of the output
