@@ -120,6 +120,10 @@ SYMBOLS = {
                                          ctypes.c_float, _vp]),
     "bf_attention_decode_gqa_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp]),
     "bf_attention_decode_gqa_len_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp]),
+    # the decoder layer's own ops (bf_decoder_blocks.hip)
+    "bf_add_rmsnorm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, ctypes.c_float, _vp]),
+    "bf_rope_qk": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "bf_swiglu": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
     "bf_generate_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                               _i64, _i, _vp, _vp]),
     "bf_generate_step_stat_probs": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
@@ -159,6 +163,12 @@ class bf_attn_decode_t(ctypes.Structure):
     _fields_ = [("N", ctypes.c_int32), ("Tq", ctypes.c_int32), ("Tk", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("Hkv", ctypes.c_int32), ("head_dim", ctypes.c_int32), ("q_stride", ctypes.c_int64 * 3),
                 ("k_stride", ctypes.c_int64 * 3), ("v_stride", ctypes.c_int64 * 3)]
+
+
+class bf_rope_t(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("T", ctypes.c_int32), ("H", ctypes.c_int32), ("Hkv", ctypes.c_int32),
+                ("head_dim", ctypes.c_int32), ("cos_batch", ctypes.c_int32), ("q_stride", ctypes.c_int64 * 3),
+                ("k_stride", ctypes.c_int64 * 3), ("q_out_stride", ctypes.c_int64 * 3), ("k_out_stride", ctypes.c_int64 * 3)]
 
 
 class bf_pgrad_t(ctypes.Structure):

@@ -26,7 +26,7 @@ from .plan import kept_weight_bytes  # noqa: F401
 from .random import (get_compute_dtype, manual_seed, set_compute_dtype, set_kl_gradient,  # noqa: F401
                      use_device_counter)
 
-__all__ = ["to_bayesian", "invalidate_caches", "fuse_activations", "fuse_residual_layernorm", "fuse_shared_inputs", "fuse_ffn_pairs", "fuse_attention", "fuse_embeddings", "enable_embedding", "nn", "manual_seed", "set_compute_dtype", "get_compute_dtype",
+__all__ = ["to_bayesian", "invalidate_caches", "fuse_activations", "fuse_residual_layernorm", "fuse_shared_inputs", "fuse_ffn_pairs", "fuse_attention", "fuse_embeddings", "fuse_decoder_blocks", "enable_embedding", "nn", "manual_seed", "set_compute_dtype", "get_compute_dtype",
            "use_device_counter", "set_kl_gradient", "kept_weight_bytes"]
 
 
@@ -818,6 +818,172 @@ def _install_pooled_last_layer(inner: torch.nn.Module) -> bool:
         head.forward = types.MethodType(_pooled_head_forward, head)
         return True
     return False
+
+
+_DECODER_LAYERS = {"LlamaDecoderLayer": "LlamaAttention", "MistralDecoderLayer": "MistralAttention",
+                   "Qwen2DecoderLayer": "Qwen2Attention"}
+
+
+def _records_grad(x, *modules) -> bool:
+    """Would autograd record an op on x under these modules' parameters?"""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in modules for p in m.parameters()))
+
+
+def _is_rmsnorm(m) -> bool:
+    return (isinstance(m, torch.nn.Module) and type(m).__name__.endswith("RMSNorm")
+            and isinstance(getattr(m, "weight", None), torch.Tensor) and m.weight.dim() == 1
+            and isinstance(getattr(m, "variance_epsilon", None), (int, float)))
+
+
+def _is_silu(fn) -> bool:
+    return isinstance(fn, torch.nn.SiLU) or type(fn).__name__ == "SiLUActivation"
+
+
+def _rmsnorm_forward(self, hidden_states):
+    """forward of an HF `*RMSNorm` on bf_add_rmsnorm.  A hidden state that the fused layer in front of this norm produced
+    carries this norm's output already (`_bf_normed`, computed in that layer's residual pass): it is handed out as it is."""
+    from . import ops
+
+    x = hidden_states
+    if not ops.rmsnorm_supported(x, None, self) or _records_grad(x, self):
+        return self._bf_plain_rmsnorm_forward(hidden_states)
+    ready = x.__dict__.pop("_bf_normed", None)
+    if ready is not None and ready[1] is self:
+        return ready[0]
+    return ops.add_rmsnorm(x, None, self.weight, self.variance_epsilon, want_sum=False)[1]
+
+
+def _decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
+                           use_cache=False, position_embeddings=None, **kwargs):
+    """forward of an HF Llama / Mistral / Qwen2 decoder layer with its two residual adds folded into the RMSNorm that
+    follows each (bf_add_rmsnorm writes the sum and the normalised row in one pass): the second add feeds the NEXT
+    layer's input norm (or the model's final norm), whose output travels on the returned hidden state as `_bf_normed`.
+    The returned tensor is always the true hidden state.  Gradients recorded, training mode, tensors off the device, a
+    hook on the norm whose forward is skipped: the module's own forward."""
+    from . import ops
+
+    h = hidden_states
+    post, nxt = self.post_attention_layernorm, self._bf_next_norm[0]
+    if (not isinstance(h, torch.Tensor) or self.training or _hooked(post) or not ops.rmsnorm_supported(h, None, post)
+            or not ops.rmsnorm_supported(h, None, nxt) or _records_grad(h, self, nxt)):
+        return self._bf_plain_layer_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                            past_key_values=past_key_values, use_cache=use_cache,
+                                            position_embeddings=position_embeddings, **kwargs)
+    a, _ = self.self_attn(hidden_states=self.input_layernorm(h), attention_mask=attention_mask, position_ids=position_ids,
+                          past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings,
+                          **kwargs)
+    if ops.rmsnorm_supported(a, h, post):
+        h1, y1 = ops.add_rmsnorm(a, h, post.weight, post.variance_epsilon)
+    else:
+        h1 = h + a
+        y1 = post(h1)
+    m = self.mlp(y1)
+    if not ops.rmsnorm_supported(m, h1, nxt):
+        return h1 + m
+    h2, y2 = ops.add_rmsnorm(m, h1, nxt.weight, nxt.variance_epsilon)
+    h2._bf_normed = (y2, nxt)
+    return h2
+
+
+def _decoder_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
+                               **kwargs):
+    """forward of an HF Llama / Mistral / Qwen2 attention module with apply_rotary_pos_emb as one launch (bf_rope_qk), in
+    place on the projections' outputs in the [B, T, heads * head_dim] layout the attention kernels read through strides.
+    The cache update, the attention interface lookup and o_proj are the module's own code path."""
+    import sys
+
+    from . import ops
+
+    x = hidden_states
+    pe = position_embeddings
+    fast = (pe is not None and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 3 and x.dtype in ops._TORCH2BF
+            and not self.training and self.head_dim in (64, 128) and not _records_grad(x, self))
+    if fast:
+        cos, sin = pe
+        fast = (cos.dim() == 3 and sin.shape == cos.shape and cos.shape[-1] == self.head_dim and cos.shape[1] == x.shape[1]
+                and cos.shape[0] in (1, x.shape[0]))
+    if not fast:
+        return self._bf_plain_attn_forward(hidden_states, position_embeddings=position_embeddings,
+                                           attention_mask=attention_mask, past_key_values=past_key_values, **kwargs)
+    mod = sys.modules[type(self).__module__]
+    input_shape = x.shape[:-1]
+    hidden_shape = (*input_shape, -1, self.head_dim)
+    query_states = self.q_proj(x).view(hidden_shape).transpose(1, 2)
+    key_states = self.k_proj(x).view(hidden_shape).transpose(1, 2)
+    value_states = self.v_proj(x).view(hidden_shape).transpose(1, 2)
+    cos, sin = (t if t.is_contiguous() else t.contiguous() for t in (cos, sin))
+    if ops.rope_supported(query_states, key_states, cos, sin):
+        query_states, key_states = ops.rope_qk(query_states, key_states, cos, sin, inplace=True)
+    else:  # a projection that came back in another dtype or layout: the framework's ops on what is already computed
+        query_states, key_states = mod.apply_rotary_pos_emb(query_states, key_states, cos, sin)
+    if past_key_values is not None:
+        key_states, value_states = past_key_values.update(key_states, value_states, self.layer_idx)
+    attention_interface = mod.ALL_ATTENTION_FUNCTIONS.get_interface(self.config._attn_implementation,
+                                                                    mod.eager_attention_forward)
+    name = type(self).__name__  # (the one difference between the three classes' forwards)
+    if name == "MistralAttention":
+        kwargs = dict(kwargs, sliding_window=getattr(self.config, "sliding_window", None))
+    elif name == "Qwen2Attention":
+        kwargs = dict(kwargs, sliding_window=self.sliding_window)
+    attn_output, attn_weights = attention_interface(self, query_states, key_states, value_states, attention_mask,
+                                                    dropout=0.0 if not self.training else self.attention_dropout,
+                                                    scaling=self.scaling, **kwargs)
+    attn_output = attn_output.reshape(*input_shape, -1).contiguous()
+    return self.o_proj(attn_output), attn_weights
+
+
+def _swiglu_mlp_forward(self, x):
+    """forward of an HF Llama-style MLP — down_proj(act_fn(gate_proj(x)) * up_proj(x)) — with the SiLU and the product as
+    one launch (bf_swiglu)."""
+    from . import ops
+
+    if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in ops._TORCH2BF or self.training
+            or _hooked(self.act_fn) or _records_grad(x, self)):
+        return self._bf_plain_mlp_forward(x)
+    gate, up = self.gate_proj(x), self.up_proj(x)
+    return self.down_proj(ops.swiglu(gate, up) if ops.swiglu_supported(gate, up) else self.act_fn(gate) * up)
+
+
+def fuse_decoder_blocks(model: torch.nn.Module) -> int:
+    """Run the memory-bound ops of HuggingFace Llama, Mistral and Qwen2 decoder layers — the two RMSNorms with the
+    residual adds in front of them, the rotary embedding of q and k, SiLU(gate) * up — as four launches per layer
+    (bf_add_rmsnorm twice, bf_rope_qk, bf_swiglu) instead of the framework's thirty or so elementwise kernels.  A layer is
+    rewritten when its class is exactly LlamaDecoderLayer, MistralDecoderLayer or Qwen2DecoderLayer with the attribute
+    shape those have (RMSNorm modules with `weight` and `variance_epsilon`, an MLP of gate / up / down projections around
+    a SiLU, an attention module with q / k / v / o projections and head_dim 64 or 128); Qwen3 (q / k norms), Gemma
+    (1 + weight), OLMo and mixture-of-experts layers are left alone.  Inference-time rewrite like the other fuse_*
+    functions: with gradients recorded, in training mode, off the device or on shapes the kernels refuse, the modules'
+    own forwards run.  Returns the number of layers rewritten; calling it again rewrites nothing twice."""
+    fused = 0
+    for parent in model.modules():
+        layers, final = getattr(parent, "layers", None), getattr(parent, "norm", None)
+        if not isinstance(layers, torch.nn.ModuleList) or not _is_rmsnorm(final):
+            continue
+        for i, layer in enumerate(layers):
+            attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
+            nxt = getattr(layers[i + 1], "input_layernorm", None) if i + 1 < len(layers) else final
+            if (type(layer).__name__ not in _DECODER_LAYERS or hasattr(layer, "_bf_plain_layer_forward")
+                    or type(attn).__name__ != _DECODER_LAYERS[type(layer).__name__]
+                    or not _is_rmsnorm(getattr(layer, "input_layernorm", None))
+                    or not _is_rmsnorm(getattr(layer, "post_attention_layernorm", None)) or not _is_rmsnorm(nxt)
+                    or not all(isinstance(getattr(mlp, n, None), torch.nn.Module) for n in ("gate_proj", "up_proj", "down_proj"))
+                    or not _is_silu(getattr(mlp, "act_fn", None))
+                    or not all(isinstance(getattr(attn, n, None), torch.nn.Module) for n in ("q_proj", "k_proj", "v_proj", "o_proj"))
+                    or getattr(attn, "head_dim", None) not in (64, 128)):
+                continue
+            layer._bf_next_norm = (nxt,)  # (in a tuple: not a child module of this layer)
+            layer._bf_plain_layer_forward = layer.forward
+            layer.forward = types.MethodType(_decoder_layer_forward, layer)
+            attn._bf_plain_attn_forward = attn.forward
+            attn.forward = types.MethodType(_decoder_attention_forward, attn)
+            mlp._bf_plain_mlp_forward = mlp.forward
+            mlp.forward = types.MethodType(_swiglu_mlp_forward, mlp)
+            for norm in (layer.input_layernorm, nxt):
+                if not hasattr(norm, "_bf_plain_rmsnorm_forward"):
+                    norm._bf_plain_rmsnorm_forward = norm.forward
+                    norm.forward = types.MethodType(_rmsnorm_forward, norm)
+            fused += 1
+    return fused
 
 
 def fuse_attention(model: torch.nn.Module) -> bool:

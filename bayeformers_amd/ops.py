@@ -1398,6 +1398,139 @@ def layernorm_supported(x: Tensor, residual: Optional[Tensor], ln) -> bool:
             ln.weight.dtype in (torch.float32, x.dtype) and ln.bias is not None and ln.bias.dtype == ln.weight.dtype)
 
 
+# ------------------------------------------------------------------------------- decoder blocks: RMSNorm, RoPE, SwiGLU
+# launches of bf_add_rmsnorm / bf_rope_qk / bf_swiglu from this process (tests, diagnostics)
+BLOCK_CALLS = {"rmsnorm": 0, "rope": 0, "swiglu": 0}
+
+
+def rmsnorm_supported(x: Tensor, residual: Optional[Tensor], norm) -> bool:
+    """Does bf_add_rmsnorm take x (and the residual) under `norm` (a module with `weight` [N])?"""
+    n = x.shape[-1]
+    w = norm.weight
+    return (x.is_cuda and x.dtype in _TORCH2BF and x.dim() >= 1 and n % 8 == 0 and n <= 8192 and x.numel() > 0 and
+            (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype and residual.is_cuda)) and
+            w.is_cuda and w.dim() == 1 and w.shape[0] == n and w.dtype in (torch.float32, x.dtype) and w.is_contiguous()
+            and w.data_ptr() % 16 == 0)
+
+
+def _rows_of(t: Tensor, n: int) -> Tensor:
+    t2 = t.reshape(-1, n)
+    return t2 if t2.is_contiguous() and t2.data_ptr() % 16 == 0 else t2.clone(memory_format=torch.contiguous_format)
+
+
+def add_rmsnorm(x: Tensor, residual: Optional[Tensor], gamma: Tensor, eps: float, want_sum: bool = True):
+    """(z, y) with z = x + residual and y = z * rsqrt(mean(z^2) + eps) * gamma over the last axis, one pass
+    (bf_add_rmsnorm).  z is bitwise torch's `residual + x`; residual None: z is x itself.  want_sum=False (or no
+    residual): z is not written and None is returned in its place."""
+    _require_device(x, "add_rmsnorm input")
+    N = x.shape[-1]
+    x2 = _rows_of(x, N)
+    r2 = None
+    if residual is not None:
+        if residual.shape != x.shape or residual.dtype != x.dtype:
+            raise _C.BayeFormersAMDError("add_rmsnorm: residual must match the input's shape and dtype")
+        r2 = _rows_of(residual, N)
+    if gamma.dtype not in (torch.float32, x.dtype):
+        raise _C.BayeFormersAMDError("add_rmsnorm: gamma must be float32 or have the input's dtype")
+    out = torch.empty_like(x2)
+    z = torch.empty_like(x2) if (want_sum and r2 is not None) else None
+    _C.check(_C.lib().bf_add_rmsnorm(x2.data_ptr(), r2.data_ptr() if r2 is not None else None, gamma.data_ptr(),
+                                     _TORCH2BF[gamma.dtype], z.data_ptr() if z is not None else None, out.data_ptr(),
+                                     _TORCH2BF[x.dtype], x2.shape[0], N, float(eps), _stream_ptr()), "bf_add_rmsnorm")
+    BLOCK_CALLS["rmsnorm"] += 1
+    if z is not None:
+        z = z.view(x.shape)
+    elif want_sum and r2 is None:
+        z = x
+    return z, out.view(x.shape)
+
+
+def rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor) -> bool:
+    """q [B, H, T, D], k [B, Hkv, T, D] with a contiguous feature dimension of 64 or 128 and (batch, head, token) strides
+    that are multiples of 8; cos / sin contiguous [1 or B, T, D] of q's dtype or fp32: what bf_rope_qk takes."""
+    if not (q.is_cuda and q.dtype in _TORCH2BF and k.dtype == q.dtype and k.is_cuda and q.dim() == 4 and k.dim() == 4):
+        return False
+    B, H, T, D = q.shape
+    if D not in (64, 128) or k.shape[0] != B or k.shape[2] != T or k.shape[3] != D or q.numel() == 0 or k.numel() == 0:
+        return False
+    if B * T * (H + k.shape[1]) * (D // 16) >= 2 ** 31:
+        return False
+    for c in (cos, sin):
+        if not (c.is_cuda and c.dtype in (torch.float32, q.dtype) and c.dim() == 3 and c.shape[0] in (1, B)
+                and tuple(c.shape[1:]) == (T, D) and c.is_contiguous() and c.data_ptr() % 16 == 0):
+            return False
+    if cos.shape != sin.shape or cos.dtype != sin.dtype:
+        return False
+    return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (q, k))
+
+
+def rope_qk(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, inplace: bool = False):
+    """(q', k') = (q cos + rotate_half(q) sin, k cos + rotate_half(k) sin), HF's apply_rotary_pos_emb, in one launch
+    (bf_rope_qk).  Shapes as rope_supported describes.  inplace: q and k are overwritten and returned; else the results
+    are new tensors laid out [B, T, heads, D] and returned as their [B, heads, T, D] views."""
+    _require_device(q, "rope_qk input")
+    if not rope_supported(q, k, cos, sin):
+        raise _C.BayeFormersAMDError("rope_qk: unsupported shapes, strides or dtypes (see ops.rope_supported)")
+    B, H, T, D = q.shape
+    Hkv = k.shape[1]
+    if inplace:
+        qo, ko = q, k
+    else:
+        qo = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device).transpose(1, 2)
+        ko = torch.empty((B, T, Hkv, D), dtype=k.dtype, device=k.device).transpose(1, 2)
+    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
+    for name, t in (("q_stride", q), ("k_stride", k), ("q_out_stride", qo), ("k_out_stride", ko)):
+        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    _C.check(_C.lib().bf_rope_qk(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
+                                 qo.data_ptr(), ko.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()),
+             "bf_rope_qk")
+    BLOCK_CALLS["rope"] += 1
+    return qo, ko
+
+
+def swiglu_supported(gate: Tensor, up: Tensor) -> bool:
+    """gate / up of one shape and dtype, [..., N] with N % 8 == 0, whose rows lie one fixed stride apart (a multiple of
+    8 elements, 16-byte aligned): contiguous tensors and the two halves of a stacked [rows, 2N] buffer."""
+    if not (gate.is_cuda and up.is_cuda and gate.dtype in _TORCH2BF and up.dtype == gate.dtype and gate.shape == up.shape
+            and gate.dim() >= 1 and gate.shape[-1] % 8 == 0 and gate.numel() > 0):
+        return False
+    return all(_row_stride(t) is not None for t in (gate, up))
+
+
+def _row_stride(t: Tensor) -> Optional[int]:
+    """Element stride between the rows of t seen as [rows, N], None when the rows are not evenly spaced."""
+    n = t.shape[-1]
+    if t.stride(-1) != 1 or t.data_ptr() % 16:
+        return None
+    rs = want = None
+    for size, stride in zip(reversed(t.shape[:-1]), reversed(t.stride()[:-1])):
+        if size == 1:
+            continue
+        if rs is None:
+            rs, want = stride, stride * size
+        elif stride != want:
+            return None
+        else:
+            want *= size
+    if rs is None:  # a single row
+        return n
+    return rs if rs >= n and rs % 8 == 0 else None
+
+
+def swiglu(gate: Tensor, up: Tensor) -> Tensor:
+    """silu(gate) * up in one launch (bf_swiglu): one rounding, against the framework's two."""
+    _require_device(gate, "swiglu input")
+    if not swiglu_supported(gate, up):
+        raise _C.BayeFormersAMDError("swiglu: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
+    N = gate.shape[-1]
+    out = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
+    _C.check(_C.lib().bf_swiglu(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), out.data_ptr(), N,
+                                _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()), "bf_swiglu")
+    BLOCK_CALLS["swiglu"] += 1
+    return out
+
+
 # ------------------------------------------------------------------------------------- Monte-Carlo predictive statistics
 _PREDICTIVE_WS = {}
 

@@ -32,8 +32,8 @@ extern "C" {
                                bf_attention_bwd_colsum; the dropout entries take first_group; 6: the dropout entries take d_call
                                (device-resident part of the call number), bf_gemm_schedule_policy / _fetch_rows,
                                bf_profile_read_launches; still 6 (additions only, no signature changed): bf_gemm_nt_rows,
-                               bf_gemm_nt_rows_workspace_bytes, bf_attention_fwd_rows, bf_add_layernorm_rows — a library
-                               without them fails to bind by the missing symbol */
+                               bf_gemm_nt_rows_workspace_bytes, bf_attention_fwd_rows, bf_add_layernorm_rows, bf_add_rmsnorm,
+                               bf_rope_qk, bf_swiglu — a library without them fails to bind by the missing symbol */
 
 /* element types of activations / sampled weights */
 enum { BF_DT_F32 = 0, BF_DT_BF16 = 1, BF_DT_F16 = 2 };
@@ -503,6 +503,50 @@ int bf_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const v
                                        const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
                                        int dtype, const bf_attn_decode_t* shape, int32_t window, float scaling,
                                        void* stream);
+
+/* ---- the decoder layer's own ops: RMSNorm, rotary embedding, SwiGLU ------------------------------------------------
+ * The memory-bound ops of a Llama-family decoder layer between its Bayesian linear layers (to_bayesian converts every
+ * nn.Linear, /root/reference/bayeformers/convert.py; the wrapped HF LlamaDecoderLayer / MistralDecoderLayer /
+ * Qwen2DecoderLayer runs its own torch ops around /root/reference/bayeformers/nn/layers/linear.py:83-104).  Each is one
+ * launch: 16-byte loads and stores, fp32 arithmetic, one rounding into `dtype` (BF16 | F16 | F32).  No allocation, no
+ * synchronisation (capturable).  Unsupported arguments return 1 with bf_last_error() set.
+ *
+ * bf_add_rmsnorm — replaces `residual + x` followed by HF LlamaRMSNorm.forward (upcast, pow, mean, add, rsqrt, mul,
+ * downcast, mul):  z = x + residual,  y = z * rsqrt(mean(z^2) + eps) * gamma  over the last axis, both results in one
+ * pass: d_sum_out receives z, d_out receives y.  d_residual may be NULL (z = x: the plain norm) and d_sum_out may be NULL.
+ * x, residual, z, y: [rows, N] of `dtype`, rows back to back; gamma [N] of `param_dtype` (BF_DT_F32 or `dtype`).  z is
+ * rounded to `dtype` once — bitwise the framework's `residual + x` — and the statistics and y are computed from that
+ * rounded z, the tensor the unfused model's norm reads; y is rounded once (HF rounds the normalised row to `dtype` before
+ * the multiply by gamma as well).  d_sum_out / d_out may be d_x or d_residual themselves (in place), no other overlap.
+ * N % 8 == 0, N <= 8192, 16-byte aligned pointers. */
+int bf_add_rmsnorm(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype, void* d_sum_out, void* d_out,
+                   int dtype, int64_t rows, int N, float eps, void* stream);
+
+/* bf_rope_qk — replaces HF apply_rotary_pos_emb (two muls, a slice / negate / cat and an add for each of q and k):
+ *   q' = q * cos + rotate_half(q) * sin,  k' likewise,  rotate_half(x) = [-x2, x1] over the two halves of a head,
+ * in one launch.  Element (b, h, t, d) of q is at b*q_stride[0] + h*q_stride[1] + t*q_stride[2] + d (the bf_attn_gqa_t
+ * convention: head_dim 64 or 128 contiguous, strides non-negative multiples of 8 elements), k the same with Hkv heads;
+ * the outputs have strides of their own.  In place (d_q_out == d_q with the same strides, d_k_out likewise) is allowed: one
+ * lane owns both elements of a rotation pair; any other overlap is not.  d_cos / d_sin: [cos_batch][T][head_dim]
+ * contiguous of `cs_dtype` (BF_DT_F32 or `dtype`), cos_batch 1 or B — what the model's rotary module returns; no
+ * trigonometry runs on the device.  Any T >= 1; B * T * (H + Hkv) * head_dim / 16 < 2^31. */
+typedef struct bf_rope {
+    int32_t B, T, H, Hkv, head_dim, cos_batch;
+    int64_t q_stride[3];     /* element strides of batch, head, token */
+    int64_t k_stride[3];
+    int64_t q_out_stride[3];
+    int64_t k_out_stride[3];
+} bf_rope_t;
+int bf_rope_qk(const void* d_q, const void* d_k, const void* d_cos, const void* d_sin, int cs_dtype, void* d_q_out,
+               void* d_k_out, int dtype, const bf_rope_t* shape, void* stream);
+
+/* bf_swiglu — replaces HF LlamaMLP's `act_fn(gate_proj(x)) * up_proj(x)` (SiLU, then a multiply):
+ *   y = gate / (1 + exp(-gate)) * up,  finite for every finite input (gate -> -inf gives -0 * up, gate -> +inf gate * up).
+ * rows x N of `dtype`; row r of gate / up / y starts r * its row stride elements in (multiples of 8, >= N), so gate and up
+ * may be the two halves of one stacked [rows, 2N] buffer.  y may be gate or up itself with the same stride.
+ * N % 8 == 0, 16-byte aligned pointers. */
+int bf_swiglu(const void* d_gate, int64_t gate_row_stride, const void* d_up, int64_t up_row_stride, void* d_out,
+              int64_t out_row_stride, int dtype, int64_t rows, int N, void* stream);
 
 /* ---- one generation step's epilogue -------------------------------------------------------------------------------
  * What sample_generate does between the predictive statistics of a step and the next decode forward, in one launch (one

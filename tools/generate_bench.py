@@ -7,6 +7,8 @@
     python tools/generate_bench.py trace --mode keep|draw [--mode dynamic|static|graph] [--steps 32] [the processors]
                                                                                          (under rocprofv3 --kernel-trace)
     python tools/generate_bench.py analyze <kernel_trace.csv> [--steps 32]
+    --fuse-blocks (e2e, trace, kernels): with fuse_decoder_blocks — e2e alternates the fused and the unfused model in one
+    process (`..._blocks` rows), trace runs the fused model, kernels measures bf_add_rmsnorm / bf_rope_qk / bf_swiglu instead
 
 kernels: per layer shape of the DESIGN 4.5 decoder (N x K), S and M rows per sample, bf16: bf_gemm_nt_skinny on kept weights,
 fused_small (bf_linear_fwd: sampling + GEMM + log-probs, what a decode step runs without keep_weights) and bf_gemm_nt_act on the
@@ -83,7 +85,42 @@ def kernels(only=None):
     return rows
 
 
-def _decoder():
+def block_kernels():
+    """bf_add_rmsnorm, bf_rope_qk and bf_swiglu at the DESIGN 4.5 decoder's prefill size (S B T = 8192 rows) and decode size (16
+    rows), bf16: time per call as in kernels(), achieved bytes/s from the algorithmic bytes; bf_add_layernorm at the same
+    rows x N in the same process beside bf_add_rmsnorm (the same structure)."""
+    from bayeformers_amd import ops
+
+    N, F, H, Hkv, D, T = 1024, 2816, 16, 4, 64, 512
+    dt = torch.bfloat16
+    out = []
+
+    def row(name, rows, nbytes, fn):
+        t = _time(fn)
+        out.append({"kernel": name, "rows": rows, "MB": round(nbytes / 1e6, 3), "us": round(t, 2),
+                    "TB_per_s": round(nbytes / (t * 1e-6) / 1e12, 3), "hbm_frac": round(nbytes / (t * 1e-6) / HBM, 3)})
+        print(json.dumps(out[-1]), flush=True)
+
+    for rows in (8192, 16):
+        x, r = (torch.randn(rows, N, device="cuda", dtype=dt) for _ in range(2))
+        g, b = torch.ones(N, device="cuda", dtype=dt), torch.zeros(N, device="cuda", dtype=dt)
+        row("add_rmsnorm (x + residual -> sum, norm)", rows, 4 * rows * N * 2, lambda: ops.add_rmsnorm(x, r, g, 1e-5))
+        row("add_rmsnorm (x + residual -> norm)", rows, 3 * rows * N * 2, lambda: ops.add_rmsnorm(x, r, g, 1e-5, want_sum=False))
+        row("add_layernorm (x + residual -> norm)", rows, 3 * rows * N * 2, lambda: ops.add_layernorm(x, r, g, b, 1e-5))
+        row("add_rmsnorm (x -> norm)", rows, 2 * rows * N * 2, lambda: ops.add_rmsnorm(x, None, g, 1e-5, want_sum=False))
+        row("add_layernorm (x -> norm)", rows, 2 * rows * N * 2, lambda: ops.add_layernorm(x, None, g, b, 1e-5))
+        B, Tq = (rows // T, T) if rows >= T else (rows, 1)
+        q = torch.randn(B, Tq, H * D, device="cuda", dtype=dt).view(B, Tq, H, D).transpose(1, 2)
+        k = torch.randn(B, Tq, Hkv * D, device="cuda", dtype=dt).view(B, Tq, Hkv, D).transpose(1, 2)
+        cos, sin = (torch.randn(1, Tq, D, device="cuda", dtype=dt) for _ in range(2))
+        row("rope_qk (in place)", rows, 2 * rows * (H + Hkv) * D * 2 + 2 * Tq * D * 2,
+            lambda: ops.rope_qk(q, k, cos, sin, inplace=True))
+        gate, up = (torch.randn(rows, F, device="cuda", dtype=dt) for _ in range(2))
+        row("swiglu", rows, 3 * rows * F * 2, lambda: ops.swiglu(gate, up))
+    return out
+
+
+def _decoder(fuse_blocks=False):
     from transformers import LlamaConfig, LlamaForCausalLM
 
     import bayeformers_amd as bf
@@ -98,6 +135,8 @@ def _decoder():
     for n, b in freqs.items():
         setattr(bmodel.get_submodule(n.rsplit(".", 1)[0]), n.rsplit(".", 1)[1], b)
     assert bf.fuse_attention(bmodel)
+    if fuse_blocks:
+        assert bf.fuse_decoder_blocks(bmodel) == 8
     bf.set_compute_dtype("bf16")
     return bmodel
 
@@ -105,11 +144,15 @@ def _decoder():
 PATHS = {"dynamic": {}, "static": {"static_cache": True}, "graph": {"graph": True}}
 
 
-def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None, processors=None):
+def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None, processors=None, fuse_blocks=False):
     import bayeformers_amd as bf
     from bayeformers_amd.sampling import sample_generate
 
-    bmodel = _decoder()
+    # (the same seed: the same weights) unfused first, then with fuse_decoder_blocks, inside every configuration
+    models = {"": _decoder()}
+    if fuse_blocks:
+        models["_blocks"] = _decoder(fuse_blocks=True)
+    bmodel = models[""]
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     variants = {"": {}} if not truncation else {"_sample": dict(do_sample=True),
                                                 "_truncated": dict(do_sample=True, **truncation)}
@@ -118,18 +161,19 @@ def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None,
         variants = {"_plain": base, "_processed": dict(base, **processors)}
     name = lambda keep, path, v="": (("keep_weights" if keep else "draw_per_step") + ("" if path == "dynamic" else "_" + path)
                                      + v)
+    variants = {v + m: (kw, model) for v, kw in variants.items() for m, model in models.items()}
     res = {name(k, p, v): [] for k in (False, True) for p in paths for v in variants}
     res["kept_bytes"] = bf.kept_weight_bytes(bmodel, 4, torch.bfloat16)
     seqs = {}
     with torch.no_grad():
         for keep in (False, True):  # warm-up
             for path in paths:
-                for v, kw in variants.items():
+                for v, (kw, bmodel) in variants.items():
                     sample_generate(bmodel, ids, samples=4, max_new_tokens=8, keep_weights=keep, **PATHS[path], **kw)
         for _ in range(runs):
             for keep in (False, True):
                 for path in paths:
-                    for v, kw in variants.items():
+                    for v, (kw, bmodel) in variants.items():
                         bf.manual_seed(0x5EED)
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
@@ -145,16 +189,19 @@ def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None,
                                           "tokens_per_s": round(4 * new_tokens / dt, 1)}), flush=True)
     first = next(iter(seqs.values()))
     res["same_tokens"] = all(bool(torch.equal(first, v)) for v in seqs.values())
+    if fuse_blocks:  # per configuration: does the fused model emit the unfused model's tokens?
+        res["same_tokens_blocks"] = {name(*k): bool(torch.equal(v, seqs[k[0], k[1], k[2] + "_blocks"]))
+                                     for k, v in seqs.items() if not k[2].endswith("_blocks")}
     for k in [k for k in res if isinstance(res[k], list)]:
         v = res[k]
         res[k + "_summary"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
     return res
 
 
-def trace(mode, new_tokens, path="dynamic", processors=None):
+def trace(mode, new_tokens, path="dynamic", processors=None, fuse_blocks=False):
     from bayeformers_amd.sampling import sample_generate
 
-    bmodel = _decoder()
+    bmodel = _decoder(fuse_blocks)
     ids = torch.randint(0, 32000, (4, 512), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
     kw = dict(keep_weights=mode == "keep", **PATHS[path], **(processors or {}))
     with torch.no_grad():
@@ -169,7 +216,8 @@ def trace(mode, new_tokens, path="dynamic", processors=None):
 
 
 def _klass(name):
-    for key, k in (("gemm_skinny", "skinny GEMM (Bayesian layers)"), ("fused_small", "fused_small (Bayesian layers)"),
+    for key, k in (("rmsnorm", "decoder blocks (rmsnorm / rope / swiglu)"), ("rope_qk", "decoder blocks (rmsnorm / rope / swiglu)"),
+                   ("swiglu", "decoder blocks (rmsnorm / rope / swiglu)"), ("gemm_skinny", "skinny GEMM (Bayesian layers)"), ("fused_small", "fused_small (Bayesian layers)"),
                    ("sample", "sampling (Bayesian layers)"), ("reduce_logprob", "sampling (Bayesian layers)"),
                    ("gemm", "tiled GEMM (Bayesian layers)"), ("attention", "attention"), ("predictive", "predictive statistics")):
         if key in name:
@@ -218,6 +266,7 @@ def main():
     ap.add_argument("--no-repeat-ngram", type=int, default=None)
     ap.add_argument("--min-new-tokens", type=int, default=None)
     ap.add_argument("--eos-token-id", type=int, default=None)
+    ap.add_argument("--fuse-blocks", action="store_true")
     a = ap.parse_args()
     processors = {k: v for k, v in (("repetition_penalty", a.repetition_penalty), ("no_repeat_ngram_size", a.no_repeat_ngram),
                                     ("min_new_tokens", a.min_new_tokens), ("eos_token_id", a.eos_token_id))
@@ -226,15 +275,15 @@ def main():
         res = analyze(a.path, a.steps)
     else:
         assert torch.cuda.is_available(), "this benchmark measures the GPU"
-        if a.what == "kernels":
-            res = kernels(tuple(int(v) for v in a.only.split(",")) if a.only else None)
         modes = a.mode or []
         paths = [m for m in modes if m in PATHS] or None
-        if a.what == "e2e":
+        if a.what == "kernels":
+            res = block_kernels() if a.fuse_blocks else kernels(tuple(int(v) for v in a.only.split(",")) if a.only else None)
+        elif a.what == "e2e":
             truncation = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p), ("min_p", a.min_p)) if v is not None}
-            res = e2e(a.runs, a.new_tokens, paths or ("dynamic", "static", "graph"), truncation, processors)
+            res = e2e(a.runs, a.new_tokens, paths or ("dynamic", "static", "graph"), truncation, processors, a.fuse_blocks)
         else:
-            trace("draw" if "draw" in modes else "keep", a.steps + 1, (paths or ["dynamic"])[-1], processors)
+            trace("draw" if "draw" in modes else "keep", a.steps + 1, (paths or ["dynamic"])[-1], processors, a.fuse_blocks)
             return
     print(json.dumps(res, indent=1))
     if a.out:
