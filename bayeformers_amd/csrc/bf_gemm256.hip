@@ -13,7 +13,7 @@
 //   * the MFMA runs with swapped operands (D rows = n, cols = m) so each lane owns 4 consecutive output features
 //     of one row of y; the epilogue moves a wave's 16 h x 64 part through a private LDS slice and stores whole
 //     128-byte lines (epilogue_wave below);
-//   * WHICH tiles a workgroup runs is decided on the host (build_schedule below): the output is cut into columns
+//   * WHICH tiles a workgroup runs is decided on the host (build_schedule, bf_gemm_schedule.hip): the output is cut into columns
 //     (sample, layer, n-tile) of ceil(M/32) units of 32 rows, every column into tiles of near-equal height, and the
 //     tiles are dealt to the 256 persistent workgroups so that all of them carry the same number of units.  With
 //     fixed 256-row tiles BERT-base's launches have 480 k tiles = 1.875 k rounds of 256 CUs — 1/16 of the CU-time is
@@ -23,21 +23,11 @@
 // Requirements: K % 64 == 0, 16-byte aligned operands; M and N are arbitrary (edge rows are clamped on load and
 // masked on store).  Everything else goes to the generic kernel in bf_gemm.hip.
 // Since round 3 the forward with 16-bit outputs and the NN input-gradient form run bf_gemm256_r5.hip (the same tile, waves,
-// schedule and epilogue with the operands streamed through a five-slot LDS ring, K >= 128); this file keeps the schedule
-// builder, the fp32-output forward, K = 64, operands past 2^30 elements, and the TN weight-gradient form with its unit ring.
-#include <stdlib.h>
-
-#include <algorithm>
-#include <map>
-#include <mutex>
-#include <tuple>
-#include <type_traits>
-#include <vector>
-
+// schedule and epilogue with the operands streamed through a five-slot LDS ring, K >= 128); this file keeps the
+// fp32-output forward, K = 64, operands past 2^30 elements, and the TN weight-gradient form with its unit ring.
 #include "bf_gemm256_dev.h"
 
 namespace {
-
 
 // ------------------------------------------------------------------------------------------------------------
 // The kernel: persistent ping-pong over a host-built tile schedule.
@@ -72,7 +62,7 @@ namespace {
 //    1   1   TN   dW = dy^T x        (weight gradient; dy [m][N], x [m][K], contraction over the batch rows m)
 //    0   1   NN   dx = dy W          (input gradient; dy [M][N], W [N][K] read as it was sampled: no transposed copy)
 //
-// RING (TN form, >= 2 k-steps): the DMA of a k-step is not issued in one burst of 8 pieces per wave at L0 but as
+// RING (TN form only, >= 2 k-steps): the DMA of a k-step is not issued in one burst of 8 pieces per wave at L0 but as
 // four UNITS of [32 contraction rows][256] (16 KiB: X0, W0 = the halves read in L0, X1, W1 = the halves read in L1),
 // one unit per wave group per L slot, each into the half-buffer whose last read is one barrier behind:
 //      G0:  L0(t): X1(t+1)    L1(t): X0(t+2)          G1:  L0(t): W1(t+1)    L1(t): W0(t+2)
@@ -80,11 +70,11 @@ namespace {
 // (vmcnt(8) = "everything but the two youngest units"): G0 at the end of its M slots, G1 at the end of its L slots.
 // The units of the next tile's first two k-steps are issued by the last two k-steps of a tile; the epilogue scratch
 // is a separate 32 KiB region, so nothing of the next tile has to wait for the epilogue.
-// Measured (dW GEMMs of the BERT-base step, one box): 940-958 -> 1067-1117 TFLOP/s.  The same ring over row-major
-// operands (units = the 32-deep halves of all rows, i.e. 64-byte row segments: code below, -DBF_RING_ROWMAJOR) is
-// 3-7 % SLOWER than the burst form at every K: half-line DMA requests cost more than the spread issue gains.
+// Measured (dW GEMMs of the BERT-base step, one box): 940-958 -> 1067-1117 TFLOP/s.  A row-major unit ring was 3-7 %
+// slower than the burst form at every K and is gone (LABBOOK.md section 4.2).
 template <typename T, typename YT, bool TRX = false, bool TRW = false, bool SEG = false, bool RING = false>
 __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams p) {
+    static_assert(!RING || (TRX && TRW && !SEG), "the unit ring: TN form only");
     using frag = typename Mfma16<T>::frag;
 
     __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE_BYTES + (RING ? 32768 : 0)];
@@ -93,7 +83,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wid >> 2, wn = wid & 3;
     const int M = p.M, N = p.N, K = p.K;
-
 
     // One tile's DMA sources: wave-uniform sample bases (SGPRs) + eight 32-bit per-lane element offsets.
     struct Src {
@@ -120,39 +109,27 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
         t.xb = xb;
         t.wb = wb;
         t.ob = wm == 0 ? xb : wb;
+        if constexpr (RING) {
+            // Group 0 only ever fetches x units, group 1 w units: each wave keeps its own operand's offsets in xo[].
+            // A unit = 16 pieces of 2 rows; wave wn of the group fetches pieces i * 4 + wn = rows i * 8 + rb (+ lane >> 5
+            // inside rb).  key(row) = (rb & 3) | (i & 1) << 2: xo[] is indexed by the piece number i.
+            auto offsets = [&](int rows, int c0) {
+                const int rb = wn * 2 + (lane >> 5);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = (lane & 31) ^ (((rb & 3) | ((e & 1) << 2)) << 1);
+                    t.xo[e] = (unsigned)rb * (unsigned)rows + (unsigned)min(c0 + c * 8, rows - 8);
+                }
+            };
+            if (wm == 0) offsets(M, m0);
+            else offsets(N, n0);
+            return;
+        }
         // contraction-major operand: piece q = i * 8 + wid = contraction rows 2 q, 2 q + 1 of the k-step; lane -> (row,
         // 16-byte position); the position holds source chunk c = position ^ (key(row) << 1), key = row bits {0, 1, 3};
         // columns past the edge are clamped (they only feed output rows / columns that are masked on store).  The key
         // does not depend on i, so one offset per operand serves all four pieces (piece i = + 16 i rows, added to the
         // wave-uniform base)
-        if constexpr (RING) {
-            // Group 0 only ever fetches x units, group 1 w units: each wave keeps its own operand's offsets in xo[].
-            // Contraction-major operand: a unit = 16 pieces of 2 rows; wave wn of the group fetches pieces i * 4 + wn = rows
-            // i * 8 + rb (+ lane >> 5 inside rb).  key(row) = (rb & 3) | (i & 1) << 2.
-            // Row-major operand: a unit = the 32-deep half of the k-step of all 256 rows = [256][64 B]; piece q = i * 4 + wn
-            // = rows 16 q .. 16 q + 15, lane -> (row lane >> 2, 16-byte position lane & 3) holding source chunk
-            // position ^ ((row >> 2) & 3) (conflict-free ds_read_b128 of a [16 rows][4 chunks] fragment block).
-            auto offsets = [&](auto tr, int rows, int c0) {
-                if constexpr (decltype(tr)::value) {
-                    const int rb = wn * 2 + (lane >> 5);
-                    // (xo[2], xo[3] repeat xo[0], xo[1]: both operand forms then index xo[] by the piece number, which
-                    // keeps the struct in registers when the two groups of a kernel use different forms)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int c = (lane & 31) ^ (((rb & 3) | ((e & 1) << 2)) << 1);
-                        t.xo[e] = (unsigned)rb * (unsigned)rows + (unsigned)min(c0 + c * 8, rows - 8);
-                    }
-                } else {
-                    const int c = (lane & 3) ^ ((lane >> 4) & 3);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        t.xo[i] = (unsigned)min(c0 + (i * 4 + wn) * 16 + (lane >> 2), rows - 1) * (unsigned)K + c * 8;
-                }
-            };
-            if (wm == 0) offsets(std::integral_constant<bool, TRX>{}, M, m0);
-            else offsets(std::integral_constant<bool, TRW>{}, N, n0);
-            return;
-        }
         const int tr_r = wid * 2 + (lane >> 5);
         const int tr_c = (lane & 31) ^ (((tr_r & 3) | ((tr_r >> 1) & 4)) << 1);
         if constexpr (TRX) {
@@ -203,51 +180,29 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
         }
     };
 
-    // RING: this wave's pieces (the first `cnt` of four) of its group's unit `half` (0 / 1) of k-step kt of tile t, into
-    // buffer buf
-    auto issue_unit = [&](const Src& t, int kt, int buf, int half, int cnt) {
+    // RING: this wave's four pieces of its group's unit `half` (0 / 1) of k-step kt of tile t, into buffer buf, through a
+    // buffer descriptor over the sample's operand — 32-bit per-lane byte offset + a scalar row offset, no 64-bit vector
+    // address arithmetic per piece (what the forward ring kernel gained 3-5 % from at K = 768, bf_gemm256_r5.hip).  A
+    // sample's operand is < 2^31 bytes (host check).
+    auto issue_unit = [&](const Src& t, int kt, int buf, int half) {
         char* dst = smem + buf * STAGE_BYTES + (wm == 0 ? 0 : X_BYTES) + half * 16384 + wn * 1024;
-        const T* b = t.ob;
-        if constexpr (SEG) {
-            const int nks = K / TK;
-            const int seg = (kt >= nks ? 1 : 0) + (kt >= 2 * nks ? 1 : 0) + (kt >= 3 * nks ? 1 : 0);
-            kt -= seg * nks;
-            b += (long long)seg * (wm == 0 ? p.x_seg_stride : p.w_seg_stride);
-        }
-        auto go = [&](auto tr, long long ld) {
-            if constexpr (decltype(tr)::value) {
-                // contraction-major unit: pieces through a buffer descriptor over the sample's operand — 32-bit per-lane byte
-                // offset + a scalar row offset, no 64-bit vector address arithmetic per piece (what the forward ring kernel
-                // gained 3-5 % from at K = 768, bf_gemm256_r5.hip).  A sample's operand is < 2^31 bytes (host check).
-                const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(b), 0, 0x7FFFFFFF, 0x00020000);
-                const int row0 = kt * TK + half * 32;
+        auto go = [&](long long ld) {
+            const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(t.ob), 0, 0x7FFFFFFF, 0x00020000);
+            const int row0 = kt * TK + half * 32;
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)(dst + i * 4096), 16, (int)(t.xo[i] * 2u),
-                                                             (int)((row0 + i * 8) * ld) * 2, 0, 0);
-            } else {
-                const T* colp = b + kt * TK + half * 32;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (i < cnt) glds16(colp + t.xo[i], dst + i * 4096);
-            }
+            for (int i = 0; i < 4; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)(dst + i * 4096), 16, (int)(t.xo[i] * 2u),
+                                                         (int)((row0 + i * 8) * ld) * 2, 0, 0);
         };
-        if (wm == 0) go(std::integral_constant<bool, TRX>{}, M);
-        else go(std::integral_constant<bool, TRW>{}, N);
+        if (wm == 0) go(M);
+        else go(N);
     };
-    auto wait_pieces = [&](int n) {  // wave-uniform: all but this wave's n most recent pieces have landed
-        switch (n) {
-            case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-            case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-            case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-            case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-            case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-            case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-            case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-            default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        }
+    // RING waits (wave-uniform): all but this wave's two / one / no most recent units (of 4 pieces) have landed
+    auto wait_units = [&](bool two, bool one) {
+        if (two) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (one) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     };
-    // row-major operands under RING: lane -> row lane & 15 of a 16-row block, chunk (lane >> 4) ^ ((row >> 2) & 3)
 
     const int fsw = (lane >> 1) & 7;
     const int foff0 = (lane & 15) * ROW_BYTES + ((((lane >> 4)) ^ fsw) << 4);
@@ -268,25 +223,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned tr_w0 = lds0 + X_BYTES + tr_lane + (((wn * 4) ^ tr_rl) << 5);
     const unsigned tr_x0 = lds0 + tr_lane + ((wm ^ tr_rl) << 5);
-    // row-major operands under RING: lane -> row lane & 15 of a 16-row block, chunk (lane >> 4) ^ ((row >> 2) & 3); the
-    // blocks of a wave are immediate offsets away (x: wm + 2 j -> 2 KiB apart, w: wn * 4 + i -> 1 KiB apart)
-    const unsigned ring_foff = (lane & 15) * 64 + (((lane >> 4) ^ ((lane >> 2) & 3)) << 4);
-    const unsigned ring_x0 = lds0 + ring_foff + wm * 1024;
-    const unsigned ring_w0 = lds0 + X_BYTES + ring_foff + wn * 4096;
-    auto ring_read = [&](unsigned a, auto off) -> frag {
-        frag v;
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(a), "n"(decltype(off)::value));
-        return v;
-    };
-    auto tr_read = [&](unsigned a0, int blk_xor, auto half) -> frag {
-        const unsigned a = a0 ^ (unsigned)(blk_xor << 5);
-        constexpr int off = decltype(half)::value * 32 * 512;
-        s16x4_t lo, hi;
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(a), "n"(off));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a), "n"(off + 4 * 512));
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(frag, v);
-    };
 
     const int nk = SEG ? p.segs * (K / TK) : K / TK;
     const int4* __restrict__ sched = p.sched + blockIdx.x;
@@ -298,9 +234,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
     tile_setup(d, cur, s, m0, n0, h);
     int g = 0;  // running k-step counter: step g lives in LDS buffer g & 1
     if constexpr (RING) {
-        issue_unit(cur, 0, 0, 0, 4);
-        issue_unit(cur, 0, 0, 1, 4);
-        issue_unit(cur, 1, 1, 0, 4);
+        issue_unit(cur, 0, 0, 0);
+        issue_unit(cur, 0, 0, 1);
+        issue_unit(cur, 1, 1, 0);
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     } else {
         stage(cur, 0, 0, h);
@@ -328,12 +264,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
                 if (!(defer && wm == 0)) dma();
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if constexpr (TRW) wf[i] = tr_read(tr_w0 + (g & 1) * STAGE_BYTES, i, std::integral_constant<int, 0>{});
+                    if constexpr (TRW) wf[i] = tr_read<frag>(tr_w0 + (g & 1) * STAGE_BYTES, i, std::integral_constant<int, 0>{});
                     else wf[i] = *reinterpret_cast<const frag*>(sb + wfrag_base + i * 16 * ROW_BYTES + foff0);
                 }
 #pragma unroll
                 for (int j = 0; j < H; ++j) {
-                    if constexpr (TRX) xf[j] = tr_read(tr_x0 + (g & 1) * STAGE_BYTES, 2 * j, std::integral_constant<int, 0>{});
+                    if constexpr (TRX) xf[j] = tr_read<frag>(tr_x0 + (g & 1) * STAGE_BYTES, 2 * j, std::integral_constant<int, 0>{});
                     else xf[j] = *reinterpret_cast<const frag*>(sb + xfrag_base + j * 32 * ROW_BYTES + foff0);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -350,12 +286,12 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
                 __builtin_amdgcn_s_barrier();
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if constexpr (TRW) wf[i] = tr_read(tr_w0 + (g & 1) * STAGE_BYTES, i, std::integral_constant<int, 1>{});
+                    if constexpr (TRW) wf[i] = tr_read<frag>(tr_w0 + (g & 1) * STAGE_BYTES, i, std::integral_constant<int, 1>{});
                     else wf[i] = *reinterpret_cast<const frag*>(sb + wfrag_base + i * 16 * ROW_BYTES + foff1);
                 }
 #pragma unroll
                 for (int j = 0; j < H; ++j) {
-                    if constexpr (TRX) xf[j] = tr_read(tr_x0 + (g & 1) * STAGE_BYTES, 2 * j, std::integral_constant<int, 1>{});
+                    if constexpr (TRX) xf[j] = tr_read<frag>(tr_x0 + (g & 1) * STAGE_BYTES, 2 * j, std::integral_constant<int, 1>{});
                     else xf[j] = *reinterpret_cast<const frag*>(sb + xfrag_base + j * 32 * ROW_BYTES + foff1);
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -376,26 +312,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
                 ++g;
             };
 
-            // the RING k-step: same slots and barriers; one unit issued per L slot, counted waits.
-            // A row-major x unit only needs the tile's 32 H rows: every wave of group 0 fetches the first CX of its four
-            // pieces (64 CX >= 32 H rows).  Units issued across a tile boundary (and by the prologue) are always whole:
-            // pieces(j, half) below is what this wave issued for that unit of k-step j (j >= nk = the next tile).
+            // the RING k-step: same slots and barriers; one unit issued per L slot, counted waits (wait_units).
             // `steady`: kt + 2 < nk — every unit issued is this tile's own, no conditions in the loop body
-            constexpr int CX = TRX ? 4 : (2 * H + 3) / 4;
-            const int cw = wm == 0 ? CX : 4;
-            auto pieces = [&](int j, int half) { return (j >= nk || j == 0 || (j == 1 && half == 0)) ? 4 : cw; };
             auto read_frags = [&](unsigned sboff, auto half) {
-                constexpr int HF = decltype(half)::value;
-                static_for<0, 4>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    if constexpr (TRW) wf[i] = tr_read(tr_w0 + sboff, i, half);
-                    else wf[i] = ring_read(ring_w0 + sboff, std::integral_constant<int, HF * 16384 + i * 1024>{});
-                });
-                static_for<0, H>([&](auto jc) {
-                    constexpr int j = decltype(jc)::value;
-                    if constexpr (TRX) xf[j] = tr_read(tr_x0 + sboff, 2 * j, half);
-                    else xf[j] = ring_read(ring_x0 + sboff, std::integral_constant<int, HF * 16384 + j * 2048>{});
-                });
+                static_for<0, 4>([&](auto ic) { wf[decltype(ic)::value] = tr_read<frag>(tr_w0 + sboff, decltype(ic)::value, half); });
+                static_for<0, H>([&](auto jc) { xf[decltype(jc)::value] = tr_read<frag>(tr_x0 + sboff, 2 * decltype(jc)::value, half); });
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             };
             Src nxt = cur;  // the next tile's sources, set up before the last two k-steps
@@ -404,14 +325,11 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
                 const bool e1 = ST || kt + 1 < nk || has_next, e2 = ST || kt + 2 < nk || has_next;
                 const unsigned sboff = (g & 1) * STAGE_BYTES;
                 if (e1) {
-                    if (ST || kt + 1 < nk) issue_unit(cur, kt + 1, (g & 1) ^ 1, 1, cw);
-                    else issue_unit(nxt, 0, (g & 1) ^ 1, 1, 4);
+                    if (ST || kt + 1 < nk) issue_unit(cur, kt + 1, (g & 1) ^ 1, 1);
+                    else issue_unit(nxt, 0, (g & 1) ^ 1, 1);
                 }
                 read_frags(sboff, std::integral_constant<int, 0>{});
-                if (wm == 1) {  // W1(kt)
-                    if constexpr (ST) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                    else wait_pieces(e1 ? 8 : 0);
-                }
+                if (wm == 1) wait_units(e1, false);  // W1(kt)
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_s_setprio(1);
@@ -420,21 +338,15 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
 #pragma unroll
                     for (int j = 0; j < H; ++j) acc[i][j] = Mfma16<T>::run(wf[i], xf[j], acc[i][j]);
                 __builtin_amdgcn_s_setprio(0);
-                if (wm == 0) {  // X1(kt)
-                    if constexpr (ST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * CX) : "memory");
-                    else wait_pieces(e1 ? pieces(kt + 1, 0) + pieces(kt + 1, 1) : 0);
-                }
+                if (wm == 0) wait_units(e1, false);  // X1(kt)
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 if (e2) {
-                    if (ST || kt + 2 < nk) issue_unit(cur, kt + 2, g & 1, 0, cw);
-                    else issue_unit(nxt, kt + 2 - nk, g & 1, 0, 4);
+                    if (ST || kt + 2 < nk) issue_unit(cur, kt + 2, g & 1, 0);
+                    else issue_unit(nxt, kt + 2 - nk, g & 1, 0);
                 }
                 read_frags(sboff, std::integral_constant<int, 1>{});
-                if (wm == 1) {  // W0(kt + 1)
-                    if constexpr (ST) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                    else wait_pieces(e1 ? (e2 ? 8 : 4) : 0);
-                }
+                if (wm == 1) wait_units(e2, e1);  // W0(kt + 1)
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_s_setprio(1);
@@ -443,10 +355,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
 #pragma unroll
                     for (int j = 0; j < H; ++j) acc[i][j] = Mfma16<T>::run(wf[i], xf[j], acc[i][j]);
                 __builtin_amdgcn_s_setprio(0);
-                if (wm == 0) {  // X0(kt + 1)
-                    if constexpr (ST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * CX) : "memory");
-                    else wait_pieces(e1 ? pieces(kt + 1, 1) + (e2 ? pieces(kt + 2, 0) : 0) : 0);
-                }
+                if (wm == 0) wait_units(e2, e1);  // X0(kt + 1)
                 __builtin_amdgcn_sched_barrier(0);
                 if (!(decltype(last)::value && wm == 1)) __builtin_amdgcn_s_barrier();
                 ++g;
@@ -456,8 +365,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
             init_acc<H>(acc, p.bias ? p.bias + (long long)s * N : nullptr, n0, N, wn, lane);
 
             if constexpr (RING) {
-                // (k-step 0 runs the steady code too: its wait at the end of M0 then counts the whole unit X0(1) as 2 CX
-                // <= 4 + CX pieces — stricter than needed, and that unit was issued before the previous epilogue)
                 for (int kt = 0; kt + 2 < nk; ++kt) kstep_ring(kt, std::false_type{}, std::true_type{});
                 if (has_next) {
                     int s2, m2, n2, h2;
@@ -507,280 +414,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_sched_kernel(const GemmParams 
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// Host side: the tile schedule.
-struct Tile {
-    int pair, xs, tn, m0, h;
-    long long key;  // locality order inside a height class
-};
-
-// XCD-aware bijective map of a block id to its position in the logical workgroup order (block b runs on XCD b % 8,
-// observed; speed only): XCD x owns a contiguous run of logical positions.
-unsigned xcd_remap(unsigned b, unsigned nwg) {
-    const unsigned xcd = b & 7u, q = nwg >> 3, r = nwg & 7u;
-    const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (b >> 3);
-}
-
-// Modelled fabric fetch of a schedule, in rows of K elements: every XCD's workgroups (block b runs on XCD b % 8, observed)
-// run their j-th tiles together and in k-lockstep, so a panel shared by several of them is fetched into the XCD's L2 once
-// per round — and nothing survives to the next round: the k-slices a round touches (a + b panels for a x b tiles, 12 x
-// 393 KB at K = 768) exceed the 4 MiB L2 under LRU.  Validated against TCC_EA0_RDREQ on the four BERT-base launches
-// (308 / 107 / 386 / 427 MB modelled, 308 / 108 / 384 / 428 MB counted: profiles/r6b_sched_l2_model.md), independent of
-// the modelled L2 size between 2 and 4 MiB.  tools/sched_l2_sim.py is the same model with an explicit LRU.
-long long schedule_fetch_rows(const std::vector<int4>& table, int rounds, int grid) {
-    long long rows = 0;
-    std::vector<long long> seen;
-    for (int xcd = 0; xcd < 8; ++xcd)
-        for (int j = 0; j < rounds; ++j) {
-            seen.clear();
-            for (int b = xcd; b < grid; b += 8) {
-                const int4 d = table[(size_t)j * grid + b];
-                const int h = d.z >> 24;
-                if (!h) continue;
-                seen.push_back(((long long)d.x << 32) | (unsigned)(d.z & 0xFFFFFF) | (1ll << 62));  // W panel (pair, n-tile)
-                for (int u = 0; u < h; ++u) seen.push_back(((long long)d.y << 32) | (unsigned)(d.w / UNIT + u));  // x unit
-            }
-            std::sort(seen.begin(), seen.end());
-            seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
-            for (long long v : seen) rows += (v >> 62) ? TN : UNIT;
-        }
-    return rows;
-}
-
-// Cut S * layers * tiles_n columns of ceil(M / 32) units into tiles of 1..8 units and deal them to at most n_cu
-// workgroups.  Returns the table ([rounds][grid] int4) and the launch grid.
-// policy bit 0: workgroups at odd logical positions run their tiles in reverse order (short tiles first), which
-// spreads the workgroups' epilogue store bursts over time instead of all of them ending a tile in the same
-// microsecond.
-// policy bit 12 (round 6): the columns that get one tile more than the others (the Bresenham remainder of the target tile
-// count) are the FIRST columns instead of being spread evenly: columns of one sample then share their row cuts, so the
-// tiles of a band of x rows that run together on an XCD fetch the same units (modelled fetch of the BERT-base FFN-up
-// launch 3.50 -> 2.90 x its operands, BERT-large Q/K/V 4.07 -> 3.33).
-// `cg` = columns per group of the locality order (policy bit 3).
-void build_schedule_cg(int S, int layers, int tiles_n, int M, int n_cu, int policy, int cg, std::vector<int4>& table,
-                       int& rounds, int& grid) {
-    const int hmax = ((policy >> 4) & 15) ? std::min(HMAX, std::max(HMIN, (policy >> 4) & 15)) : HMAX;
-    const int C = S * layers * tiles_n;
-    const int Hc = (M + UNIT - 1) / UNIT;
-    const long long U = (long long)C * Hc;
-    const int n_min = (Hc + hmax - 1) / hmax;
-    const int n_max = std::max(n_min, Hc / HMIN);
-    long long T = std::max<long long>(1, (U + (long long)hmax * n_cu - 1) / ((long long)hmax * n_cu));  // tiles per CU
-    std::vector<Tile> tiles;
-    for (int iter = 0; iter < 4; ++iter) {
-        const long long target = T * n_cu;
-        tiles.clear();
-        for (int c = 0; c < C; ++c) {
-            // spread of the target tile count over the columns: Bresenham, or (bit 12) the remainder on the first columns
-            long long n = (target * (c + 1)) / C - (target * c) / C;
-            if (policy & 0x1000) n = target / C + (c < target % C ? 1 : 0);
-            n = std::min<long long>(std::max<long long>(n, n_min), n_max);
-            if (policy & 2) n = n_min;  // fixed full-height tiles (the round-1 decomposition)
-            const int q = Hc / (int)n, r = Hc % (int)n;
-            const int xs = c / (tiles_n * layers), cn = c % (tiles_n * layers);
-            const int layer = cn / tiles_n, tn = cn % tiles_n;
-            int u = 0;
-            for (int i = 0; i < (int)n; ++i) {
-                const int hh = q + (i < r ? 1 : 0);
-                Tile t;
-                t.pair = layer * S + xs;
-                t.xs = xs;
-                t.tn = tn;
-                t.m0 = u * UNIT;
-                t.h = hh;
-                // (sample, band of 1024 rows, column, row): the 32 concurrent tiles of an XCD share few panels
-                t.key = (((long long)xs * 4096 + t.m0 / 1024) * 4096 + cn) * 65536 + (t.m0 / UNIT);
-                // policy bit 3: (sample, group of cg columns, 256-row band, column) — an XCD that walks this order keeps
-                // cg W panels in its L2 while the x bands stream past them (groups of 3 / 4 / 6 / 9 / 12 columns measured
-                // in the BERT-base step on one box, round 3: GEMM 7.13 / 7.10 / 7.20 / 7.29 / 7.22 ms, L2 fills 302 / 307 /
-                // 299 / 310 / 318 MB per launch)
-                if (policy & 8) t.key = ((((long long)xs * 4096 + cn / cg) * 65536 + t.m0 / 256) * 4096 + cn) * 8 + (t.m0 / UNIT) % 8;
-                tiles.push_back(t);
-                u += hh;
-            }
-        }
-        if ((long long)tiles.size() <= target) break;
-        T = ((long long)tiles.size() + n_cu - 1) / n_cu;  // the height cap forced more tiles than T rounds hold
-    }
-    const int total = (int)tiles.size();
-    grid = std::min(total, n_cu);
-    std::vector<std::vector<int>> lists(grid);  // per logical workgroup: indices into `tiles`, in running order
-    // class-by-class dealing: tiles sorted tallest first (locality order inside a height class); round r takes the next
-    // `grid` tiles.  Odd rounds are dealt backwards so that a workgroup that drew a tall tile in one round draws a
-    // short one in the next — either over all workgroups, or (policy bit 4, the default) only among the 32 workgroups of
-    // each XCD, which keeps an XCD on the same range of every height class (measured in the BERT-base step: 7.18 vs
-    // 7.25 ms of GEMM time).
-    std::stable_sort(tiles.begin(), tiles.end(), [](const Tile& a, const Tile& b) {
-        return a.h != b.h ? a.h > b.h : a.key < b.key;
-    });
-    const bool per_xcd = (policy & 4) && grid % 8 == 0 && total >= grid;
-    // (only when every height class fills whole rounds: then a workgroup that takes every 32nd tile of its XCD's list
-    // gets the same number of tiles of every class; otherwise the span dealing below, which balances odd classes)
-    bool whole_classes = (policy & 8) && grid % 8 == 0 && total >= grid;
-    for (int a = 0; a < total && whole_classes;) {
-        int b = a;
-        while (b < total && tiles[b].h == tiles[a].h) ++b;
-        if ((b - a) % grid) whole_classes = false;
-        a = b;
-    }
-    if (whole_classes) {
-        // Every XCD takes a CONTIGUOUS share of each height class (shares rotate so that the XCDs' tile counts stay
-        // within one of each other) and its 32 workgroups walk that share 32 tiles at a time: consecutive rounds of an
-        // XCD are neighbours in the locality order.  A workgroup draws every 32nd tile of its XCD's list, i.e. the same
-        // number of tiles of every class: the unit balance of the class-by-class dealing is kept.
-        const int span = grid / 8;
-        std::vector<std::vector<int>> share(8);
-        int carry = 0;
-        for (int a = 0; a < total;) {
-            int b = a;
-            while (b < total && tiles[b].h == tiles[a].h) ++b;
-            const int n = b - a;
-            int start = a;
-            for (int i = 0; i < 8; ++i) {
-                const int x = (i + carry) % 8;
-                const int cnt = (int)(((long long)n * (i + 1)) / 8 - ((long long)n * i) / 8);
-                for (int k = start; k < start + cnt; ++k) share[x].push_back(k);
-                start += cnt;
-            }
-            carry = (carry + n % 8) % 8;
-            a = b;
-        }
-        for (int x = 0; x < 8; ++x)
-            for (size_t j = 0; j < share[x].size(); ++j) {
-                const int r = (int)(j / span), in = (int)(j % span);
-                lists[x * span + ((r & 1) ? span - 1 - in : in)].push_back(share[x][j]);
-            }
-    } else if (!per_xcd) {
-        for (int k = 0; k < total; ++k) {
-            const int r = k / grid, pos = k % grid;
-            lists[(r & 1) ? grid - 1 - pos : pos].push_back(k);
-        }
-    } else {
-        // round r = tiles [r grid, (r+1) grid) cut into 8 spans of grid/8; XCD x takes span x of every round unless
-        // swapping two XCDs' spans of some round evens out their totals (only where a height class ends inside a round)
-        const int span = grid / 8, nr = (total + grid - 1) / grid;
-        std::vector<std::vector<long long>> sum(nr, std::vector<long long>(8, 0));
-        for (int k = 0; k < total; ++k) sum[k / grid][(k % grid) / span] += tiles[k].h;
-        std::vector<std::vector<int>> perm(nr, std::vector<int>(8));
-        for (int r = 0; r < nr; ++r)
-            for (int x = 0; x < 8; ++x) perm[r][x] = x;
-        auto tot = [&](int x) {
-            long long t = 0;
-            for (int r = 0; r < nr; ++r) t += sum[r][perm[r][x]];
-            return t;
-        };
-        for (int it = 0; it < 64; ++it) {
-            int hi = 0, lo = 0;
-            for (int x = 1; x < 8; ++x) {
-                if (tot(x) > tot(hi)) hi = x;
-                if (tot(x) < tot(lo)) lo = x;
-            }
-            const long long th = tot(hi), tl = tot(lo);
-            int best_r = -1;
-            long long best = th;
-            for (int r = 0; r < nr; ++r) {
-                const long long d = sum[r][perm[r][hi]] - sum[r][perm[r][lo]];
-                const long long m = std::max(th - d, tl + d);
-                if (d > 0 && m < best) best = m, best_r = r;
-            }
-            if (best_r < 0) break;
-            std::swap(perm[best_r][hi], perm[best_r][lo]);
-        }
-        for (int r = 0; r < nr; ++r)
-            for (int x = 0; x < 8; ++x)
-                for (int in = 0; in < span; ++in) {
-                    const int k = r * grid + perm[r][x] * span + in;
-                    if (k < total) lists[x * span + ((r & 1) ? span - 1 - in : in)].push_back(k);
-                }
-    }
-    if (policy & 1)
-        for (int li = 1; li < grid; li += 2) std::reverse(lists[li].begin(), lists[li].end());
-    rounds = 0;
-    for (const auto& l : lists) rounds = std::max(rounds, (int)l.size());
-    table.assign((size_t)rounds * grid, int4{0, 0, 0, 0});
-    for (int b = 0; b < grid; ++b) {
-        const std::vector<int>& l = lists[xcd_remap((unsigned)b, (unsigned)grid)];
-        for (size_t j = 0; j < l.size(); ++j) {
-            const Tile& t = tiles[l[j]];
-            table[j * grid + b] = int4{t.pair, t.xs, t.tn | (t.h << 24), t.m0};
-        }
-    }
-}
-
-// policy bits 8-11: columns per group of the locality order (0 = 4).  policy bit 13 (round 6): the group size is CHOSEN per
-// shape — among 3, 4, 6, 8 and all columns of a sample — by the modelled fabric fetch of the resulting schedule
-// (schedule_fetch_rows); the tiles, their heights and every workgroup's unit count are the same for every candidate.
-void build_schedule(int S, int layers, int tiles_n, int M, int n_cu, int policy, std::vector<int4>& table, int& rounds,
-                    int& grid) {
-    const int cg0 = ((policy >> 8) & 15) ? (policy >> 8) & 15 : 4;
-    if (!(policy & 0x2000) || !(policy & 8)) return build_schedule_cg(S, layers, tiles_n, M, n_cu, policy, cg0, table, rounds, grid);
-    const int cols = tiles_n * layers;
-    long long best = -1;
-    for (int cg : {4, 3, 6, 8, cols}) {  // (the first candidate wins a tie: 4 is the round-3 default)
-        if (cg > cols && cg != 4) continue;
-        std::vector<int4> t;
-        int r = 0, g = 0;
-        build_schedule_cg(S, layers, tiles_n, M, n_cu, policy, cg, t, r, g);
-        const long long f = schedule_fetch_rows(t, r, g);
-        if (best < 0 || f < best) best = f, table.swap(t), rounds = r, grid = g;
-    }
-}
-
-typedef Gemm256Sched Sched;
-typedef std::tuple<int, int, int, int, int, int, int> SchedKey;  // device, S, layers, tiles_n, M, n_cu, policy
-std::mutex g_sched_mu;
-std::map<SchedKey, Sched> g_sched;
-
-// The schedule of a shape is built once per device and kept in device memory for the life of the process (a few KB
-// per shape).  The first launch of a shape therefore allocates: it cannot happen inside a stream capture.
-int get_schedule(int S, int layers, int tiles_n, int M, int policy, hipStream_t stream, Sched& out) {
-    int dev = 0;
-    BF_HIP_CHECK(hipGetDevice(&dev));
-    static std::map<int, int> cu_of;
-    std::lock_guard<std::mutex> lk(g_sched_mu);
-    int n_cu = cu_of[dev];
-    if (!n_cu) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess) n_cu = 256;
-        else n_cu = prop.multiProcessorCount / 8 * 8;
-        if (n_cu < 8) n_cu = 8;
-        cu_of[dev] = n_cu;
-    }
-    const SchedKey key(dev, S, layers, tiles_n, M, n_cu, policy);
-    auto it = g_sched.find(key);
-    if (it != g_sched.end()) {
-        out = it->second;
-        return 0;
-    }
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        BF_FAIL("bf_gemm_nt: the first launch of a shape (S=%d M=%d) builds its tile schedule and allocates device "
-                "memory; call bf_gemm_prepare() for it, or run the step once, before capturing it into a graph", S, M);
-    // Tables are NEVER freed or rewritten: a captured HIP graph keeps the raw d_table pointer in its kernel arguments
-    // (bf_gemm_prepare / bench --graph), so a table must stay valid for the life of the process.  Variable-length batches
-    // make every new M a new shape; a table is a few KB to a few hundred KB, so the cache is bounded by BYTES per device
-    // (default 1 GiB, BF_GEMM_SCHED_CACHE_BYTES) and a shape past the bound is refused loudly instead of evicting.
-    static std::map<int, size_t> bytes_of;
-    static const size_t cap = [] {
-        const char* e = getenv("BF_GEMM_SCHED_CACHE_BYTES");
-        const long long v = e ? atoll(e) : 0;
-        return v > 0 ? (size_t)v : ((size_t)1 << 30);
-    }();
-    std::vector<int4> table;
-    Sched sc;
-    build_schedule(S, layers, tiles_n, M, n_cu, policy, table, sc.rounds, sc.grid);
-    if (bytes_of[dev] + table.size() * sizeof(int4) > cap)
-        BF_FAIL("bf_gemm_nt: the tile schedules of this device already hold %zu bytes (%zu shapes in the process); raise "
-                "BF_GEMM_SCHED_CACHE_BYTES (now %zu) or bucket the batch sizes", bytes_of[dev], g_sched.size(), cap);
-    bytes_of[dev] += table.size() * sizeof(int4);
-    BF_HIP_CHECK(hipMalloc((void**)&sc.d_table, table.size() * sizeof(int4)));
-    BF_HIP_CHECK(hipMemcpy(sc.d_table, table.data(), table.size() * sizeof(int4), hipMemcpyHostToDevice));
-    g_sched[key] = sc;
-    out = sc;
-    return 0;
-}
-
 template <typename T>
 int launch256_tn(const GemmParams& p, hipStream_t stream, int grid) {
     // the unit ring needs two k-steps to wrap around (the contraction here is over the S * B * L batch rows: always)
@@ -813,10 +446,6 @@ int launch256(const GemmParams& p, int y_dtype, hipStream_t stream, int grid) {
 
 }  // namespace
 
-int bf_gemm256_get_schedule(int S, int layers, int tiles_n, int M, int policy, hipStream_t stream, Gemm256Sched& out) {
-    return get_schedule(S, layers, tiles_n, M, policy, stream, out);
-}
-
 bool bf_gemm256_supported(int x_dtype, int w_dtype, int y_dtype, int S, int M, int N, int K, const void* d_x,
                           const void* d_w, int64_t x_sample_stride) {
     if (w_dtype != BF_DT_BF16 && w_dtype != BF_DT_F16) return false;
@@ -833,56 +462,14 @@ bool bf_gemm256_supported(int x_dtype, int w_dtype, int y_dtype, int S, int M, i
     return true;
 }
 
-extern "C" int bf_gemm_prepare(int S, int L, int M, int N, void* stream) {
-    if (S < 1 || L < 1 || M < 1 || N < 1) BF_FAIL("bf_gemm_prepare: bad shape S=%d L=%d M=%d N=%d", S, L, M, N);
-    Sched sc;
-    return get_schedule(S, L, (N + TN - 1) / TN, M, BF_SCHED_POLICY, (hipStream_t)stream, sc);
-}
-
-extern "C" size_t bf_gemm_schedule(int S, int L, int M, int N, int n_cu, int32_t* out, size_t cap_values, int* rounds,
-                                   int* grid) {
-    return bf_gemm_schedule_policy(S, L, M, N, n_cu, -1, out, cap_values, rounds, grid);
-}
-
-extern "C" int64_t bf_gemm_schedule_fetch_rows(const int32_t* table, int rounds, int grid) {
-    if (!table || rounds < 1 || grid < 1) return -1;
-    std::vector<int4> t((size_t)rounds * grid);
-    for (size_t i = 0; i < t.size(); ++i) t[i] = int4{table[4 * i], table[4 * i + 1], table[4 * i + 2], table[4 * i + 3]};
-    return schedule_fetch_rows(t, rounds, grid);
-}
-
-extern "C" size_t bf_gemm_schedule_policy(int S, int L, int M, int N, int n_cu, int policy, int32_t* out, size_t cap_values,
-                                          int* rounds, int* grid) {
-    if (S < 1 || L < 1 || M < 1 || N < 1 || n_cu < 1) return 0;
-    std::vector<int4> table;
-    int r = 0, g = 0;
-    build_schedule(S, L, (N + TN - 1) / TN, M, n_cu, policy < 0 ? BF_SCHED_POLICY : policy, table, r, g);
-    if (rounds) *rounds = r;
-    if (grid) *grid = g;
-    const size_t n = table.size() * 4;
-    if (out && cap_values >= n)
-        for (size_t i = 0; i < table.size(); ++i) {
-            out[4 * i] = table[i].x;
-            out[4 * i + 1] = table[i].y;
-            out[4 * i + 2] = table[i].z;
-            out[4 * i + 3] = table[i].w;
-        }
-    return n;
-}
-
 int bf_launch_gemm256(const GemmParams& p0, int w_dtype, int y_dtype, hipStream_t stream) {
     GemmParams p = p0;
-    if (p.layers < 1) p.layers = 1;
-    p.tiles_m = (p.M + TM - 1) / TM;
-    p.tiles_n = (p.N + TN - 1) / TN;
-    Sched sc;
-    if (get_schedule(p.S, p.layers, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
-    p.sched = sc.d_table;
-    p.sched_rounds = sc.rounds;
+    const int grid = gemm256_plan(p, stream);
+    if (!grid) return 1;
     // forward form: the five-slot ring (bf_gemm256_r5.hip) where it applies, the burst kernel for the other shapes
-    if (bf_gemm256_r5_supported(p, w_dtype, y_dtype)) return bf_launch_gemm256_r5(p, w_dtype, stream, sc.grid);
-    if (w_dtype == BF_DT_BF16) return launch256<__bf16>(p, y_dtype, stream, sc.grid);
-    return launch256<_Float16>(p, y_dtype, stream, sc.grid);
+    if (bf_gemm256_r5_supported(p, w_dtype, y_dtype)) return bf_launch_gemm256_r5(p, w_dtype, stream, grid);
+    if (w_dtype == BF_DT_BF16) return launch256<__bf16>(p, y_dtype, stream, grid);
+    return launch256<_Float16>(p, y_dtype, stream, grid);
 }
 
 // out[b][n][k] = sum_m a[b][m][n] * bmat[b][m][k]  (fp32 out): the weight-gradient GEMM dW = dy^T x of the backward pass
@@ -911,17 +498,12 @@ int bf_launch_gemm256_tn(const void* d_a, const void* d_b, float* d_out, int dty
     p.N = Kl;
     p.K = Mc;
     p.act = BF_ACT_NONE;
-    p.layers = 1;
-    p.tiles_m = (p.M + TM - 1) / TM;
-    p.tiles_n = (p.N + TN - 1) / TN;
-    Sched sc;
-    if (get_schedule(p.S, 1, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
-    p.sched = sc.d_table;
-    p.sched_rounds = sc.rounds;
+    const int grid = gemm256_plan(p, stream);
+    if (!grid) return 1;
     // the two-buffer unit ring of this file: the TN form on the five-slot ring measured bit-identical and 0-1.4 % per
     // launch in round 6, nothing in the training step
-    if (dtype == BF_DT_BF16) return launch256_tn<__bf16>(p, stream, sc.grid);
-    return launch256_tn<_Float16>(p, stream, sc.grid);
+    if (dtype == BF_DT_BF16) return launch256_tn<__bf16>(p, stream, grid);
+    return launch256_tn<_Float16>(p, stream, grid);
 }
 
 // y[s][m][k] = sum_n x[s][m][n] * w[s][n][k]  (16-bit in and out): the input-gradient GEMM dx = dy W of the backward pass
@@ -964,15 +546,10 @@ int bf_launch_gemm256_nn(const void* d_x, const void* d_w, void* d_y, int dtype,
     p.x_seg_stride = (long long)S * M * Nl;
     p.w_seg_stride = (long long)S * Nl * Kl;
     p.act = BF_ACT_NONE;
-    p.layers = 1;
-    p.tiles_m = (p.M + TM - 1) / TM;
-    p.tiles_n = (p.N + TN - 1) / TN;
-    Sched sc;
-    if (get_schedule(p.S, 1, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
-    p.sched = sc.d_table;
-    p.sched_rounds = sc.rounds;
+    const int grid = gemm256_plan(p, stream);
+    if (!grid) return 1;
     // the five-slot ring (bf_gemm256_r5.hip) where it applies, the burst kernel for the other shapes
-    if (bf_gemm256_r5_supported(p, dtype, dtype)) return bf_launch_gemm256_r5_nn(p, dtype, stream, sc.grid);
-    if (dtype == BF_DT_BF16) return launch256_nn<__bf16>(p, stream, sc.grid);
-    return launch256_nn<_Float16>(p, stream, sc.grid);
+    if (bf_gemm256_r5_supported(p, dtype, dtype)) return bf_launch_gemm256_r5_nn(p, dtype, stream, grid);
+    if (dtype == BF_DT_BF16) return launch256_nn<__bf16>(p, stream, grid);
+    return launch256_nn<_Float16>(p, stream, grid);
 }

@@ -1,5 +1,6 @@
 // bf_gemm256_dev.h — device helpers and the tile-schedule interface shared by the translation units of the 256-wide
-// sampled-weight GEMM (bf_gemm256.hip: burst / unit-ring forms; bf_gemm256_r5.hip: the five-slot ring of the forward).
+// sampled-weight GEMM (bf_gemm256.hip: burst / unit-ring forms; bf_gemm256_r5.hip: the five-slot ring of the forward;
+// bf_gemm_schedule.hip: the host-built tile schedule).
 // Everything here is internal (anonymous namespace per translation unit); the C-ABI is include/bayeformers_amd.h.
 #pragma once
 #include <type_traits>
@@ -17,7 +18,7 @@
 #define BF_SCHED_POLICY 0x300C
 #endif
 
-// The tile schedule of a shape (built on the host once per device, kept in device memory): bf_gemm256.hip.
+// The tile schedule of a shape (built on the host once per device, kept in device memory): bf_gemm_schedule.hip.
 struct Gemm256Sched {
     int4* d_table;
     int rounds, grid;
@@ -42,6 +43,19 @@ constexpr int ROW_BYTES = TK * 2;                 // 128
 constexpr int X_BYTES = TM * ROW_BYTES;           // 32 KiB
 constexpr int STAGE_BYTES = (TM + TN) * ROW_BYTES;  // 64 KiB
 
+// The launch preamble of every 256-wide launcher: normalises p.layers, fills the tile counts, fetches the shape's schedule
+// (built and uploaded on its first use) and points p at it.  Returns the launch grid, 0 after a failure (bf_last_error).
+inline int gemm256_plan(GemmParams& p, hipStream_t stream) {
+    if (p.layers < 1) p.layers = 1;
+    p.tiles_m = (p.M + TM - 1) / TM;
+    p.tiles_n = (p.N + TN - 1) / TN;
+    Gemm256Sched sc;
+    if (bf_gemm256_get_schedule(p.S, p.layers, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 0;
+    p.sched = sc.d_table;
+    p.sched_rounds = sc.rounds;
+    return sc.grid;
+}
+
 template <typename T>
 struct Mfma16;
 template <>
@@ -60,13 +74,8 @@ struct Mfma16<_Float16> {
 };
 
 template <>
-struct Mfma16<float> {  // a 16-byte fragment = 4 consecutive k of fp32: four 16x16x4 MFMAs (bf_gemm256_r5.hip orders them itself)
+struct Mfma16<float> {  // a 16-byte fragment = 4 consecutive k of fp32: four 16x16x4 MFMAs, ordered by bf_gemm256_r5.hip itself
     using frag = f32x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[k], b[k], c, 0, 0, 0);
-        return c;
-    }
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -75,6 +84,31 @@ typedef const __attribute__((address_space(1))) void glb_void;
 __device__ __forceinline__ void glds16(const void* g, char* lds_wave_base) {
     // 64 lanes x 16 B: lane i lands at lds_wave_base + 16*i (wave-uniform base)
     __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)lds_wave_base, 16, 0, 0);
+}
+
+// Segmented contraction (NN form): k-step kt lies in segment kt / nks, nks = k-steps per segment (at most 4 segments);
+// kt becomes the k-step inside the segment.  All wave-uniform arithmetic.
+__device__ __forceinline__ int segment_of(int& kt, int nks) {
+    const int seg = (kt >= nks ? 1 : 0) + (kt >= 2 * nks ? 1 : 0) + (kt >= 3 * nks ? 1 : 0);
+    kt -= seg * nks;
+    return seg;
+}
+
+// Fragment of a contraction-major tile (512-byte rows, 32-byte granules XOR-swizzled by the row) through the LDS transpose
+// read: two ds_read_b64_tr_b16 give a lane the 8 contraction values of its row that a ds_read_b128 of a K-contiguous
+// operand delivers.  a0 = the lane's address in the wave's first block, blk = block (one XOR away), half = integral_constant
+// 0 / 1 (the 32-row half: an immediate offset).
+typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+typedef __attribute__((ext_vector_type(8))) short s16x8_t;
+template <typename frag, typename Half>
+__device__ __forceinline__ frag tr_read(unsigned a0, int blk, Half) {
+    const unsigned a = a0 ^ (unsigned)(blk << 5);
+    constexpr int off = Half::value * 32 * 512;
+    s16x4_t lo, hi;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(a), "n"(off));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a), "n"(off + 4 * 512));
+    const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(frag, v);
 }
 
 // acc[nb][mb][j] starts at bias[n] (n = the lane's 4 consecutive features of fragment nb): the bias add costs no
@@ -253,9 +287,5 @@ __device__ __forceinline__ void epilogue_wave(char* scratch, const f32x4_t (&acc
         }
     }
 }
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
 
 }  // namespace

@@ -16,8 +16,8 @@
 //      waited for (vmcnt(4) = all but the newest unit) before the barrier that ends M1(t) (group 0) / L1(t) (group 1)
 //
 // Every L slot carries 4 pieces instead of 8 or 0, an x unit has 4 slots to land and a W unit 6 (W_s is the operand that
-// comes cold from HBM: it is read once per step), and every piece is still 8 FULL 128-byte rows (the k-half ring of the
-// burst kernel's -DBF_RING_ROWMAJOR build splits every line in two and loses).  The last two k-steps of a tile issue
+// comes cold from HBM: it is read once per step), and every piece is still 8 FULL 128-byte rows (a ring of k-halves, which
+// splits every line in two, was 3-7 % slower than the burst form: LABBOOK.md section 4.2).  The last two k-steps of a tile issue
 // W(0), X(0), W(1) of the workgroup's next tile, so a tile boundary costs the ring nothing; the wave-private epilogue
 // (16-bit outputs: 4 KiB of scratch per wave) fits in ONE of the two slots the last k-step consumed, the one whose next
 // unit is issued two barriers into the next tile — no DMA ever waits for an epilogue (the burst kernel's `defer`).
@@ -49,18 +49,13 @@ constexpr int NSLOT = 5;
 // fixed order).  That MFMA runs 1/16 of the 16-bit rate (32 cycles per 2048 flop): an M slot is 4096 cycles beside an L
 // slot of a few hundred, so the k-loop is bound by the matrix pipe alone.  fp32 outputs: the wave-private epilogue moves a
 // 16-row block through ONE 4 KiB slice per wave (eight of them = the one consumed slot).
-template <typename T>
-struct FragOf { using type = typename Mfma16<T>::frag; };
-template <>
-struct FragOf<float> { using type = f32x4_t; };
-
 // AG (round 6, NN form): the epilogue multiplies the stored rows by act'(p.gpre) (bf_gemm_nn_actgrad) — an instantiation of its
 // own, so that the plain input-gradient launches are the kernel they were.
 template <typename T, typename YT, bool TRW = false, bool SEG = false, bool AG = false>
 __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams p) {
     static_assert(!AG || (TRW && !SEG && sizeof(YT) == 2), "the activation-gradient epilogue: NN form, 16-bit outputs");
     static_assert(sizeof(T) == 2 || (!TRW && !SEG && sizeof(YT) == 4), "fp32 operands: forward form, fp32 outputs");
-    using frag = typename FragOf<T>::type;
+    using frag = typename Mfma16<T>::frag;
     constexpr unsigned ES = sizeof(T);            // bytes per operand element
     constexpr int TKE = ROW_BYTES / (int)ES;      // k-values per k-step: 64 (16-bit) or 32 (fp32)
     constexpr int CE = 16 / (int)ES;              // elements per 16-byte chunk
@@ -125,14 +120,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
         const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), 0, (int)bytes, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)dst, 16, (int)off, soff, 0, 0);
     };
-    // segmented contraction: k-step kt lies in segment kt / (K / TK) (wave-uniform arithmetic)
     auto segment = [&](int& kt) -> int {
-        if constexpr (SEG) {
-            const int nks = K / TK;
-            const int seg = (kt >= nks ? 1 : 0) + (kt >= 2 * nks ? 1 : 0) + (kt >= 3 * nks ? 1 : 0);
-            kt -= seg * nks;
-            return seg;
-        }
+        if constexpr (SEG) return segment_of(kt, K / TK);
         return 0;
     };
     // this wave's pieces of unit X(kt) / W(kt) into ring slot `slot`; only the 4 h pieces of the tile's rows of x are
@@ -158,8 +147,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
 
     // fragment reads: inline asm (the k-loop's own waits order them against the DMA and the MFMAs; the compiler's
     // wait-count pass would otherwise drain every in-flight DMA before an LDS load it can see)
-    const int fsw = (lane >> 1) & 7;
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    const int fsw = (lane >> 1) & 7;
     const unsigned foff0 = (lane & 15) * ROW_BYTES + ((((lane >> 4)) ^ fsw) << 4);
     const unsigned foff1 = (lane & 15) * ROW_BYTES + (((4 + (lane >> 4)) ^ fsw) << 4);
     const unsigned xrow0 = lds0 + wm * 16 * ROW_BYTES;  // + j * 32 rows: wave group wm owns blocks wm, wm + 2, ...
@@ -174,15 +163,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
     // the block's 32-byte granule; granule' = granule ^ key(row).  Fragment block i of the wave: one XOR away.
     const int tr_rl = ((lane & 15) >> 2) | (((lane >> 4) & 1) << 2);
     const unsigned tr_w0 = lds0 + ((lane >> 4) * 8 + ((lane & 15) >> 2)) * 512 + (lane & 3) * 8 + (((wn * 4) ^ tr_rl) << 5);
-    auto tr_read = [&](unsigned a0, int blk, auto half) -> frag {
-        const unsigned a = a0 ^ (unsigned)(blk << 5);
-        constexpr int off = decltype(half)::value * 32 * 512;
-        s16x4_t lo, hi;
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(a), "n"(off));
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a), "n"(off + 4 * 512));
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(frag, v);
-    };
 
     const int nk = SEG ? p.segs * (K / TK) : K / TKE;
     // the schedule is read through the scalar cache (it was written before the launch): entries arrive in SGPRs
@@ -226,7 +206,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
                 if constexpr (TRW) {
                     const unsigned aw = tr_w0 + slot_w * SLOT_BYTES;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) wf[i] = tr_read(aw, i, half);
+                    for (int i = 0; i < 4; ++i) wf[i] = tr_read<frag>(aw, i, half);
                 } else {
                     const unsigned aw = wrow0 + slot_w * SLOT_BYTES + (HF ? foff1 : foff0);
                     static_for<0, 4>([&](auto ic) {
@@ -384,14 +364,9 @@ bool bf_gemm256_f32_supported(int S, int M, int N, int K, const void* d_x, const
 
 int bf_launch_gemm256_f32(const GemmParams& p0, hipStream_t stream) {
     GemmParams p = p0;
-    if (p.layers < 1) p.layers = 1;
-    p.tiles_m = (p.M + TM - 1) / TM;
-    p.tiles_n = (p.N + TN - 1) / TN;
-    Gemm256Sched sc;
-    if (bf_gemm256_get_schedule(p.S, p.layers, p.tiles_n, p.M, BF_SCHED_POLICY, stream, sc)) return 1;
-    p.sched = sc.d_table;
-    p.sched_rounds = sc.rounds;
-    return launch_r5<float, float, false, false>(p, stream, sc.grid);
+    const int grid = gemm256_plan(p, stream);
+    if (!grid) return 1;
+    return launch_r5<float, float, false, false>(p, stream, grid);
 }
 
 // NN form (x K-contiguous, W contraction-major as sampled, 16-bit out): y[s][m][k] = sum_n x[s][m][n] w[s][n][k]

@@ -18,7 +18,7 @@ struct GemmParams {
     int tiles_m, tiles_n;
     int act;      // BF_ACT_* applied to y in the epilogue
     int layers;   // L >= 1 layers that share x: w is [L][S][N][K], bias [L][S][N], y [L][S][M][N] (bf_gemm_nt_layers)
-    // tile schedule of the 256-wide persistent kernel (bf_gemm256.hip): workgroup b runs sched[j * gridDim.x + b],
+    // tile schedule of the 256-wide persistent kernels (built by bf_gemm_schedule.hip): workgroup b runs sched[j * gridDim.x + b],
     // j = 0 .. sched_rounds - 1, until an entry with height 0
     const int4* sched;
     int sched_rounds;
@@ -30,7 +30,8 @@ struct GemmParams {
     long long x_rstride;
 };
 
-// fast 256-wide LDS-DMA kernel (bf_gemm256.hip)
+// fast 256-wide LDS-DMA kernels (launchers in bf_gemm256.hip, which hands the 16-bit forward and NN forms with K >= 128 to
+// bf_gemm256_r5.hip; tile schedule: bf_gemm_schedule.hip)
 bool bf_gemm256_supported(int x_dtype, int w_dtype, int y_dtype, int S, int M, int N, int K, const void* d_x,
                           const void* d_w, int64_t x_sample_stride);
 int bf_launch_gemm256(const GemmParams& p, int w_dtype, int y_dtype, hipStream_t stream);

@@ -1,4 +1,4 @@
-"""Host-side tile schedule of the 256-wide persistent GEMM (bf_gemm_schedule, csrc/bf_gemm256.hip): every 32-row unit
+"""Host-side tile schedule of the 256-wide persistent GEMM (bf_gemm_schedule, csrc/bf_gemm_schedule.hip): every 32-row unit
 of every (sample, layer, n-tile) column is covered exactly once, no tile is taller than 8 units, and the units are
 spread evenly over the workgroups — the property that removes the partial last round of fixed 256-row tiles
 (BERT-base: 480 k tiles on 256 CUs = 1.875 k rounds).  CPU-only: the schedule is plain host code."""
