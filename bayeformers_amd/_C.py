@@ -124,6 +124,11 @@ SYMBOLS = {
     "bf_add_rmsnorm": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i64, _i, ctypes.c_float, _vp]),
     "bf_rope_qk": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "bf_swiglu": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
+    # ... and their backward
+    "bf_add_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i]),
+    "bf_add_rmsnorm_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i64, _i, ctypes.c_float, _vp]),
+    "bf_rope_qk_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "bf_swiglu_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
     "bf_generate_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                               _i64, _i, _vp, _vp]),
     "bf_generate_step_stat_probs": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp,

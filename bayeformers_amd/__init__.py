@@ -839,17 +839,30 @@ def _is_silu(fn) -> bool:
     return isinstance(fn, torch.nn.SiLU) or type(fn).__name__ == "SiLUActivation"
 
 
+def _blocks_backward(module) -> bool:
+    """Did fuse_decoder_blocks(backward=True) rewrite this module?  Then its fast form also runs under recorded gradients
+    and in training mode, through the autograd functions over the backward kernels."""
+    return getattr(module, "_bf_blocks_backward", False)
+
+
 def _rmsnorm_forward(self, hidden_states):
     """forward of an HF `*RMSNorm` on bf_add_rmsnorm.  A hidden state that the fused layer in front of this norm produced
-    carries this norm's output already (`_bf_normed`, computed in that layer's residual pass): it is handed out as it is."""
+    carries this norm's output already (`_bf_normed`, computed in that layer's residual pass): it is handed out as it is.
+    Under recorded gradients (fuse_decoder_blocks(backward=True)) the attached tensor is the second output of the autograd
+    function whose first output is the hidden state; it is taken only when it carries a grad_fn — whatever this forward
+    returns under recorded gradients must be part of the graph, and reentrant checkpointing or layers run under no_grad
+    hand out graph-less ones — and it stays attached, so a recomputation of this forward sees what the first run saw."""
     from . import ops
 
     x = hidden_states
-    if not ops.rmsnorm_supported(x, None, self) or _records_grad(x, self):
+    rec = _records_grad(x, self)
+    if not ops.rmsnorm_supported(x, None, self) or (rec and not _blocks_backward(self)):
         return self._bf_plain_rmsnorm_forward(hidden_states)
-    ready = x.__dict__.pop("_bf_normed", None)
-    if ready is not None and ready[1] is self:
+    ready = x.__dict__.get("_bf_normed") if rec else x.__dict__.pop("_bf_normed", None)
+    if ready is not None and ready[1] is self and not (rec and ready[0].grad_fn is None):
         return ready[0]
+    if rec:
+        return ops.AddRMSNormFn.apply(x, None, self.weight, self.variance_epsilon)
     return ops.add_rmsnorm(x, None, self.weight, self.variance_epsilon, want_sum=False)[1]
 
 
@@ -858,29 +871,32 @@ def _decoder_layer_forward(self, hidden_states, attention_mask=None, position_id
     """forward of an HF Llama / Mistral / Qwen2 decoder layer with its two residual adds folded into the RMSNorm that
     follows each (bf_add_rmsnorm writes the sum and the normalised row in one pass): the second add feeds the NEXT
     layer's input norm (or the model's final norm), whose output travels on the returned hidden state as `_bf_normed`.
-    The returned tensor is always the true hidden state.  Gradients recorded, training mode, tensors off the device, a
-    hook on the norm whose forward is skipped: the module's own forward."""
+    The returned tensor is always the true hidden state.  Tensors off the device, a hook on the norm whose forward is
+    skipped: the module's own forward; gradients recorded or training mode as well, unless the layer was rewritten with
+    backward=True — then the two passes run through ops.AddRMSNormFn, whose backward is bf_add_rmsnorm_bwd."""
     from . import ops
 
     h = hidden_states
     post, nxt = self.post_attention_layernorm, self._bf_next_norm[0]
-    if (not isinstance(h, torch.Tensor) or self.training or _hooked(post) or not ops.rmsnorm_supported(h, None, post)
-            or not ops.rmsnorm_supported(h, None, nxt) or _records_grad(h, self, nxt)):
+    rec = isinstance(h, torch.Tensor) and _records_grad(h, self, nxt)
+    if (not isinstance(h, torch.Tensor) or _hooked(post) or not ops.rmsnorm_supported(h, None, post)
+            or not ops.rmsnorm_supported(h, None, nxt) or ((self.training or rec) and not _blocks_backward(self))):
         return self._bf_plain_layer_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
                                             past_key_values=past_key_values, use_cache=use_cache,
                                             position_embeddings=position_embeddings, **kwargs)
     a, _ = self.self_attn(hidden_states=self.input_layernorm(h), attention_mask=attention_mask, position_ids=position_ids,
                           past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings,
                           **kwargs)
+    add_rmsnorm = ops.AddRMSNormFn.apply if rec else ops.add_rmsnorm
     if ops.rmsnorm_supported(a, h, post):
-        h1, y1 = ops.add_rmsnorm(a, h, post.weight, post.variance_epsilon)
+        h1, y1 = add_rmsnorm(a, h, post.weight, post.variance_epsilon)
     else:
         h1 = h + a
         y1 = post(h1)
     m = self.mlp(y1)
     if not ops.rmsnorm_supported(m, h1, nxt):
         return h1 + m
-    h2, y2 = ops.add_rmsnorm(m, h1, nxt.weight, nxt.variance_epsilon)
+    h2, y2 = add_rmsnorm(m, h1, nxt.weight, nxt.variance_epsilon)
     h2._bf_normed = (y2, nxt)
     return h2
 
@@ -889,15 +905,19 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings=None, at
                                **kwargs):
     """forward of an HF Llama / Mistral / Qwen2 attention module with apply_rotary_pos_emb as one launch (bf_rope_qk), in
     place on the projections' outputs in the [B, T, heads * head_dim] layout the attention kernels read through strides.
-    The cache update, the attention interface lookup and o_proj are the module's own code path."""
+    The cache update, the attention interface lookup and o_proj are the module's own code path.  Rewritten with
+    backward=True it also runs under recorded gradients and in training mode (unless attention dropout would be active):
+    out of place through ops.RopeQKFn, whose outputs have the same [B, T, heads, head_dim] layout."""
     import sys
 
     from . import ops
 
     x = hidden_states
     pe = position_embeddings
+    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
     fast = (pe is not None and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 3 and x.dtype in ops._TORCH2BF
-            and not self.training and self.head_dim in (64, 128) and not _records_grad(x, self))
+            and self.head_dim in (64, 128) and (_blocks_backward(self) or not (self.training or rec))
+            and not (self.training and self.attention_dropout > 0))
     if fast:
         cos, sin = pe
         fast = (cos.dim() == 3 and sin.shape == cos.shape and cos.shape[-1] == self.head_dim and cos.shape[1] == x.shape[1]
@@ -913,7 +933,10 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings=None, at
     value_states = self.v_proj(x).view(hidden_shape).transpose(1, 2)
     cos, sin = (t if t.is_contiguous() else t.contiguous() for t in (cos, sin))
     if ops.rope_supported(query_states, key_states, cos, sin):
-        query_states, key_states = ops.rope_qk(query_states, key_states, cos, sin, inplace=True)
+        if rec:  # the in-place form would overwrite what the projections' backward reads
+            query_states, key_states = ops.RopeQKFn.apply(query_states, key_states, cos, sin)
+        else:
+            query_states, key_states = ops.rope_qk(query_states, key_states, cos, sin, inplace=True)
     else:  # a projection that came back in another dtype or layout: the framework's ops on what is already computed
         query_states, key_states = mod.apply_rotary_pos_emb(query_states, key_states, cos, sin)
     if past_key_values is not None:
@@ -934,26 +957,34 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings=None, at
 
 def _swiglu_mlp_forward(self, x):
     """forward of an HF Llama-style MLP — down_proj(act_fn(gate_proj(x)) * up_proj(x)) — with the SiLU and the product as
-    one launch (bf_swiglu)."""
+    one launch (bf_swiglu); rewritten with backward=True, under recorded gradients and in training mode too, through
+    ops.SwiGLUFn."""
     from . import ops
 
-    if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in ops._TORCH2BF or self.training
-            or _hooked(self.act_fn) or _records_grad(x, self)):
+    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
+    if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in ops._TORCH2BF or _hooked(self.act_fn)
+            or ((self.training or rec) and not _blocks_backward(self))):
         return self._bf_plain_mlp_forward(x)
     gate, up = self.gate_proj(x), self.up_proj(x)
-    return self.down_proj(ops.swiglu(gate, up) if ops.swiglu_supported(gate, up) else self.act_fn(gate) * up)
+    if not ops.swiglu_supported(gate, up):
+        return self.down_proj(self.act_fn(gate) * up)
+    return self.down_proj(ops.SwiGLUFn.apply(gate, up) if rec else ops.swiglu(gate, up))
 
 
-def fuse_decoder_blocks(model: torch.nn.Module) -> int:
+def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False) -> int:
     """Run the memory-bound ops of HuggingFace Llama, Mistral and Qwen2 decoder layers — the two RMSNorms with the
     residual adds in front of them, the rotary embedding of q and k, SiLU(gate) * up — as four launches per layer
     (bf_add_rmsnorm twice, bf_rope_qk, bf_swiglu) instead of the framework's thirty or so elementwise kernels.  A layer is
     rewritten when its class is exactly LlamaDecoderLayer, MistralDecoderLayer or Qwen2DecoderLayer with the attribute
     shape those have (RMSNorm modules with `weight` and `variance_epsilon`, an MLP of gate / up / down projections around
     a SiLU, an attention module with q / k / v / o projections and head_dim 64 or 128); Qwen3 (q / k norms), Gemma
-    (1 + weight), OLMo and mixture-of-experts layers are left alone.  Inference-time rewrite like the other fuse_*
-    functions: with gradients recorded, in training mode, off the device or on shapes the kernels refuse, the modules'
-    own forwards run.  Returns the number of layers rewritten; calling it again rewrites nothing twice."""
+    (1 + weight), OLMo and mixture-of-experts layers are left alone.  By default an inference-time rewrite like the
+    other fuse_* functions: with gradients recorded, in training mode, off the device or on shapes the kernels refuse, the
+    modules' own forwards run.  backward=True: the fast forms also run under recorded gradients and in training mode,
+    through autograd functions whose backward is one launch each (bf_add_rmsnorm_bwd, bf_rope_qk_bwd, bf_swiglu_bwd) — a
+    training step's decoder glue on the kernels in both directions; an attention module whose dropout would be active
+    still runs its own forward.  Returns the number of layers rewritten; calling it again rewrites nothing twice (a second
+    call with backward=True turns the backward on for the layers already rewritten, and counts none of them)."""
     fused = 0
     for parent in model.modules():
         layers, final = getattr(parent, "layers", None), getattr(parent, "norm", None)
@@ -962,6 +993,9 @@ def fuse_decoder_blocks(model: torch.nn.Module) -> int:
         for i, layer in enumerate(layers):
             attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
             nxt = getattr(layers[i + 1], "input_layernorm", None) if i + 1 < len(layers) else final
+            if backward and hasattr(layer, "_bf_plain_layer_forward"):
+                for m in (layer, attn, mlp, layer.input_layernorm, nxt):
+                    m._bf_blocks_backward = True
             if (type(layer).__name__ not in _DECODER_LAYERS or hasattr(layer, "_bf_plain_layer_forward")
                     or type(attn).__name__ != _DECODER_LAYERS[type(layer).__name__]
                     or not _is_rmsnorm(getattr(layer, "input_layernorm", None))
@@ -982,6 +1016,9 @@ def fuse_decoder_blocks(model: torch.nn.Module) -> int:
                 if not hasattr(norm, "_bf_plain_rmsnorm_forward"):
                     norm._bf_plain_rmsnorm_forward = norm.forward
                     norm.forward = types.MethodType(_rmsnorm_forward, norm)
+            if backward:
+                for m in (layer, attn, mlp, layer.input_layernorm, nxt):
+                    m._bf_blocks_backward = True
             fused += 1
     return fused
 

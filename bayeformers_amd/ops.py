@@ -1531,6 +1531,156 @@ def swiglu(gate: Tensor, up: Tensor) -> Tensor:
     return out
 
 
+# ---- their backward: bf_add_rmsnorm_bwd / bf_rope_qk_bwd / bf_swiglu_bwd, and the autograd functions over both directions
+# launches of the three backward entries from this process (the forwards of a training step count in BLOCK_CALLS)
+BLOCK_BWD_CALLS = {"rmsnorm": 0, "rope": 0, "swiglu": 0}
+
+
+def rmsnorm_bwd_supported(x: Tensor, residual: Optional[Tensor], norm) -> bool:
+    """Does bf_add_rmsnorm_bwd take what bf_add_rmsnorm took?  The same limits: N % 8 == 0, N <= 8192."""
+    return rmsnorm_supported(x, residual, norm)
+
+
+def _grad_rows(g: Tensor, like: Tensor, n: int) -> Tensor:
+    return _rows_of(g if g.dtype == like.dtype else g.to(like.dtype), n)
+
+
+def add_rmsnorm_backward(z: Tensor, gamma: Tensor, grad_out: Tensor, eps: float, grad_sum: Optional[Tensor] = None):
+    """Gradients of add_rmsnorm (bf_add_rmsnorm_bwd) from the sum z it returned (x itself without a residual): (dz,
+    dgamma).  dz is the gradient of both x and the residual, dgamma is fp32.  grad_sum: the gradient that reached z
+    through its other consumer, added to dz inside the kernel."""
+    _require_device(z, "add_rmsnorm_backward input")
+    N = z.shape[-1]
+    if gamma.dtype not in (torch.float32, z.dtype):
+        raise _C.BayeFormersAMDError("add_rmsnorm_backward: gamma must be float32 or have the input's dtype")
+    if grad_out.shape != z.shape or (grad_sum is not None and grad_sum.shape != z.shape):
+        raise _C.BayeFormersAMDError("add_rmsnorm_backward: the gradients must have the input's shape")
+    z2, g2 = _rows_of(z, N), _grad_rows(grad_out, z, N)
+    h2 = _grad_rows(grad_sum, z, N) if grad_sum is not None else None
+    dz = torch.empty_like(z2)
+    dgamma = torch.empty(N, dtype=torch.float32, device=z.device)
+    lib = _C.lib()
+    ws = workspace(z.device, lib.bf_add_rmsnorm_bwd_workspace_bytes(z2.shape[0], N))
+    _C.check(lib.bf_add_rmsnorm_bwd(z2.data_ptr(), gamma.data_ptr(), _TORCH2BF[gamma.dtype], g2.data_ptr(),
+                                    h2.data_ptr() if h2 is not None else None, dz.data_ptr(), dgamma.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), _TORCH2BF[z.dtype], z2.shape[0], N, float(eps), _stream_ptr()),
+             "bf_add_rmsnorm_bwd")
+    BLOCK_BWD_CALLS["rmsnorm"] += 1
+    return dz.view(z.shape), dgamma
+
+
+class AddRMSNormFn(torch.autograd.Function):
+    """add_rmsnorm with both directions in the HIP kernels.  With a residual it returns (z, y), the two outputs of one
+    launch; backward receives their gradients separately and hands z's — the next residual add's, a returned hidden
+    state's — to the kernel, which adds it on load.  Without a residual it returns y alone.  Saves z (an output, or x) and
+    gamma, nothing else."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, eps):
+        ctx.eps, ctx.has_res = eps, residual is not None
+        z, y = add_rmsnorm(x, residual, gamma, eps)
+        ctx.save_for_backward(z, gamma)
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
+        return (z, y) if ctx.has_res else y
+
+    @staticmethod
+    def backward(ctx, *grads):
+        z, gamma = ctx.saved_tensors
+        grad_z, grad_y = grads if ctx.has_res else (None, grads[0])
+        need = ctx.needs_input_grad
+        if grad_y is None:  # only the sum was used: the add's own backward
+            return grad_z if need[0] else None, grad_z if need[1] else None, None, None
+        dz, dgamma = add_rmsnorm_backward(z, gamma, grad_y, ctx.eps, grad_sum=grad_z)
+        if need[2] and dgamma.dtype != gamma.dtype:
+            dgamma = dgamma.to(gamma.dtype)  # the kernel emits fp32
+        return dz if need[0] else None, dz if (ctx.has_res and need[1]) else None, dgamma if need[2] else None, None
+
+
+def _rope_grad(g: Tensor, like: Tensor) -> Tensor:
+    g = g if g.dtype == like.dtype else g.to(like.dtype)
+    ok = g.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in g.stride()[:3]) and g.data_ptr() % 16 == 0
+    return g if ok else g.contiguous()
+
+
+def rope_qk_backward(grad_q: Tensor, grad_k: Tensor, cos: Tensor, sin: Tensor):
+    """Gradients of rope_qk (bf_rope_qk_bwd), its transpose: grad_q [B, H, T, D] / grad_k [B, Hkv, T, D] in any layout
+    rope_supported takes (read where the attention backward left them) -> (dq, dk), new tensors laid out [B, T, heads, D]
+    — what the backward of the projections reads — and returned as their [B, heads, T, D] views."""
+    _require_device(grad_q, "rope_qk_backward input")
+    grad_q, grad_k = _rope_grad(grad_q, grad_q), _rope_grad(grad_k, grad_q)
+    if not rope_supported(grad_q, grad_k, cos, sin):
+        raise _C.BayeFormersAMDError("rope_qk_backward: unsupported shapes, strides or dtypes (see ops.rope_supported)")
+    B, H, T, D = grad_q.shape
+    Hkv = grad_k.shape[1]
+    dq = torch.empty((B, T, H, D), dtype=grad_q.dtype, device=grad_q.device).transpose(1, 2)
+    dk = torch.empty((B, T, Hkv, D), dtype=grad_k.dtype, device=grad_k.device).transpose(1, 2)
+    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
+    for name, t in (("q_stride", grad_q), ("k_stride", grad_k), ("q_out_stride", dq), ("k_out_stride", dk)):
+        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    _C.check(_C.lib().bf_rope_qk_bwd(grad_q.data_ptr(), grad_k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
+                                     dq.data_ptr(), dk.data_ptr(), _TORCH2BF[grad_q.dtype], ctypes.byref(s), _stream_ptr()),
+             "bf_rope_qk_bwd")
+    BLOCK_BWD_CALLS["rope"] += 1
+    return dq, dk
+
+
+class RopeQKFn(torch.autograd.Function):
+    """rope_qk (out of place) with both directions in the HIP kernels; saves the two tables."""
+
+    @staticmethod
+    def forward(ctx, q, k, cos, sin):
+        ctx.save_for_backward(cos, sin)
+        return rope_qk(q, k, cos, sin)
+
+    @staticmethod
+    def backward(ctx, grad_q, grad_k):
+        cos, sin = ctx.saved_tensors
+        dq, dk = rope_qk_backward(grad_q, grad_k, cos, sin)
+        return dq, dk, None, None
+
+
+def swiglu_bwd_supported(gate: Tensor, up: Tensor) -> bool:
+    """What bf_swiglu_bwd takes of the forward's inputs: what bf_swiglu took."""
+    return swiglu_supported(gate, up)
+
+
+def swiglu_backward(gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool = False):
+    """Gradients of swiglu (bf_swiglu_bwd): (dgate, dup) from the forward's inputs.  stacked: the two are the halves of
+    one [..., 2N] buffer (the layout a stacked gate / up projection's backward reads) instead of two tensors."""
+    _require_device(gate, "swiglu_backward input")
+    if not swiglu_bwd_supported(gate, up) or grad_out.shape != gate.shape:
+        raise _C.BayeFormersAMDError("swiglu_backward: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
+    g = grad_out if grad_out.dtype == gate.dtype else grad_out.to(gate.dtype)
+    if not g.is_cuda or _row_stride(g) is None:
+        g = g.contiguous()
+    N = gate.shape[-1]
+    if stacked:
+        both = torch.empty((*gate.shape[:-1], 2 * N), dtype=gate.dtype, device=gate.device)
+        dgate, dup = both[..., :N], both[..., N:]
+    else:
+        dgate, dup = (torch.empty(gate.shape, dtype=gate.dtype, device=gate.device) for _ in range(2))
+    _C.check(_C.lib().bf_swiglu_bwd(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), g.data_ptr(),
+                                    _row_stride(g), dgate.data_ptr(), 2 * N if stacked else N, dup.data_ptr(),
+                                    2 * N if stacked else N, _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()),
+             "bf_swiglu_bwd")
+    BLOCK_BWD_CALLS["swiglu"] += 1
+    return dgate, dup
+
+
+class SwiGLUFn(torch.autograd.Function):
+    """swiglu with both directions in the HIP kernels; saves gate and up (the projections' outputs), nothing new."""
+
+    @staticmethod
+    def forward(ctx, gate, up):
+        ctx.save_for_backward(gate, up)
+        return swiglu(gate, up)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gate, up = ctx.saved_tensors
+        return swiglu_backward(gate, up, grad_out)
+
+
 # ------------------------------------------------------------------------------------- Monte-Carlo predictive statistics
 _PREDICTIVE_WS = {}
 

@@ -33,7 +33,8 @@ extern "C" {
                                (device-resident part of the call number), bf_gemm_schedule_policy / _fetch_rows,
                                bf_profile_read_launches; still 6 (additions only, no signature changed): bf_gemm_nt_rows,
                                bf_gemm_nt_rows_workspace_bytes, bf_attention_fwd_rows, bf_add_layernorm_rows, bf_add_rmsnorm,
-                               bf_rope_qk, bf_swiglu — a library without them fails to bind by the missing symbol */
+                               bf_rope_qk, bf_swiglu, bf_add_rmsnorm_bwd(_workspace_bytes), bf_rope_qk_bwd, bf_swiglu_bwd — a
+                               library without them fails to bind by the missing symbol */
 
 /* element types of activations / sampled weights */
 enum { BF_DT_F32 = 0, BF_DT_BF16 = 1, BF_DT_F16 = 2 };
@@ -547,6 +548,49 @@ int bf_rope_qk(const void* d_q, const void* d_k, const void* d_cos, const void* 
  * N % 8 == 0, 16-byte aligned pointers. */
 int bf_swiglu(const void* d_gate, int64_t gate_row_stride, const void* d_up, int64_t up_row_stride, void* d_out,
               int64_t out_row_stride, int dtype, int64_t rows, int N, void* stream);
+
+/* ---- their backward ---------------------------------------------------------------------------------------------------
+ * The same style: one streaming pass each, fp32 arithmetic, one rounding into `dtype`, no allocation, no synchronisation,
+ * no float atomics (a replayed capture gives the eager step's bits).  The forwards keep nothing for them beyond tensors a
+ * training step holds anyway.
+ *
+ * bf_add_rmsnorm_bwd — replaces autograd's backward of `residual + x` and HF LlamaRMSNorm.forward (about a dozen
+ * elementwise and reduction launches, and the add of the sum's two incoming gradients).  With z = x + residual as
+ * bf_add_rmsnorm wrote it to d_sum_out (d_z is x itself when there was no residual), r = rsqrt(mean(z^2) + eps)
+ * recomputed from z, and a = gamma o dy:
+ *     dz = r * a - z * r^3 * mean_row(z o a) + dz_in        (the gradient of x and of the residual alike)
+ *     dgamma = sum_rows dy o z * r                            (fp32 [N])
+ * d_dz_in (nullable): the gradient that reaches z through its other consumer (the next residual add, a returned hidden
+ * state), added on load.  z, dy, dz_in, dz: [rows, N] of `dtype`, rows back to back; gamma [N] of `param_dtype` (BF_DT_F32
+ * or `dtype`); d_dz may be d_dy or d_dz_in themselves (in place), no other overlap.  dgamma is reduced in a fixed order:
+ * per-workgroup partial rows in d_workspace (bf_add_rmsnorm_bwd_workspace_bytes(rows, N) bytes, 16-byte aligned), summed by
+ * a second small launch.  rows == 0 zeroes dgamma.  N % 8 == 0, N <= 8192, 16-byte aligned pointers. */
+size_t bf_add_rmsnorm_bwd_workspace_bytes(int64_t rows, int N);
+int bf_add_rmsnorm_bwd(const void* d_z, const void* d_gamma, int param_dtype, const void* d_dy, const void* d_dz_in,
+                       void* d_dz, float* d_dgamma, void* d_workspace, size_t workspace_bytes, int dtype, int64_t rows, int N,
+                       float eps, void* stream);
+
+/* bf_rope_qk_bwd — replaces autograd's backward of HF apply_rotary_pos_emb.  The transpose of bf_rope_qk: with the
+ * forward's y1 = x1 c1 - x2 s1, y2 = x2 c2 + x1 s2 over the two halves of a head (c1, s1 / c2, s2: the two halves of the
+ * tables, which need not be equal),
+ *     dx1 = dy1 c1 + dy2 s2,   dx2 = dy2 c2 - dy1 s1.
+ * d_dq / d_dk are the gradients of the rotated q / k, addressed by q_stride / k_stride (wherever the attention backward
+ * left them); d_dq_out / d_dk_out receive the gradients of the unrotated q / k by q_out_stride / k_out_stride (the
+ * projections' [B, T, heads * head_dim] layout, say).  Every other argument, limit and check is bf_rope_qk's, the in-place
+ * form included. */
+int bf_rope_qk_bwd(const void* d_dq, const void* d_dk, const void* d_cos, const void* d_sin, int cs_dtype, void* d_dq_out,
+                   void* d_dk_out, int dtype, const bf_rope_t* shape, void* stream);
+
+/* bf_swiglu_bwd — replaces autograd's backward of `act_fn(gate) * up` (SiLU backward and two multiplies).  With
+ * s = 1 / (1 + exp(-gate)):
+ *     dgate = dy * up * s * (1 + gate * (1 - s)),   dup = dy * gate * s,
+ * evaluated from exp(-|gate|), so finite for every finite input (gate -> -inf gives 0 and 0, gate -> +inf dy * up and
+ * dy * gate).  rows x N of `dtype`, each of the five tensors with a row stride of its own (multiples of 8, >= N): dgate and
+ * dup may be the halves of one stacked [rows, 2N] buffer, as gate and up may.  dgate / dup may be gate / up / dy themselves
+ * with the same stride.  N % 8 == 0, 16-byte aligned pointers. */
+int bf_swiglu_bwd(const void* d_gate, int64_t gate_row_stride, const void* d_up, int64_t up_row_stride, const void* d_dy,
+                  int64_t dy_row_stride, void* d_dgate, int64_t dgate_row_stride, void* d_dup, int64_t dup_row_stride,
+                  int dtype, int64_t rows, int N, void* stream);
 
 /* ---- one generation step's epilogue -------------------------------------------------------------------------------
  * What sample_generate does between the predictive statistics of a step and the next decode forward, in one launch (one
