@@ -1,21 +1,17 @@
 // bf_attention.hip — softmax(Q K^T * scale + mask) V for the attention block that sits between the Bayesian
 // query/key/value projections and the Bayesian output projection of the transformers the reference converts
-// (HF BertSelfAttention around bnn.Linear.forward, /root/reference/bayeformers/nn/layers/linear.py:83-104; the
-// reference itself runs whatever the wrapped model runs).  Inference-time forward only.
+// (HF BertSelfAttention around bnn.Linear.forward; the reference itself runs whatever the wrapped model runs).
 //
-// Shape of the kernel (head size 64, keys/queries in tiles of 128, bf16 or fp16):
+// Shape of the kernel (head size 64, keys/queries in tiles of 128, bf16 or fp16; fragment layouts and LDS images:
+// bf_attention_tiles.h):
 //   * one 256-thread workgroup per (128 queries, head, sequence); each of its 4 waves owns 32 queries;
-//   * a 128-key tile of K ([key][d], 16-byte chunks XOR-swizzled by key & 7) and of V ([key][d], 160-byte rows) is
-//     staged in LDS with 16-byte accesses;
-//   * S^T = K Q^T on v_mfma_f32_16x16x32 with K as the row operand: a lane ends up with 4 consecutive keys of ONE query
-//     per 16-key block, so the softmax statistics of a query are 32 in-lane values + two cross-lane steps, and the
-//     probabilities of two neighbouring key blocks are already the 8-element column operand of the P V product —
-//     the k index of that product is a fixed permutation of the keys, applied identically to the V^T fragments, which
-//     come straight out of the row-major V tile through gfx950's LDS transpose read (ds_read_b64_tr_b16);
-//   * O^T = V^T P^T accumulates in fp32; longer sequences walk the key tiles with the usual running max / sum rescale;
+//   * a 128-key tile of K (swizzled image) and of V (padded image) is staged in LDS with 16-byte accesses;
+//   * S^T = K Q^T with K as the row operand, the softmax statistics of a query in-lane + two cross-lane steps, the
+//     probabilities of two neighbouring key blocks the column operand of O^T = V^T P^T, V^T through the LDS transpose read;
+//   * O^T accumulates in fp32; longer sequences walk the key tiles with the usual running max / sum rescale;
 //   * a lane owns 4 consecutive features of one query at the end: 8-byte stores into the [B, T, H, 64] output.
 // Algorithmic HBM bytes: (3 reads + 1 write) * B*T*H*64 * 2 B.
-#include "bf_common.h"
+#include "bf_attention_tiles.h"
 #include "bf_philox.h"
 
 namespace {
@@ -26,37 +22,11 @@ namespace {
 template <typename V>
 __device__ __forceinline__ void attn_st8(V* p, V v) { *p = v; }
 
-
 constexpr int HD = 64;          // head size
 constexpr int TQ = 128;         // queries per workgroup
 constexpr int TKEY = 128;       // keys per tile
-constexpr int K_ROW = HD * 2;   // 128 B
-constexpr int V_ROW = HD * 2 + 32;     // 160 B: the 8 key rows a 32-lane half of a transpose-read touches tile one bank row
-constexpr int K_BYTES = TKEY * K_ROW;  // 16 KiB
-constexpr int V_BYTES = TKEY * V_ROW;  // 20 KiB
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<__bf16> {
-    using frag = bf16x8_t;
-    using half4 = bf16x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <>
-struct Mfma<_Float16> {
-    using frag = f16x8_t;
-    using half4 = f16x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
+constexpr int K_BYTES = TKEY * Rows<HD>::SWZ;  // 16 KiB
+constexpr int V_BYTES = TKEY * Rows<HD>::PAD;  // 20 KiB
 
 struct AttnParams {
     const void* q;
@@ -126,18 +96,18 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 
     for (int key0 = 0; key0 < p.T; key0 += TKEY) {
         if (key0) __syncthreads();  // the previous tile's fragment reads are done
-        // stage K ([key][d], chunk ^= key & 7) and V ([key][d], 160-byte rows), 16 bytes per lane
+        // stage K (swizzled) and V (padded), 16 bytes per lane; not two stage<> calls: the assembly of those is longer
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = tid + 256 * i, row = c >> 3, c8 = c & 7;
             const f32x4_t kv = *reinterpret_cast<const f32x4_t*>(kb + (long long)(key0 + row) * p.tok_stride + c8 * 8);
-            *reinterpret_cast<f32x4_t*>(ks + row * K_ROW + ((c8 ^ (row & 7)) << 4)) = kv;
+            *reinterpret_cast<f32x4_t*>(ks + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = kv;
             const f32x4_t vv = *reinterpret_cast<const f32x4_t*>(vb + (long long)(key0 + row) * p.tok_stride + c8 * 8);
-            *reinterpret_cast<f32x4_t*>(vs + row * V_ROW + (c8 << 4)) = vv;
+            *reinterpret_cast<f32x4_t*>(vs + row * Rows<HD>::PAD + (c8 << 4)) = vv;
         }
         if (mask && tid < TKEY / 4)
             *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
-                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * 1.4426950408889634f;
+                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
         __syncthreads();
 
         // One block of 16 queries at a time (keeps the live scores at 32 registers, 4 waves per SIMD fit).
@@ -150,11 +120,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
             for (int kbk = 0; kbk < 8; ++kbk) {
                 s[kbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int dh = 0; dh < 2; ++dh) {
-                    const int row = kbk * 16 + li;
-                    const frag kf = *reinterpret_cast<const frag*>(ks + row * K_ROW + (((dh * 4 + lg) ^ (row & 7)) << 4));
-                    s[kbk] = Mfma<T>::run(kf, qf[qi][dh], s[kbk]);
-                }
+                for (int dh = 0; dh < 2; ++dh) s[kbk] = Mfma<T>::run(row_frag<T, HD>(ks, kbk, dh, li, lg), qf[qi][dh], s[kbk]);
             }
             // scale (+ additive key mask: a lane's 4 keys of a block are one 16-byte LDS read), in log2 units
             float mx = -INFINITY;
@@ -208,23 +174,12 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
             }
 #pragma unroll
             for (int db = 0; db < 4; ++db) o[qi][db] *= corr;
-            // O^T[d][query] += V^T[d][k] P^T[k][query], k walking 32 keys at a time in the order
-            // (group lg, slot j):  j < 4 -> key (2c)*16 + 4*lg + j,  j >= 4 -> key (2c+1)*16 + 4*lg + (j - 4)
+            // O^T[d][query] += V^T[d][k] P^T[k][query], k walking 32 keys at a time in the order pack2 / tr_frag share
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const f32x8_t pv = {s[2 * c][0],     s[2 * c][1],     s[2 * c][2],     s[2 * c][3],
-                                    s[2 * c + 1][0], s[2 * c + 1][1], s[2 * c + 1][2], s[2 * c + 1][3]};
-                const frag pf = __builtin_convertvector(pv, frag);
+                const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
 #pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    // V^T fragment by the LDS transpose read: the 16 lanes of a group point at the [4 keys][16 d]
-                    // block (lane -> key li >> 2, features 4 * (li & 3) ..), each gets its column = 4 keys of feature li
-                    const char* vblk = vs + (lg * 4 + (li >> 2)) * V_ROW + (db * 16 + (li & 3) * 4) * 2;
-                    const s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vblk + (2 * c) * 16 * V_ROW));
-                    const s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(vblk + (2 * c + 1) * 16 * V_ROW));
-                    const s16x8_t v01 = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    o[qi][db] = Mfma<T>::run(__builtin_bit_cast(frag, v01), pf, o[qi][db]);
-                }
+                for (int db = 0; db < 4; ++db) o[qi][db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[qi][db]);
             }
         }
     }
@@ -258,6 +213,12 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
     }
 }
 
+// ROWS: one workgroup per (sequence, head)
+template <typename T, bool DROP, bool ROWS>
+void launch(const AttnParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL((attention_fwd_kernel<T, DROP, ROWS>), dim3(ROWS ? 1 : p.T / TQ, p.H, p.B), dim3(256), 0, stream, p);
+}
+
 }  // namespace
 
 int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
@@ -284,31 +245,26 @@ int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, c
     p.B = B;
     p.T = T;
     p.H = H;
-    p.scale_log2e = scaling * 1.4426950408889634f;
-    const dim3 grid(T / TQ, H, B);
+    p.scale_log2e = scaling * LOG2E;
     p.keep_bits = nullptr;
     p.drop = bf_dropout_t{0, 0, 0, 0, 0, 1.0f, 0, 0, nullptr};
     p.q_rows = q_rows;
+    const bool bf16 = dtype == BF_DT_BF16;
     if (q_rows) {
         if (q_rows < 1 || q_rows > 16) BF_FAIL("bf_attention_fwd_rows: q_rows=%d (1 .. 16)", q_rows);
         if (d_lse || (drop && drop->thresh)) BF_FAIL("bf_attention_fwd_rows: inference only (no log-sum-exp rows, no dropout)");
-        const dim3 rgrid(1, H, B);
-        if (dtype == BF_DT_BF16) hipLaunchKernelGGL((attention_fwd_kernel<__bf16, false, true>), rgrid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((attention_fwd_kernel<_Float16, false, true>), rgrid, dim3(256), 0, stream, p);
-        BF_HIP_CHECK(hipGetLastError());
-        return 0;
-    }
-    if (drop && drop->thresh) {
+        if (bf16) launch<__bf16, false, true>(p, stream);
+        else launch<_Float16, false, true>(p, stream);
+    } else if (drop && drop->thresh) {
         if (d_keep_bits && ((uintptr_t)d_keep_bits & 3)) BF_FAIL("bf_attention_fwd: keep bits must be 4-byte aligned");
         p.drop = *drop;
         p.keep_bits = d_keep_bits;
-        if (dtype == BF_DT_BF16) hipLaunchKernelGGL((attention_fwd_kernel<__bf16, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((attention_fwd_kernel<_Float16, true>), grid, dim3(256), 0, stream, p);
-        BF_HIP_CHECK(hipGetLastError());
-        return 0;
+        if (bf16) launch<__bf16, true, false>(p, stream);
+        else launch<_Float16, true, false>(p, stream);
+    } else {
+        if (bf16) launch<__bf16, false, false>(p, stream);
+        else launch<_Float16, false, false>(p, stream);
     }
-    if (dtype == BF_DT_BF16) hipLaunchKernelGGL(attention_fwd_kernel<__bf16>, grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(attention_fwd_kernel<_Float16>, grid, dim3(256), 0, stream, p);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }

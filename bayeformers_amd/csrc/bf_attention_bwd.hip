@@ -1,55 +1,28 @@
-// bf_attention_bwd.hip — backward of bf_attention_fwd (csrc/bf_attention.hip): autograd through the attention
-// block between the Bayesian query/key/value projections and the Bayesian output projection in the reference's
-// training loop (/root/reference/examples/bert_glue.py:239, `loss.backward()` through HF BertSelfAttention).
+// bf_attention_bwd.hip — backward of bf_attention_fwd (bf_attention.hip): autograd through the attention block between the
+// Bayesian query/key/value projections and the Bayesian output projection in the reference's training loop
+// (examples/bert_glue.py, `loss.backward()` through HF BertSelfAttention).
 //
 // With P = softmax(scale Q K^T + mask) (recomputed from Q, K and the log-sum-exp rows the forward saved),
 // delta_q = sum_d dO[q][d] O[q][d] and dS = P o (dO V^T - delta):
 //     dV = P^T dO,   dK = scale dS^T Q,   dQ = scale dS K.
-// Two kernels, no atomics (deterministic), head size 64, queries / keys in tiles of 128, bf16 or fp16:
-//   * dq kernel — one workgroup per (128 queries, head, sequence), each of its 4 waves owns 32 queries and walks the
-//     key tiles.  Same orientation as the forward: S^T = K Q^T and dP^T = V dO^T on v_mfma_f32_16x16x32 with the key
-//     operand as rows, so a lane holds 4 consecutive keys of ONE query per 16-key block; dS^T of two neighbouring
-//     blocks is the column operand of dQ^T = K^T dS^T, and the K^T fragments come out of a row-major K tile through the
-//     LDS transpose read (ds_read_b64_tr_b16), exactly as V^T does in the forward.  Also leaves delta for the second kernel.
-//   * dk/dv kernel — one workgroup per (128 keys, head, sequence), each of its 8 waves owns 16 keys and walks the query tiles
-//     with the roles swapped: S = Q K^T and dP = dO V^T with the QUERY operand as rows, so a lane holds 4 consecutive
-//     queries of one key; P and dS are the column operands of dV^T = dO^T P and dK^T = Q^T dS, with dO^T / Q^T through
-//     the transpose read.
+// Two kernels, no atomics (deterministic), head size 64, queries / keys in tiles of 128, bf16 or fp16; the fragment layouts
+// and LDS images are the forward's (bf_attention_tiles.h):
+//   * dq kernel — one workgroup per (128 queries, head, sequence), 4 waves x 32 queries, walking the key tiles in the
+//     forward's orientation: S^T = K Q^T and dP^T = V dO^T with the keys as rows, dS^T the column operand of
+//     dQ^T = K^T dS^T, K^T through the transpose read.  Also leaves delta for the second kernel.
+//   * dk/dv kernel — one workgroup per (128 keys, head, sequence), 8 waves x 16 keys, walking the query tiles with the roles
+//     swapped: S = Q K^T and dP = dO V^T with the QUERIES as rows; P and dS are the column operands of dV^T = dO^T P and
+//     dK^T = Q^T dS, dO^T / Q^T through the transpose read.
 // Algorithmic HBM bytes: dq kernel 5 reads (Q, K, V, O, dO) + 1 write; dk/dv kernel 4 reads + 2 writes, x B*T*H*64*2 B.
-#include "bf_common.h"
+#include "bf_attention_tiles.h"
 #include "bf_device.h"
 
 namespace {
 
 constexpr int HD = 64;
-constexpr int TT = 128;                 // queries / keys per tile
-constexpr int S_ROW = HD * 2;           // 128 B: swizzled image for direct 16-byte fragment reads (chunk ^= row & 7)
-constexpr int P_ROW = HD * 2 + 32;      // 160 B: padded image for the transpose reads (see bf_attention.hip)
-constexpr int S_BYTES = TT * S_ROW;     // 16 KiB
-constexpr int P_BYTES = TT * P_ROW;     // 20 KiB
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<__bf16> {
-    using frag = bf16x8_t;
-    using half4 = bf16x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-};
-template <>
-struct Mfma<_Float16> {
-    using frag = f16x8_t;
-    using half4 = f16x4_t;
-    static __device__ __forceinline__ f32x4_t run(frag a, frag b, f32x4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-};
+constexpr int TT = 128;                      // queries / keys per tile
+constexpr int S_BYTES = TT * Rows<HD>::SWZ;  // 16 KiB: a swizzled tile
+constexpr int P_BYTES = TT * Rows<HD>::PAD;  // 20 KiB: a padded tile
 
 struct BwdParams {
     const void* q;
@@ -68,8 +41,8 @@ struct BwdParams {
     int B, T, H;
     float scale, scale_log2e;
     // attention_probs_dropout (the forward's DROP instantiation): the keep decisions the forward stored, one bit per
-    // probability — word (b, h, q, tile, lg), bit c * 8 + e * 4 + j <-> key tile * 128 + (2c + e) * 16 + 4 lg + j — and the
-    // 1 / (1 - p) factor.  NULL: no dropout.  With P~ = P o keep / (1 - p):  dV = P~^T dO,  dS = P o (keep / (1 - p) o dP~ - delta).
+    // probability in AttnParams' layout (bf_attention.hip), and the 1 / (1 - p) factor.  NULL: no dropout.
+    // With P~ = P o keep / (1 - p):  dV = P~^T dO,  dS = P o (keep / (1 - p) o dP~ - delta).
     const uint32_t* keep_bits;
     float inv_keep;
     // one-tile kernel only (round 5): per (sequence, head) the sums over the 128 tokens of dq, dk, dv AS STORED —
@@ -77,42 +50,6 @@ struct BwdParams {
     // query / key / value layers take as their bias gradient (bf_linear_bwd: d_dy_colsum).  NULL: not wanted.
     float* cs_partial;
 };
-
-// stage a [128][64] tile (rows `row0`.. of a [tokens][stride] tensor) into the swizzled and / or the padded image
-template <typename T, int NT = 256>
-__device__ __forceinline__ void stage_tile(const T* base, long long stride, int row0, char* swz, char* pad, int tid) {
-#pragma unroll
-    for (int i = 0; i < 1024 / NT; ++i) {
-        const int c = tid + NT * i, row = c >> 3, c8 = c & 7;
-        const f32x4_t x = *reinterpret_cast<const f32x4_t*>(base + (long long)(row0 + row) * stride + c8 * 8);
-        if (swz) *reinterpret_cast<f32x4_t*>(swz + row * S_ROW + ((c8 ^ (row & 7)) << 4)) = x;
-        if (pad) *reinterpret_cast<f32x4_t*>(pad + row * P_ROW + (c8 << 4)) = x;
-    }
-}
-
-// row-operand fragment (16 rows x 32 features) of block `blk` of a swizzled tile: lane (row li, k group lg)
-template <typename T>
-__device__ __forceinline__ typename Mfma<T>::frag row_frag(const char* swz, int blk, int dh, int li, int lg) {
-    const int row = blk * 16 + li;
-    return *reinterpret_cast<const typename Mfma<T>::frag*>(swz + row * S_ROW + (((dh * 4 + lg) ^ (row & 7)) << 4));
-}
-
-// transposed fragment: rows = features db*16 + li, k = the 32 tile rows {(2c)*16 + 4 lg + 0..3, (2c+1)*16 + 4 lg + 0..3}
-// of a padded tile, by two LDS transpose reads (the 16 lanes of a group point at a [4 rows][16 features] block)
-template <typename T, int ROW = P_ROW>
-__device__ __forceinline__ typename Mfma<T>::frag tr_frag(const char* pad, int c, int db, int li, int lg) {
-    const char* blk = pad + (lg * 4 + (li >> 2)) * ROW + (db * 16 + (li & 3) * 4) * 2;
-    const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c) * 16 * ROW));
-    const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c + 1) * 16 * ROW));
-    const s16x8_t ab = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(typename Mfma<T>::frag, ab);
-}
-
-template <typename T>
-__device__ __forceinline__ typename Mfma<T>::frag pack2(const f32x4_t a, const f32x4_t b) {
-    const f32x8_t v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_convertvector(v, typename Mfma<T>::frag);
-}
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
 template <typename T, bool DROP = false>
@@ -167,11 +104,11 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
 
     for (int key0 = 0; key0 < p.T; key0 += TT) {
         if (key0) __syncthreads();
-        stage_tile<T>(kb, p.tok_stride, key0, ks, kp, tid);
-        stage_tile<T>(vb, p.tok_stride, key0, vs, nullptr, tid);
+        stage<T, HD, TT, 256>(kb, p.tok_stride, key0, ks, kp, tid);
+        stage<T, HD, TT, 256>(vb, p.tok_stride, key0, vs, nullptr, tid);
         if (mask && tid < TT / 4)
             *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
-                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * 1.4426950408889634f;
+                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
         __syncthreads();
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi) {
@@ -187,8 +124,8 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
                 s[kbk] = dp[kbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int dh = 0; dh < 2; ++dh) {
-                    s[kbk] = Mfma<T>::run(row_frag<T>(ks, kbk, dh, li, lg), qf[qi][dh], s[kbk]);
-                    dp[kbk] = Mfma<T>::run(row_frag<T>(vs, kbk, dh, li, lg), dof[qi][dh], dp[kbk]);
+                    s[kbk] = Mfma<T>::run(row_frag<T, HD>(ks, kbk, dh, li, lg), qf[qi][dh], s[kbk]);
+                    dp[kbk] = Mfma<T>::run(row_frag<T, HD>(vs, kbk, dh, li, lg), dof[qi][dh], dp[kbk]);
                 }
             }
 #pragma unroll
@@ -211,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
             for (int c = 0; c < 4; ++c) {
                 const frag dsf = pack2<T>(s[2 * c], s[2 * c + 1]);
 #pragma unroll
-                for (int db = 0; db < 4; ++db) dq[qi][db] = Mfma<T>::run(tr_frag<T>(kp, c, db, li, lg), dsf, dq[qi][db]);
+                for (int db = 0; db < 4; ++db) dq[qi][db] = Mfma<T>::run(tr_frag<T, HD>(kp, c, db, li, lg), dsf, dq[qi][db]);
             }
         }
     }
@@ -265,15 +202,15 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
         kf[dh] = *reinterpret_cast<const frag*>(kb + key * p.tok_stride + dh * 32 + lg * 8);
         vf[dh] = *reinterpret_cast<const frag*>(vb + key * p.tok_stride + dh * 32 + lg * 8);
     }
-    const float mk = mask ? mask[(long long)b * p.T + key] * 1.4426950408889634f : 0.f;
+    const float mk = mask ? mask[(long long)b * p.T + key] * LOG2E : 0.f;
     f32x4_t dk[4], dv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     for (int q0 = 0; q0 < p.T; q0 += TT) {
         if (q0) __syncthreads();
-        stage_tile<T, 512>(qb, p.tok_stride, q0, qs, qp, tid);
-        stage_tile<T, 512>(dob, ostride, q0, dos, dop, tid);
+        stage<T, HD, TT, 512>(qb, p.tok_stride, q0, qs, qp, tid);
+        stage<T, HD, TT, 512>(dob, ostride, q0, dos, dop, tid);
         if (tid < TT / 4) {
             *reinterpret_cast<f32x4_t*>(lse_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(lse_g + q0 + tid * 4);
             *reinterpret_cast<f32x4_t*>(del_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(del_g + q0 + tid * 4);
@@ -288,8 +225,8 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
             s[qbk] = dp[qbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int dh = 0; dh < 2; ++dh) {
-                s[qbk] = Mfma<T>::run(row_frag<T>(qs, qbk, dh, li, lg), kf[dh], s[qbk]);
-                dp[qbk] = Mfma<T>::run(row_frag<T>(dos, qbk, dh, li, lg), vf[dh], dp[qbk]);
+                s[qbk] = Mfma<T>::run(row_frag<T, HD>(qs, qbk, dh, li, lg), kf[dh], s[qbk]);
+                dp[qbk] = Mfma<T>::run(row_frag<T, HD>(dos, qbk, dh, li, lg), vf[dh], dp[qbk]);
             }
         }
 #pragma unroll
@@ -317,8 +254,8 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
             const frag dsf = pack2<T>(dp[2 * c], dp[2 * c + 1]);
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
-                dv[db] = Mfma<T>::run(tr_frag<T>(dop, c, db, li, lg), pf, dv[db]);
-                dk[db] = Mfma<T>::run(tr_frag<T>(qp, c, db, li, lg), dsf, dk[db]);
+                dv[db] = Mfma<T>::run(tr_frag<T, HD>(dop, c, db, li, lg), pf, dv[db]);
+                dk[db] = Mfma<T>::run(tr_frag<T, HD>(qp, c, db, li, lg), dsf, dk[db]);
             }
         }
     }
@@ -380,10 +317,10 @@ __global__ __launch_bounds__(512, 4) void attention_bwd_tile_kernel(const BwdPar
         vf[dh] = *reinterpret_cast<const frag*>(vb + row * p.tok_stride + dh * 32 + lg * 8);
         of[dh] = *reinterpret_cast<const frag*>(ob + row * ostride + dh * 32 + lg * 8);
     }
-    const float mk = mask ? mask[(long long)b * p.T + row] * 1.4426950408889634f : 0.f;
+    const float mk = mask ? mask[(long long)b * p.T + row] * LOG2E : 0.f;
 
-    stage_tile<T, 512>(qb, p.tok_stride, 0, qs, qp, tid);
-    stage_tile<T, 512>(dob, ostride, 0, dos, dop, tid);
+    stage<T, HD, TT, 512>(qb, p.tok_stride, 0, qs, qp, tid);
+    stage<T, HD, TT, 512>(dob, ostride, 0, dos, dop, tid);
     if (tid < TT / 4)
         *reinterpret_cast<f32x4_t*>(lse_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(lse_g + tid * 4);
     if constexpr (DROP) keep_s[tid] = p.keep_bits[(((long long)b * p.H + h) * p.T) * 4 + tid];  // 512 words = 128 x 4
@@ -393,7 +330,7 @@ __global__ __launch_bounds__(512, 4) void attention_bwd_tile_kernel(const BwdPar
         float part = 0.f;
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh) {
-            const frag df = row_frag<T>(dos, wid, dh, li, lg);
+            const frag df = row_frag<T, HD>(dos, wid, dh, li, lg);
 #pragma unroll
             for (int e = 0; e < 8; ++e) part = fmaf((float)df[e], (float)of[dh][e], part);
         }
@@ -411,14 +348,14 @@ __global__ __launch_bounds__(512, 4) void attention_bwd_tile_kernel(const BwdPar
         s[qbk] = dp[qbk] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh) {
-            s[qbk] = Mfma<T>::run(row_frag<T>(qs, qbk, dh, li, lg), kf[dh], s[qbk]);
-            dp[qbk] = Mfma<T>::run(row_frag<T>(dos, qbk, dh, li, lg), vf[dh], dp[qbk]);
+            s[qbk] = Mfma<T>::run(row_frag<T, HD>(qs, qbk, dh, li, lg), kf[dh], s[qbk]);
+            dp[qbk] = Mfma<T>::run(row_frag<T, HD>(dos, qbk, dh, li, lg), vf[dh], dp[qbk]);
         }
         if (qbk & 1) __builtin_amdgcn_sched_barrier(0);  // (keeps the fragment reads of later blocks from piling up in registers)
     }
     __syncthreads();  // delta of all 128 queries is in LDS; the swizzled Q and dO images are dead
 #pragma unroll
-    for (int dh = 0; dh < 2; ++dh) *reinterpret_cast<frag*>(kp + row * P_ROW + (dh * 32 + lg * 8) * 2) = kf[dh];
+    for (int dh = 0; dh < 2; ++dh) *reinterpret_cast<frag*>(kp + row * Rows<HD>::PAD + (dh * 32 + lg * 8) * 2) = kf[dh];
     // P and dS leave the fp32 accumulators as 16-bit column operands right away (half the registers through the dV /
     // dK products: no spills at 128 VGPRs); pf[c] / dsf[c] = query blocks 2c, 2c + 1
     frag pf[4], dsf[4];
@@ -456,8 +393,8 @@ __global__ __launch_bounds__(512, 4) void attention_bwd_tile_kernel(const BwdPar
     for (int c = 0; c < 4; ++c) {
 #pragma unroll
         for (int db = 0; db < 4; ++db) {
-            dv[db] = Mfma<T>::run(tr_frag<T>(dop, c, db, li, lg), pf[c], dv[db]);
-            dk[db] = Mfma<T>::run(tr_frag<T>(qp, c, db, li, lg), dsf[c], dk[db]);
+            dv[db] = Mfma<T>::run(tr_frag<T, HD>(dop, c, db, li, lg), pf[c], dv[db]);
+            dk[db] = Mfma<T>::run(tr_frag<T, HD>(qp, c, db, li, lg), dsf[c], dk[db]);
         }
     }
     T* dkb = reinterpret_cast<T*>(p.dk) + (long long)b * p.T * ostride + hoff;
@@ -503,9 +440,9 @@ __global__ __launch_bounds__(512, 4) void attention_bwd_tile_kernel(const BwdPar
     for (int j = 0; j < 4; ++j) dq[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        const frag dsf = tr_frag<T, DS_ROW>(dst, c, wid, li, lg);
+        const frag dsf = tr_frag_row<T, DS_ROW>(dst, c, wid, li, lg);
 #pragma unroll
-        for (int db = 0; db < 4; ++db) dq[db] = Mfma<T>::run(tr_frag<T>(kp, c, db, li, lg), dsf, dq[db]);
+        for (int db = 0; db < 4; ++db) dq[db] = Mfma<T>::run(tr_frag<T, HD>(kp, c, db, li, lg), dsf, dq[db]);
     }
     T* dqb = reinterpret_cast<T*>(p.dq) + (long long)b * p.T * ostride + hoff;
     half4 hq[4];
@@ -534,6 +471,18 @@ __global__ __launch_bounds__(64) void attention_colsum_finish_kernel(const float
     for (int i = 0; i < seq_per_sample; ++i)
         acc += partial[(((long long)s * seq_per_sample + i) * H + h) * 3 * HD + t * HD + d];
     out[((long long)t * S + s) * H * HD + h * HD + d] = acc;
+}
+
+// one tile (T = 128): dQ, dK, dV in one launch; else the dq kernel, then the dk/dv kernel that reads its delta
+template <typename T, bool DROP>
+void launch(const BwdParams& p, bool one_tile, hipStream_t stream) {
+    const dim3 grid(p.T / TT, p.H, p.B);
+    if (one_tile) {
+        hipLaunchKernelGGL((attention_bwd_tile_kernel<T, DROP>), grid, dim3(512), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL((attention_bwd_dq_kernel<T, DROP>), grid, dim3(256), 0, stream, p);
+        hipLaunchKernelGGL((attention_bwd_dkv_kernel<T, DROP>), grid, dim3(512), 0, stream, p);
+    }
 }
 
 }  // namespace
@@ -574,44 +523,21 @@ int bf_launch_attention_bwd(const void* d_q, const void* d_k, const void* d_v, c
     p.T = T;
     p.H = H;
     p.scale = scaling;
-    p.scale_log2e = scaling * 1.4426950408889634f;
+    p.scale_log2e = scaling * LOG2E;
     p.keep_bits = d_keep_bits;
     p.inv_keep = inv_keep;
     p.cs_partial = d_colsum ? d_cs_partial : nullptr;
-    const dim3 grid(T / TT, H, B);
-    auto finish = [&]() -> int {
-        if (d_colsum)
-            hipLaunchKernelGGL(attention_colsum_finish_kernel, dim3(3 * H, samples), dim3(64), 0, stream, d_cs_partial, B / samples,
-                               H, samples, d_colsum);
-        BF_HIP_CHECK(hipGetLastError());
-        return 0;
-    };
-    if (d_keep_bits) {
-        if ((uintptr_t)d_keep_bits & 3) BF_FAIL("bf_attention_bwd: keep bits must be 4-byte aligned");
-        if (T == TT) {
-            if (dtype == BF_DT_BF16) hipLaunchKernelGGL((attention_bwd_tile_kernel<__bf16, true>), grid, dim3(512), 0, stream, p);
-            else hipLaunchKernelGGL((attention_bwd_tile_kernel<_Float16, true>), grid, dim3(512), 0, stream, p);
-        } else if (dtype == BF_DT_BF16) {
-            hipLaunchKernelGGL((attention_bwd_dq_kernel<__bf16, true>), grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL((attention_bwd_dkv_kernel<__bf16, true>), grid, dim3(512), 0, stream, p);
-        } else {
-            hipLaunchKernelGGL((attention_bwd_dq_kernel<_Float16, true>), grid, dim3(256), 0, stream, p);
-            hipLaunchKernelGGL((attention_bwd_dkv_kernel<_Float16, true>), grid, dim3(512), 0, stream, p);
-        }
-        return finish();
-    }
-    if (T == TT) {  // one tile: dQ, dK, dV in one launch
-        if (dtype == BF_DT_BF16) hipLaunchKernelGGL(attention_bwd_tile_kernel<__bf16>, grid, dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL(attention_bwd_tile_kernel<_Float16>, grid, dim3(512), 0, stream, p);
-        return finish();
-    }
+    if (d_keep_bits && ((uintptr_t)d_keep_bits & 3)) BF_FAIL("bf_attention_bwd: keep bits must be 4-byte aligned");
     if (dtype == BF_DT_BF16) {
-        hipLaunchKernelGGL(attention_bwd_dq_kernel<__bf16>, grid, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(attention_bwd_dkv_kernel<__bf16>, grid, dim3(512), 0, stream, p);
+        if (d_keep_bits) launch<__bf16, true>(p, T == TT, stream);
+        else launch<__bf16, false>(p, T == TT, stream);
     } else {
-        hipLaunchKernelGGL(attention_bwd_dq_kernel<_Float16>, grid, dim3(256), 0, stream, p);
-        hipLaunchKernelGGL(attention_bwd_dkv_kernel<_Float16>, grid, dim3(512), 0, stream, p);
+        if (d_keep_bits) launch<_Float16, true>(p, T == TT, stream);
+        else launch<_Float16, false>(p, T == TT, stream);
     }
+    if (d_colsum)
+        hipLaunchKernelGGL(attention_colsum_finish_kernel, dim3(3 * H, samples), dim3(64), 0, stream, d_cs_partial, B / samples,
+                           H, samples, d_colsum);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -5,7 +5,7 @@
 //   out[b,t,h,:] = sum_{j <= t (causal), key j visible in b} softmax_j(scale q[b,t,h] . k[b,j,g] + mask[b,j]) v[b,j,g,:],
 //   g = h / (H / Hkv).
 //
-// Siblings of bf_attention.hip / bf_attention_bwd.hip (same fragment layouts, same online softmax, same LDS images), made
+// Siblings of bf_attention.hip / bf_attention_bwd.hip (same online softmax; layouts and LDS images: bf_attention_tiles.h), made
 // generic over the head size (64, 128), the key / query tile of the inner loop, causality and the K/V head group, and
 // reading q, k and v through their own (batch, head, token) strides.  The BERT entries keep their own kernels: the new
 // entry hands the case they cover (non-causal, one K/V head per query head, head size 64, packed heads) to them.

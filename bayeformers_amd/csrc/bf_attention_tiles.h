@@ -1,5 +1,14 @@
-// bf_attention_tiles.h — MFMA fragment layouts and LDS images shared by the attention kernels of bf_attention_gqa.hip
-// and bf_attention_decode.hip (bf16 / fp16 operands, mfma_f32_16x16x32, head size 64 or 128).
+// bf_attention_tiles.h — MFMA fragment layouts and LDS images shared by the attention kernels of bf_attention.hip,
+// bf_attention_bwd.hip, bf_attention_gqa.hip and bf_attention_decode.hip (bf16 / fp16 operands, mfma_f32_16x16x32, head
+// size 64 or 128).  The contract all of them lean on:
+//   * lane (li, lg) = (lane & 15, lane >> 4).  As an operand it holds 8 consecutive features (k group lg) of row / column li.
+//     S^T = K Q^T with the keys as rows leaves it 4 consecutive keys, blk*16 + 4 lg + 0..3, of ONE query li per 16-key block:
+//     a query's softmax statistics are in-lane values + two cross-lane steps (the dk/dv kernels swap the roles);
+//   * two neighbouring blocks are then the 8-element column operand of the next product as they stand (pack2), its k index
+//     a fixed permutation of the keys: (2c)*16 + 4 lg + 0..3, then (2c + 1)*16 + 4 lg + 0..3.  tr_frag(c) applies the same
+//     order to the other operand, straight out of a row-major image through gfx950's LDS transpose read (ds_read_b64_tr_b16);
+//   * the dropout keep-bit layout (AttnParams, bf_attention.hip: bit c*8 + e*4 + j of word lg) is that order written
+//     down, and the backward kernels read the bits by it.  Changing the order changes all of these at once.
 #pragma once
 #include "bf_common.h"
 
@@ -31,7 +40,7 @@ struct Mfma<_Float16> {
 };
 
 // Row stride of the LDS images: swizzled (16-byte chunk ^= row & 7, for direct row-operand reads) and padded (+32 B, for
-// the transpose reads)
+// the transpose reads: the 8 rows a 32-lane half of one touches tile one bank row)
 template <int HD>
 struct Rows {
     static constexpr int SWZ = HD * 2;
@@ -59,15 +68,22 @@ __device__ __forceinline__ typename Mfma<T>::frag row_frag(const char* swz, int 
     return *reinterpret_cast<const typename Mfma<T>::frag*>(swz + row * Rows<HD>::SWZ + (((dh * 4 + lg) ^ (row & 7)) << 4));
 }
 
-// transposed fragment: rows = features db*16 + li, k = the 32 image rows {(2c)*16 + 4 lg + 0..3, (2c+1)*16 + 4 lg + 0..3}
-template <typename T, int HD>
-__device__ __forceinline__ typename Mfma<T>::frag tr_frag(const char* pad, int c, int db, int li, int lg) {
-    constexpr int ROW = Rows<HD>::PAD;
+// transposed fragment of a row-major image with rows of ROW bytes: rows = features db*16 + li, k = the 32 image rows
+// {(2c)*16 + 4 lg + 0..3, (2c+1)*16 + 4 lg + 0..3}, by two LDS transpose reads (the 16 lanes of a group point at a
+// [4 rows][16 features] block: lane -> row li >> 2, features 4 * (li & 3) .., each gets its column = 4 rows of feature li)
+template <typename T, int ROW>
+__device__ __forceinline__ typename Mfma<T>::frag tr_frag_row(const char* pad, int c, int db, int li, int lg) {
     const char* blk = pad + (lg * 4 + (li >> 2)) * ROW + (db * 16 + (li & 3) * 4) * 2;
     const s16x4_t a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c) * 16 * ROW));
     const s16x4_t b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + (2 * c + 1) * 16 * ROW));
     const s16x8_t ab = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     return __builtin_bit_cast(typename Mfma<T>::frag, ab);
+}
+
+// ... of a padded image of head size HD
+template <typename T, int HD>
+__device__ __forceinline__ typename Mfma<T>::frag tr_frag(const char* pad, int c, int db, int li, int lg) {
+    return tr_frag_row<T, Rows<HD>::PAD>(pad, c, db, li, lg);
 }
 
 template <typename T>
