@@ -1,4 +1,8 @@
-// bf_api.hip — the extern "C" surface declared in include/bayeformers_amd.h.
+// bf_api.hip — the part of the extern "C" surface (include/bayeformers_amd.h) that belongs to the library itself: the error
+// string, the version, the sample and stale counters, the device info, the profiler, the probe kernel and the host twins of
+// the generators; and the entries that time a launch (ProfScope, private to this file) or compose the launchers of several
+// translation units: bf_sample_logprob(_table), the bf_gemm_nt* family, bf_linear_fwd and bf_linear_bwd.  Every other entry
+// is defined in the .hip file that owns its kernels, with its argument checks and the (hipStream_t) cast.
 #include <math.h>
 #include <string.h>
 
@@ -225,17 +229,6 @@ int bf_philox_normal_host(float* out, uint64_t n, uint64_t seed, uint32_t sample
     return 0;
 }
 
-int bf_philox_normal(float* d_out, uint64_t n, int S, uint64_t seed, uint32_t sample_base, uint32_t stream_id,
-                     void* stream) {
-    if (!d_out && n) BF_FAIL("bf_philox_normal: d_out is NULL");
-    return bf_launch_philox_normal(d_out, n, S, seed, sample_base, stream_id, (hipStream_t)stream);
-}
-
-size_t bf_sample_logprob_workspace_bytes(const bf_tensor_t* tensors, int n_tensors, int S) {
-    if (!tensors || n_tensors < 1 || S < 1) return 0;
-    return bf_sample_partials_bytes(tensors, n_tensors, S);
-}
-
 int bf_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, uint64_t seed, uint32_t sample_base,
                       double* d_logprob_out, void* d_workspace, size_t workspace_bytes, void* stream) {
     if (!tensors) BF_FAIL("bf_sample_logprob: tensors is NULL");
@@ -245,27 +238,11 @@ int bf_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, uint64_t
                                     workspace_bytes, (hipStream_t)stream);
 }
 
-size_t bf_sample_table_bytes(const bf_tensor_t* tensors, int n_tensors, uint32_t* total_blocks) {
-    if (!tensors || n_tensors < 1) return 0;
-    return bf_table_blob_bytes(tensors, n_tensors, total_blocks);
-}
-
-int bf_sample_table_build(const bf_tensor_t* tensors, int n_tensors, void* h_blob, size_t blob_bytes,
-                          uint32_t* h_block_begin, int32_t* h_kinds) {
-    if (!tensors || n_tensors < 1) BF_FAIL("bf_sample_table_build: no tensors");
-    return bf_table_build(tensors, n_tensors, h_blob, blob_bytes, h_block_begin, h_kinds);
-}
-
 int bf_sample_logprob_table(const void* d_blob, int n_tensors, uint32_t block_begin, uint32_t block_end, int S,
                             uint64_t seed, uint32_t sample_base, double* d_partials, int prior_kinds, void* stream) {
     ProfScope prof(BF_PROF_SAMPLE, 0.0, (hipStream_t)stream);
     return bf_launch_sample_table(d_blob, n_tensors, block_begin, block_end, S, seed, sample_base, d_partials,
                                   (hipStream_t)stream, prior_kinds);
-}
-
-int bf_reduce_logprob(const double* d_partials, const uint32_t* d_rows, int n_groups, int S, double* d_out,
-                      void* stream) {
-    return bf_launch_reduce_groups(d_partials, d_rows, n_groups, S, d_out, (hipStream_t)stream);
 }
 
 int bf_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
@@ -314,23 +291,6 @@ int bf_gemm_nt_rows(const void* d_x, int x_dtype, int64_t x_sample_stride, int64
     return bf_launch_gemm_nt(d_x, x_dtype, x_sample_stride, d_w, w_dtype, d_bias, d_y, y_dtype, S, M, N, K,
                              (hipStream_t)stream, act, 1, nullptr, x_row_stride, d_workspace, workspace_bytes);
 }
-
-size_t bf_gemm_nt_rows_workspace_bytes(int dtype, int S, int M, int N, int K) {
-    if (S < 1 || M < 1 || N < 1 || K < 1) return 0;
-    return bf_gemm_nt_rows_workspace_impl(dtype, S, M, N, K);
-}
-
-int bf_gemm_nt_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
-                      const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
-                      size_t workspace_bytes, void* stream) {
-    if ((uintptr_t)d_y & 7) BF_FAIL("bf_gemm_nt_skinny: y must be 8-byte aligned");
-    return bf_launch_gemm_skinny(d_x, x_dtype, x_sample_stride, d_w, w_dtype, d_bias, d_y, y_dtype, S, M, N, K, act,
-                                 d_workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-size_t bf_gemm_nt_skinny_workspace_bytes(int S, int M, int N, int K) { return bf_gemm_skinny_workspace_impl(S, M, N, K); }
-
-int bf_gemm_nt_skinny_max_rows(void) { return bf_gemm_skinny_max_rows_impl(); }
 
 // workspace layout of bf_linear_fwd: [W_s : S*N*K compute_dtype][b_s : S*N fp32][log-prob partials]
 static void linear_ws_layout(int S, int N, int K, int has_bias, int compute_dtype, size_t* off_w, size_t* off_b,
@@ -414,186 +374,6 @@ int bf_linear_fwd(const void* d_x, int x_dtype, int64_t x_sample_stride, const b
                              (hipStream_t)stream);
 }
 
-int bf_kl_grad(const bf_tensor_t* tensor, int S, uint64_t seed, uint32_t sample_base, const double* d_g,
-               float* d_dmu, float* d_drho, void* stream) {
-    return bf_launch_kl_grad(tensor, S, seed, sample_base, d_g, d_dmu, d_drho, (hipStream_t)stream);
-}
-
-int bf_embedding_fwd(const int64_t* d_ids, const float* d_mu, const float* d_rho, void* d_out, int out_dtype,
-                     int64_t n_tokens, int64_t tokens_per_sample, int64_t V, int D, uint64_t seed, uint32_t sample_base,
-                     uint32_t stream_id, void* stream) {
-    return bf_launch_embedding_fwd((const long long*)d_ids, d_mu, d_rho, d_out, out_dtype, n_tokens, tokens_per_sample, V,
-                                   D, seed, sample_base, stream_id, (hipStream_t)stream);
-}
-
-int bf_embedding_bwd(const int64_t* d_ids, const void* d_grad, int grad_dtype, const float* d_rho, float* d_dmu,
-                     float* d_drho, int64_t n_tokens, int64_t tokens_per_sample, int64_t V, int D, uint64_t seed,
-                     uint32_t sample_base, uint32_t stream_id, void* stream) {
-    return bf_launch_embedding_bwd((const long long*)d_ids, d_grad, grad_dtype, d_rho, d_dmu, d_drho, n_tokens,
-                                   tokens_per_sample, V, D, seed, sample_base, stream_id, (hipStream_t)stream);
-}
-
-int bf_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, int param_dtype,
-                     void* d_out, int dtype, int64_t rows, int N, float eps, void* stream) {
-    return bf_launch_add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps,
-                                   (hipStream_t)stream);
-}
-
-int bf_add_layernorm_rows(const void* d_x, const void* d_residual, int64_t residual_row_stride, const void* d_gamma,
-                          const void* d_beta, int param_dtype, void* d_out, int dtype, int64_t rows, int N, float eps,
-                          void* stream) {
-    if (!d_residual) BF_FAIL("bf_add_layernorm_rows: d_residual is NULL");
-    if (residual_row_stride < N) BF_FAIL("bf_add_layernorm_rows: residual row stride %lld < N=%d", (long long)residual_row_stride, N);
-    return bf_launch_add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps,
-                                   (hipStream_t)stream, nullptr, residual_row_stride);
-}
-
-int bf_embed_layernorm(const int64_t* d_ids, const int64_t* d_type_ids, const int64_t* d_pos_ids, const void* d_word,
-                       const void* d_type, const void* d_pos, const void* d_gamma, const void* d_beta, int param_dtype,
-                       void* d_out, int dtype, int64_t rows, int N, int seq_len, int64_t pos_rows, int64_t word_rows,
-                       int64_t type_rows, int64_t pos_table_rows, float eps, void* stream) {
-    return bf_launch_embed_layernorm((const long long*)d_ids, (const long long*)d_type_ids, (const long long*)d_pos_ids,
-                                     d_word, d_type, d_pos, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, seq_len,
-                                     pos_rows, word_rows, type_rows, pos_table_rows, eps, (hipStream_t)stream);
-}
-
-int bf_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                     void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, int64_t token_stride,
-                     float scaling, void* stream) {
-    return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim,
-                                   token_stride, scaling, (hipStream_t)stream);
-}
-
-int bf_attention_fwd_rows(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                          void* d_out, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, int q_rows,
-                          float scaling, void* stream) {
-    if (q_rows < 1 || q_rows > 16) BF_FAIL("bf_attention_fwd_rows: q_rows=%d (1 .. 16)", q_rows);
-    return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, nullptr, dtype, B, T, H, head_dim,
-                                   token_stride, scaling, (hipStream_t)stream, nullptr, nullptr, q_rows);
-}
-
-int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                     const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
-                     void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
-                     void* stream) {
-    return bf_launch_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv,
-                                   dtype, B, T, H, head_dim, token_stride, scaling, (hipStream_t)stream);
-}
-
-int bf_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                         void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
-    return bf_launch_attention_fwd_gqa(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, scaling,
-                                       (hipStream_t)stream);
-}
-
-int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                         const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
-                         void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
-    return bf_launch_attention_bwd_gqa(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv,
-                                       dtype, shape, scaling, (hipStream_t)stream);
-}
-
-int bf_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                            void* d_out, void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
-                            void* stream) {
-    return bf_launch_attention_decode_gqa(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_workspace, dtype, shape, scaling,
-                                          (hipStream_t)stream);
-}
-
-int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
-    return bf_launch_attention_decode_workspace_bytes(shape);
-}
-
-int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
-                                int dtype, const bf_attn_decode_t* shape, float scaling, void* stream) {
-    return bf_launch_attention_decode_gqa_len(d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape,
-                                              scaling, (hipStream_t)stream);
-}
-
-int bf_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape,
-                                int32_t window, float scaling, void* stream) {
-    return bf_launch_attention_fwd_gqa_window(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, scaling,
-                                              (hipStream_t)stream);
-}
-
-int bf_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
-                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
-                                int32_t window, float scaling, void* stream) {
-    return bf_launch_attention_bwd_gqa_window(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk,
-                                              d_dv, dtype, shape, window, scaling, (hipStream_t)stream);
-}
-
-int bf_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                   const uint8_t* d_mask_off, void* d_out, void* d_workspace, int dtype,
-                                   const bf_attn_decode_t* shape, int32_t window, float scaling, void* stream) {
-    return bf_launch_attention_decode_gqa_window(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_workspace, dtype, shape, window,
-                                                 scaling, (hipStream_t)stream);
-}
-
-int bf_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
-                                       int dtype, const bf_attn_decode_t* shape, int32_t window, float scaling,
-                                       void* stream) {
-    return bf_launch_attention_decode_gqa_len_window(d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype,
-                                                     shape, window, scaling, (hipStream_t)stream);
-}
-
-int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
-                     const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
-                     int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
-                     uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
-                     int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed, void* stream) {
-    return bf_launch_generate_step(d_probs, nullptr, d_predictive_entropy, d_expected_entropy, d_mutual_information, B, V,
-                                   S, d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished, d_lengths,
-                                   d_next_ids, d_positions, eos_token_id, pad_token_id, do_sample, d_seed,
-                                   (hipStream_t)stream);
-}
-
-int bf_generate_step_stat_probs(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
-                                const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
-                                int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences,
-                                int64_t seq_stride, int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths,
-                                int64_t* d_next_ids, int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id,
-                                int do_sample, const uint64_t* d_seed, void* stream) {
-    if (!d_stat_probs) BF_FAIL("bf_generate_step_stat_probs: NULL argument");
-    return bf_launch_generate_step(d_probs, d_stat_probs, d_predictive_entropy, d_expected_entropy, d_mutual_information,
-                                   B, V, S, d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished,
-                                   d_lengths, d_next_ids, d_positions, eos_token_id, pad_token_id, do_sample, d_seed,
-                                   (hipStream_t)stream);
-}
-
-int bf_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
-                      float min_p, void* stream) {
-    return bf_launch_probs_truncate(d_probs, d_out, R, V, top_k, top_p, min_p, (hipStream_t)stream);
-}
-
-int bf_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
-                      const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0, const int64_t* d_step,
-                      int64_t step, float repetition_penalty, int64_t no_repeat_ngram_size, int64_t min_new_tokens,
-                      int64_t eos_token_id, float temperature, void* stream) {
-    return bf_launch_logits_process(d_logits, dtype, R, V, row_stride, d_out, d_sequences, B, seq_stride, T0, d_step, step,
-                                    repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id, temperature,
-                                    (hipStream_t)stream);
-}
-
-static bf_dropout_t make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,
-                                 const uint32_t* d_call = nullptr) {
-    bf_dropout_t d;
-    d.d_call = d_call;
-    d.k0 = (uint32_t)seed;
-    d.k1 = (uint32_t)(seed >> 32);
-    d.call = call;
-    d.site = site;
-    d.g0_lo = (uint32_t)first_group;
-    d.g0_hi = (uint32_t)(first_group >> 32);
-    d.thresh = bf_dropout_thresh(p_drop);
-    d.inv_keep = 1.0f / (1.0f - (float)d.thresh / 65536.0f);
-    return d;
-}
-
 int bf_dropout_keep_host(uint8_t* out, uint64_t first_group, uint64_t n_groups, float p_drop, uint64_t seed, uint32_t call,
                          uint32_t site) {
     if (!out && n_groups) BF_FAIL("bf_dropout_keep_host: out is NULL");
@@ -605,116 +385,6 @@ int bf_dropout_keep_host(uint8_t* out, uint64_t first_group, uint64_t n_groups, 
         for (int j = 0; j < 8; ++j) out[8 * i + j] = (uint8_t)((keep >> j) & 1u);
     }
     return 0;
-}
-
-int bf_attention_fwd_dropout(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                             void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, int64_t token_stride,
-                             float scaling, float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group, uint32_t* d_keep_bits,
-                             const uint32_t* d_call, void* stream) {
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_fwd_dropout: p must be in [0, 1) (got %g)", p_drop);
-    const bf_dropout_t d = make_dropout(p_drop, seed, call, site, first_group, d_call);
-    return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim, token_stride,
-                                   scaling, (hipStream_t)stream, &d, d_keep_bits);
-}
-
-int bf_attention_bwd_dropout(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                             const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
-                             void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
-                             float p_drop, const uint32_t* d_keep_bits, void* stream) {
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_bwd_dropout: p must be in [0, 1) (got %g)", p_drop);
-    const bf_dropout_t d = make_dropout(p_drop, 0, 0, 0);
-    if (d.thresh && !d_keep_bits) BF_FAIL("bf_attention_bwd_dropout: the forward's keep bits are needed");
-    return bf_launch_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype,
-                                   B, T, H, head_dim, token_stride, scaling, (hipStream_t)stream,
-                                   d.thresh ? d_keep_bits : nullptr, d.inv_keep);
-}
-
-int bf_attention_bwd_colsum(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
-                            const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
-                            void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
-                            float p_drop, const uint32_t* d_keep_bits, int samples, float* d_partial, float* d_colsum,
-                            void* stream) {
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_bwd_colsum: p must be in [0, 1) (got %g)", p_drop);
-    if (!d_partial || !d_colsum) BF_FAIL("bf_attention_bwd_colsum: needs d_partial ([B][H][3][64] fp32) and d_colsum ([3][samples][H*64] fp32)");
-    const bf_dropout_t d = make_dropout(p_drop, 0, 0, 0);
-    if (d.thresh && !d_keep_bits) BF_FAIL("bf_attention_bwd_colsum: the forward's keep bits are needed");
-    return bf_launch_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype,
-                                   B, T, H, head_dim, token_stride, scaling, (hipStream_t)stream,
-                                   d.thresh ? d_keep_bits : nullptr, d.inv_keep, samples, d_partial, d_colsum);
-}
-
-int bf_add_layernorm_dropout(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, int param_dtype,
-                             void* d_out, int dtype, int64_t rows, int N, float eps, float p_drop, uint64_t seed, uint32_t call,
-                             uint32_t site, uint64_t first_group, const uint32_t* d_call, void* stream) {
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_add_layernorm_dropout: p must be in [0, 1) (got %g)", p_drop);
-    const bf_dropout_t d = make_dropout(p_drop, seed, call, site, first_group, d_call);
-    return bf_launch_add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps,
-                                   (hipStream_t)stream, &d);
-}
-
-int bf_add_layernorm_dropout_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
-                                 const void* d_dy, void* d_dz, void* d_dx, float* d_dgamma, float* d_dbeta, void* d_workspace,
-                                 size_t workspace_bytes, int dtype, int64_t rows, int N, float eps, float p_drop, uint64_t seed,
-                                 uint32_t call, uint32_t site, uint64_t first_group, const uint32_t* d_call, void* stream) {
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_add_layernorm_dropout_bwd: p must be in [0, 1) (got %g)", p_drop);
-    const bf_dropout_t d = make_dropout(p_drop, seed, call, site, first_group, d_call);
-    return bf_launch_add_layernorm_bwd(d_x, d_residual, d_gamma, param_dtype, d_dy, d_dz, d_dgamma, d_dbeta, d_workspace,
-                                       workspace_bytes, dtype, rows, N, eps, (hipStream_t)stream, &d, d_dx);
-}
-
-int bf_add_layernorm_bwd_sum(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype, const void* d_dy,
-                             const void* d_dy2, void* d_dz, void* d_dx, float* d_dgamma, float* d_dbeta, void* d_workspace,
-                             size_t workspace_bytes, int dtype, int64_t rows, int N, float eps, float p_drop, uint64_t seed,
-                             uint32_t call, uint32_t site, uint64_t first_group, const uint32_t* d_call, void* stream) {
-    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_add_layernorm_bwd_sum: p must be in [0, 1) (got %g)", p_drop);
-    const bf_dropout_t d = make_dropout(p_drop, seed, call, site, first_group, d_call);
-    return bf_launch_add_layernorm_bwd(d_x, d_residual, d_gamma, param_dtype, d_dy, d_dz, d_dgamma, d_dbeta, d_workspace,
-                                       workspace_bytes, dtype, rows, N, eps, (hipStream_t)stream, d.thresh ? &d : nullptr, d_dx,
-                                       d_dy2);
-}
-
-size_t bf_add_layernorm_bwd_workspace_bytes(int64_t rows, int N) { return bf_add_layernorm_bwd_ws_bytes(rows, N); }
-
-int bf_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype, const void* d_dy,
-                         void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace, size_t workspace_bytes, int dtype,
-                         int64_t rows, int N, float eps, void* stream) {
-    return bf_launch_add_layernorm_bwd(d_x, d_residual, d_gamma, param_dtype, d_dy, d_dz, d_dgamma, d_dbeta, d_workspace,
-                                       workspace_bytes, dtype, rows, N, eps, (hipStream_t)stream);
-}
-
-int bf_gemm_tn(const void* d_a, const void* d_bm, float* d_out, int dtype, int batch, int Mc, int N, int K, void* stream) {
-    if (!d_a || !d_bm || !d_out) BF_FAIL("bf_gemm_tn: null pointer");
-    if (!bf_gemm256_tn_supported(dtype, batch, Mc, N, K, d_a, d_bm, d_out))
-        BF_FAIL("bf_gemm_tn: needs a 16-bit dtype, Mc %% 64 == 0, N %% 8 == 0, K %% 8 == 0 and 16-byte aligned pointers");
-    return bf_launch_gemm256_tn(d_a, d_bm, d_out, dtype, batch, Mc, N, K, (hipStream_t)stream);
-}
-
-int bf_gemm_nn(const void* d_x, const void* d_w, void* d_y, int dtype, int S, int M, int N, int K, void* stream) {
-    if (!d_x || !d_w || !d_y) BF_FAIL("bf_gemm_nn: null pointer");
-    if (!bf_gemm256_nn_supported(dtype, S, M, N, K, d_x, d_w, d_y))
-        BF_FAIL("bf_gemm_nn: needs a 16-bit dtype, N %% 64 == 0, K %% 8 == 0, M * K >= 16384 and 16-byte aligned pointers");
-    return bf_launch_gemm256_nn(d_x, d_w, d_y, dtype, S, M, N, K, (hipStream_t)stream);
-}
-
-int bf_gemm_nn_actgrad_supported(const void* d_x, const void* d_w, const void* d_y, const void* d_pre, int dtype, int S, int M,
-                                 int N, int K) {
-    return bf_gemm256_nn_actgrad_supported(dtype, S, M, N, K, d_x, d_w, d_y, d_pre) ? 1 : 0;
-}
-
-int bf_gemm_nn_actgrad(const void* d_x, const void* d_w, void* d_y, const void* d_pre, int dtype, int S, int M, int N, int K,
-                       int act, void* stream) {
-    if (!d_x || !d_w || !d_y || !d_pre) BF_FAIL("bf_gemm_nn_actgrad: null pointer");
-    if (act != BF_ACT_GELU) BF_FAIL("bf_gemm_nn_actgrad: unknown activation %d", act);
-    return bf_launch_gemm256_nn(d_x, d_w, d_y, dtype, S, M, N, K, (hipStream_t)stream, 1, d_pre, act);
-}
-
-int bf_gemm_nn_layers(const void* d_x, const void* d_w, void* d_y, int dtype, int L, int S, int M, int N, int K,
-                      void* stream) {
-    if (!d_x || !d_w || !d_y) BF_FAIL("bf_gemm_nn_layers: null pointer");
-    if (L < 1 || L > 4) BF_FAIL("bf_gemm_nn_layers: L must be 1..4 (got %d)", L);
-    if (!bf_gemm256_nn_supported(dtype, S, M, N, K, d_x, d_w, d_y) || (long long)L * S * M * N >= (1ll << 40))
-        BF_FAIL("bf_gemm_nn_layers: needs a 16-bit dtype, N %% 64 == 0, K %% 8 == 0, M * K >= 16384 and 16-byte aligned pointers");
-    return bf_launch_gemm256_nn(d_x, d_w, d_y, dtype, S, M, N, K, (hipStream_t)stream, L);
 }
 
 // workspace layout of bf_linear_bwd
@@ -780,21 +450,6 @@ size_t bf_linear_bwd_workspace_bytes(int S, int M, int N, int K, int has_bias, i
 int bf_linear_bwd_splits(int S, int M, int N, int K, int dtype) {
     if (S < 1 || M < 1 || N < 1 || K < 1) return 0;
     return bwd_splits(S, M, N, K, dtype);
-}
-
-size_t bf_param_grad_table_bytes(const bf_pgrad_t* entries, int n, uint32_t* total_blocks) {
-    if (!entries || n < 1) return 0;
-    return bf_pgrad_table_bytes(entries, n, total_blocks);
-}
-
-int bf_param_grad_table_build(const bf_pgrad_t* entries, int n, void* h_blob, size_t blob_bytes) {
-    if (!entries || n < 1 || !h_blob) BF_FAIL("bf_param_grad_table_build: no entries or no blob");
-    return bf_pgrad_table_build(entries, n, h_blob, blob_bytes);
-}
-
-int bf_param_grad_table(const void* d_blob, int n, uint32_t total_blocks, int S, uint64_t seed, uint32_t sample_base,
-                        void* stream) {
-    return bf_launch_pgrad_table(d_blob, n, total_blocks, S, seed, sample_base, (hipStream_t)stream);
 }
 
 int bf_linear_bwd(const void* d_x, int64_t x_sample_stride, const void* d_dy, int dtype, const bf_tensor_t* weight,

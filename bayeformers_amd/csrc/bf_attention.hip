@@ -221,10 +221,11 @@ void launch(const AttnParams& p, hipStream_t stream) {
 
 }  // namespace
 
-int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                            const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype, int B, int T, int H,
-                            int head_dim, long long token_stride, float scaling, hipStream_t stream,
-                            const bf_dropout_t* drop, uint32_t* d_keep_bits, int q_rows) {
+// the three entries' shared worker: drop / d_keep_bits for the dropout entry, q_rows for the rows entry
+static int attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, long long token_stride,
+                         float scaling, hipStream_t stream, const bf_dropout_t* drop = nullptr, uint32_t* d_keep_bits = nullptr,
+                         int q_rows = 0) {
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("bf_attention_fwd: NULL argument");
     if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("bf_attention_fwd: dtype must be bf16 or fp16");
     if (head_dim != HD) BF_FAIL("bf_attention_fwd: head size %d (only %d)", head_dim, HD);
@@ -267,4 +268,29 @@ int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, c
     }
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int bf_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                     void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, int64_t token_stride,
+                     float scaling, void* stream) {
+    return attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim, token_stride, scaling,
+                         (hipStream_t)stream);
+}
+
+int bf_attention_fwd_rows(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                          void* d_out, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, int q_rows,
+                          float scaling, void* stream) {
+    if (q_rows < 1 || q_rows > 16) BF_FAIL("bf_attention_fwd_rows: q_rows=%d (1 .. 16)", q_rows);
+    return attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, nullptr, dtype, B, T, H, head_dim, token_stride, scaling,
+                         (hipStream_t)stream, nullptr, nullptr, q_rows);
+}
+
+int bf_attention_fwd_dropout(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                             void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, int64_t token_stride,
+                             float scaling, float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group,
+                             uint32_t* d_keep_bits, const uint32_t* d_call, void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_fwd_dropout: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, seed, call, site, first_group, d_call);
+    return attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim, token_stride, scaling,
+                         (hipStream_t)stream, &d, d_keep_bits);
 }

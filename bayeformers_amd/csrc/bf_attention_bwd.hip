@@ -16,6 +16,7 @@
 // Algorithmic HBM bytes: dq kernel 5 reads (Q, K, V, O, dO) + 1 write; dk/dv kernel 4 reads + 2 writes, x B*T*H*64*2 B.
 #include "bf_attention_tiles.h"
 #include "bf_device.h"
+#include "bf_philox.h"
 
 namespace {
 
@@ -487,11 +488,12 @@ void launch(const BwdParams& p, bool one_tile, hipStream_t stream) {
 
 }  // namespace
 
-int bf_launch_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                            const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
-                            float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, int B, int T, int H,
-                            int head_dim, long long token_stride, float scaling, hipStream_t stream,
-                            const uint32_t* d_keep_bits, float inv_keep, int samples, float* d_cs_partial, float* d_colsum) {
+// the three entries' shared worker: d_keep_bits / inv_keep for the dropout entries, the rest for the column sums
+static int attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                         void* d_dv, int dtype, int B, int T, int H, int head_dim, long long token_stride, float scaling,
+                         hipStream_t stream, const uint32_t* d_keep_bits = nullptr, float inv_keep = 1.0f, int samples = 0,
+                         float* d_cs_partial = nullptr, float* d_colsum = nullptr) {
     if (!d_q || !d_k || !d_v || !d_out || !d_dout || !d_lse || !d_delta || !d_dq || !d_dk || !d_dv)
         BF_FAIL("bf_attention_bwd: NULL argument");
     if (d_colsum && (T != TT || !d_cs_partial || samples < 1 || B % samples || samples > 65535))
@@ -540,4 +542,37 @@ int bf_launch_attention_bwd(const void* d_q, const void* d_k, const void* d_v, c
                            H, samples, d_colsum);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                     const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                     void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
+                     void* stream) {
+    return attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, B, T, H,
+                         head_dim, token_stride, scaling, (hipStream_t)stream);
+}
+
+int bf_attention_bwd_dropout(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                             const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                             void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
+                             float p_drop, const uint32_t* d_keep_bits, void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_bwd_dropout: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, 0, 0, 0);
+    if (d.thresh && !d_keep_bits) BF_FAIL("bf_attention_bwd_dropout: the forward's keep bits are needed");
+    return attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, B, T, H,
+                         head_dim, token_stride, scaling, (hipStream_t)stream, d.thresh ? d_keep_bits : nullptr, d.inv_keep);
+}
+
+int bf_attention_bwd_colsum(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                            const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                            void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
+                            float p_drop, const uint32_t* d_keep_bits, int samples, float* d_partial, float* d_colsum,
+                            void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_bwd_colsum: p must be in [0, 1) (got %g)", p_drop);
+    if (!d_partial || !d_colsum) BF_FAIL("bf_attention_bwd_colsum: needs d_partial ([B][H][3][64] fp32) and d_colsum ([3][samples][H*64] fp32)");
+    const bf_dropout_t d = bf_make_dropout(p_drop, 0, 0, 0);
+    if (d.thresh && !d_keep_bits) BF_FAIL("bf_attention_bwd_colsum: the forward's keep bits are needed");
+    return attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, B, T, H,
+                         head_dim, token_stride, scaling, (hipStream_t)stream, d.thresh ? d_keep_bits : nullptr, d.inv_keep,
+                         samples, d_partial, d_colsum);
 }

@@ -283,7 +283,7 @@ int64_t workspace_bytes(const bf_attn_decode_t* s) {
 
 }  // namespace
 
-int64_t bf_launch_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
+int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
     if (check_shape("bf_attention_decode_workspace_bytes", shape, BF_DT_BF16)) return -1;
     return workspace_bytes(shape);
 }
@@ -354,38 +354,38 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
 
 }  // namespace
 
-int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                   const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
-                                   const bf_attn_decode_t* shape, float scaling, hipStream_t stream) {
+int bf_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                            void* d_out, void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
+                            void* stream) {
     return decode("bf_attention_decode_gqa", d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, 0,
-                  scaling, stream);
+                  scaling, (hipStream_t)stream);
 }
 
-int bf_launch_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                          const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
-                                          const bf_attn_decode_t* shape, int window, float scaling, hipStream_t stream) {
+int bf_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                   const uint8_t* d_mask_off, void* d_out, void* d_workspace, int dtype,
+                                   const bf_attn_decode_t* shape, int32_t window, float scaling, void* stream) {
     const char* what = "bf_attention_decode_gqa_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
     return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, window, scaling,
-                  stream);
+                  (hipStream_t)stream);
 }
 
-int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
-                                       void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
-                                       hipStream_t stream) {
+int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                int dtype, const bf_attn_decode_t* shape, float scaling, void* stream) {
     const char* what = "bf_attention_decode_gqa_len";
     if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
-    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, 0, scaling, stream);
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, 0, scaling,
+                  (hipStream_t)stream);
 }
 
-int bf_launch_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                              const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
-                                              void* d_workspace, int dtype, const bf_attn_decode_t* shape, int window,
-                                              float scaling, hipStream_t stream) {
+int bf_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                       const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                       int dtype, const bf_attn_decode_t* shape, int32_t window, float scaling,
+                                       void* stream) {
     const char* what = "bf_attention_decode_gqa_len_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
     if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
     return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, scaling,
-                  stream);
+                  (hipStream_t)stream);
 }

@@ -491,8 +491,8 @@ int fwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     if (window && fill_window(what, p, shape, window)) return 1;
     long long ts;
     if (!window && bert_case(shape, &ts))
-        return bf_launch_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape->B, shape->T, shape->H,
-                                       64, ts, scaling, stream);
+        return bf_attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape->B, shape->T, shape->H, 64, ts,
+                                scaling, stream);
     if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
     if ((d_mask && ((uintptr_t)d_mask & 15)) || (d_lse && ((uintptr_t)d_lse & 15))) BF_FAIL("%s: mask / lse must be 16-byte aligned", what);
     p.q = d_q;
@@ -518,8 +518,8 @@ int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     if (window && fill_window(what, p, shape, window)) return 1;
     long long ts;
     if (!window && bert_case(shape, &ts))
-        return bf_launch_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype,
-                                       shape->B, shape->T, shape->H, 64, ts, scaling, stream);
+        return bf_attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype,
+                                shape->B, shape->T, shape->H, 64, ts, scaling, stream);
     const uintptr_t al = (uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_dout |
                          (uintptr_t)d_dq | (uintptr_t)d_dk | (uintptr_t)d_dv | (uintptr_t)d_lse | (uintptr_t)d_delta;
     if (al & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
@@ -543,34 +543,33 @@ int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
 
 }  // namespace
 
-int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
-                                const bf_attn_gqa_t* shape, float scaling, hipStream_t stream) {
-    return fwd_gqa("bf_attention_fwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, 0, scaling, stream);
+int bf_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
+    return fwd_gqa("bf_attention_fwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, 0, scaling,
+                   (hipStream_t)stream);
 }
 
-int bf_launch_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
-                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream) {
+int bf_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape,
+                                int32_t window, float scaling, void* stream) {
     const char* what = "bf_attention_fwd_gqa_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
-    return fwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, scaling, stream);
+    return fwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, scaling, (hipStream_t)stream);
 }
 
-int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
-                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
-                                float scaling, hipStream_t stream) {
+int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                         void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
     return bwd_gqa("bf_attention_bwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv,
-                   dtype, shape, 0, scaling, stream);
+                   dtype, shape, 0, scaling, (hipStream_t)stream);
 }
 
-int bf_launch_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const unsigned char* d_mask_off, const void* d_out, const void* d_dout,
-                                       const float* d_lse, float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype,
-                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream) {
+int bf_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                int32_t window, float scaling, void* stream) {
     const char* what = "bf_attention_bwd_gqa_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
     return bwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, shape,
-                   window, scaling, stream);
+                   window, scaling, (hipStream_t)stream);
 }

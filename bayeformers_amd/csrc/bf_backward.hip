@@ -486,9 +486,11 @@ __global__ __launch_bounds__(256) void embedding_bwd_kernel(const long long* __r
 
 }  // namespace
 
-int bf_launch_embedding_fwd(const long long* d_ids, const float* d_mu, const float* d_rho, void* d_out, int out_dtype,
-                            long long n_tokens, long long tokens_per_sample, long long V, int D, uint64_t seed,
-                            uint32_t sample_base, uint32_t stream_id, hipStream_t stream) {
+int bf_embedding_fwd(const int64_t* d_ids_, const float* d_mu, const float* d_rho, void* d_out, int out_dtype,
+                     int64_t n_tokens, int64_t tokens_per_sample, int64_t V, int D, uint64_t seed, uint32_t sample_base,
+                     uint32_t stream_id, void* stream_) {
+    const long long* d_ids = (const long long*)d_ids_;  // the kernels' index type
+    hipStream_t stream = (hipStream_t)stream_;
     if (!d_ids || !d_mu || !d_rho || !d_out) BF_FAIL("bf_embedding_fwd: NULL argument");
     if (n_tokens < 1 || tokens_per_sample < 1 || V < 1 || D < 4 || D % 4) BF_FAIL("bf_embedding_fwd: bad shape (D must be a multiple of 4)");
     if (((uintptr_t)d_mu | (uintptr_t)d_rho | (uintptr_t)d_out) & 15) BF_FAIL("bf_embedding_fwd: operands must be 16-byte aligned");
@@ -508,9 +510,11 @@ int bf_launch_embedding_fwd(const long long* d_ids, const float* d_mu, const flo
     return 0;
 }
 
-int bf_launch_embedding_bwd(const long long* d_ids, const void* d_grad, int grad_dtype, const float* d_rho, float* d_dmu,
-                            float* d_drho, long long n_tokens, long long tokens_per_sample, long long V, int D,
-                            uint64_t seed, uint32_t sample_base, uint32_t stream_id, hipStream_t stream) {
+int bf_embedding_bwd(const int64_t* d_ids_, const void* d_grad, int grad_dtype, const float* d_rho, float* d_dmu,
+                     float* d_drho, int64_t n_tokens, int64_t tokens_per_sample, int64_t V, int D, uint64_t seed,
+                     uint32_t sample_base, uint32_t stream_id, void* stream_) {
+    const long long* d_ids = (const long long*)d_ids_;
+    hipStream_t stream = (hipStream_t)stream_;
     if (!d_ids || !d_grad || !d_rho || !d_drho) BF_FAIL("bf_embedding_bwd: NULL argument");
     if (n_tokens < 1 || tokens_per_sample < 1 || V < 1 || D < 4 || D % 4) BF_FAIL("bf_embedding_bwd: bad shape");
     const long long work = n_tokens * (D / 4);
@@ -529,8 +533,8 @@ int bf_launch_embedding_bwd(const long long* d_ids, const void* d_grad, int grad
     return 0;
 }
 
-int bf_launch_kl_grad(const bf_tensor_t* t, int S, uint64_t seed, uint32_t sample_base, const double* d_g,
-                      float* d_dmu, float* d_drho, hipStream_t stream) {
+int bf_kl_grad(const bf_tensor_t* t, int S, uint64_t seed, uint32_t sample_base, const double* d_g, float* d_dmu,
+               float* d_drho, void* stream) {
     if (!t || !t->d_mu || !t->d_rho || !d_g || !d_drho) BF_FAIL("bf_kl_grad: NULL argument");
     if (t->n == 0 || S < 1) BF_FAIL("bf_kl_grad: empty");
     KlParams p{};
@@ -551,7 +555,7 @@ int bf_launch_kl_grad(const bf_tensor_t* t, int S, uint64_t seed, uint32_t sampl
         BF_FAIL("bf_kl_grad: gaussian prior needs d_mu/d_rho");
     }
     const uint64_t groups = (t->n + 3) / 4;
-    hipLaunchKernelGGL(kl_grad_kernel, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(kl_grad_kernel, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -632,7 +636,7 @@ int bf_launch_gelu(const void* d_in, void* d_out, int dtype, uint64_t n, hipStre
     return 0;
 }
 
-bool bf_gelu_bwd_colsum_supported(int dtype, int S, int M, int N, const void* d_dy, const void* d_pre, const void* d_out) {
+static bool gelu_bwd_colsum_supported(int dtype, int S, int M, int N, const void* d_dy, const void* d_pre, const void* d_out) {
     return dtype != BF_DT_F32 && N % 8 == 0 && S >= 1 && S <= 65535 && M >= 1 &&
            (((uintptr_t)d_dy | (uintptr_t)d_pre | (uintptr_t)d_out) & 15) == 0;
 }
@@ -640,7 +644,7 @@ bool bf_gelu_bwd_colsum_supported(int dtype, int S, int M, int N, const void* d_
 int bf_launch_gelu_bwd_colsum(const void* d_dy, const void* d_pre, void* d_dpre, int dtype, int S, int M, int N,
                               float* d_partial, float* d_colsum, hipStream_t stream) {
     if (!d_dy || !d_pre || !d_dpre || !d_partial || !d_colsum) BF_FAIL("bf_gelu_bwd_colsum: NULL argument");
-    if (!bf_gelu_bwd_colsum_supported(dtype, S, M, N, d_dy, d_pre, d_dpre))
+    if (!gelu_bwd_colsum_supported(dtype, S, M, N, d_dy, d_pre, d_dpre))
         BF_FAIL("bf_gelu_bwd_colsum: needs 16-bit tensors, N %% 8 == 0 and 16-byte aligned pointers");
     const int chunks = (M + kColsumRows - 1) / kColsumRows;
     dim3 pgrid((N / 8 + 63) / 64, chunks, S);
@@ -684,16 +688,17 @@ int bf_launch_colsum(const void* d_dy, int dtype, float* d_out, int S, int M, in
 
 static uint32_t pg_blocks(uint64_t n) { return (uint32_t)(((n + 3) / 4 + 255) / 256); }
 
-size_t bf_pgrad_table_bytes(const bf_pgrad_t* t, int n, uint32_t* total_blocks) {
+size_t bf_param_grad_table_bytes(const bf_pgrad_t* t, int n, uint32_t* total_blocks) {
+    if (!t || n < 1) return 0;
     uint64_t blocks = 0;
     for (int i = 0; i < n; ++i) blocks += pg_blocks(t[i].n);
     if (total_blocks) *total_blocks = (uint32_t)blocks;
     return bf_align_up((size_t)n * sizeof(PgEntry), 256) + (size_t)blocks * sizeof(uint32_t);
 }
 
-int bf_pgrad_table_build(const bf_pgrad_t* t, int n, void* h_blob, size_t blob_bytes) {
-    uint32_t total = 0;
-    if (blob_bytes < bf_pgrad_table_bytes(t, n, &total)) BF_FAIL("bf_param_grad_table_build: blob too small");
+int bf_param_grad_table_build(const bf_pgrad_t* t, int n, void* h_blob, size_t blob_bytes) {
+    if (!t || n < 1 || !h_blob) BF_FAIL("bf_param_grad_table_build: no entries or no blob");
+    if (blob_bytes < bf_param_grad_table_bytes(t, n, nullptr)) BF_FAIL("bf_param_grad_table_build: blob too small");
     PgEntry* ent = reinterpret_cast<PgEntry*>(h_blob);
     uint32_t* map = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(h_blob) + bf_align_up((size_t)n * sizeof(PgEntry), 256));
     uint32_t blk = 0;
@@ -711,12 +716,12 @@ int bf_pgrad_table_build(const bf_pgrad_t* t, int n, void* h_blob, size_t blob_b
     return 0;
 }
 
-int bf_launch_pgrad_table(const void* d_blob, int n, uint32_t total_blocks, int S, uint64_t seed, uint32_t sample_base,
-                          hipStream_t stream) {
+int bf_param_grad_table(const void* d_blob, int n, uint32_t total_blocks, int S, uint64_t seed, uint32_t sample_base,
+                        void* stream) {
     if (!d_blob || n < 1 || total_blocks < 1 || S < 1) BF_FAIL("bf_param_grad_table: empty launch");
     const PgEntry* ent = reinterpret_cast<const PgEntry*>(d_blob);
     const uint32_t* map = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(d_blob) + bf_align_up((size_t)n * sizeof(PgEntry), 256));
-    hipLaunchKernelGGL(param_grad_table_kernel, dim3(total_blocks), dim3(256), 0, stream, ent, map, S, (uint32_t)seed,
+    hipLaunchKernelGGL(param_grad_table_kernel, dim3(total_blocks), dim3(256), 0, (hipStream_t)stream, ent, map, S, (uint32_t)seed,
                        (uint32_t)(seed >> 32), sample_base, bf_sample_counter());
     BF_HIP_CHECK(hipGetLastError());
     return 0;

@@ -64,42 +64,56 @@ __device__ __forceinline__ void bf_stale_bump(uint32_t* counter) {
     if (counter) __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// internal launchers (defined in bf_sample.hip / bf_gemm.hip), all asynchronous on `stream`
-int bf_launch_philox_normal(float* d_out, uint64_t n, int S, uint64_t seed, uint32_t sample_base, uint32_t stream_id,
-                            hipStream_t stream);
+// Launchers that a translation unit other than their own calls, all asynchronous on `stream`.  (An entry of the public
+// header is defined in the .hip file that owns its kernels; what only that entry called is private to that file.)
+//
+// bf_sample.hip, for bf_sample_logprob / bf_sample_logprob_table / bf_linear_fwd / bf_linear_bwd (bf_api.hip)
 size_t bf_sample_partials_bytes(const bf_tensor_t* tensors, int n_tensors, int S);
 int bf_launch_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, uint64_t seed, uint32_t sample_base,
                              double* d_logprob_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream);
-size_t bf_table_blob_bytes(const bf_tensor_t* tensors, int n_tensors, uint32_t* total_blocks);
-int bf_table_build(const bf_tensor_t* tensors, int n_tensors, void* h_blob, size_t blob_bytes, uint32_t* h_block_begin, int32_t* h_kinds = nullptr);
 int bf_launch_sample_table(const void* d_blob, int n_tensors, uint32_t block_begin, uint32_t block_end, int S,
-                           uint64_t seed, uint32_t sample_base, double* d_partials, hipStream_t stream, int prior_kinds = 0);
-int bf_launch_reduce_groups(const double* d_partials, const uint32_t* d_rows, int G, int S, double* d_out,
-                            hipStream_t stream);
+                           uint64_t seed, uint32_t sample_base, double* d_partials, hipStream_t stream, int prior_kinds);
+int bf_launch_reduce_partials(const double* d_partials, uint32_t nrows, int S, double* d_out, hipStream_t stream);
+// bf_gemm.hip, for the bf_gemm_nt* entries, bf_linear_fwd and bf_linear_bwd (bf_api.hip)
 int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                       const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, hipStream_t stream,
                       int act = BF_ACT_NONE, int layers = 1, void* d_pre = nullptr, int64_t x_row_stride = 0,
                       void* d_workspace = nullptr, size_t workspace_bytes = 0);
 // x_row_stride: elements between consecutive rows of x (0 = K, rows back to back).  A call that names one (bf_gemm_nt_rows)
 // runs the weight-streaming kernel of bf_gemm_skinny.hip when bf_gemm_skinny_refuses() is NULL (d_workspace: its split-K
-// scratch, bf_gemm_nt_rows_workspace_impl bytes — missing or too small is an error), else the generic 128 x 128 kernel.
-size_t bf_gemm_nt_rows_workspace_impl(int dtype, int S, int M, int N, int K);
-// skinny NT GEMM on kept weights (bf_gemm_skinny.hip)
+// scratch, bf_gemm_nt_rows_workspace_bytes — missing or too small is an error), else the generic 128 x 128 kernel.
+//
+// bf_gemm_skinny.hip, for bf_launch_gemm_nt and bf_gemm_nt_rows_workspace_bytes (bf_gemm.hip)
 int bf_launch_gemm_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
                           const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act,
                           void* d_workspace, size_t workspace_bytes, hipStream_t stream, int64_t x_row_stride = 0);
-size_t bf_gemm_skinny_workspace_impl(int S, int M, int N, int K);
 // NULL when the skinny kernel takes these dtypes, this shape and these operand / stride alignments, else the reason
 const char* bf_gemm_skinny_refuses(int x_dtype, int w_dtype, int y_dtype, int S, int M, int N, int K,
                                    int64_t x_sample_stride, int64_t x_row_stride, const void* d_x, const void* d_w);
-int bf_gemm_skinny_max_rows_impl();
-// out = gelu(in) elementwise (16-bit or fp32 tensors of n elements)
+// bf_backward.hip, for bf_launch_gemm_nt (bf_gemm.hip): out = gelu(in) elementwise (16-bit or fp32 tensors of n elements)
 int bf_launch_gelu(const void* d_in, void* d_out, int dtype, uint64_t n, hipStream_t stream);
+// bf_backward.hip, for bf_linear_bwd (bf_api.hip)
 // dpre = dy * gelu'(pre) elementwise on [S][M][N] 16-bit tensors, with the column sums of dpre per sample
 // (d_colsum [S][N] fp32; d_partial: bf_colsum_workspace_bytes of scratch)
-bool bf_gelu_bwd_colsum_supported(int dtype, int S, int M, int N, const void* d_dy, const void* d_pre, const void* d_out);
 int bf_launch_gelu_bwd_colsum(const void* d_dy, const void* d_pre, void* d_dpre, int dtype, int S, int M, int N,
                               float* d_partial, float* d_colsum, hipStream_t stream);
+int bf_launch_transpose(const void* d_in, void* d_out, int elem_size, int batch, int rows, int cols, hipStream_t stream);
+size_t bf_colsum_workspace_bytes(int S, int M, int N);
+bool bf_transpose_colsum_supported(int dtype, int batch, int rows, int cols, const void* d_in, const void* d_out);
+int bf_launch_transpose_colsum(const void* d_in, void* d_out, int dtype, int batch, int rows, int cols,
+                               int batch_per_group, float* d_partial, float* d_out_sums, hipStream_t stream);
+int bf_launch_colsum(const void* d_dy, int dtype, float* d_out, int S, int M, int N, float* d_partial,
+                     hipStream_t stream);
+int bf_launch_param_grad(const float* d_dw, const float* d_rho, uint64_t n, int S, int splits, uint64_t seed,
+                         uint32_t sample_base, uint32_t stream_id, float* d_dmu, float* d_drho, hipStream_t stream);
+// bf_fused_small.hip, for bf_linear_fwd (bf_api.hip)
+bool bf_fused_small_supported(int x_dtype, int y_dtype, int compute_dtype, int64_t x_sample_stride, const void* d_x,
+                              const bf_tensor_t* weight, const bf_tensor_t* bias, int S, int M, int N, int K);
+size_t bf_fused_small_partial_rows(int N);
+int bf_launch_fused_small(const void* d_x, int x_dtype, int64_t x_sample_stride, const bf_tensor_t* weight,
+                          const bf_tensor_t* bias, void* d_y, int compute_dtype, int S, int M, int N, int K, uint64_t seed,
+                          uint32_t sample_base, double* d_partials, hipStream_t stream);
+// (the 256-wide GEMM's launchers and bf_gemm256_*_supported, which bf_linear_bwd calls too: bf_gemm_params.h)
 
 // erf-GELU x/2 (1 + erf(x / sqrt 2)), the activation of HF BERT's intermediate layer, on the fp32 accumulators.
 // With q = 1/2 erfc(|x| / sqrt 2) = Phi(-|x|):  gelu(x) = x (1 - q) for x >= 0 and x q for x < 0, i.e. in one
@@ -179,99 +193,3 @@ __device__ __forceinline__ f32x4_t bf_apply_act(f32x4_t v, int act) {
     }
     return v;
 }
-int bf_launch_transpose(const void* d_in, void* d_out, int elem_size, int batch, int rows, int cols, hipStream_t stream);
-size_t bf_colsum_workspace_bytes(int S, int M, int N);
-bool bf_transpose_colsum_supported(int dtype, int batch, int rows, int cols, const void* d_in, const void* d_out);
-int bf_launch_transpose_colsum(const void* d_in, void* d_out, int dtype, int batch, int rows, int cols,
-                               int batch_per_group, float* d_partial, float* d_out_sums, hipStream_t stream);
-int bf_launch_colsum(const void* d_dy, int dtype, float* d_out, int S, int M, int N, float* d_partial,
-                     hipStream_t stream);
-int bf_launch_param_grad(const float* d_dw, const float* d_rho, uint64_t n, int S, int splits, uint64_t seed,
-                         uint32_t sample_base, uint32_t stream_id, float* d_dmu, float* d_drho, hipStream_t stream);
-size_t bf_pgrad_table_bytes(const bf_pgrad_t* t, int n, uint32_t* total_blocks);
-int bf_pgrad_table_build(const bf_pgrad_t* t, int n, void* h_blob, size_t blob_bytes);
-int bf_launch_pgrad_table(const void* d_blob, int n, uint32_t total_blocks, int S, uint64_t seed, uint32_t sample_base,
-                          hipStream_t stream);
-int bf_launch_reduce_partials(const double* d_partials, uint32_t nrows, int S, double* d_out, hipStream_t stream);
-bool bf_fused_small_supported(int x_dtype, int y_dtype, int compute_dtype, int64_t x_sample_stride, const void* d_x,
-                              const bf_tensor_t* weight, const bf_tensor_t* bias, int S, int M, int N, int K);
-size_t bf_fused_small_partial_rows(int N);
-int bf_launch_fused_small(const void* d_x, int x_dtype, int64_t x_sample_stride, const bf_tensor_t* weight,
-                          const bf_tensor_t* bias, void* d_y, int compute_dtype, int S, int M, int N, int K, uint64_t seed,
-                          uint32_t sample_base, double* d_partials, hipStream_t stream);
-int bf_launch_kl_grad(const bf_tensor_t* t, int S, uint64_t seed, uint32_t sample_base, const double* d_g,
-                      float* d_dmu, float* d_drho, hipStream_t stream);
-int bf_launch_embedding_fwd(const long long* d_ids, const float* d_mu, const float* d_rho, void* d_out, int out_dtype,
-                            long long n_tokens, long long tokens_per_sample, long long V, int D, uint64_t seed,
-                            uint32_t sample_base, uint32_t stream_id, hipStream_t stream);
-int bf_launch_embedding_bwd(const long long* d_ids, const void* d_grad, int grad_dtype, const float* d_rho, float* d_dmu,
-                            float* d_drho, long long n_tokens, long long tokens_per_sample, long long V, int D,
-                            uint64_t seed, uint32_t sample_base, uint32_t stream_id, hipStream_t stream);
-struct bf_dropout_t;  // bf_philox.h
-int bf_launch_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta,
-                            int param_dtype, void* d_out, int dtype, long long rows, int N, float eps,
-                            hipStream_t stream, const bf_dropout_t* drop = nullptr, long long residual_row_stride = 0);
-int bf_launch_embed_layernorm(const long long* d_ids, const long long* d_type_ids, const long long* d_pos_ids,
-                              const void* d_word, const void* d_type, const void* d_pos, const void* d_gamma,
-                              const void* d_beta, int param_dtype, void* d_out, int dtype, long long rows, int N,
-                              int seq_len, long long pos_rows, long long word_rows, long long type_rows,
-                              long long pos_table_rows, float eps, hipStream_t stream);
-int bf_launch_attention_fwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                            const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype, int B, int T, int H,
-                            int head_dim, long long token_stride, float scaling, hipStream_t stream,
-                            const bf_dropout_t* drop = nullptr, uint32_t* d_keep_bits = nullptr, int q_rows = 0);
-int bf_launch_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                            const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
-                            float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, int B, int T, int H,
-                            int head_dim, long long token_stride, float scaling, hipStream_t stream,
-                            const uint32_t* d_keep_bits = nullptr, float inv_keep = 1.0f, int samples = 0,
-                            float* d_cs_partial = nullptr, float* d_colsum = nullptr);
-int bf_launch_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
-                                const bf_attn_gqa_t* shape, float scaling, hipStream_t stream);
-int bf_launch_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
-                                float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
-                                float scaling, hipStream_t stream);
-int bf_launch_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                   const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
-                                   const bf_attn_decode_t* shape, float scaling, hipStream_t stream);
-int64_t bf_launch_attention_decode_workspace_bytes(const bf_attn_decode_t* shape);
-int bf_launch_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
-                                       void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
-                                       hipStream_t stream);
-// the sliding-window siblings of the four above (window >= 1, causal shapes)
-int bf_launch_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype,
-                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream);
-int bf_launch_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                       const unsigned char* d_mask_off, const void* d_out, const void* d_dout,
-                                       const float* d_lse, float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype,
-                                       const bf_attn_gqa_t* shape, int window, float scaling, hipStream_t stream);
-int bf_launch_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                          const unsigned char* d_mask_off, void* d_out, void* d_workspace, int dtype,
-                                          const bf_attn_decode_t* shape, int window, float scaling, hipStream_t stream);
-int bf_launch_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
-                                              const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out,
-                                              void* d_workspace, int dtype, const bf_attn_decode_t* shape, int window,
-                                              float scaling, hipStream_t stream);
-// one generation step's epilogue (bf_generate.hip)
-int bf_launch_generate_step(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
-                            const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
-                            int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride,
-                            int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids,
-                            int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id, int do_sample,
-                            const uint64_t* d_seed, hipStream_t stream);
-int bf_launch_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
-                             float min_p, hipStream_t stream);
-int bf_launch_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
-                             const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0,
-                             const int64_t* d_step, int64_t step, float repetition_penalty,
-                             int64_t no_repeat_ngram_size, int64_t min_new_tokens, int64_t eos_token_id,
-                             float temperature, hipStream_t stream);
-size_t bf_add_layernorm_bwd_ws_bytes(long long rows, int N);
-int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
-                                const void* d_dy, void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace,
-                                size_t workspace_bytes, int dtype, long long rows, int N, float eps, hipStream_t stream,
-                                const bf_dropout_t* drop = nullptr, void* d_dx = nullptr, const void* d_dy2 = nullptr);

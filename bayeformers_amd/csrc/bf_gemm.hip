@@ -370,3 +370,9 @@ int bf_launch_gemm_nt(const void* d_x, int x_dtype, int64_t x_sample_stride, con
     if (w_dtype == BF_DT_F16) return launch_16_xy<_Float16>(p, x_dtype, y_dtype, BF_DT_F16, aligned, stream);
     BF_FAIL("bf_gemm_nt: bad w dtype %d", w_dtype);
 }
+
+size_t bf_gemm_nt_rows_workspace_bytes(int dtype, int S, int M, int N, int K) {
+    // (whatever the streaming kernel refuses by shape — S, M, N < 1 included — runs the tiled kernel: no scratch)
+    if (bf_gemm_skinny_refuses(dtype, dtype, dtype, S, M, N, K, 0, 0, nullptr, nullptr)) return 0;
+    return bf_gemm_nt_skinny_workspace_bytes(S, M, N, K);
+}

@@ -517,8 +517,8 @@ bool bf_gemm256_nn_supported(int dtype, int S, int M, int Nl, int Kl, const void
     return (long long)M * Kl >= 128 * 128;
 }
 
-bool bf_gemm256_nn_actgrad_supported(int dtype, int S, int M, int Nl, int Kl, const void* d_x, const void* d_w, const void* d_y,
-                                     const void* d_gpre) {
+static bool nn_actgrad_supported(int dtype, int S, int M, int Nl, int Kl, const void* d_x, const void* d_w, const void* d_y,
+                                 const void* d_gpre) {
     if (!bf_gemm256_nn_supported(dtype, S, M, Nl, Kl, d_x, d_w, d_y) || !d_gpre || ((uintptr_t)d_gpre & 15)) return false;
     GemmParams p{};
     p.M = M, p.N = Kl, p.K = Nl;
@@ -528,7 +528,7 @@ bool bf_gemm256_nn_actgrad_supported(int dtype, int S, int M, int Nl, int Kl, co
 int bf_launch_gemm256_nn(const void* d_x, const void* d_w, void* d_y, int dtype, int S, int M, int Nl, int Kl,
                          hipStream_t stream, int segs, const void* d_gpre, int act) {
     if (segs < 1 || segs > 4) BF_FAIL("bf_gemm_nn: 1 to 4 layers (got %d)", segs);
-    if (d_gpre && (segs != 1 || act != BF_ACT_GELU || !bf_gemm256_nn_actgrad_supported(dtype, S, M, Nl, Kl, d_x, d_w, d_y, d_gpre)))
+    if (d_gpre && (segs != 1 || act != BF_ACT_GELU || !nn_actgrad_supported(dtype, S, M, Nl, Kl, d_x, d_w, d_y, d_gpre)))
         BF_FAIL("bf_gemm_nn_actgrad: needs the ring form of the NN GEMM (16-bit, K %% 8 == 0, contraction >= 128), the GELU and one layer");
     GemmParams p{};
     p.x = d_x;
@@ -552,4 +552,39 @@ int bf_launch_gemm256_nn(const void* d_x, const void* d_w, void* d_y, int dtype,
     if (bf_gemm256_r5_supported(p, dtype, dtype)) return bf_launch_gemm256_r5_nn(p, dtype, stream, grid);
     if (dtype == BF_DT_BF16) return launch256_nn<__bf16>(p, stream, grid);
     return launch256_nn<_Float16>(p, stream, grid);
+}
+
+int bf_gemm_tn(const void* d_a, const void* d_bm, float* d_out, int dtype, int batch, int Mc, int N, int K, void* stream) {
+    if (!d_a || !d_bm || !d_out) BF_FAIL("bf_gemm_tn: null pointer");
+    if (!bf_gemm256_tn_supported(dtype, batch, Mc, N, K, d_a, d_bm, d_out))
+        BF_FAIL("bf_gemm_tn: needs a 16-bit dtype, Mc %% 64 == 0, N %% 8 == 0, K %% 8 == 0 and 16-byte aligned pointers");
+    return bf_launch_gemm256_tn(d_a, d_bm, d_out, dtype, batch, Mc, N, K, (hipStream_t)stream);
+}
+
+int bf_gemm_nn(const void* d_x, const void* d_w, void* d_y, int dtype, int S, int M, int N, int K, void* stream) {
+    if (!d_x || !d_w || !d_y) BF_FAIL("bf_gemm_nn: null pointer");
+    if (!bf_gemm256_nn_supported(dtype, S, M, N, K, d_x, d_w, d_y))
+        BF_FAIL("bf_gemm_nn: needs a 16-bit dtype, N %% 64 == 0, K %% 8 == 0, M * K >= 16384 and 16-byte aligned pointers");
+    return bf_launch_gemm256_nn(d_x, d_w, d_y, dtype, S, M, N, K, (hipStream_t)stream);
+}
+
+int bf_gemm_nn_actgrad_supported(const void* d_x, const void* d_w, const void* d_y, const void* d_pre, int dtype, int S, int M,
+                                 int N, int K) {
+    return nn_actgrad_supported(dtype, S, M, N, K, d_x, d_w, d_y, d_pre) ? 1 : 0;
+}
+
+int bf_gemm_nn_actgrad(const void* d_x, const void* d_w, void* d_y, const void* d_pre, int dtype, int S, int M, int N, int K,
+                       int act, void* stream) {
+    if (!d_x || !d_w || !d_y || !d_pre) BF_FAIL("bf_gemm_nn_actgrad: null pointer");
+    if (act != BF_ACT_GELU) BF_FAIL("bf_gemm_nn_actgrad: unknown activation %d", act);
+    return bf_launch_gemm256_nn(d_x, d_w, d_y, dtype, S, M, N, K, (hipStream_t)stream, 1, d_pre, act);
+}
+
+int bf_gemm_nn_layers(const void* d_x, const void* d_w, void* d_y, int dtype, int L, int S, int M, int N, int K,
+                      void* stream) {
+    if (!d_x || !d_w || !d_y) BF_FAIL("bf_gemm_nn_layers: null pointer");
+    if (L < 1 || L > 4) BF_FAIL("bf_gemm_nn_layers: L must be 1..4 (got %d)", L);
+    if (!bf_gemm256_nn_supported(dtype, S, M, N, K, d_x, d_w, d_y) || (long long)L * S * M * N >= (1ll << 40))
+        BF_FAIL("bf_gemm_nn_layers: needs a 16-bit dtype, N %% 64 == 0, K %% 8 == 0, M * K >= 16384 and 16-byte aligned pointers");
+    return bf_launch_gemm256_nn(d_x, d_w, d_y, dtype, S, M, N, K, (hipStream_t)stream, L);
 }

@@ -48,5 +48,3 @@ int bf_launch_gemm256_tn(const void* d_a, const void* d_b, float* d_out, int dty
 bool bf_gemm256_nn_supported(int dtype, int S, int M, int Nl, int Kl, const void* d_x, const void* d_w, const void* d_y);
 int bf_launch_gemm256_nn(const void* d_x, const void* d_w, void* d_y, int dtype, int S, int M, int Nl, int Kl,
                          hipStream_t stream, int segs = 1, const void* d_gpre = nullptr, int act = 0);
-bool bf_gemm256_nn_actgrad_supported(int dtype, int S, int M, int Nl, int Kl, const void* d_x, const void* d_w, const void* d_y,
-                                     const void* d_gpre);

@@ -242,9 +242,9 @@ int launch(SkinnyParams p, hipStream_t stream) {
 
 }  // namespace
 
-int bf_gemm_skinny_max_rows_impl() { return kMaxRows; }
+int bf_gemm_nt_skinny_max_rows(void) { return kMaxRows; }
 
-size_t bf_gemm_skinny_workspace_impl(int S, int M, int N, int K) {
+size_t bf_gemm_nt_skinny_workspace_bytes(int S, int M, int N, int K) {
     if (S < 1 || M < 1 || N < 1 || K < 32) return 0;
     const int sp = skinny_splits(S, N, K);
     return sp > 1 ? (size_t)sp * S * M * N * sizeof(float) : 0;
@@ -259,12 +259,6 @@ const char* bf_gemm_skinny_refuses(int x_dtype, int w_dtype, int y_dtype, int S,
     if (((uintptr_t)d_x | (uintptr_t)d_w | (uintptr_t)(x_sample_stride * 2) | (uintptr_t)(x_row_stride * 2)) & 15)
         return "x, w and the x sample and row strides must be 16-byte aligned";
     return nullptr;
-}
-
-size_t bf_gemm_nt_rows_workspace_impl(int dtype, int S, int M, int N, int K) {
-    // (whatever the streaming kernel refuses by shape runs the tiled kernel: no scratch)
-    if (bf_gemm_skinny_refuses(dtype, dtype, dtype, S, M, N, K, 0, 0, nullptr, nullptr)) return 0;
-    return bf_gemm_skinny_workspace_impl(S, M, N, K);
 }
 
 int bf_launch_gemm_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
@@ -298,4 +292,12 @@ int bf_launch_gemm_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride,
     }
     if (w_dtype == BF_DT_BF16) return launch<__bf16>(p, stream);
     return launch<_Float16>(p, stream);
+}
+
+int bf_gemm_nt_skinny(const void* d_x, int x_dtype, int64_t x_sample_stride, const void* d_w, int w_dtype,
+                      const float* d_bias, void* d_y, int y_dtype, int S, int M, int N, int K, int act, void* d_workspace,
+                      size_t workspace_bytes, void* stream) {
+    if ((uintptr_t)d_y & 7) BF_FAIL("bf_gemm_nt_skinny: y must be 8-byte aligned");
+    return bf_launch_gemm_skinny(d_x, x_dtype, x_sample_stride, d_w, w_dtype, d_bias, d_y, y_dtype, S, M, N, K, act,
+                                 d_workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -200,12 +200,13 @@ __global__ __launch_bounds__(THREADS) void generate_step_kernel(const GenParams 
 
 }  // namespace
 
-int bf_launch_generate_step(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
-                            const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
-                            int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride,
-                            int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids,
-                            int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id, int do_sample,
-                            const uint64_t* d_seed, hipStream_t stream) {
+// bf_generate_step and bf_generate_step_stat_probs (d_stat_probs NULL: the statistics read d_probs)
+static int generate_step(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
+                         const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V, int S,
+                         int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0,
+                         float* d_stats, uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
+                         int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed,
+                         hipStream_t stream) {
     const char* what = "bf_generate_step";
     if (B < 1 || B > 0x7fffffff || V < 1 || S < 1 || max_new_tokens < 1)
         BF_FAIL("%s: B=%lld, V=%lld, S=%d, max_new_tokens=%lld must be positive", what, (long long)B, (long long)V, S,
@@ -248,6 +249,28 @@ int bf_launch_generate_step(const float* d_probs, const float* d_stat_probs, con
     generate_step_kernel<<<(unsigned)B, THREADS, 0, stream>>>(p);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int bf_generate_step(const float* d_probs, const float* d_predictive_entropy, const float* d_expected_entropy,
+                     const float* d_mutual_information, int64_t B, int64_t V, int S, int64_t* d_state,
+                     int64_t max_new_tokens, int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats,
+                     uint8_t* d_finished, int64_t* d_lengths, int64_t* d_next_ids, int64_t* d_positions,
+                     int64_t eos_token_id, int64_t pad_token_id, int do_sample, const uint64_t* d_seed, void* stream) {
+    return generate_step(d_probs, nullptr, d_predictive_entropy, d_expected_entropy, d_mutual_information, B, V, S, d_state,
+                         max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished, d_lengths, d_next_ids, d_positions,
+                         eos_token_id, pad_token_id, do_sample, d_seed, (hipStream_t)stream);
+}
+
+int bf_generate_step_stat_probs(const float* d_probs, const float* d_stat_probs, const float* d_predictive_entropy,
+                                const float* d_expected_entropy, const float* d_mutual_information, int64_t B, int64_t V,
+                                int S, int64_t* d_state, int64_t max_new_tokens, int64_t* d_sequences,
+                                int64_t seq_stride, int64_t T0, float* d_stats, uint8_t* d_finished, int64_t* d_lengths,
+                                int64_t* d_next_ids, int64_t* d_positions, int64_t eos_token_id, int64_t pad_token_id,
+                                int do_sample, const uint64_t* d_seed, void* stream) {
+    if (!d_stat_probs) BF_FAIL("bf_generate_step_stat_probs: NULL argument");
+    return generate_step(d_probs, d_stat_probs, d_predictive_entropy, d_expected_entropy, d_mutual_information, B, V, S,
+                         d_state, max_new_tokens, d_sequences, seq_stride, T0, d_stats, d_finished, d_lengths, d_next_ids,
+                         d_positions, eos_token_id, pad_token_id, do_sample, d_seed, (hipStream_t)stream);
 }
 
 // ---- bf_probs_truncate: top-k / top-p / min-p on the model-average rows ---------------------------------------------
@@ -473,8 +496,9 @@ __global__ __launch_bounds__(TR_THREADS) void probs_truncate_kernel(const TruncP
 
 }  // namespace
 
-int bf_launch_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
-                             float min_p, hipStream_t stream) {
+int bf_probs_truncate(const float* d_probs, float* d_out, int64_t R, int64_t V, int64_t top_k, float top_p,
+                      float min_p, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     const char* what = "bf_probs_truncate";
     if (R < 1 || R > 65535 || V < 1 || V > (int64_t)MAX_TILES * TILE)
         BF_FAIL("%s: R=%lld must be in [1, 65535] and V=%lld in [1, %d]", what, (long long)R, (long long)V,
@@ -605,11 +629,11 @@ void launch_logits_process(const ProcParams& p, bool vec, dim3 grid, hipStream_t
 
 }  // namespace
 
-int bf_launch_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
-                             const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0,
-                             const int64_t* d_step, int64_t step, float repetition_penalty,
-                             int64_t no_repeat_ngram_size, int64_t min_new_tokens, int64_t eos_token_id,
-                             float temperature, hipStream_t stream) {
+int bf_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int64_t row_stride, float* d_out,
+                      const int64_t* d_sequences, int64_t B, int64_t seq_stride, int64_t T0, const int64_t* d_step,
+                      int64_t step, float repetition_penalty, int64_t no_repeat_ngram_size, int64_t min_new_tokens,
+                      int64_t eos_token_id, float temperature, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
     const char* what = "bf_logits_process";
     if (dtype != BF_DT_F32 && dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype=%d is not a BF_DT_*", what, dtype);
     if (B < 1 || B > 65535 || R < B || R % B != 0 || R / B > 0x7fffffff)

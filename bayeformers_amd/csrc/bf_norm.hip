@@ -461,9 +461,10 @@ int launch_embed(const long long* ids, const long long* type_ids, const long lon
 
 }  // namespace
 
-int bf_launch_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta,
-                            int param_dtype, void* d_out, int dtype, long long rows, int N, float eps,
-                            hipStream_t stream, const bf_dropout_t* drop, long long residual_row_stride) {
+// the forward entries' shared worker: drop for the dropout entry, residual_row_stride for the rows entry
+static int add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, int param_dtype,
+                         void* d_out, int dtype, long long rows, int N, float eps, hipStream_t stream,
+                         const bf_dropout_t* drop = nullptr, long long residual_row_stride = 0) {
     if (rows < 0 || N <= 0) BF_FAIL("bf_add_layernorm: bad shape rows=%lld N=%d", rows, N);
     // residual rows that do not lie back to back (the [CLS] rows of a [B*L, N] activation); x and out are always compact
     const long long rs = residual_row_stride ? residual_row_stride : N;
@@ -482,17 +483,39 @@ int bf_launch_add_layernorm(const void* d_x, const void* d_residual, const void*
     BF_FAIL("bf_add_layernorm: unknown dtype %d", dtype);
 }
 
+int bf_add_layernorm(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, int param_dtype,
+                     void* d_out, int dtype, int64_t rows, int N, float eps, void* stream) {
+    return add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps, (hipStream_t)stream);
+}
 
-int bf_launch_embed_layernorm(const long long* d_ids, const long long* d_type_ids, const long long* d_pos_ids,
-                              const void* d_word, const void* d_type, const void* d_pos, const void* d_gamma,
-                              const void* d_beta, int param_dtype, void* d_out, int dtype, long long rows, int N,
-                              int seq_len, long long pos_rows, long long word_rows, long long type_rows,
-                              long long pos_table_rows, float eps, hipStream_t stream) {
+int bf_add_layernorm_rows(const void* d_x, const void* d_residual, int64_t residual_row_stride, const void* d_gamma,
+                          const void* d_beta, int param_dtype, void* d_out, int dtype, int64_t rows, int N, float eps,
+                          void* stream) {
+    if (!d_residual) BF_FAIL("bf_add_layernorm_rows: d_residual is NULL");
+    if (residual_row_stride < N) BF_FAIL("bf_add_layernorm_rows: residual row stride %lld < N=%d", (long long)residual_row_stride, N);
+    return add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps, (hipStream_t)stream, nullptr,
+                         residual_row_stride);
+}
+
+int bf_add_layernorm_dropout(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, int param_dtype,
+                             void* d_out, int dtype, int64_t rows, int N, float eps, float p_drop, uint64_t seed, uint32_t call,
+                             uint32_t site, uint64_t first_group, const uint32_t* d_call, void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_add_layernorm_dropout: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, seed, call, site, first_group, d_call);
+    return add_layernorm(d_x, d_residual, d_gamma, d_beta, param_dtype, d_out, dtype, rows, N, eps, (hipStream_t)stream, &d);
+}
+
+int bf_embed_layernorm(const int64_t* d_ids, const int64_t* d_type_ids, const int64_t* d_pos_ids, const void* d_word,
+                       const void* d_type, const void* d_pos, const void* d_gamma, const void* d_beta, int param_dtype,
+                       void* d_out, int dtype, int64_t rows, int N, int seq_len, int64_t pos_rows, int64_t word_rows,
+                       int64_t type_rows, int64_t pos_table_rows, float eps, void* stream) {
     if (word_rows < 1 || type_rows < 1 || pos_table_rows < 1)
-        BF_FAIL("bf_embed_layernorm: empty table (%lld / %lld / %lld rows)", word_rows, type_rows, pos_table_rows);
+        BF_FAIL("bf_embed_layernorm: empty table (%lld / %lld / %lld rows)", (long long)word_rows, (long long)type_rows,
+                (long long)pos_table_rows);
     if (!d_pos_ids && seq_len > pos_table_rows)
-        BF_FAIL("bf_embed_layernorm: seq_len=%d exceeds the position table (%lld rows)", seq_len, pos_table_rows);
-    if (rows < 0 || N <= 0 || seq_len < 1) BF_FAIL("bf_embed_layernorm: bad shape rows=%lld N=%d seq_len=%d", rows, N, seq_len);
+        BF_FAIL("bf_embed_layernorm: seq_len=%d exceeds the position table (%lld rows)", seq_len, (long long)pos_table_rows);
+    if (rows < 0 || N <= 0 || seq_len < 1)
+        BF_FAIL("bf_embed_layernorm: bad shape rows=%lld N=%d seq_len=%d", (long long)rows, N, seq_len);
     if (rows == 0) return 0;
     if (!d_ids || !d_word || !d_type || !d_pos || !d_gamma || !d_beta || !d_out) BF_FAIL("bf_embed_layernorm: null pointer");
     if (d_pos_ids && pos_rows < 1) BF_FAIL("bf_embed_layernorm: pos_rows must be >= 1 with explicit position ids");
@@ -502,11 +525,12 @@ int bf_launch_embed_layernorm(const long long* d_ids, const long long* d_type_id
     if (al & 15) BF_FAIL("bf_embed_layernorm: pointers must be 16-byte aligned");
     if (param_dtype != dtype && param_dtype != BF_DT_F32) BF_FAIL("bf_embed_layernorm: gamma/beta must be fp32 or the table dtype");
     const bool pf = param_dtype == BF_DT_F32;
+    const long long *ids = (const long long*)d_ids, *type_ids = (const long long*)d_type_ids, *pos_ids = (const long long*)d_pos_ids;
 #define BF_EMB_T(T)                                                                                                     \
-    return pf ? launch_embed<T, float>(d_ids, d_type_ids, d_pos_ids, d_word, d_type, d_pos, d_gamma, d_beta, d_out, rows, N, \
-                                       seq_len, pos_rows, word_rows, type_rows, pos_table_rows, eps, stream)               \
-              : launch_embed<T, T>(d_ids, d_type_ids, d_pos_ids, d_word, d_type, d_pos, d_gamma, d_beta, d_out, rows, N,    \
-                                   seq_len, pos_rows, word_rows, type_rows, pos_table_rows, eps, stream)
+    return pf ? launch_embed<T, float>(ids, type_ids, pos_ids, d_word, d_type, d_pos, d_gamma, d_beta, d_out, rows, N, seq_len, \
+                                       pos_rows, word_rows, type_rows, pos_table_rows, eps, (hipStream_t)stream)              \
+              : launch_embed<T, T>(ids, type_ids, pos_ids, d_word, d_type, d_pos, d_gamma, d_beta, d_out, rows, N, seq_len,    \
+                                   pos_rows, word_rows, type_rows, pos_table_rows, eps, (hipStream_t)stream)
     switch (dtype) {
         case BF_DT_BF16: BF_EMB_T(__bf16);
         case BF_DT_F16: BF_EMB_T(_Float16);
@@ -521,15 +545,16 @@ static int bwd_blocks(long long rows) {
     return (int)(need < kBwdBlocks ? (need < 1 ? 1 : need) : kBwdBlocks);
 }
 
-size_t bf_add_layernorm_bwd_ws_bytes(long long rows, int N) {
+size_t bf_add_layernorm_bwd_workspace_bytes(int64_t rows, int N) {
     if (rows < 1 || N < 1) return 0;
     return (size_t)bwd_blocks(rows) * 2 * N * sizeof(float);
 }
 
-int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
-                                const void* d_dy, void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace,
-                                size_t workspace_bytes, int dtype, long long rows, int N, float eps, hipStream_t stream,
-                                const bf_dropout_t* drop, void* d_dx, const void* d_dy2) {
+// the backward entries' shared worker: drop / d_dx for the dropout entries, d_dy2 for the two-gradient one
+static int add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype, const void* d_dy,
+                             void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace, size_t workspace_bytes, int dtype,
+                             long long rows, int N, float eps, hipStream_t stream, const bf_dropout_t* drop = nullptr,
+                             void* d_dx = nullptr, const void* d_dy2 = nullptr) {
     if ((uintptr_t)d_dy2 & 15) BF_FAIL("bf_add_layernorm_bwd: the second gradient must be 16-byte aligned");
     if (drop && drop->thresh && (!d_dx || ((uintptr_t)d_dx & 15)))
         BF_FAIL("bf_add_layernorm_bwd: dropout needs a 16-byte aligned d_dx (the gradient of the dropped input)");
@@ -544,7 +569,7 @@ int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const v
     if (!d_x || !d_gamma || !d_dy || !d_dz) BF_FAIL("bf_add_layernorm_bwd: null pointer");
     const uintptr_t al = (uintptr_t)d_x | (uintptr_t)d_residual | (uintptr_t)d_gamma | (uintptr_t)d_dy | (uintptr_t)d_dz;
     if (al & 15) BF_FAIL("bf_add_layernorm_bwd: pointers must be 16-byte aligned");
-    const size_t need = bf_add_layernorm_bwd_ws_bytes(rows, N);
+    const size_t need = bf_add_layernorm_bwd_workspace_bytes(rows, N);
     if (!d_workspace || workspace_bytes < need) BF_FAIL("bf_add_layernorm_bwd: workspace too small (%zu < %zu)", workspace_bytes, need);
     const int nb = bwd_blocks(rows);
     float* partial = reinterpret_cast<float*>(d_workspace);
@@ -565,4 +590,31 @@ int bf_launch_add_layernorm_bwd(const void* d_x, const void* d_residual, const v
                        d_dbeta);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+int bf_add_layernorm_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype, const void* d_dy,
+                         void* d_dz, float* d_dgamma, float* d_dbeta, void* d_workspace, size_t workspace_bytes, int dtype,
+                         int64_t rows, int N, float eps, void* stream) {
+    return add_layernorm_bwd(d_x, d_residual, d_gamma, param_dtype, d_dy, d_dz, d_dgamma, d_dbeta, d_workspace, workspace_bytes,
+                             dtype, rows, N, eps, (hipStream_t)stream);
+}
+
+int bf_add_layernorm_dropout_bwd(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype,
+                                 const void* d_dy, void* d_dz, void* d_dx, float* d_dgamma, float* d_dbeta, void* d_workspace,
+                                 size_t workspace_bytes, int dtype, int64_t rows, int N, float eps, float p_drop, uint64_t seed,
+                                 uint32_t call, uint32_t site, uint64_t first_group, const uint32_t* d_call, void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_add_layernorm_dropout_bwd: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, seed, call, site, first_group, d_call);
+    return add_layernorm_bwd(d_x, d_residual, d_gamma, param_dtype, d_dy, d_dz, d_dgamma, d_dbeta, d_workspace, workspace_bytes,
+                             dtype, rows, N, eps, (hipStream_t)stream, &d, d_dx);
+}
+
+int bf_add_layernorm_bwd_sum(const void* d_x, const void* d_residual, const void* d_gamma, int param_dtype, const void* d_dy,
+                             const void* d_dy2, void* d_dz, void* d_dx, float* d_dgamma, float* d_dbeta, void* d_workspace,
+                             size_t workspace_bytes, int dtype, int64_t rows, int N, float eps, float p_drop, uint64_t seed,
+                             uint32_t call, uint32_t site, uint64_t first_group, const uint32_t* d_call, void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_add_layernorm_bwd_sum: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, seed, call, site, first_group, d_call);
+    return add_layernorm_bwd(d_x, d_residual, d_gamma, param_dtype, d_dy, d_dz, d_dgamma, d_dbeta, d_workspace, workspace_bytes,
+                             dtype, rows, N, eps, (hipStream_t)stream, d.thresh ? &d : nullptr, d_dx, d_dy2);
 }

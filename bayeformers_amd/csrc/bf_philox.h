@@ -136,6 +136,21 @@ struct bf_dropout_t {
     // every replay on to fresh masks (the sample counter's scheme, bf_set_sample_counter)
     const uint32_t* d_call;
 };
+// host side: the struct for a dropout entry's arguments
+static inline bf_dropout_t bf_make_dropout(float p_drop, uint64_t seed, uint32_t call, uint32_t site, uint64_t first_group = 0,
+                                           const uint32_t* d_call = nullptr) {
+    bf_dropout_t d;
+    d.d_call = d_call;
+    d.k0 = (uint32_t)seed;
+    d.k1 = (uint32_t)(seed >> 32);
+    d.call = call;
+    d.site = site;
+    d.g0_lo = (uint32_t)first_group;
+    d.g0_hi = (uint32_t)(first_group >> 32);
+    d.thresh = bf_dropout_thresh(p_drop);
+    d.inv_keep = 1.0f / (1.0f - (float)d.thresh / 65536.0f);
+    return d;
+}
 
 #if defined(__HIPCC__) || defined(__HIP__)
 BF_D uint32_t bf_dropout_call(const bf_dropout_t& d) { return d.call + (d.d_call ? *d.d_call : 0u); }

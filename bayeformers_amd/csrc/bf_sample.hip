@@ -499,12 +499,18 @@ size_t bf_sample_partials_bytes(const bf_tensor_t* tensors, int n_tensors, int S
     return bf_align_up((size_t)nblk * (size_t)S * 2 * sizeof(double), 256);
 }
 
-int bf_launch_philox_normal(float* d_out, uint64_t n, int S, uint64_t seed, uint32_t sample_base, uint32_t stream_id,
-                            hipStream_t stream) {
+size_t bf_sample_logprob_workspace_bytes(const bf_tensor_t* tensors, int n_tensors, int S) {
+    if (!tensors || n_tensors < 1 || S < 1) return 0;
+    return bf_sample_partials_bytes(tensors, n_tensors, S);
+}
+
+int bf_philox_normal(float* d_out, uint64_t n, int S, uint64_t seed, uint32_t sample_base, uint32_t stream_id,
+                     void* stream) {
+    if (!d_out && n) BF_FAIL("bf_philox_normal: d_out is NULL");
     if (n == 0 || S <= 0) return 0;
     const uint64_t groups = (n + 3) / 4;
     dim3 grid((uint32_t)((groups + 255) / 256), (uint32_t)S);
-    hipLaunchKernelGGL(bf_philox_normal_kernel, grid, dim3(256), 0, stream, d_out, (unsigned long long)n, S,
+    hipLaunchKernelGGL(bf_philox_normal_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_out, (unsigned long long)n, S,
                        (uint32_t)seed, (uint32_t)(seed >> 32), sample_base, stream_id);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
@@ -617,17 +623,18 @@ static int validate_tensor(const bf_tensor_t& T, int t) {
     return 0;
 }
 
-size_t bf_table_blob_bytes(const bf_tensor_t* tensors, int n_tensors, uint32_t* total_blocks) {
+size_t bf_sample_table_bytes(const bf_tensor_t* tensors, int n_tensors, uint32_t* total_blocks) {
+    if (!tensors || n_tensors < 1) return 0;
     uint64_t blk = 0;
     for (int t = 0; t < n_tensors; ++t) blk += blocks_for(tensors[t].n);
     if (total_blocks) *total_blocks = (uint32_t)blk;
     return bf_align_up((size_t)n_tensors * sizeof(TableEntry), 256) + bf_align_up((size_t)blk * sizeof(uint32_t), 256);
 }
 
-int bf_table_build(const bf_tensor_t* tensors, int n_tensors, void* h_blob, size_t blob_bytes, uint32_t* h_block_begin,
-                   int32_t* h_kinds) {
-    uint32_t total = 0;
-    const size_t need = bf_table_blob_bytes(tensors, n_tensors, &total);
+int bf_sample_table_build(const bf_tensor_t* tensors, int n_tensors, void* h_blob, size_t blob_bytes,
+                          uint32_t* h_block_begin, int32_t* h_kinds) {
+    if (!tensors || n_tensors < 1) BF_FAIL("bf_sample_table_build: no tensors");
+    const size_t need = bf_sample_table_bytes(tensors, n_tensors, nullptr);
     if (!h_blob || blob_bytes < need) BF_FAIL("bf_sample_table_build: blob too small (%zu < %zu bytes)", blob_bytes, need);
     TableEntry* ent = reinterpret_cast<TableEntry*>(h_blob);
     uint32_t* map = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(h_blob) +
@@ -698,11 +705,10 @@ int bf_launch_reduce_partials(const double* d_partials, uint32_t nrows, int S, d
     return 0;
 }
 
-int bf_launch_reduce_groups(const double* d_partials, const uint32_t* d_rows, int G, int S, double* d_out,
-                            hipStream_t stream) {
+int bf_reduce_logprob(const double* d_partials, const uint32_t* d_rows, int G, int S, double* d_out, void* stream) {
     if (!d_partials || !d_rows || !d_out) BF_FAIL("bf_reduce_logprob: NULL argument");
     if (G < 1 || S < 1) BF_FAIL("bf_reduce_logprob: bad G=%d S=%d", G, S);
-    hipLaunchKernelGGL(bf_reduce_groups_kernel, dim3((uint32_t)(2 * S), (uint32_t)G), dim3(256), 0, stream,
+    hipLaunchKernelGGL(bf_reduce_groups_kernel, dim3((uint32_t)(2 * S), (uint32_t)G), dim3(256), 0, (hipStream_t)stream,
                        d_partials, d_rows, S, d_out);
     BF_HIP_CHECK(hipGetLastError());
     return 0;

@@ -914,26 +914,22 @@ def attention_decode_workspace_bytes(q: Tensor, k: Tensor, v: Tensor) -> int:
     return n
 
 
-def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
-                             mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
-                             window: Optional[int] = None) -> Tensor:
-    """Causal attention of Tq new queries against a KV cache (bf_attention_decode_gqa): q [N, H, Tq, D], k / v
-    [N, Hkv, Tk, D] as described by attention_decode_supported; query i sees keys 0 .. Tk - Tq + i.  key_mask: additive
-    fp32 [N, Tk] or None; mask_off: optional 1-element device flag, true = the mask hides nothing.  Returns [N, Tq, H, D]
-    contiguous (a query with no visible key gives 0).  The split partials go to `workspace` (uint8, at least
-    attention_decode_workspace_bytes) or to a fresh tensor of the caching allocator — either way capturable.  window: a
-    sliding window of that many keys (bf_attention_decode_gqa_window): query i sees keys Tk - Tq + i - window + 1 ..
-    Tk - Tq + i; the workspace is the same."""
-    _require_device(q, "attention_forward_decode: q")
+def _attention_decode(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
+                      scaling: float, mask_off: Optional[Tensor], workspace: Optional[Tensor],
+                      window: Optional[int]) -> Tensor:
+    """attention_forward_decode (kv_len None) and attention_forward_decode_len; `name` is the caller's, for the messages."""
+    _require_device(q, f"{name}: q")
     if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
             or k.shape[3] != q.shape[3]:
-        raise _C.BayeFormersAMDError(f"attention_forward_decode: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
+        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
                                      "are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
     if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
             or v.device != q.device:
-        raise _C.BayeFormersAMDError("attention_forward_decode: q, k and v must share one dtype and one device")
+        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one dtype and one device")
     if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
-        raise _C.BayeFormersAMDError("attention_forward_decode: the feature dimension of q, k and v must be contiguous")
+        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q, k and v must be contiguous")
+    if kv_len is not None and (kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device):
+        raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
     N, H, Tq, D = q.shape
     out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
     shape = _decode_shape(q, k, v)
@@ -944,21 +940,36 @@ def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional
     if nbytes:
         ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
         if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
-            raise _C.BayeFormersAMDError(f"attention_forward_decode: the workspace needs {nbytes} device bytes")
+            raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
     if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
                                  or not key_mask.is_contiguous()):
-        raise _C.BayeFormersAMDError("attention_forward_decode: key_mask must be contiguous fp32 [N, Tk]")
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk]")
+    args = [q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
             mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), ws.data_ptr() if ws is not None else None,
-            _TORCH2BF[q.dtype], ctypes.byref(shape))
-    if window is None:
-        _C.check(_C.lib().bf_attention_decode_gqa(*args, float(scaling), _stream_ptr()), "bf_attention_decode_gqa")
-        DECODE_CALLS["fwd"] += 1
-    else:
-        _C.check(_C.lib().bf_attention_decode_gqa_window(*args, int(window), float(scaling), _stream_ptr()),
-                 "bf_attention_decode_gqa_window")
-        DECODE_CALLS["window"] += 1
+            _TORCH2BF[q.dtype], ctypes.byref(shape)]
+    entry, key = "bf_attention_decode_gqa", "fwd"
+    if kv_len is not None:
+        args.insert(5, kv_len.data_ptr())
+        entry, key = entry + "_len", "len"
+    if window is not None:
+        args.append(int(window))
+        entry, key = entry + "_window", "window" if kv_len is None else "len_window"
+    _C.check(getattr(_C.lib(), entry)(*args, float(scaling), _stream_ptr()), entry)
+    DECODE_CALLS[key] += 1
     return out
+
+
+def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
+                             mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+                             window: Optional[int] = None) -> Tensor:
+    """Causal attention of Tq new queries against a KV cache (bf_attention_decode_gqa): q [N, H, Tq, D], k / v
+    [N, Hkv, Tk, D] as described by attention_decode_supported; query i sees keys 0 .. Tk - Tq + i.  key_mask: additive
+    fp32 [N, Tk] or None; mask_off: optional 1-element device flag, true = the mask hides nothing.  Returns [N, Tq, H, D]
+    contiguous (a query with no visible key gives 0).  The split partials go to `workspace` (uint8, at least
+    attention_decode_workspace_bytes) or to a fresh tensor of the caching allocator — either way capturable.  window: a
+    sliding window of that many keys (bf_attention_decode_gqa_window): query i sees keys Tk - Tq + i - window + 1 ..
+    Tk - Tq + i; the workspace is the same."""
+    return _attention_decode("attention_forward_decode", q, k, v, None, key_mask, scaling, mask_off, workspace, window)
 
 
 def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
@@ -970,43 +981,9 @@ def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor
     captured call replays correctly while the cache fills; at L == capacity it is bitwise attention_forward_decode.
     window: a sliding window of that many keys (bf_attention_decode_gqa_len_window): query i sees keys
     L - Tq + i - window + 1 .. L - Tq + i, and the key split is laid over the keys some query sees."""
-    _require_device(q, "attention_forward_decode_len: q")
-    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
-            or k.shape[3] != q.shape[3]:
-        raise _C.BayeFormersAMDError(f"attention_forward_decode_len: q {tuple(q.shape)}, k {tuple(k.shape)}, "
-                                     f"v {tuple(v.shape)} are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
-    if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
-            or v.device != q.device:
-        raise _C.BayeFormersAMDError("attention_forward_decode_len: q, k and v must share one dtype and one device")
-    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
-        raise _C.BayeFormersAMDError("attention_forward_decode_len: the feature dimension of q, k and v must be contiguous")
-    if kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device:
+    if kv_len is None:
         raise _C.BayeFormersAMDError("attention_forward_decode_len: kv_len must be one int64 on the device of q")
-    N, H, Tq, D = q.shape
-    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
-    shape = _decode_shape(q, k, v)
-    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
-    if nbytes < 0:
-        _C.check(1, "bf_attention_decode_workspace_bytes")
-    ws = None
-    if nbytes:
-        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
-            raise _C.BayeFormersAMDError(f"attention_forward_decode_len: the workspace needs {nbytes} device bytes")
-    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
-                                 or not key_mask.is_contiguous()):
-        raise _C.BayeFormersAMDError("attention_forward_decode_len: key_mask must be contiguous fp32 [N, Tk]")
-    args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
-            mask_off.data_ptr() if mask_off is not None else None, kv_len.data_ptr(), out.data_ptr(),
-            ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype], ctypes.byref(shape))
-    if window is None:
-        _C.check(_C.lib().bf_attention_decode_gqa_len(*args, float(scaling), _stream_ptr()), "bf_attention_decode_gqa_len")
-        DECODE_CALLS["len"] += 1
-    else:
-        _C.check(_C.lib().bf_attention_decode_gqa_len_window(*args, int(window), float(scaling), _stream_ptr()),
-                 "bf_attention_decode_gqa_len_window")
-        DECODE_CALLS["len_window"] += 1
-    return out
+    return _attention_decode("attention_forward_decode_len", q, k, v, kv_len, key_mask, scaling, mask_off, workspace, window)
 
 
 GENERATE_CALLS = [0]  # launches of bf_generate_step through generate_step (tests, diagnostics)

@@ -115,6 +115,56 @@ def test_header_and_library_export_the_same_symbols():
     assert _C.lib().bf_version() == _C.ABI_VERSION == 6
 
 
+def _c_type_class(decl):
+    """(class, bytes) of one C parameter or return declaration of the header: pointer, integer of n bytes, float, double."""
+    if "*" in decl:
+        return ("pointer", 8)
+    words = [w for w in re.findall(r"[A-Za-z_][A-Za-z0-9_]*", decl) if w != "const"]
+    assert words, decl
+    base = words[0]  # (a parameter's name, when there is one, follows its type)
+    table = {"float": ("float", 4), "double": ("float", 8), "int": ("int", 4), "int32_t": ("int", 4), "uint32_t": ("int", 4),
+             "int64_t": ("int", 8), "uint64_t": ("int", 8), "size_t": ("int", 8), "void": ("void", 0)}
+    assert base in table, f"unknown C type in {decl!r}"
+    return table[base]
+
+
+def _ctypes_class(t):
+    if t is None:
+        return ("void", 0)
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return ("pointer", ctypes.sizeof(t))
+    code = getattr(t, "_type_", None)
+    if code in ("f", "d"):
+        return ("float", ctypes.sizeof(t))
+    assert code in tuple("bBhHiIlLqQ"), f"unknown ctypes type {t!r}"
+    return ("int", ctypes.sizeof(t))
+
+
+def test_header_prototypes_match_the_ctypes_signatures():
+    """Every prototype of include/bayeformers_amd.h against _C.SYMBOLS: the argument count and, for the return value and
+    each argument, the class and width (pointer, integer of n bytes, float, double).  Not ctypes identity: c_uint64 and
+    c_size_t are one object here and int32_t is int."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "bayeformers_amd.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    header = re.sub(r"^\s*#.*$", "", header, flags=re.M)
+    header = re.sub(r"\{[^{}]*\}", "{}", header)  # struct and enum bodies (none nests)
+    parsed = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ \t\n\*]*?)\b(bf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", header):
+        assert name not in parsed, name
+        params = [a.strip() for a in params.split(",")]
+        if params == ["void"]:
+            params = []
+        parsed[name] = (_c_type_class(ret), [_c_type_class(a) for a in params])
+    assert set(parsed) == set(_C.SYMBOLS) and len(parsed) == 90, set(parsed) ^ set(_C.SYMBOLS)
+    for name, (res, args) in _C.SYMBOLS.items():
+        c_res, c_args = parsed[name]
+        assert _ctypes_class(res) == c_res, (name, "return", res, c_res)
+        assert len(args) == len(c_args), (name, len(args), len(c_args))
+        for i, (a, c) in enumerate(zip(args, c_args)):
+            assert _ctypes_class(a) == c, (name, i, a, c)
+
+
 def test_struct_layout_matches_header():
     # 4 + 3*4 + 5*8 = 56 bytes; tensor = 8+8+8+56+4+4+8 = 96 bytes (natural alignment, as the C compiler lays it out)
     assert ctypes.sizeof(_C.bf_prior_t) == 56 and ctypes.sizeof(_C.bf_tensor_t) == 96
