@@ -340,7 +340,8 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     ([B, T, H, D], None).  Runs bf_attention_fwd (with bf_attention_bwd as its backward when a gradient is needed) when
     it applies (head size 64, T a multiple of 128, no mask or a key-padding mask; attention_probs_dropout runs inside the
     kernels on the Philox keep-mask of csrc/bf_philox.h); anything else goes to the
-    framework's scaled-dot-product attention."""
+    framework's scaled-dot-product attention.  Causal calls (decoders) go to `_causal_attention`, whose kernels take any
+    sequence length; the T % 128 limit here is the encoder kernels' alone."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
@@ -388,8 +389,10 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
 
 def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):
     """The causal half of _attention_interface: bf_attention_fwd_gqa (bf_attention_bwd_gqa behind it) for equal query and
-    key lengths with no mask or _padding_mask_interface's causal mask; a decode step against a KV cache (fewer than 17
-    new queries, no gradient, no dropout) on bf_attention_decode_gqa, or on bf_attention_decode_gqa_len when the cache has
+    key lengths — any length: one that is no multiple of 128 runs the kernels' tail forms, unless `ragged_attention(False)`
+    or BF_NO_RAGGED_ATTENTION sends it to the framework — with no mask or _padding_mask_interface's causal mask; a decode
+    step against a KV cache (fewer than 17 new queries, no gradient, no dropout) on bf_attention_decode_gqa, or on
+    bf_attention_decode_gqa_len when the cache has
     a fixed capacity (the mask carries the filled length `_bf_kv_len`); other masks, longer cached chunks and attention
     dropout go to the framework's scaled-dot-product attention.  A sliding-window mask (`_bf_window`) takes the window
     siblings of the same entries, unless the module's own `sliding_window` argument disagrees with it or the call carries
@@ -428,6 +431,7 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
             return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off, window=window), None
     key_mask = mask_off = None
     usable = (dropout == 0.0 and query.shape[2] == key.shape[2]
+              and (query.shape[2] % 128 == 0 or ragged_attention_enabled())
               and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1]))
     if usable and window is not None:  # the sliding mask of the cache-free sequence (key mask None: nothing padded)
         key_mask = getattr(attention_mask, "_bf_key_mask", None)
@@ -635,6 +639,22 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     out._bf_key_mask = additive
     out._bf_mask_off = visible.all().reshape(1)  # stays on the device
     return out
+
+
+_RAGGED_ATTENTION = [True]
+
+
+def ragged_attention(enable: bool = True) -> None:
+    """Switch the causal attention kernels for sequence lengths that are no multiple of 128 (the tail forms of
+    bf_attention_fwd_gqa / bf_attention_bwd_gqa and their window siblings) on or off for this process;
+    BF_NO_RAGGED_ATTENTION in the environment switches them off too.  Off: such a prefill or training step runs the
+    framework's scaled-dot-product attention, as every length but the multiples of 128 did before.  The switch is part of
+    what a captured forward bakes in (graphs.baked_state): a replayed forward is captured again after a flip."""
+    _RAGGED_ATTENTION[0] = bool(enable)
+
+
+def ragged_attention_enabled() -> bool:
+    return _RAGGED_ATTENTION[0] and os.environ.get("BF_NO_RAGGED_ATTENTION") is None
 
 
 _POOLED_LAST_LAYER = [True]
@@ -1026,7 +1046,9 @@ def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False) -> int:
 def fuse_attention(model: torch.nn.Module) -> bool:
     """Route the wrapped HuggingFace model's attention through bf_attention_fwd: registers an attention function in
     transformers' AttentionInterface (mask format: the scaled-dot-product one) and selects it in the model's config.
-    The function falls back to the framework's attention for anything it does not take.  Returns False (and changes
+    The function falls back to the framework's attention for anything it does not take.  A decoder's causal attention
+    (Llama, Mistral, Qwen2: grouped heads, sliding windows) runs bf_attention_fwd_gqa at any sequence length
+    (`ragged_attention(False)` or BF_NO_RAGGED_ATTENTION: at multiples of 128 only).  Returns False (and changes
     nothing) when the model has no HuggingFace config or transformers lacks the interface.
     A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation
     forwards that ask for neither hidden states nor attentions, everything behind the last layer's key / value

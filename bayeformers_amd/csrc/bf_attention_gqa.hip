@@ -45,8 +45,23 @@ struct GqaParams {
     float scale, scale_log2e;
 };
 
+// The TAIL instantiations run a sequence whose length is no multiple of TQ (any T >= 1): the last tile's missing rows are
+// never read or written.  A load of row >= T re-reads row T - 1 (finite values of the caller's, no branch), keys >= T get
+// a score of -inf (P = 0), queries >= T contribute P = dS = 0 and nothing of theirs is stored: rows < T see the arithmetic
+// of a launch zero-padded to the next multiple of TQ.  The T % TQ == 0 launches keep the instantiations without the flag.
+template <bool TAIL>
+__device__ __forceinline__ int tail_row(int row, int T) {
+    return TAIL ? min(row, T - 1) : row;
+}
+
+template <bool TAIL, typename T, int HD, int NR, int NT>
+__device__ __forceinline__ void stage_rows(const T* base, long long stride, int row0, int rows, char* swz, char* pad, int tid) {
+    if (TAIL) stage_clamped<T, HD, NR, NT>(base, stride, row0, rows - 1, swz, pad, tid);
+    else stage<T, HD, NR, NT>(base, stride, row0, swz, pad, tid);
+}
+
 // ---------------------------------------------------------------------------------------------------- forward
-template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, int MINB>
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, int MINB>
 __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -71,7 +86,8 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
     for (int qi = 0; qi < 2; ++qi)
 #pragma unroll
         for (int dh = 0; dh < NDH; ++dh)
-            qf[qi][dh] = *reinterpret_cast<const frag*>(qb + (long long)(q0 + qi * 16 + li) * p.qs[2] + dh * 32 + lg * 8);
+            qf[qi][dh] = *reinterpret_cast<const frag*>(qb + (long long)tail_row<TAIL>(q0 + qi * 16 + li, p.T) * p.qs[2] +
+                                                        dh * 32 + lg * 8);
 
     f32x4_t o[2][NDB];
 #pragma unroll
@@ -80,13 +96,15 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
         for (int j = 0; j < NDB; ++j) o[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float run_max[2] = {-INFINITY, -INFINITY}, run_sum[2] = {0.f, 0.f};
 
-    const int kend = CAUSAL ? (qt + 1) * TQ : p.T;
+    const int kend = CAUSAL ? (TAIL ? min((qt + 1) * TQ, p.T) : (qt + 1) * TQ) : p.T;
     const int kbeg = LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;  // the tile of the tile's first window key
     for (int key0 = kbeg; key0 < kend; key0 += KT) {
         if (key0 != kbeg) __syncthreads();
-        stage<T, HD, KT, 256>(kb, p.ks[2], key0, ks, nullptr, tid);
-        stage<T, HD, KT, 256>(vb, p.vs[2], key0, nullptr, vs, tid);
-        if (mask && tid < KT / 4)
+        stage_rows<TAIL, T, HD, KT, 256>(kb, p.ks[2], key0, p.T, ks, nullptr, tid);
+        stage_rows<TAIL, T, HD, KT, 256>(vb, p.vs[2], key0, p.T, nullptr, vs, tid);
+        if (TAIL) {  // the dense [B][T] rows are not 16-byte aligned: element-wise, with a bound
+            if (mask && tid < KT) ms[tid] = key0 + tid < p.T ? mask[(long long)b * p.T + key0 + tid] * LOG2E : 0.f;
+        } else if (mask && tid < KT / 4)
             *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
                 *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
         __syncthreads();
@@ -94,6 +112,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi) {
             const int qr0 = q0 + qi * 16;  // the block's first query
+            if (TAIL && qr0 >= p.T) continue;  // no query of the block exists (after the barriers: every wave stages)
             if (CAUSAL && key0 > qr0 + 15) continue;  // the tile lies wholly above the diagonal for these 16 queries
             if (LOCAL && key0 + KT - 1 < qr0 - p.window + 1) continue;  // ... or wholly before their windows
             f32x4_t s[NKB];
@@ -105,6 +124,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
             }
             const bool diag = CAUSAL && key0 + KT - 1 > qr0;
             const bool edge = LOCAL && key0 < qr0 + 16 - p.window;  // the tile crosses a window's lower edge
+            const bool past = TAIL && key0 + KT > p.T;              // the tile crosses the sequence's end
             float mx = -INFINITY;
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -115,6 +135,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
                     s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) s[kbk][j] = -INFINITY;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) s[kbk][j] = -INFINITY;
+                    if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) s[kbk][j] = -INFINITY;
                     mx = fmaxf(mx, s[kbk][j]);
                 }
             }
@@ -150,6 +171,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
         const float inv = run_sum[qi] > 0.f ? 1.0f / run_sum[qi] : 0.f;
+        if (TAIL && q0 + qi * 16 + li >= p.T) continue;  // rows >= T are never written
         if (p.lse && lg == 0)
             p.lse[((long long)b * p.H + h) * p.T + q0 + qi * 16 + li] =
                 run_sum[qi] > 0.f ? run_max[qi] + __builtin_amdgcn_logf(run_sum[qi]) : INFINITY;
@@ -161,7 +183,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
-template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL>
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL>
 __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -190,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
     float delta[2], lse[2];
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
-        const long long q = q0 + qi * 16 + li;
+        const long long q = tail_row<TAIL>(q0 + qi * 16 + li, p.T);  // TAIL: a missing row re-reads the last one
         float part = 0.f;
 #pragma unroll
         for (int dh = 0; dh < NDH; ++dh) {
@@ -204,7 +226,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
         part += __shfl_xor(part, 32);
         delta[qi] = part;
         lse[qi] = p.lse[((long long)b * p.H + h) * p.T + q];
-        if (lg == 0) p.delta[((long long)b * p.H + h) * p.T + q] = part;
+        if (lg == 0 && (!TAIL || q0 + qi * 16 + li < p.T)) p.delta[((long long)b * p.H + h) * p.T + q] = part;
     }
 
     f32x4_t dq[2][NDB];
@@ -213,19 +235,22 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
 #pragma unroll
         for (int j = 0; j < NDB; ++j) dq[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    const int kend = CAUSAL ? (qt + 1) * TQ : p.T;
+    const int kend = CAUSAL ? (TAIL ? min((qt + 1) * TQ, p.T) : (qt + 1) * TQ) : p.T;
     const int kbeg = LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;
     for (int key0 = kbeg; key0 < kend; key0 += KT) {
         if (key0 != kbeg) __syncthreads();
-        stage<T, HD, KT, 256>(kb, p.ks[2], key0, ks, kp, tid);
-        stage<T, HD, KT, 256>(vb, p.vs[2], key0, vs, nullptr, tid);
-        if (mask && tid < KT / 4)
+        stage_rows<TAIL, T, HD, KT, 256>(kb, p.ks[2], key0, p.T, ks, kp, tid);
+        stage_rows<TAIL, T, HD, KT, 256>(vb, p.vs[2], key0, p.T, vs, nullptr, tid);
+        if (TAIL) {  // the dense [B][T] rows are not 16-byte aligned: element-wise, with a bound
+            if (mask && tid < KT) ms[tid] = key0 + tid < p.T ? mask[(long long)b * p.T + key0 + tid] * LOG2E : 0.f;
+        } else if (mask && tid < KT / 4)
             *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
                 *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
         __syncthreads();
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi) {
             const int qr0 = q0 + qi * 16;
+            if (TAIL && qr0 >= p.T) continue;
             if (CAUSAL && key0 > qr0 + 15) continue;
             if (LOCAL && key0 + KT - 1 < qr0 - p.window + 1) continue;
             f32x4_t s[NKB], dp[NKB];
@@ -240,6 +265,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
             }
             const bool diag = CAUSAL && key0 + KT - 1 > qr0;
             const bool edge = LOCAL && key0 < qr0 + 16 - p.window;
+            const bool past = TAIL && key0 + KT > p.T;
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
                 f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
@@ -249,6 +275,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
+                    if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
                     s[kbk][j] = pr * (dp[kbk][j] - delta[qi]);  // dS^T
                 }
             }
@@ -263,6 +290,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
     T* dqb = reinterpret_cast<T*>(p.dq) + ooff;
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
+        if (TAIL && q0 + qi * 16 + li >= p.T) continue;
         T* row = dqb + (long long)(q0 + qi * 16 + li) * ostride;
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
@@ -271,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dK, dV
-template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, int MINB>
+template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, bool TAIL, int MINB>
 __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -291,6 +319,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
     const int kt = blockIdx.z, g = blockIdx.x, b = blockIdx.y;  // causal: the low key tiles are the heavy ones
     const int wkey0 = kt * TQ + wid * 16;                        // the wave's first key
     const long long key = wkey0 + li;
+    const long long krow = tail_row<TAIL>(wkey0 + li, p.T);  // TAIL: a missing key re-reads the last one and is not stored
     const T* kb = reinterpret_cast<const T*>(p.k) + b * p.ks[0] + g * p.ks[1];
     const T* vb = reinterpret_cast<const T*>(p.v) + b * p.vs[0] + g * p.vs[1];
     const long long ostride = (long long)p.H * HD;
@@ -298,10 +327,10 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
     frag kf[NDH], vf[NDH];
 #pragma unroll
     for (int dh = 0; dh < NDH; ++dh) {
-        kf[dh] = *reinterpret_cast<const frag*>(kb + key * p.ks[2] + dh * 32 + lg * 8);
-        vf[dh] = *reinterpret_cast<const frag*>(vb + key * p.vs[2] + dh * 32 + lg * 8);
+        kf[dh] = *reinterpret_cast<const frag*>(kb + krow * p.ks[2] + dh * 32 + lg * 8);
+        vf[dh] = *reinterpret_cast<const frag*>(vb + krow * p.vs[2] + dh * 32 + lg * 8);
     }
-    const float mk = mask ? mask[(long long)b * p.T + key] * LOG2E : 0.f;
+    const float mk = mask ? mask[(long long)b * p.T + krow] * LOG2E : 0.f;
     f32x4_t dk[NDB], dv[NDB];
 #pragma unroll
     for (int j = 0; j < NDB; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -318,13 +347,20 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
         for (int q0 = qbeg; q0 < qend; q0 += QT) {
             if (!first) __syncthreads();
             first = false;
-            stage<T, HD, QT, 512>(qb, p.qs[2], q0, qs, qp, tid);
-            stage<T, HD, QT, 512>(dob, ostride, q0, dos, dop, tid);
-            if (tid < QT / 4) {
+            stage_rows<TAIL, T, HD, QT, 512>(qb, p.qs[2], q0, p.T, qs, qp, tid);
+            stage_rows<TAIL, T, HD, QT, 512>(dob, ostride, q0, p.T, dos, dop, tid);
+            if (TAIL) {  // dense ragged rows are not 16-byte aligned; a missing query gets lse = +inf, delta = 0: P = dS = 0
+                if (tid < QT) {
+                    const bool in = q0 + tid < p.T;
+                    lse_s[tid] = in ? lse_g[q0 + tid] : INFINITY;
+                    del_s[tid] = in ? del_g[q0 + tid] : 0.f;
+                }
+            } else if (tid < QT / 4) {
                 *reinterpret_cast<f32x4_t*>(lse_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(lse_g + q0 + tid * 4);
                 *reinterpret_cast<f32x4_t*>(del_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(del_g + q0 + tid * 4);
             }
             __syncthreads();
+            if (TAIL && wkey0 >= p.T) continue;  // no key of the wave exists (after the barriers: every wave stages)
             if (CAUSAL && q0 + QT - 1 < wkey0) continue;  // every query of the tile precedes the wave's keys
             if (LOCAL && q0 > wkey0 + 15 + p.window - 1) continue;  // ... or lies past all their windows
             f32x4_t s[NQB], dp[NQB];
@@ -339,6 +375,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
             }
             const bool diag = CAUSAL && q0 < wkey0 + 15;
             const bool edge = LOCAL && q0 + QT - 1 > wkey0 + p.window - 1;  // some query lies past a key's window
+            const bool past = TAIL && q0 + QT > p.T;                        // the tile crosses the sequence's end
 #pragma unroll
             for (int qbk = 0; qbk < NQB; ++qbk) {
                 const f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(lse_s + qbk * 16 + lg * 4);
@@ -348,6 +385,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
                     if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
                     if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
+                    if (past && q0 + qbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
                     s[qbk][j] = pr;                          // P
                     dp[qbk][j] = pr * (dp[qbk][j] - d4[j]);  // dS
                 }
@@ -367,6 +405,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
     const long long kvstride = (long long)p.Hkv * HD;
     T* dkb = reinterpret_cast<T*>(p.dk) + ((long long)b * p.T * p.Hkv + g) * HD;
     T* dvb = reinterpret_cast<T*>(p.dv) + ((long long)b * p.T * p.Hkv + g) * HD;
+    if (TAIL && key >= p.T) return;  // keys >= T are never written (no barrier follows)
 #pragma unroll
     for (int db = 0; db < NDB; ++db) {
         *reinterpret_cast<half4*>(dkb + key * kvstride + db * 16 + lg * 4) = __builtin_convertvector(dk[db] * p.scale, half4);
@@ -392,25 +431,32 @@ struct Shape<128> {
 // The tile index is the grid's SLOWEST dimension: the hardware hands consecutive workgroups to the 8 XCDs in turn, so with
 // the tiles fastest (as the BERT kernels order them) every XCD would get the tiles of one position — under a causal mask one
 // XCD all the heaviest — while tiles-slowest issues the heavy tiles of every (head, sequence) first, spread over all XCDs.
-template <typename T, int HD, bool CAUSAL, bool LOCAL>
+// TAIL (T % TQ != 0): one more tile, whose rows >= T the kernels neither read nor write.
+template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL>
 void launch_fwd(const GqaParams& p, hipStream_t stream) {
-    const dim3 grid(p.H, p.B, p.T / TQ);
-    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, Shape<HD>::FWD_MINB>), grid, dim3(256), 0, stream,
-                       p);
+    const dim3 grid(p.H, p.B, (p.T + TQ - 1) / TQ);
+    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, TAIL, Shape<HD>::FWD_MINB>), grid, dim3(256), 0,
+                       stream, p);
 }
 
-template <typename T, int HD, bool CAUSAL, bool LOCAL>
+template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL>
 void launch_bwd(const GqaParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL>), dim3(p.H, p.B, p.T / TQ), dim3(256), 0,
+    const int tiles = (p.T + TQ - 1) / TQ;
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL>), dim3(p.H, p.B, tiles), dim3(256), 0,
                        stream, p);
-    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, Shape<HD>::DKV_MINB>),
-                       dim3(p.Hkv, p.B, p.T / TQ), dim3(512), 0, stream, p);
+    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, TAIL, Shape<HD>::DKV_MINB>),
+                       dim3(p.Hkv, p.B, tiles), dim3(512), 0, stream, p);
 }
 
 template <typename T, int HD, bool CAUSAL, bool LOCAL = false>
 void launch(const GqaParams& p, bool bwd, hipStream_t stream) {
-    if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL>(p, stream);
-    else launch_fwd<T, HD, CAUSAL, LOCAL>(p, stream);
+    if (p.T % TQ) {
+        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, true>(p, stream);
+        else launch_fwd<T, HD, CAUSAL, LOCAL, true>(p, stream);
+    } else {
+        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, false>(p, stream);
+        else launch_fwd<T, HD, CAUSAL, LOCAL, false>(p, stream);
+    }
 }
 
 // local: the sliding-window instantiations (causal only); the others are the kernels the plain entries always ran
@@ -437,8 +483,8 @@ int fill_shape(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int dtype
     if (!s) BF_FAIL("%s: shape is NULL", what);
     if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
     if (s->head_dim != 64 && s->head_dim != 128) BF_FAIL("%s: head size %d (64 or 128)", what, s->head_dim);
-    if (s->B < 1 || s->H < 1 || s->Hkv < 1 || s->T < TQ || s->T % TQ)
-        BF_FAIL("%s: T=%d must be a positive multiple of %d (B=%d, H=%d, Hkv=%d)", what, s->T, TQ, s->B, s->H, s->Hkv);
+    if (s->B < 1 || s->H < 1 || s->Hkv < 1 || s->T < 1)
+        BF_FAIL("%s: T=%d, B=%d, H=%d and Hkv=%d must be at least 1", what, s->T, s->B, s->H, s->Hkv);
     if (s->H % s->Hkv) BF_FAIL("%s: %d query heads do not divide into %d K/V head groups", what, s->H, s->Hkv);
     if (s->B > 65535 || s->H > 65535) BF_FAIL("%s: B or H exceeds the grid", what);
     if (s->causal != 0 && s->causal != 1) BF_FAIL("%s: causal must be 0 or 1", what);
@@ -462,15 +508,16 @@ int fill_shape(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int dtype
     return 0;
 }
 
-// the case bf_attention_fwd / bf_attention_bwd take: non-causal, one K/V head per query head, head size 64, q / k / v
-// element (b, t, h, d) at (b T + t) token_stride + 64 h + d with one token stride
+// the case bf_attention_fwd / bf_attention_bwd take: non-causal, one K/V head per query head, head size 64, T a multiple of
+// 128 (their own limit: a ragged T runs the generic kernels here), q / k / v element (b, t, h, d) at
+// (b T + t) token_stride + 64 h + d with one token stride
 bool bert_case(const bf_attn_gqa_t* s, long long* token_stride) {
     const long long ts = s->q_stride[2];
     const int64_t want[3] = {(int64_t)s->T * ts, 64, ts};
     for (int i = 0; i < 3; ++i)
         if (s->q_stride[i] != want[i] || s->k_stride[i] != want[i] || s->v_stride[i] != want[i]) return false;
     *token_stride = ts;
-    return !s->causal && s->H == s->Hkv && s->head_dim == 64 && ts >= (long long)s->H * 64;
+    return !s->causal && s->H == s->Hkv && s->head_dim == 64 && s->T % TQ == 0 && ts >= (long long)s->H * 64;
 }
 
 // The window entries' extra arguments: causal shapes only, window >= 1 (clamped to T: a wider window hides nothing)

@@ -61,6 +61,22 @@ __device__ __forceinline__ void stage(const T* base, long long stride, int row0,
     }
 }
 
+// ... of a tensor that ends at row `last`: a row past it re-reads row `last` (a finite value of the caller's, never what lies
+// behind the tensor; no branch).  The caller gives such rows no weight and stores nothing for them.
+template <typename T, int HD, int NR, int NT>
+__device__ __forceinline__ void stage_clamped(const T* base, long long stride, int row0, int last, char* swz, char* pad,
+                                              int tid) {
+    constexpr int CPR = HD / 8;
+    static_assert((NR * CPR) % NT == 0, "whole passes");
+#pragma unroll
+    for (int i = 0; i < NR * CPR / NT; ++i) {
+        const int c = tid + NT * i, row = c / CPR, c8 = c % CPR;
+        const f32x4_t x = *reinterpret_cast<const f32x4_t*>(base + (long long)min(row0 + row, last) * stride + c8 * 8);
+        if (swz) *reinterpret_cast<f32x4_t*>(swz + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = x;
+        if (pad) *reinterpret_cast<f32x4_t*>(pad + row * Rows<HD>::PAD + (c8 << 4)) = x;
+    }
+}
+
 // row-operand fragment (16 rows x 32 features, half dh) of block `blk` of a swizzled image: lane (row li, k group lg)
 template <typename T, int HD>
 __device__ __forceinline__ typename Mfma<T>::frag row_frag(const char* swz, int blk, int dh, int li, int lg) {

@@ -772,7 +772,7 @@ def embed_layernorm(ids: Tensor, type_ids: Optional[Tensor], pos_ids: Optional[T
 def attention_supported(q: Tensor, k: Tensor, v: Tensor, causal: bool = False, kv_heads: Optional[int] = None) -> bool:
     """q, k, v as the attention hook gets them: [B, H, T, 64] views of the projections' [B*T, H*64] outputs
     (bf_attention_fwd).  With causal=True or kv_heads given: what bf_attention_fwd_gqa takes instead — q [B, H, T, D],
-    k and v [B, Hkv, T, D] with Hkv (= kv_heads) dividing H, D 64 or 128, T a multiple of 128, each with its own
+    k and v [B, Hkv, T, D] with Hkv (= kv_heads) dividing H, D 64 or 128, any T >= 1, each with its own
     (batch, head, token) strides and a contiguous feature dimension."""
     if not (q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype):
         return False
@@ -794,7 +794,7 @@ def _gqa_supported(q: Tensor, k: Tensor, v: Tensor, kv_heads: Optional[int]) -> 
     Hkv = k.shape[1] if kv_heads is None else int(kv_heads)
     if tuple(k.shape) != (B, Hkv, T, D) or Hkv < 1 or H % Hkv:
         return False
-    if D not in (64, 128) or T < 128 or T % 128 or B > 65535 or H > 65535:
+    if D not in (64, 128) or T < 1 or B > 65535 or H > 65535:  # (any length: T % 128 != 0 runs the kernels' tail forms)
         return False
     return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
                for t in (q, k, v))

@@ -426,11 +426,17 @@ int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const fl
  *   g = h / (H / Hkv).
  * Element (b, t, h, d) of q is at b*q_stride[0] + h*q_stride[1] + t*q_stride[2] + d (k and v: head g, their own strides);
  * the feature dimension is contiguous, every stride a multiple of 8 elements.  head_dim 64 or 128, Hkv divides H,
- * T a multiple of 128, bf16 or fp16, 16-byte aligned pointers.  d_mask / d_mask_off / d_lse as for bf_attention_fwd;
+ * any T >= 1 (T < 1 is refused), bf16 or fp16, 16-byte aligned pointers.  d_mask / d_mask_off / d_lse as for
+ * bf_attention_fwd, dense for every T: d_mask [B][T], d_lse and d_delta [B][H][T], so with T % 4 != 0 only their first row
+ * is 16-byte aligned (the pointer is what is checked).  A T that is no multiple of 128 runs tail forms of the same
+ * kernels: token rows >= T of q, k, v, d_out and d_dout and elements >= T of a mask / lse / delta row are never read, no
+ * output row >= T is written, and rows < T get the arithmetic of a launch zero-padded to the next multiple of 128 (bitwise
+ * its results).  T % 128 == 0 runs the kernels it always ran;
  * a query with no visible key outputs 0 and stores lse = +inf (its gradients are then 0).  d_out, d_dout, d_dq:
  * [B][T][H][head_dim] contiguous; d_dk, d_dv: [B][T][Hkv][head_dim] contiguous, summed over the query heads of a group
- * inside one workgroup (no atomics: deterministic).  Non-causal, Hkv == H, head_dim 64 with the packed strides of
- * bf_attention_fwd runs bf_attention_fwd / bf_attention_bwd themselves. */
+ * inside one workgroup (no atomics: deterministic).  Non-causal, Hkv == H, head_dim 64, T a multiple of 128 with the packed
+ * strides of bf_attention_fwd runs bf_attention_fwd / bf_attention_bwd themselves (those keep their T % 128 limit; the same
+ * call with another T runs the generic kernels here). */
 typedef struct bf_attn_gqa {
     int32_t B, T, H, Hkv, head_dim, causal;  /* causal: 0 or 1 */
     int64_t q_stride[3];                     /* element strides of batch, head, token */

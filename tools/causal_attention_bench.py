@@ -2,15 +2,19 @@
 (is_causal=True, enable_gqa=True), interleaved in one process, and a Bayesian decoder's Monte-Carlo forward with and
 without fuse_attention.
 
-    python tools/causal_attention_bench.py [--kernels] [--model] [--iters N]
+    python tools/causal_attention_bench.py [--kernels] [--model] [--iters N] [--lengths T [T ...]]
 
 Kernel shapes (S*B, H, Hkv, D, T): (a) 16, 16, 4, 64, 1024; (b) 8, 32, 8, 128, 2048; (c) the non-causal kernel at (a).
 Causal forward flops = 2 * 2 * D * T * (T + 1) / 2 per (sequence, head) (QK^T and PV over the visible half), the
 backward 2.5x that; the non-causal forward 4 * D * T^2.  Peak: 2.5 PFLOP/s dense bf16.  Times here are host-timed events
 around each launch sequence (median); kernel-only times come from a rocprofv3 --kernel-trace --stats run of the same
-script.
+script.  --lengths: shapes (a) and (b) at each of the given sequence lengths instead of their own (any T >= 1: a length
+that is no multiple of 128 runs the kernels' tail forms), the same interleaved rounds; prints one line per (shape, T).
+--against LIB: shapes (a) and (b) on this tree's library and on another build of it (e.g. one linked from another commit's
+objects), both loaded into this process and timed in alternating pairs; says whether the two give the same bits.
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -37,11 +41,14 @@ def timed(fn, iters):
     return statistics.median(ts)
 
 
-def kernels(iters):
+def kernels(iters, lengths=None):
     from bayeformers_amd import ops
 
+    shapes = SHAPES
+    if lengths:
+        shapes = {f"{n}@{T}": SHAPES[n][:4] + (T, True) for n in ("a", "b") for T in lengths}
     rows = []
-    for name, (B, H, Hkv, D, T, causal) in SHAPES.items():
+    for name, (B, H, Hkv, D, T, causal) in shapes.items():
         g = torch.Generator(device="cuda").manual_seed(0)
         q = torch.randn(B, T, H * D, device="cuda", generator=g, dtype=torch.bfloat16).view(B, T, H, D).transpose(1, 2)
         k, v = (torch.randn(B, T, Hkv * D, device="cuda", generator=g, dtype=torch.bfloat16).view(B, T, Hkv, D).transpose(1, 2)
@@ -62,11 +69,69 @@ def kernels(iters):
         row = {"shape": name, "B": B, "H": H, "Hkv": Hkv, "D": D, "T": T, "causal": causal}
         for key, vals in res.items():
             t = min(vals)
+            row[key + "_rounds_ms"] = [round(x * 1e3, 4) for x in vals]
             flops = fwd_flops * (2.5 if key.endswith("bwd") else 1.0)
             row[key] = {"ms": round(t * 1e3, 4), "tflops": round(flops / t / 1e12, 1), "peak_frac": round(flops / t / PEAK, 3)}
         rows.append(row)
         print(json.dumps(row), flush=True)
     return rows
+
+
+def against(path, iters, pairs=15):
+    """this tree's bf_attention_fwd_gqa / bf_attention_bwd_gqa and those of the library at `path`, in alternating pairs"""
+    from bayeformers_amd import _C, ops
+
+    def load(p):
+        l = ctypes.CDLL(p)
+        for name in ("bf_attention_fwd_gqa", "bf_attention_bwd_gqa", "bf_version"):
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = _C.SYMBOLS[name]
+        assert l.bf_version() == _C.ABI_VERSION, p
+        return l
+
+    libs = {"this": load(_C.LIB_PATH), "other": load(path)}
+    for name in ("a", "b"):
+        B, H, Hkv, D, T, _ = SHAPES[name]
+        g = torch.Generator(device="cuda").manual_seed(0)
+        q = torch.randn(B, T, H * D, device="cuda", generator=g, dtype=torch.bfloat16).view(B, T, H, D).transpose(1, 2)
+        k, v = (torch.randn(B, T, Hkv * D, device="cuda", generator=g, dtype=torch.bfloat16).view(B, T, Hkv, D).transpose(1, 2)
+                for _ in range(2))
+        go = torch.randn(B, T, H, D, device="cuda", generator=g, dtype=torch.bfloat16)
+        shape, scale = ops._gqa_shape(q, k, v, True), D ** -0.5
+        new = lambda *s, dt=torch.bfloat16: torch.empty(*s, device="cuda", dtype=dt)
+        res = {l: dict(out=new(B, T, H, D), lse=new(B, H, T, dt=torch.float32), delta=new(B, H, T, dt=torch.float32),
+                       dq=new(B, T, H, D), dk=new(B, T, Hkv, D), dv=new(B, T, Hkv, D)) for l in libs}
+
+        def fwd(l):
+            r = res[l]
+            assert libs[l].bf_attention_fwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, None, r["out"].data_ptr(),
+                                                r["lse"].data_ptr(), _C.BF_DT_BF16, ctypes.byref(shape), scale,
+                                                ops._stream_ptr()) == 0
+
+        def bwd(l):
+            r = res[l]
+            assert libs[l].bf_attention_bwd_gqa(q.data_ptr(), k.data_ptr(), v.data_ptr(), None, None, r["out"].data_ptr(),
+                                                go.data_ptr(), r["lse"].data_ptr(), r["delta"].data_ptr(), r["dq"].data_ptr(),
+                                                r["dk"].data_ptr(), r["dv"].data_ptr(), _C.BF_DT_BF16, ctypes.byref(shape),
+                                                scale, ops._stream_ptr()) == 0
+
+        for l in libs:
+            for _ in range(3):
+                fwd(l)
+                bwd(l)
+        torch.cuda.synchronize()
+        row = {"shape": name, "T": T, "same_bits": all(torch.equal(res["this"][n], res["other"][n]) for n in res["this"])}
+        for what, fn in (("fwd", fwd), ("bwd", bwd)):
+            t = {"this": [], "other": []}
+            for i in range(pairs):
+                for l in (("this", "other") if i % 2 == 0 else ("other", "this")):
+                    t[l].append(timed(lambda: fn(l), iters) * 1e3)
+            ratios = [a / b for a, b in zip(t["this"], t["other"])]
+            row[what] = {l + "_ms": {"median": round(statistics.median(x), 4), "min": round(min(x), 4), "max": round(max(x), 4)}
+                         for l, x in t.items()}
+            row[what]["pair_ratio_this_over_other"] = {"median": round(statistics.median(ratios), 4),
+                                                       "min": round(min(ratios), 4), "max": round(max(ratios), 4)}
+        print(json.dumps(row), flush=True)
 
 
 def model(iters):
@@ -114,11 +179,18 @@ def main():
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--model", action="store_true")
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--lengths", type=int, nargs="+", default=None, help="time shapes (a) and (b) at these sequence lengths")
+    ap.add_argument("--against", default=None, help="another build of the library: alternating pairs at shapes (a) and (b)")
     a = ap.parse_args()
+    if a.against:
+        against(a.against, a.iters)
+        return
+    if a.lengths:
+        a.kernels = True
     if not (a.kernels or a.model):
         a.kernels = a.model = True
     if a.kernels:
-        kernels(a.iters)
+        kernels(a.iters, a.lengths)
     if a.model:
         model(max(3, a.iters // 4))
 
