@@ -395,15 +395,18 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     bf_attention_decode_gqa_len when the cache has
     a fixed capacity (the mask carries the filled length `_bf_kv_len`); other masks, longer cached chunks and attention
     dropout go to the framework's scaled-dot-product attention.  A sliding-window mask (`_bf_window`) takes the window
-    siblings of the same entries, unless the module's own `sliding_window` argument disagrees with it or the call carries
-    attention sinks (`s_aux`) or logit soft-capping (`softcap`), which the kernels do not apply: those go to the framework."""
+    siblings of the same entries, unless the module's own `sliding_window` argument disagrees with it.  A call that carries
+    attention sinks (`s_aux`) or logit soft-capping (`softcap`), which the kernels do not apply, goes to the framework with
+    or without a window, on the prefill, decode and fixed-capacity paths alike.  Head size 256 (Gemma): a full-attention
+    forward without gradients and without a mask stays on the framework's attention too, whose is_causal form measured
+    faster (ops.prefill_kernel_wins)."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
 
     window = getattr(attention_mask, "_bf_window", None) if attention_mask is not None else None
-    if window is not None and (("sliding_window" in kwargs and kwargs["sliding_window"] != window)
-                               or kwargs.get("s_aux", None) is not None or kwargs.get("softcap", None) is not None):
+    if (window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window) \
+            or kwargs.get("s_aux", None) is not None or kwargs.get("softcap", None) is not None:
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     kv_len = getattr(attention_mask, "_bf_kv_len", None) if attention_mask is not None else None
     # the keys a decode step reads: all Tk, or with a window the ~W + Tq - 1 some query sees (decode_kernel_wins' Tk)
@@ -432,7 +435,9 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     key_mask = mask_off = None
     usable = (dropout == 0.0 and query.shape[2] == key.shape[2]
               and (query.shape[2] % 128 == 0 or ragged_attention_enabled())
-              and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1]))
+              and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1])
+              and ops.prefill_kernel_wins(query.shape[1], key.shape[1], query.shape[2], query.shape[3], need_grad, window,
+                                          masked=attention_mask is not None))
     if usable and window is not None:  # the sliding mask of the cache-free sequence (key mask None: nothing padded)
         key_mask = getattr(attention_mask, "_bf_key_mask", None)
         usable = key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])
@@ -1047,8 +1052,9 @@ def fuse_attention(model: torch.nn.Module) -> bool:
     """Route the wrapped HuggingFace model's attention through bf_attention_fwd: registers an attention function in
     transformers' AttentionInterface (mask format: the scaled-dot-product one) and selects it in the model's config.
     The function falls back to the framework's attention for anything it does not take.  A decoder's causal attention
-    (Llama, Mistral, Qwen2: grouped heads, sliding windows) runs bf_attention_fwd_gqa at any sequence length
-    (`ragged_attention(False)` or BF_NO_RAGGED_ATTENTION: at multiples of 128 only).  Returns False (and changes
+    (Llama, Mistral, Qwen2, Gemma: grouped heads, sliding windows, head size 64, 128 or 256) runs bf_attention_fwd_gqa
+    at any sequence length (`ragged_attention(False)` or BF_NO_RAGGED_ATTENTION: at multiples of 128 only); a call with
+    logit soft-capping or attention sinks (Gemma 2, gpt-oss) goes to the framework.  Returns False (and changes
     nothing) when the model has no HuggingFace config or transformers lacks the interface.
     A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation
     forwards that ask for neither hidden states nor attentions, everything behind the last layer's key / value

@@ -259,7 +259,8 @@ void launch(const DecodeParams& p, hipStream_t stream) {
 int check_shape(const char* what, const bf_attn_decode_t* s, int dtype) {
     if (!s) BF_FAIL("%s: shape is NULL", what);
     if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
-    if (s->head_dim != 64 && s->head_dim != 128) BF_FAIL("%s: head size %d (64 or 128)", what, s->head_dim);
+    if (s->head_dim != 64 && s->head_dim != 128 && s->head_dim != 256)
+        BF_FAIL("%s: head size %d (64, 128 or 256)", what, s->head_dim);
     if (s->Tq < 1 || s->Tq > 16) BF_FAIL("%s: Tq=%d new queries (1 .. 16)", what, s->Tq);
     if (s->Tk < s->Tq) BF_FAIL("%s: Tk=%d cached keys, fewer than Tq=%d", what, s->Tk, s->Tq);
     if (s->N < 1 || s->H < 1 || s->Hkv < 1) BF_FAIL("%s: N=%d, H=%d, Hkv=%d must be positive", what, s->N, s->H, s->Hkv);
@@ -343,10 +344,12 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
     p.scale_log2e = scaling * LOG2E;
     if (dtype == BF_DT_BF16) {
         if (shape->head_dim == 64) launch<__bf16, 64>(p, stream);
-        else launch<__bf16, 128>(p, stream);
+        else if (shape->head_dim == 128) launch<__bf16, 128>(p, stream);
+        else launch<__bf16, 256>(p, stream);
     } else {
         if (shape->head_dim == 64) launch<_Float16, 64>(p, stream);
-        else launch<_Float16, 128>(p, stream);
+        else if (shape->head_dim == 128) launch<_Float16, 128>(p, stream);
+        else launch<_Float16, 256>(p, stream);
     }
     BF_HIP_CHECK(hipGetLastError());
     return 0;

@@ -6,7 +6,7 @@
 //   g = h / (H / Hkv).
 //
 // Siblings of bf_attention.hip / bf_attention_bwd.hip (same online softmax; layouts and LDS images: bf_attention_tiles.h), made
-// generic over the head size (64, 128), the key / query tile of the inner loop, causality and the K/V head group, and
+// generic over the head size (64, 128, 256), the key / query tile of the inner loop, causality and the K/V head group, and
 // reading q, k and v through their own (batch, head, token) strides.  The BERT entries keep their own kernels: the new
 // entry hands the case they cover (non-causal, one K/V head per query head, head size 64, packed heads) to them.
 //   * forward — one 256-thread workgroup per (128 queries, head, sequence), 4 waves x 32 queries, walking key tiles of KT.
@@ -17,13 +17,42 @@
 //   * dk/dv kernel — one 512-thread workgroup per (128 keys, K/V head, sequence), 8 waves x 16 keys, walking the query
 //     tiles (QT) of every query head of the group in turn: the group sum stays in registers, no atomics, deterministic.
 //     Causal: key tile j visits query tiles from j on; the low key tiles (heavy) come first in the grid.
+//     Head size 256 (Gemma, Qwen3-Next): 256 threads per 64 keys, and so twice the key tiles in the grid (Shape).
 // Rows with no visible key (left padding under a causal mask) output 0 and store lse = +inf, so the backward recomputes
 // P = 0 for them and their gradients are 0.
 #include "bf_attention_tiles.h"
 
 namespace {
 
-constexpr int TQ = 128;   // queries per forward / dq workgroup, keys per dk/dv workgroup
+constexpr int TQ = 128;   // queries per forward / dq workgroup, keys per dk/dv workgroup (head size 256: Shape)
+
+// Tile shapes.  Head size 64: the BERT kernels' (128-key tiles; dk/dv over 128-query tiles, 72 KiB of LDS, 2 workgroups per
+// CU).  Head size 128: 128-key tiles in the forward (68 KiB of LDS: 2 workgroups per CU), 64-key tiles in the dq kernel and
+// 64-query tiles in the dk/dv kernel (50 / 68 KiB), whose 128-row variants would hold one workgroup per CU by LDS alone.
+// Head size 256 keeps a wave's 32 queries of q, dO and dq (dq kernel), or its 16 keys of k, v, dk and dv (dk/dv kernel), in
+// more than the 256 registers that two waves per SIMD leave each lane, so every kernel holds one wave per SIMD, each lane with
+// the whole 512-register file (accumulators in the AGPR half), no scratch: the forward over 64-key tiles (66 KiB of LDS), the
+// dq kernel at one workgroup per CU (DQ_MINB) over 32-key tiles (49 KiB; with 64 its causal form spills 8 - 20 bytes a lane),
+// the dk/dv kernel with 4 waves over 64 keys (DKV_KEYS: 16 keys a wave) and 64-query tiles (133 KiB of the CU's 160).
+template <int HD>
+struct Shape;
+template <>
+struct Shape<64> {
+    static constexpr int FWD_KT = 128, FWD_MINB = 3, DQ_KT = 128, DKV_QT = 128, DKV_MINB = 2;
+    static constexpr int DQ_MINB = 2, DKV_KEYS = TQ;
+};
+// (the head-128 alternatives were measured: profiles/causal_attention.md)
+template <>
+struct Shape<128> {
+    static constexpr int FWD_KT = 128, FWD_MINB = 2, DQ_KT = 64, DKV_QT = 64, DKV_MINB = 1;
+    static constexpr int DQ_MINB = 2, DKV_KEYS = TQ;
+};
+// (measured against the framework's attention: profiles/head256_attention.md)
+template <>
+struct Shape<256> {
+    static constexpr int FWD_KT = 64, FWD_MINB = 1, DQ_KT = 32, DKV_QT = 64, DKV_MINB = 1;
+    static constexpr int DQ_MINB = 1, DKV_KEYS = 64;
+};
 
 struct GqaParams {
     const void* q;
@@ -184,7 +213,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
 template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL>
-__global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
+__global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
@@ -300,10 +329,11 @@ __global__ __launch_bounds__(256, 2) void gqa_bwd_dq_kernel(const GqaParams p) {
 
 // ---------------------------------------------------------------------------------------------------- dK, dV
 template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, bool TAIL, int MINB>
-__global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams p) {
+__global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_kernel(const GqaParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NQB = QT / 16;
+    constexpr int KEYS = Shape<HD>::DKV_KEYS, NT = KEYS * 4;  // keys per workgroup: 16 a wave
     constexpr int S_BYTES = QT * Rows<HD>::SWZ, P_BYTES = QT * Rows<HD>::PAD;
     __shared__ __attribute__((aligned(16))) char smem[2 * S_BYTES + 2 * P_BYTES + 2 * QT * 4];
     char* const qs = smem;                           // Q, swizzled: row operand of S
@@ -317,7 +347,7 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int kt = blockIdx.z, g = blockIdx.x, b = blockIdx.y;  // causal: the low key tiles are the heavy ones
-    const int wkey0 = kt * TQ + wid * 16;                        // the wave's first key
+    const int wkey0 = kt * KEYS + wid * 16;                      // the wave's first key
     const long long key = wkey0 + li;
     const long long krow = tail_row<TAIL>(wkey0 + li, p.T);  // TAIL: a missing key re-reads the last one and is not stored
     const T* kb = reinterpret_cast<const T*>(p.k) + b * p.ks[0] + g * p.ks[1];
@@ -335,9 +365,9 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
 #pragma unroll
     for (int j = 0; j < NDB; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-    const int qbeg = CAUSAL ? kt * TQ : 0;
+    const int qbeg = CAUSAL ? kt * KEYS : 0;
     // LOCAL: up to the query tile of the last query that sees the tile's last key
-    const int qend = LOCAL ? min(p.T, (kt * TQ + TQ - 1 + p.window - 1) / QT * QT + QT) : p.T;
+    const int qend = LOCAL ? min(p.T, (kt * KEYS + KEYS - 1 + p.window - 1) / QT * QT + QT) : p.T;
     bool first = true;
     for (int h = g * p.group; h < (g + 1) * p.group; ++h) {  // the group's query heads, in order: a fixed summation order
         const T* qb = reinterpret_cast<const T*>(p.q) + b * p.qs[0] + h * p.qs[1];
@@ -347,8 +377,8 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
         for (int q0 = qbeg; q0 < qend; q0 += QT) {
             if (!first) __syncthreads();
             first = false;
-            stage_rows<TAIL, T, HD, QT, 512>(qb, p.qs[2], q0, p.T, qs, qp, tid);
-            stage_rows<TAIL, T, HD, QT, 512>(dob, ostride, q0, p.T, dos, dop, tid);
+            stage_rows<TAIL, T, HD, QT, NT>(qb, p.qs[2], q0, p.T, qs, qp, tid);
+            stage_rows<TAIL, T, HD, QT, NT>(dob, ostride, q0, p.T, dos, dop, tid);
             if (TAIL) {  // dense ragged rows are not 16-byte aligned; a missing query gets lse = +inf, delta = 0: P = dS = 0
                 if (tid < QT) {
                     const bool in = q0 + tid < p.T;
@@ -413,21 +443,6 @@ __global__ __launch_bounds__(512, MINB) void gqa_bwd_dkv_kernel(const GqaParams 
     }
 }
 
-// Tile shapes.  Head size 64: the BERT kernels' (128-key tiles; dk/dv over 128-query tiles, 72 KiB of LDS, 2 workgroups per
-// CU).  Head size 128: 128-key tiles in the forward (68 KiB of LDS: 2 workgroups per CU), 64-key tiles in the dq kernel and
-// 64-query tiles in the dk/dv kernel (50 / 68 KiB), whose 128-row variants would hold one workgroup per CU by LDS alone.
-template <int HD>
-struct Shape;
-template <>
-struct Shape<64> {
-    static constexpr int FWD_KT = 128, FWD_MINB = 3, DQ_KT = 128, DKV_QT = 128, DKV_MINB = 2;
-};
-// (the head-128 alternatives were measured: profiles/causal_attention.md)
-template <>
-struct Shape<128> {
-    static constexpr int FWD_KT = 128, FWD_MINB = 2, DQ_KT = 64, DKV_QT = 64, DKV_MINB = 1;
-};
-
 // The tile index is the grid's SLOWEST dimension: the hardware hands consecutive workgroups to the 8 XCDs in turn, so with
 // the tiles fastest (as the BERT kernels order them) every XCD would get the tiles of one position — under a causal mask one
 // XCD all the heaviest — while tiles-slowest issues the heavy tiles of every (head, sequence) first, spread over all XCDs.
@@ -441,11 +456,11 @@ void launch_fwd(const GqaParams& p, hipStream_t stream) {
 
 template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL>
 void launch_bwd(const GqaParams& p, hipStream_t stream) {
-    const int tiles = (p.T + TQ - 1) / TQ;
-    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL>), dim3(p.H, p.B, tiles), dim3(256), 0,
-                       stream, p);
+    constexpr int KEYS = Shape<HD>::DKV_KEYS;  // keys per dk/dv workgroup: its own tile count
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL>), dim3(p.H, p.B, (p.T + TQ - 1) / TQ),
+                       dim3(256), 0, stream, p);
     hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, TAIL, Shape<HD>::DKV_MINB>),
-                       dim3(p.Hkv, p.B, tiles), dim3(512), 0, stream, p);
+                       dim3(p.Hkv, p.B, (p.T + KEYS - 1) / KEYS), dim3(KEYS * 4), 0, stream, p);
 }
 
 template <typename T, int HD, bool CAUSAL, bool LOCAL = false>
@@ -466,10 +481,14 @@ void launch(const GqaParams& p, int D, bool causal, bool local, bool bwd, hipStr
         if (local) launch<T, 64, true, true>(p, bwd, stream);
         else if (causal) launch<T, 64, true>(p, bwd, stream);
         else launch<T, 64, false>(p, bwd, stream);
-    } else {
+    } else if (D == 128) {
         if (local) launch<T, 128, true, true>(p, bwd, stream);
         else if (causal) launch<T, 128, true>(p, bwd, stream);
         else launch<T, 128, false>(p, bwd, stream);
+    } else {
+        if (local) launch<T, 256, true, true>(p, bwd, stream);
+        else if (causal) launch<T, 256, true>(p, bwd, stream);
+        else launch<T, 256, false>(p, bwd, stream);
     }
 }
 
@@ -482,7 +501,8 @@ void dispatch(const GqaParams& p, int dtype, int D, bool causal, bool local, boo
 int fill_shape(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int dtype, float scaling) {
     if (!s) BF_FAIL("%s: shape is NULL", what);
     if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
-    if (s->head_dim != 64 && s->head_dim != 128) BF_FAIL("%s: head size %d (64 or 128)", what, s->head_dim);
+    if (s->head_dim != 64 && s->head_dim != 128 && s->head_dim != 256)
+        BF_FAIL("%s: head size %d (64, 128 or 256)", what, s->head_dim);
     if (s->B < 1 || s->H < 1 || s->Hkv < 1 || s->T < 1)
         BF_FAIL("%s: T=%d, B=%d, H=%d and Hkv=%d must be at least 1", what, s->T, s->B, s->H, s->Hkv);
     if (s->H % s->Hkv) BF_FAIL("%s: %d query heads do not divide into %d K/V head groups", what, s->H, s->Hkv);

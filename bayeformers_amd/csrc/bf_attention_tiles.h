@@ -1,6 +1,6 @@
 // bf_attention_tiles.h — MFMA fragment layouts and LDS images shared by the attention kernels of bf_attention.hip,
 // bf_attention_bwd.hip, bf_attention_gqa.hip and bf_attention_decode.hip (bf16 / fp16 operands, mfma_f32_16x16x32, head
-// size 64 or 128).  The contract all of them lean on:
+// size 64, 128 or 256).  The contract all of them lean on:
 //   * lane (li, lg) = (lane & 15, lane >> 4).  As an operand it holds 8 consecutive features (k group lg) of row / column li.
 //     S^T = K Q^T with the keys as rows leaves it 4 consecutive keys, blk*16 + 4 lg + 0..3, of ONE query li per 16-key block:
 //     a query's softmax statistics are in-lane values + two cross-lane steps (the dk/dv kernels swap the roles);

@@ -772,7 +772,7 @@ def embed_layernorm(ids: Tensor, type_ids: Optional[Tensor], pos_ids: Optional[T
 def attention_supported(q: Tensor, k: Tensor, v: Tensor, causal: bool = False, kv_heads: Optional[int] = None) -> bool:
     """q, k, v as the attention hook gets them: [B, H, T, 64] views of the projections' [B*T, H*64] outputs
     (bf_attention_fwd).  With causal=True or kv_heads given: what bf_attention_fwd_gqa takes instead — q [B, H, T, D],
-    k and v [B, Hkv, T, D] with Hkv (= kv_heads) dividing H, D 64 or 128, any T >= 1, each with its own
+    k and v [B, Hkv, T, D] with Hkv (= kv_heads) dividing H, D 64, 128 or 256, any T >= 1, each with its own
     (batch, head, token) strides and a contiguous feature dimension."""
     if not (q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype):
         return False
@@ -794,7 +794,7 @@ def _gqa_supported(q: Tensor, k: Tensor, v: Tensor, kv_heads: Optional[int]) -> 
     Hkv = k.shape[1] if kv_heads is None else int(kv_heads)
     if tuple(k.shape) != (B, Hkv, T, D) or Hkv < 1 or H % Hkv:
         return False
-    if D not in (64, 128) or T < 1 or B > 65535 or H > 65535:  # (any length: T % 128 != 0 runs the kernels' tail forms)
+    if D not in (64, 128, 256) or T < 1 or B > 65535 or H > 65535:  # (any length: T % 128 != 0 runs the kernels' tail forms)
         return False
     return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
                for t in (q, k, v))
@@ -872,7 +872,7 @@ DECODE_MAX_QUERIES = 16
 
 def attention_decode_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bool = True) -> bool:
     """What bf_attention_decode_gqa takes: q [N, H, Tq, D] (1 <= Tq <= 16), k and v [N, Hkv, Tk, D] with Tq <= Tk, Hkv
-    dividing H, D 64 or 128, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8
+    dividing H, D 64, 128 or 256, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8
     elements) and a contiguous feature dimension.  check_device=False judges the shapes, dtypes and strides alone (CPU or
     meta tensors)."""
     if check_device and not (q.is_cuda and k.is_cuda and v.is_cuda):
@@ -883,7 +883,7 @@ def attention_decode_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bo
         return False
     N, H, Tq, D = q.shape
     Hkv, Tk = k.shape[1], k.shape[2]
-    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in (64, 128):
+    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in (64, 128, 256):
         return False
     if not (1 <= Tq <= DECODE_MAX_QUERIES and Tq <= Tk) or N * Hkv > 65535:
         return False
@@ -894,8 +894,38 @@ def attention_decode_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bo
 def decode_kernel_wins(H: int, Hkv: int, Tq: int, Tk: int, D: int) -> bool:
     """The dispatch rule of cached decode steps, from the measurement of profiles/decode_attention.md: every measured class
     runs faster on bf_attention_decode_gqa than on the framework's SDPA except one query per sequence on plain multi-head
-    attention (one query row per workgroup of 64) with head size 128 and a short cache (Tk 512: 0.93x), which stays on SDPA."""
+    attention (one query row per workgroup of 64) with head size 128 and a short cache (Tk 512: 0.93x), which stays on SDPA.
+    Head size 256 rests on profiles/head256_attention.md: every measured class (H / Hkv 8 / 4, 16 / 16 and 8 / 1, Tq 1 and 4,
+    Tk 512 .. 32768) runs 1.12x .. 14x faster on the kernel — the smallest margin is that same class, multi-head, one query,
+    Tk 512 (37 against 43 us, within SDPA's spread there) — so none of them is sent to SDPA."""
     return not (H == Hkv and Tq == 1 and D == 128 and Tk <= 512)
+
+
+def prefill_kernel_wins(H: int, Hkv: int, T: int, D: int, backward: bool, window: Optional[int] = None,
+                        masked: bool = False) -> bool:
+    """The dispatch rule of cache-free causal calls (prefill, training), beside decode_kernel_wins: True = the kernels,
+    False = the framework's SDPA as the fallback would call it.  `masked`: the call carries a mask, so the fallback would run
+    SDPA over _padding_mask_interface's dense [B, 1, T, T] mask and not its is_causal form.  Head sizes 64 and 128 run the
+    kernels everywhere (profiles/causal_attention.md, ragged_attention.md, sliding_window.md).  Head size 256 rests on
+    profiles/head256_attention.md (bf16, B 4, H / Hkv 8 / 4, 16 / 16 and 8 / 1 at T 512, 2048, 8192, 8 / 4 also at 256,
+    each with and without a padded row, against sdpa_attention_forward in one process; x = SDPA time / kernel time):
+      * a sliding window shorter than T wins all six measured points (8 / 4 only; W 256 .. 4096, T 512 .. 8192: forward
+        1.6x .. 4.8x, forward + backward 1.7x .. 10.9x); other head layouts are extrapolated from them;
+      * forward + backward wins every class (1.19x .. 3.07x) but one: one K/V head, T 512, padded (0.70x), sent to SDPA;
+      * the forward with a mask wins (1.07x .. 1.52x) except multi-head at T 512 (0.95x against spreads of 1.4 / 2.3 %),
+        sent to SDPA;
+      * the forward without a mask loses to SDPA's is_causal form by more than the spread in seven of ten classes
+        (0.40x .. 0.86x) and ties it, inside the spread, in three (8 / 4 at T 256: 0.95x, 16 / 16 at 512: 1.00x, 8 / 1 at
+        2048: 0.97x) whose neighbours in T on either side lose: the ties go with their neighbours, so the whole class is on
+        SDPA and the rule stays monotone in T.
+    T 512 verdicts hold up to 1024, the midpoint (in ratio) to the next measured length; nothing below 256 was timed."""
+    if D != 256 or (window is not None and window < T):
+        return True
+    if backward:
+        return not (masked and Hkv == 1 and T <= 1024)
+    if masked:
+        return not (H == Hkv and T <= 1024)
+    return False
 
 
 def _decode_shape(q: Tensor, k: Tensor, v: Tensor):

@@ -425,7 +425,7 @@ int bf_attention_bwd(const void* d_q, const void* d_k, const void* d_v, const fl
  *   out[b][t][h][:] = sum over keys j (j <= t when causal) of softmax_j(scaling q[b][t][h] . k[b][j][g] + mask[b][j]) v[b][j][g],
  *   g = h / (H / Hkv).
  * Element (b, t, h, d) of q is at b*q_stride[0] + h*q_stride[1] + t*q_stride[2] + d (k and v: head g, their own strides);
- * the feature dimension is contiguous, every stride a multiple of 8 elements.  head_dim 64 or 128, Hkv divides H,
+ * the feature dimension is contiguous, every stride a multiple of 8 elements.  head_dim 64, 128 or 256, Hkv divides H,
  * any T >= 1 (T < 1 is refused), bf16 or fp16, 16-byte aligned pointers.  d_mask / d_mask_off / d_lse as for
  * bf_attention_fwd, dense for every T: d_mask [B][T], d_lse and d_delta [B][H][T], so with T % 4 != 0 only their first row
  * is 16-byte aligned (the pointer is what is checked).  A T that is no multiple of 128 runs tail forms of the same
@@ -458,7 +458,7 @@ int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, cons
  * wrapped decoder while it generates (the layers to_bayesian converts: /root/reference/bayeformers/__init__.py:19-63,
  * /root/reference/bayeformers/convert.py; the Monte-Carlo loop it runs under: examples/bert_glue.py:56-73).  Query i of a
  * sequence sees keys 0 .. Tk - Tq + i.  q element (n, h, i, d) at n q_stride[0] + h q_stride[1] + i q_stride[2] + d, k / v
- * (n, g, j, d) likewise with g = h / (H / Hkv); head_dim 64 or 128; strides non-negative multiples of 8 elements, 16-byte
+ * (n, g, j, d) likewise with g = h / (H / Hkv); head_dim 64, 128 or 256; strides non-negative multiples of 8 elements, 16-byte
  * aligned pointers.  d_mask: additive fp32 [N][Tk] over the keys or NULL, d_mask_off: NULL or a device byte, non-zero =
  * the mask hides nothing.  d_out: [N][Tq][H][head_dim] contiguous; a query with no visible key gives 0.
  * The keys are split into a number of parts that depends on the shape only, and the parts are merged in a fixed order:
