@@ -181,6 +181,17 @@ class bf_pgrad_t(ctypes.Structure):
                 ("n", ctypes.c_uint64), ("stream_id", ctypes.c_uint32), ("splits", ctypes.c_int32)]
 
 
+# what include/bayeformers_amd_softcap.h declares (the soft-cap attention entries, Gemma 2): the arguments of the window
+# entries with int32 window (0 = none) and float softcap before scaling; the decode entry takes a nullable kv_len
+SOFTCAP_SYMBOLS = {
+    "bf_attention_fwd_gqa_softcap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, ctypes.c_float,
+                                          _vp]),
+    "bf_attention_bwd_gqa_softcap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i,
+                                          ctypes.c_float, ctypes.c_float, _vp]),
+    "bf_attention_decode_gqa_softcap": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float,
+                                             ctypes.c_float, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -202,7 +213,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m bayeformers_amd.build` "
                 "(there is no CPU or PyTorch fallback for the Monte-Carlo forward path)")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SOFTCAP_SYMBOLS.items()):
             fn = getattr(l, name)  # AttributeError here = header/library drift
             fn.restype = res
             fn.argtypes = args

@@ -396,8 +396,10 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     a fixed capacity (the mask carries the filled length `_bf_kv_len`); other masks, longer cached chunks and attention
     dropout go to the framework's scaled-dot-product attention.  A sliding-window mask (`_bf_window`) takes the window
     siblings of the same entries, unless the module's own `sliding_window` argument disagrees with it.  A call that carries
-    attention sinks (`s_aux`) or logit soft-capping (`softcap`), which the kernels do not apply, goes to the framework with
-    or without a window, on the prefill, decode and fixed-capacity paths alike.  Head size 256 (Gemma): a full-attention
+    attention sinks (`s_aux`), which the kernels do not apply, goes to the framework with or without a window, on the
+    prefill, decode and fixed-capacity paths alike.  Logit soft-capping (`softcap`, Gemma 2) takes the soft-cap entries
+    (`_softcap_attention`) when `softcap_attention()` is on; with the switch off (the default) such a call goes to the
+    framework's scaled-dot-product attention too, which does NOT apply the cap.  Head size 256 (Gemma): a full-attention
     forward without gradients and without a mask stays on the framework's attention too, whose is_causal form measured
     faster (ops.prefill_kernel_wins)."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
@@ -406,8 +408,12 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
 
     window = getattr(attention_mask, "_bf_window", None) if attention_mask is not None else None
     if (window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window) \
-            or kwargs.get("s_aux", None) is not None or kwargs.get("softcap", None) is not None:
+            or kwargs.get("s_aux", None) is not None \
+            or (kwargs.get("softcap", None) is not None and not softcap_attention_enabled()):
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
+    if kwargs.get("softcap", None) is not None:
+        return _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window,
+                                  float(kwargs["softcap"]))
     kv_len = getattr(attention_mask, "_bf_kv_len", None) if attention_mask is not None else None
     # the keys a decode step reads: all Tk, or with a window the ~W + Tq - 1 some query sees (decode_kernel_wins' Tk)
     read = key.shape[2] if window is None else min(key.shape[2], window + query.shape[2] - 1)
@@ -459,6 +465,71 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     if need_grad:
         return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True), None
     return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off), None
+
+
+def _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window, softcap):
+    """_causal_attention for a call with logit soft-capping (HF Gemma2Attention: softcap = attn_logit_softcapping), under
+    `softcap_attention()`: the same cases on the soft-cap entries — bf_attention_fwd_gqa_softcap (with
+    bf_attention_bwd_gqa_softcap behind it) for prefill and training at any length (subject to `ragged_attention`),
+    bf_attention_decode_gqa_softcap for a step against a cache, with the fill `_bf_kv_len` when its capacity is fixed, each
+    with or without a window and a padding key mask.  The dispatch rules that weigh the kernels against the framework's
+    attention are not consulted: that attention does not compute this function.  What the kernels do not take (attention
+    dropout, a cached chunk of more than 16 queries, other masks, unsupported shapes or dtypes) runs `_softcap_eager`,
+    never the framework's scaled-dot-product attention."""
+    from . import ops
+
+    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+    Tq, Tk = query.shape[2], key.shape[2]
+    marked = attention_mask is not None
+    key_mask = getattr(attention_mask, "_bf_key_mask", None) if marked else None
+    mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+    keys_ok = key_mask is None or tuple(key_mask.shape) == (query.shape[0], Tk)
+    kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
+    plain = not need_grad and dropout == 0.0 and keys_ok
+    if kv_len is not None:  # a step against a fixed-capacity cache
+        if Tq < Tk and plain and ops.attention_decode_supported(query, key, value):
+            return ops.attention_forward_decode_len(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
+                                                    softcap=softcap), None
+    elif Tq < Tk:  # a step against a cache: no mask (one query, nothing padded) or _padding_mask_interface's
+        if plain and ops.attention_decode_supported(query, key, value) \
+                and (not marked or bool(getattr(attention_mask, "_bf_decode", False))):
+            return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off, window=window,
+                                                softcap=softcap), None
+    elif (dropout == 0.0 and Tq == Tk and keys_ok and (Tq % 128 == 0 or ragged_attention_enabled())
+          and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1])
+          # no mask, the sliding mask (key mask None: nothing padded) or the causal padding mask
+          and (not marked or window is not None or (getattr(attention_mask, "_bf_causal", False) and key_mask is not None))):
+        if need_grad:
+            return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True, window, softcap), None
+        return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off, window=window,
+                                         softcap=softcap), None
+    return _softcap_eager(module, query, key, value, attention_mask, dropout, scale, softcap), None
+
+
+def _softcap_eager(module, query, key, value, attention_mask, dropout, scaling, softcap):
+    """The fallback of `_softcap_attention`: the model's own eager chain (transformers' gemma2 eager_attention_forward:
+    repeat_kv, matmul, `/ softcap`, tanh, `* softcap`, `+ mask`, fp32 softmax, dropout, matmul) in plain torch.  The mask
+    arrives in the SDPA format (bool, True = visible) and is turned into the additive one the chain adds; no mask means
+    causal, bottom-right aligned (the module's is_causal).  Returns [B, Tq, H, D]."""
+    B, H, Tq, D = query.shape
+    Tk, rep = key.shape[2], H // key.shape[1]
+    if rep > 1:
+        key = key[:, :, None].expand(B, key.shape[1], rep, Tk, D).reshape(B, H, Tk, D)
+        value = value[:, :, None].expand(B, value.shape[1], rep, Tk, D).reshape(B, H, Tk, D)
+    w = torch.matmul(query, key.transpose(2, 3)) * scaling
+    w = torch.tanh(w / softcap) * softcap
+    lowest = torch.finfo(w.dtype).min
+    if attention_mask is None:
+        if Tq > 1:
+            seen = torch.ones((Tq, Tk), dtype=torch.bool, device=w.device).tril(Tk - Tq)
+            w = w + torch.where(seen, 0.0, lowest).to(w.dtype)
+    elif attention_mask.dtype == torch.bool:
+        w = w + torch.where(attention_mask, 0.0, lowest).to(w.dtype)
+    else:
+        w = w + attention_mask.to(w.dtype)
+    w = torch.nn.functional.softmax(w, dim=-1, dtype=torch.float32).to(query.dtype)
+    w = torch.nn.functional.dropout(w, p=dropout, training=bool(getattr(module, "training", False)))
+    return torch.matmul(w, value).transpose(1, 2).contiguous()
 
 
 def _sliding_window_of(mask_function):
@@ -660,6 +731,25 @@ def ragged_attention(enable: bool = True) -> None:
 
 def ragged_attention_enabled() -> bool:
     return _RAGGED_ATTENTION[0] and os.environ.get("BF_NO_RAGGED_ATTENTION") is None
+
+
+_SOFTCAP_ATTENTION = [False]
+
+
+def softcap_attention(enable: bool = True) -> None:
+    """Switch the soft-cap attention kernels (bf_attention_fwd_gqa_softcap / bf_attention_bwd_gqa_softcap /
+    bf_attention_decode_gqa_softcap) on or off for this process; BF_SOFTCAP_ATTENTION in the environment switches them on
+    too.  OFF by default.  On: a causal attention call that carries `softcap` (HF Gemma 2: attn_logit_softcapping) runs
+    them — prefill, training, cached decode and fixed-capacity decode — and what they do not take runs the model's eager
+    chain with the cap.  Off: such a call goes to the framework's scaled-dot-product attention, which ignores `softcap`:
+    the result is then NOT the model's function (keep such a model on its `eager` attention, or switch this on).  The
+    switch is part of what a captured forward bakes in (graphs.baked_state): a replayed forward is captured again after a
+    flip."""
+    _SOFTCAP_ATTENTION[0] = bool(enable)
+
+
+def softcap_attention_enabled() -> bool:
+    return _SOFTCAP_ATTENTION[0] or os.environ.get("BF_SOFTCAP_ATTENTION") is not None
 
 
 _POOLED_LAST_LAYER = [True]
@@ -1054,7 +1144,10 @@ def fuse_attention(model: torch.nn.Module) -> bool:
     The function falls back to the framework's attention for anything it does not take.  A decoder's causal attention
     (Llama, Mistral, Qwen2, Gemma: grouped heads, sliding windows, head size 64, 128 or 256) runs bf_attention_fwd_gqa
     at any sequence length (`ragged_attention(False)` or BF_NO_RAGGED_ATTENTION: at multiples of 128 only); a call with
-    logit soft-capping or attention sinks (Gemma 2, gpt-oss) goes to the framework.  Returns False (and changes
+    attention sinks (gpt-oss) goes to the framework.  Logit soft-capping (Gemma 2) runs the soft-cap entries
+    (bf_attention_fwd_gqa_softcap and its backward and decode siblings) once `softcap_attention()` or BF_SOFTCAP_ATTENTION
+    switches them on; with that switch off, the default, such a call goes to the framework's scaled-dot-product attention,
+    which ignores the cap — the model then computes another function than its `eager` attention.  Returns False (and changes
     nothing) when the model has no HuggingFace config or transformers lacks the interface.
     A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation
     forwards that ask for neither hidden states nor attentions, everything behind the last layer's key / value

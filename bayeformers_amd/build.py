@@ -31,7 +31,7 @@ def _hipcc():
 
 def _headers():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs.append(os.path.join(INCLUDE, "bayeformers_amd.h"))
+    hs += [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE) if f.endswith(".h")]
     return hs
 
 

@@ -23,6 +23,7 @@
 #include "bf_attention_tiles.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -48,6 +49,14 @@ struct DecodeParams {
     float scale_log2e;
 };
 
+// CAP: the soft-capped logits of bf_attention_gqa.hip's CAP forward (softcap * tanh(scale q.k / softcap), then the mask): a
+// compile-time flag with a parameter block of its own; the instantiations without it compile to the code they had.
+struct DecodeCapParams : DecodeParams {
+    float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
+};
+template <bool CAP>
+using ParamsOf = std::conditional_t<CAP, DecodeCapParams, DecodeParams>;
+
 struct Split {
     int n, keys;  // splits, keys per split (a multiple of KT; the last split ends at Tk)
 };
@@ -72,8 +81,8 @@ Split decode_split(const bf_attn_decode_t* s) {
     return Split{(tiles + per - 1) / per, per * KT};
 }
 
-template <typename T, int HD, bool LOCAL>
-__global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
+template <typename T, int HD, bool LOCAL, bool CAP>
+__global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
@@ -165,7 +174,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeParams p) {
             for (int j = 0; j < 4; ++j) {
                 const int key = key0 + kbk * 16 + lg * 4 + j;
                 const bool seen = key < k_hi && key <= lim && (!LOCAL || key > lim - p.window);
-                s[kbk][j] = seen ? fmaf(s[kbk][j], p.scale_log2e, mk[j]) : -INFINITY;
+                if constexpr (CAP) s[kbk][j] = seen ? fmaf(softcap_tanh(s[kbk][j] * p.cap_x), p.cap_log2e, mk[j]) : -INFINITY;
+                else s[kbk][j] = seen ? fmaf(s[kbk][j], p.scale_log2e, mk[j]) : -INFINITY;
                 mx = fmaxf(mx, s[kbk][j]);
             }
         }
@@ -245,10 +255,14 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(const DecodeParams p)
 }
 
 template <typename T, int HD>
-void launch(const DecodeParams& p, hipStream_t stream) {
+void launch(const DecodeCapParams& cp, bool cap, hipStream_t stream) {
+    const DecodeParams& p = cp;
     const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
-    if (p.window) decode_kernel<T, HD, true><<<grid, 256, 0, stream>>>(p);
-    else decode_kernel<T, HD, false><<<grid, 256, 0, stream>>>(p);
+    if (cap) {
+        if (p.window) decode_kernel<T, HD, true, true><<<grid, 256, 0, stream>>>(cp);
+        else decode_kernel<T, HD, false, true><<<grid, 256, 0, stream>>>(cp);
+    } else if (p.window) decode_kernel<T, HD, true, false><<<grid, 256, 0, stream>>>(p);
+    else decode_kernel<T, HD, false, false><<<grid, 256, 0, stream>>>(p);
     if (p.nsplit > 1) {
         const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
         decode_merge_kernel<T, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
@@ -291,10 +305,10 @@ int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
 
 namespace {
 
-// window 0: the plain entries; >= 1: the sliding-window ones
+// window 0: the plain entries; >= 1: the sliding-window ones.  softcap 0: no cap
 int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
            const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
-           const bf_attn_decode_t* shape, int window, float scaling, hipStream_t stream) {
+           const bf_attn_decode_t* shape, int window, float softcap, float scaling, hipStream_t stream) {
     if (window < 0) BF_FAIL("%s: window=%d must be at least 1", what, window);
     if (check_shape(what, shape, dtype)) return 1;
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
@@ -304,7 +318,7 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
     const Split sp = decode_split(shape);
     if (sp.n > 1 && !d_workspace) BF_FAIL("%s: %d key splits need a workspace of %lld bytes", what, sp.n,
                                           (long long)workspace_bytes(shape));
-    DecodeParams p = {};
+    DecodeCapParams p = {};
     p.q = d_q;
     p.k = d_k;
     p.v = d_v;
@@ -342,14 +356,20 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
         p.vs[i] = shape->v_stride[i];
     }
     p.scale_log2e = scaling * LOG2E;
+    if (softcap != 0.f) {
+        p.cap_x = scaling / softcap;
+        p.cap_log2e = softcap * LOG2E;
+        if (!(p.cap_log2e < INFINITY) || !(fabsf(p.cap_x) < INFINITY))
+            BF_FAIL("%s: softcap=%g: scaling / softcap or softcap * log2(e) is not finite", what, (double)softcap);
+    }
     if (dtype == BF_DT_BF16) {
-        if (shape->head_dim == 64) launch<__bf16, 64>(p, stream);
-        else if (shape->head_dim == 128) launch<__bf16, 128>(p, stream);
-        else launch<__bf16, 256>(p, stream);
+        if (shape->head_dim == 64) launch<__bf16, 64>(p, softcap != 0.f, stream);
+        else if (shape->head_dim == 128) launch<__bf16, 128>(p, softcap != 0.f, stream);
+        else launch<__bf16, 256>(p, softcap != 0.f, stream);
     } else {
-        if (shape->head_dim == 64) launch<_Float16, 64>(p, stream);
-        else if (shape->head_dim == 128) launch<_Float16, 128>(p, stream);
-        else launch<_Float16, 256>(p, stream);
+        if (shape->head_dim == 64) launch<_Float16, 64>(p, softcap != 0.f, stream);
+        else if (shape->head_dim == 128) launch<_Float16, 128>(p, softcap != 0.f, stream);
+        else launch<_Float16, 256>(p, softcap != 0.f, stream);
     }
     BF_HIP_CHECK(hipGetLastError());
     return 0;
@@ -361,7 +381,7 @@ int bf_attention_decode_gqa(const void* d_q, const void* d_k, const void* d_v, c
                             void* d_out, void* d_workspace, int dtype, const bf_attn_decode_t* shape, float scaling,
                             void* stream) {
     return decode("bf_attention_decode_gqa", d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, 0,
-                  scaling, (hipStream_t)stream);
+                  0.f, scaling, (hipStream_t)stream);
 }
 
 int bf_attention_decode_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
@@ -369,7 +389,7 @@ int bf_attention_decode_gqa_window(const void* d_q, const void* d_k, const void*
                                    const bf_attn_decode_t* shape, int32_t window, float scaling, void* stream) {
     const char* what = "bf_attention_decode_gqa_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
-    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, window, scaling,
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, nullptr, d_out, d_workspace, dtype, shape, window, 0.f, scaling,
                   (hipStream_t)stream);
 }
 
@@ -378,7 +398,7 @@ int bf_attention_decode_gqa_len(const void* d_q, const void* d_k, const void* d_
                                 int dtype, const bf_attn_decode_t* shape, float scaling, void* stream) {
     const char* what = "bf_attention_decode_gqa_len";
     if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
-    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, 0, scaling,
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, 0, 0.f, scaling,
                   (hipStream_t)stream);
 }
 
@@ -389,6 +409,18 @@ int bf_attention_decode_gqa_len_window(const void* d_q, const void* d_k, const v
     const char* what = "bf_attention_decode_gqa_len_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
     if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
-    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, scaling,
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, 0.f, scaling,
+                  (hipStream_t)stream);
+}
+
+int bf_attention_decode_gqa_softcap(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                    const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace,
+                                    int dtype, const bf_attn_decode_t* shape, int32_t window, float softcap, float scaling,
+                                    void* stream) {
+    const char* what = "bf_attention_decode_gqa_softcap";
+    if (!(softcap > 0.f) || !(softcap < INFINITY)) BF_FAIL("%s: softcap=%g must be finite and positive", what, (double)softcap);
+    if (window < 0) BF_FAIL("%s: window=%d must be at least 0 (0: no window)", what, window);
+    if (d_kv_len && ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, softcap, scaling,
                   (hipStream_t)stream);
 }

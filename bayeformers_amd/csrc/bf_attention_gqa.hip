@@ -22,6 +22,8 @@
 // P = 0 for them and their gradients are 0.
 #include "bf_attention_tiles.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int TQ = 128;   // queries per forward / dq workgroup, keys per dk/dv workgroup (head size 256: Shape)
@@ -74,6 +76,18 @@ struct GqaParams {
     float scale, scale_log2e;
 };
 
+// The CAP instantiations soft-cap the logits (Gemma 2): the score is softcap * tanh(scale q.k / softcap) in place of
+// scale q.k, in log2 units th * cap_log2e with th = tanh(s * cap_x); the mask and the -inf of the diagonal, the window
+// edge, the tail and the unseen keys come after the cap, and the online softmax is the same.  The backward recomputes th
+// with P and multiplies dS by d tanh = 1 - th^2 (the dk/dv kernel's P for dv goes without).  A compile-time flag with a
+// parameter block and branches of its own: the instantiations without it take the block, keep the statements and compile
+// to the code they had.
+struct GqaCapParams : GqaParams {
+    float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
+};
+template <bool CAP>
+using ParamsOf = std::conditional_t<CAP, GqaCapParams, GqaParams>;
+
 // The TAIL instantiations run a sequence whose length is no multiple of TQ (any T >= 1): the last tile's missing rows are
 // never read or written.  A load of row >= T re-reads row T - 1 (finite values of the caller's, no branch), keys >= T get
 // a score of -inf (P = 0), queries >= T contribute P = dS = 0 and nothing of theirs is stored: rows < T see the arithmetic
@@ -90,8 +104,8 @@ __device__ __forceinline__ void stage_rows(const T* base, long long stride, int 
 }
 
 // ---------------------------------------------------------------------------------------------------- forward
-template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, int MINB>
-__global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, int MINB>
+__global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
@@ -161,7 +175,8 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
                 if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
+                    if constexpr (CAP) s[kbk][j] = fmaf(softcap_tanh(s[kbk][j] * p.cap_x), p.cap_log2e, mk[j]);
+                    else s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) s[kbk][j] = -INFINITY;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) s[kbk][j] = -INFINITY;
                     if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) s[kbk][j] = -INFINITY;
@@ -212,8 +227,8 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const GqaParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
-template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL>
-__global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(const GqaParams p) {
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP>
+__global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(const ParamsOf<CAP> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
@@ -301,6 +316,15 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
                 if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
+                    if constexpr (CAP) {  // (a branch of its own: the plain form below keeps the statements, and the code, it had)
+                        const float th = softcap_tanh(s[kbk][j] * p.cap_x);
+                        float pr = __builtin_amdgcn_exp2f(fmaf(th, p.cap_log2e, mk[j]) - lse[qi]);
+                        if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
+                        if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
+                        if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
+                        s[kbk][j] = pr * (dp[kbk][j] - delta[qi]) * fmaf(-th, th, 1.0f);  // dS^T through the cap
+                        continue;
+                    }
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
@@ -328,8 +352,8 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
 }
 
 // ---------------------------------------------------------------------------------------------------- dK, dV
-template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, bool TAIL, int MINB>
-__global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_kernel(const GqaParams p) {
+template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, int MINB>
+__global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_kernel(const ParamsOf<CAP> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NQB = QT / 16;
@@ -412,6 +436,16 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
                 const f32x4_t d4 = *reinterpret_cast<const f32x4_t*>(del_s + qbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
+                    if constexpr (CAP) {  // (a branch of its own: the plain form below keeps the statements, and the code, it had)
+                        const float th = softcap_tanh(s[qbk][j] * p.cap_x);
+                        float pr = __builtin_amdgcn_exp2f(fmaf(th, p.cap_log2e, mk) - l4[j]);
+                        if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
+                        if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
+                        if (past && q0 + qbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
+                        s[qbk][j] = pr;                                                   // P (for dv: without the factor)
+                        dp[qbk][j] = pr * (dp[qbk][j] - d4[j]) * fmaf(-th, th, 1.0f);  // dS through the cap
+                        continue;
+                    }
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
                     if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
                     if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
@@ -447,31 +481,45 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
 // the tiles fastest (as the BERT kernels order them) every XCD would get the tiles of one position — under a causal mask one
 // XCD all the heaviest — while tiles-slowest issues the heavy tiles of every (head, sequence) first, spread over all XCDs.
 // TAIL (T % TQ != 0): one more tile, whose rows >= T the kernels neither read nor write.
-template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL>
-void launch_fwd(const GqaParams& p, hipStream_t stream) {
+template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP>
+void launch_fwd(const ParamsOf<CAP>& p, hipStream_t stream) {
     const dim3 grid(p.H, p.B, (p.T + TQ - 1) / TQ);
-    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, TAIL, Shape<HD>::FWD_MINB>), grid, dim3(256), 0,
+    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, TAIL, CAP, Shape<HD>::FWD_MINB>), grid, dim3(256), 0,
                        stream, p);
 }
 
-template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL>
-void launch_bwd(const GqaParams& p, hipStream_t stream) {
+template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP>
+void launch_bwd(const ParamsOf<CAP>& p, hipStream_t stream) {
     constexpr int KEYS = Shape<HD>::DKV_KEYS;  // keys per dk/dv workgroup: its own tile count
-    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL>), dim3(p.H, p.B, (p.T + TQ - 1) / TQ),
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL, CAP>), dim3(p.H, p.B, (p.T + TQ - 1) / TQ),
                        dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, TAIL, Shape<HD>::DKV_MINB>),
+    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, TAIL, CAP, Shape<HD>::DKV_MINB>),
                        dim3(p.Hkv, p.B, (p.T + KEYS - 1) / KEYS), dim3(KEYS * 4), 0, stream, p);
 }
 
-template <typename T, int HD, bool CAUSAL, bool LOCAL = false>
-void launch(const GqaParams& p, bool bwd, hipStream_t stream) {
+template <typename T, int HD, bool CAUSAL, bool LOCAL = false, bool CAP = false>
+void launch(const ParamsOf<CAP>& p, bool bwd, hipStream_t stream) {
     if (p.T % TQ) {
-        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, true>(p, stream);
-        else launch_fwd<T, HD, CAUSAL, LOCAL, true>(p, stream);
+        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, true, CAP>(p, stream);
+        else launch_fwd<T, HD, CAUSAL, LOCAL, true, CAP>(p, stream);
     } else {
-        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, false>(p, stream);
-        else launch_fwd<T, HD, CAUSAL, LOCAL, false>(p, stream);
+        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, false, CAP>(p, stream);
+        else launch_fwd<T, HD, CAUSAL, LOCAL, false, CAP>(p, stream);
     }
+}
+
+// the soft-cap instantiations: causal only, with or without a window
+template <typename T, int HD>
+void launch_cap(const GqaCapParams& p, bool local, bool bwd, hipStream_t stream) {
+    if (local) launch<T, HD, true, true, true>(p, bwd, stream);
+    else launch<T, HD, true, false, true>(p, bwd, stream);
+}
+
+template <typename T>
+void launch_cap(const GqaCapParams& p, int D, bool local, bool bwd, hipStream_t stream) {
+    if (D == 64) launch_cap<T, 64>(p, local, bwd, stream);
+    else if (D == 128) launch_cap<T, 128>(p, local, bwd, stream);
+    else launch_cap<T, 256>(p, local, bwd, stream);
 }
 
 // local: the sliding-window instantiations (causal only); the others are the kernels the plain entries always ran
@@ -492,8 +540,13 @@ void launch(const GqaParams& p, int D, bool causal, bool local, bool bwd, hipStr
     }
 }
 
-void dispatch(const GqaParams& p, int dtype, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
-    if (dtype == BF_DT_BF16) launch<__bf16>(p, D, causal, local, bwd, stream);
+// cap: the soft-cap instantiations with their parameter block (fill_softcap: causal shapes only); else the plain block
+void dispatch(const GqaCapParams& cp, bool cap, int dtype, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
+    const GqaParams& p = cp;
+    if (cap) {
+        if (dtype == BF_DT_BF16) launch_cap<__bf16>(cp, D, local, bwd, stream);
+        else launch_cap<_Float16>(cp, D, local, bwd, stream);
+    } else if (dtype == BF_DT_BF16) launch<__bf16>(p, D, causal, local, bwd, stream);
     else launch<_Float16>(p, D, causal, local, bwd, stream);
 }
 
@@ -548,13 +601,24 @@ int fill_window(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int wind
     return 0;
 }
 
-// window 0: the plain entries; >= 1: the sliding-window ones
+// The soft-cap entries' extra argument (finite and > 0: the entries checked it): causal shapes only
+int fill_softcap(const char* what, GqaCapParams& p, const bf_attn_gqa_t* s, float softcap, float scaling) {
+    if (s->causal != 1) BF_FAIL("%s: the soft-cap kernels need a causal shape (causal=%d)", what, s->causal);
+    p.cap_x = scaling / softcap;
+    p.cap_log2e = softcap * LOG2E;
+    if (!(p.cap_log2e < INFINITY) || !(fabsf(p.cap_x) < INFINITY))
+        BF_FAIL("%s: softcap=%g: scaling / softcap or softcap * log2(e) is not finite", what, (double)softcap);
+    return 0;
+}
+
+// window 0: the plain entries; >= 1: the sliding-window ones.  softcap 0: no cap
 int fwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
             const unsigned char* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, int window,
-            float scaling, hipStream_t stream) {
+            float softcap, float scaling, hipStream_t stream) {
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
-    GqaParams p = {};
+    GqaCapParams p = {};
     if (fill_shape(what, p, shape, dtype, scaling)) return 1;
+    if (softcap != 0.f && fill_softcap(what, p, shape, softcap, scaling)) return 1;
     if (window && fill_window(what, p, shape, window)) return 1;
     long long ts;
     if (!window && bert_case(shape, &ts))
@@ -569,19 +633,20 @@ int fwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     p.mask_off = d_mask_off;
     p.out = d_out;
     p.lse = d_lse;
-    dispatch(p, dtype, shape->head_dim, shape->causal, window > 0, false, stream);
+    dispatch(p, softcap != 0.f, dtype, shape->head_dim, shape->causal, window > 0, false, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
             const unsigned char* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse, float* d_delta,
-            void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape, int window, float scaling,
-            hipStream_t stream) {
+            void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape, int window, float softcap,
+            float scaling, hipStream_t stream) {
     if (!d_q || !d_k || !d_v || !d_out || !d_dout || !d_lse || !d_delta || !d_dq || !d_dk || !d_dv)
         BF_FAIL("%s: NULL argument", what);
-    GqaParams p = {};
+    GqaCapParams p = {};
     if (fill_shape(what, p, shape, dtype, scaling)) return 1;
+    if (softcap != 0.f && fill_softcap(what, p, shape, softcap, scaling)) return 1;
     if (window && fill_window(what, p, shape, window)) return 1;
     long long ts;
     if (!window && bert_case(shape, &ts))
@@ -603,7 +668,7 @@ int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     p.dq = d_dq;
     p.dk = d_dk;
     p.dv = d_dv;
-    dispatch(p, dtype, shape->head_dim, shape->causal, window > 0, true, stream);
+    dispatch(p, softcap != 0.f, dtype, shape->head_dim, shape->causal, window > 0, true, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -612,7 +677,7 @@ int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
 
 int bf_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
                          void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
-    return fwd_gqa("bf_attention_fwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, 0, scaling,
+    return fwd_gqa("bf_attention_fwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, 0, 0.f, scaling,
                    (hipStream_t)stream);
 }
 
@@ -621,14 +686,15 @@ int bf_attention_fwd_gqa_window(const void* d_q, const void* d_k, const void* d_
                                 int32_t window, float scaling, void* stream) {
     const char* what = "bf_attention_fwd_gqa_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
-    return fwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, scaling, (hipStream_t)stream);
+    return fwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, 0.f, scaling,
+                   (hipStream_t)stream);
 }
 
 int bf_attention_bwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
                          const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
                          void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
     return bwd_gqa("bf_attention_bwd_gqa", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv,
-                   dtype, shape, 0, scaling, (hipStream_t)stream);
+                   dtype, shape, 0, 0.f, scaling, (hipStream_t)stream);
 }
 
 int bf_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
@@ -638,5 +704,26 @@ int bf_attention_bwd_gqa_window(const void* d_q, const void* d_k, const void* d_
     const char* what = "bf_attention_bwd_gqa_window";
     if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
     return bwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, shape,
-                   window, scaling, (hipStream_t)stream);
+                   window, 0.f, scaling, (hipStream_t)stream);
+}
+
+int bf_attention_fwd_gqa_softcap(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                 const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape,
+                                 int32_t window, float softcap, float scaling, void* stream) {
+    const char* what = "bf_attention_fwd_gqa_softcap";
+    if (!(softcap > 0.f) || !(softcap < INFINITY)) BF_FAIL("%s: softcap=%g must be finite and positive", what, (double)softcap);
+    if (window < 0) BF_FAIL("%s: window=%d must be at least 0 (0: no window)", what, window);
+    return fwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, shape, window, softcap, scaling,
+                   (hipStream_t)stream);
+}
+
+int bf_attention_bwd_gqa_softcap(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                 const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                 float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, const bf_attn_gqa_t* shape,
+                                 int32_t window, float softcap, float scaling, void* stream) {
+    const char* what = "bf_attention_bwd_gqa_softcap";
+    if (!(softcap > 0.f) || !(softcap < INFINITY)) BF_FAIL("%s: softcap=%g must be finite and positive", what, (double)softcap);
+    if (window < 0) BF_FAIL("%s: window=%d must be at least 0 (0: no window)", what, window);
+    return bwd_gqa(what, d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, shape,
+                   window, softcap, scaling, (hipStream_t)stream);
 }

@@ -16,6 +16,17 @@ namespace {
 
 constexpr float LOG2E = 1.4426950408889634f;
 
+// tanh for the soft-capped logits (gfx950 has no tanh instruction): 1 - 2 / (1 + e^2x) from the exp2 and rcp units.  e^2x
+// overflows to +inf (rcp gives 0: th = 1) and underflows to 0 (th = -1): saturation, never NaN, at both ends.  Near 0 that
+// form cancels — its error is an ulp of 1, which is all of a tiny x — so the result is held between x and x - x^3 / 3, which
+// bracket tanh(x) for either sign (one median instruction, no branch): the error is the smaller of the two, and a cap far
+// above the logits gives the uncapped scores to rounding.  (An overflowing x^3 leaves -inf / +inf as the far bound.)
+__device__ __forceinline__ float softcap_tanh(float x) {
+    const float e = __builtin_amdgcn_exp2f(x * (2.0f * LOG2E));
+    const float th = fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + e), 1.0f);
+    return __builtin_amdgcn_fmed3f(th, x, fmaf(x * x * x, -1.0f / 3.0f, x));
+}
+
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 typedef __attribute__((address_space(3))) s16x4_t lds_s16x4;

@@ -803,6 +803,9 @@ def _gqa_supported(q: Tensor, k: Tensor, v: Tensor, kv_heads: Optional[int]) -> 
 # launches of bf_attention_fwd_gqa / bf_attention_bwd_gqa from this process (a test can assert that the causal path ran);
 # "fwd_window" / "bwd_window": of their sliding-window siblings bf_attention_fwd_gqa_window / bf_attention_bwd_gqa_window
 GQA_CALLS = {"fwd": 0, "bwd": 0, "fwd_window": 0, "bwd_window": 0}
+# launches of the soft-cap entries (bf_attention_fwd_gqa_softcap / bf_attention_bwd_gqa_softcap /
+# bf_attention_decode_gqa_softcap without and with a kv_len), with or without a window; they count here alone
+SOFTCAP_CALLS = {"fwd": 0, "bwd": 0, "decode": 0, "decode_len": 0}
 
 
 def _gqa_shape(q: Tensor, k: Tensor, v: Tensor, causal: bool):
@@ -814,12 +817,15 @@ def _gqa_shape(q: Tensor, k: Tensor, v: Tensor, causal: bool):
 
 
 def attention_forward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float, causal: bool = True,
-                          mask_off: Optional[Tensor] = None, want_lse: bool = False, window: Optional[int] = None):
+                          mask_off: Optional[Tensor] = None, want_lse: bool = False, window: Optional[int] = None,
+                          softcap: Optional[float] = None):
     """Causal and / or grouped-query attention (bf_attention_fwd_gqa): q [B, H, T, D], k / v [B, Hkv, T, D] as described by
     attention_supported(..., causal=True); key_mask: additive fp32 [B, T] or None.  Returns [B, T, H, D] contiguous (a
     query with no visible key gives 0) — and, with want_lse, the [B, H, T] fp32 log-sum-exp rows of the backward.
     window: a sliding window of that many keys (bf_attention_fwd_gqa_window; causal only): query i sees keys
-    i - window + 1 .. i."""
+    i - window + 1 .. i.
+    softcap: the logits become softcap * tanh(scaling q.k / softcap) before the mask (bf_attention_fwd_gqa_softcap, with
+    or without a window; causal only); None is the call without it."""
     B, H, T, D = q.shape
     out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device) if want_lse else None
@@ -827,7 +833,11 @@ def attention_forward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Te
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
             mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
             lse.data_ptr() if lse is not None else None, _TORCH2BF[q.dtype], ctypes.byref(shape))
-    if window is None:
+    if softcap is not None:
+        _C.check(_C.lib().bf_attention_fwd_gqa_softcap(*args, int(window or 0), float(softcap), float(scaling),
+                                                       _stream_ptr()), "bf_attention_fwd_gqa_softcap")
+        SOFTCAP_CALLS["fwd"] += 1
+    elif window is None:
         _C.check(_C.lib().bf_attention_fwd_gqa(*args, float(scaling), _stream_ptr()), "bf_attention_fwd_gqa")
         GQA_CALLS["fwd"] += 1
     else:
@@ -839,8 +849,9 @@ def attention_forward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Te
 
 def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], mask_off: Optional[Tensor],
                            out: Tensor, grad_out: Tensor, lse: Tensor, scaling: float, causal: bool = True,
-                           window: Optional[int] = None):
-    """Gradients of attention_forward_gqa (bf_attention_bwd_gqa, or bf_attention_bwd_gqa_window with a window):
+                           window: Optional[int] = None, softcap: Optional[float] = None):
+    """Gradients of attention_forward_gqa (bf_attention_bwd_gqa, bf_attention_bwd_gqa_window with a window, or
+    bf_attention_bwd_gqa_softcap with a softcap: `lse` is then the capped forward's):
     (dq [B, T, H, D], dk [B, T, Hkv, D], dv [B, T, Hkv, D]), contiguous; dk / dv summed over the query heads of each
     group."""
     B, H, T, D = q.shape
@@ -853,7 +864,11 @@ def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[T
     args = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
             mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), go.data_ptr(), lse.data_ptr(),
             delta.data_ptr(), dq.data_ptr(), dkv[0].data_ptr(), dkv[1].data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(shape))
-    if window is None:
+    if softcap is not None:
+        _C.check(_C.lib().bf_attention_bwd_gqa_softcap(*args, int(window or 0), float(softcap), float(scaling),
+                                                       _stream_ptr()), "bf_attention_bwd_gqa_softcap")
+        SOFTCAP_CALLS["bwd"] += 1
+    elif window is None:
         _C.check(_C.lib().bf_attention_bwd_gqa(*args, float(scaling), _stream_ptr()), "bf_attention_bwd_gqa")
         GQA_CALLS["bwd"] += 1
     else:
@@ -946,7 +961,7 @@ def attention_decode_workspace_bytes(q: Tensor, k: Tensor, v: Tensor) -> int:
 
 def _attention_decode(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
                       scaling: float, mask_off: Optional[Tensor], workspace: Optional[Tensor],
-                      window: Optional[int]) -> Tensor:
+                      window: Optional[int], softcap: Optional[float] = None) -> Tensor:
     """attention_forward_decode (kv_len None) and attention_forward_decode_len; `name` is the caller's, for the messages."""
     _require_device(q, f"{name}: q")
     if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
@@ -977,6 +992,12 @@ def _attention_decode(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Option
     args = [q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
             mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), ws.data_ptr() if ws is not None else None,
             _TORCH2BF[q.dtype], ctypes.byref(shape)]
+    if softcap is not None:  # one entry: a nullable kv_len, window 0 = none
+        args.insert(5, kv_len.data_ptr() if kv_len is not None else None)
+        _C.check(_C.lib().bf_attention_decode_gqa_softcap(*args, int(window or 0), float(softcap), float(scaling),
+                                                          _stream_ptr()), "bf_attention_decode_gqa_softcap")
+        SOFTCAP_CALLS["decode" if kv_len is None else "decode_len"] += 1
+        return out
     entry, key = "bf_attention_decode_gqa", "fwd"
     if kv_len is not None:
         args.insert(5, kv_len.data_ptr())
@@ -991,29 +1012,34 @@ def _attention_decode(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Option
 
 def attention_forward_decode(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
                              mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
-                             window: Optional[int] = None) -> Tensor:
+                             window: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
     """Causal attention of Tq new queries against a KV cache (bf_attention_decode_gqa): q [N, H, Tq, D], k / v
     [N, Hkv, Tk, D] as described by attention_decode_supported; query i sees keys 0 .. Tk - Tq + i.  key_mask: additive
     fp32 [N, Tk] or None; mask_off: optional 1-element device flag, true = the mask hides nothing.  Returns [N, Tq, H, D]
     contiguous (a query with no visible key gives 0).  The split partials go to `workspace` (uint8, at least
     attention_decode_workspace_bytes) or to a fresh tensor of the caching allocator — either way capturable.  window: a
     sliding window of that many keys (bf_attention_decode_gqa_window): query i sees keys Tk - Tq + i - window + 1 ..
-    Tk - Tq + i; the workspace is the same."""
-    return _attention_decode("attention_forward_decode", q, k, v, None, key_mask, scaling, mask_off, workspace, window)
+    Tk - Tq + i; the workspace is the same.  softcap: soft-capped logits as attention_forward_gqa's
+    (bf_attention_decode_gqa_softcap), the same workspace again."""
+    return _attention_decode("attention_forward_decode", q, k, v, None, key_mask, scaling, mask_off, workspace, window,
+                             softcap)
 
 
 def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
                                  scaling: float, mask_off: Optional[Tensor] = None,
-                                 workspace: Optional[Tensor] = None, window: Optional[int] = None) -> Tensor:
+                                 workspace: Optional[Tensor] = None, window: Optional[int] = None,
+                                 softcap: Optional[float] = None) -> Tensor:
     """attention_forward_decode over a fixed-capacity cache (bf_attention_decode_gqa_len): k / v [N, Hkv, capacity, D] of
     which the first L = kv_len keys are filled, kv_len a one-element int64 device tensor read by the kernel (keys past it
     are never read).  Query i sees keys 0 .. L - Tq + i; key_mask is [N, capacity].  One launch serves every L, so a
     captured call replays correctly while the cache fills; at L == capacity it is bitwise attention_forward_decode.
     window: a sliding window of that many keys (bf_attention_decode_gqa_len_window): query i sees keys
-    L - Tq + i - window + 1 .. L - Tq + i, and the key split is laid over the keys some query sees."""
+    L - Tq + i - window + 1 .. L - Tq + i, and the key split is laid over the keys some query sees.  softcap:
+    soft-capped logits (bf_attention_decode_gqa_softcap with the kv_len)."""
     if kv_len is None:
         raise _C.BayeFormersAMDError("attention_forward_decode_len: kv_len must be one int64 on the device of q")
-    return _attention_decode("attention_forward_decode_len", q, k, v, kv_len, key_mask, scaling, mask_off, workspace, window)
+    return _attention_decode("attention_forward_decode_len", q, k, v, kv_len, key_mask, scaling, mask_off, workspace, window,
+                             softcap)
 
 
 GENERATE_CALLS = [0]  # launches of bf_generate_step through generate_step (tests, diagnostics)
@@ -1157,18 +1183,20 @@ class AttentionGqaFn(torch.autograd.Function):
     without it).  Keeps q, k, v, the output and one fp32 row statistic per query."""
 
     @staticmethod
-    def forward(ctx, q, k, v, key_mask, mask_off, scaling, causal=True, window=None):
-        out, lse = attention_forward_gqa(q, k, v, key_mask, scaling, causal, mask_off, want_lse=True, window=window)
+    def forward(ctx, q, k, v, key_mask, mask_off, scaling, causal=True, window=None, softcap=None):
+        cap = {} if softcap is None else {"softcap": softcap}
+        out, lse = attention_forward_gqa(q, k, v, key_mask, scaling, causal, mask_off, want_lse=True, window=window, **cap)
         ctx.save_for_backward(q, k, v, out, lse)
         ctx.key_mask, ctx.mask_off, ctx.scaling, ctx.causal, ctx.window = key_mask, mask_off, scaling, causal, window
+        ctx.cap = cap
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         q, k, v, out, lse = ctx.saved_tensors
         dq, dk, dv = attention_backward_gqa(q, k, v, ctx.key_mask, ctx.mask_off, out, grad_out, lse, ctx.scaling, ctx.causal,
-                                            ctx.window)
-        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None
+                                            ctx.window, **ctx.cap)
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None, None
 
 
 def attention_forward(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,

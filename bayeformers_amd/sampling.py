@@ -970,7 +970,7 @@ _FINISHED_EVERY = 8  # graph replays between two all-finished checks (host synch
 # function, which the window kernels then apply over a full-capacity cache): a family joins together with a test of its
 # static / graph generation.  Others with sliding layers — a Llama config that carries layer_types, whose attention
 # ignores them — stay refused.
-_SLIDING_STATIC_FAMILIES = ("mistral", "qwen2", "qwen3")
+_SLIDING_STATIC_FAMILIES = ("mistral", "qwen2", "qwen3", "gemma2")
 
 
 def _static_cache(model: Model, capacity: int):
@@ -981,13 +981,17 @@ def _static_cache(model: Model, capacity: int):
     from transformers import StaticCache
     from transformers.cache_utils import StaticLayer
 
-    from . import _ATTENTION_NAME
+    from . import _ATTENTION_NAME, softcap_attention_enabled
 
     inner = model.model if model.model is not None else model
     config = getattr(inner, "config", None)
     if config is None or getattr(config, "_attn_implementation", None) != _ATTENTION_NAME:
         raise RuntimeError("sample_generate: static_cache / graph need the model's attention routed through the HIP kernels "
                            "— call bayeformers_amd.fuse_attention(model) first")
+    if getattr(config, "attn_logit_softcapping", None) is not None and not softcap_attention_enabled():
+        # (without the switch the decode steps would run the framework's attention, which ignores the cap)
+        raise RuntimeError("sample_generate: static_cache / graph on a config with attn_logit_softcapping need the "
+                           "soft-cap kernels — call bayeformers_amd.softcap_attention() first")
     cache = StaticCache(config=config, max_cache_len=int(capacity))
     if getattr(config, "model_type", None) in _SLIDING_STATIC_FAMILIES:
         cache.layers = [StaticLayer(max_cache_len=int(capacity)) if getattr(layer, "is_sliding", False) else layer

@@ -829,4 +829,8 @@ int bf_mc_predictive_finish(const void* d_partial, int64_t R, int64_t C, int S_t
 #ifdef __cplusplus
 }
 #endif
+
+/* the soft-cap attention entries (Gemma 2), a part of this ABI kept in a file of its own */
+#include "bayeformers_amd_softcap.h"
+
 #endif /* BAYEFORMERS_AMD_H */
