@@ -288,4 +288,88 @@ __device__ __forceinline__ void epilogue_wave(char* scratch, const f32x4_t (&acc
     }
 }
 
+// The LDS image of a 16-row block in epilogue_wave_full: 128-byte rows, the 16-byte chunks of a row XOR-swizzled by
+// (row >> 1) & 7 — the formulas of epilogue_wave's 16-bit case.  (Each epilogue writes and reads its own image, so the two need
+// not agree; epilogue_wave keeps its inline arithmetic because routing it through these helpers reorders instructions in every
+// kernel that uses it.)  Write side: lane (row m_l = lane & 15, q = lane >> 4) holds the 4 consecutive features 16 nb + 4 q of
+// its row; read side: chunk rc of row r.  Byte offsets inside the block.
+__device__ __forceinline__ int epi16_wr_off(int m_l, int q, int nb) {
+    return m_l * 128 + (((nb * 2 + (q >> 1)) ^ ((m_l >> 1) & 7)) << 4) + (q & 1) * 8;
+}
+__device__ __forceinline__ int epi16_rd_off(int r, int rc) { return r * 128 + ((rc ^ ((r >> 1) & 7)) << 4); }
+
+// The epilogue of a FULL tile of 16-bit outputs (every row of the tile's template height inside M, all 256 columns inside
+// N, whole aligned 16-byte chunks, no second output): the same values on the same route as epilogue_wave — act() on the
+// fp32 accumulators, rounded once, through the wave's two 2 KiB slices, out as nontemporal 16-byte stores of whole lines —
+// with nothing per lane left to decide and two blocks in flight.
+//  - No predicate, no EXEC change, one wave-uniform choice of the activation per tile instead of one per fragment.
+//  - Stores go through a buffer descriptor whose base is this wave's part of the tile (`yw` = its first element: row 16 wm of
+//    the tile at column 64 wn): ONE per-lane byte offset per tile ((lane / 8) rows + 16 (lane % 8) bytes), and store `it` of
+//    block mb adds (32 mb + 8 it) rows as the SCALAR offset, so the element written is row m0 + 16 wm + 32 mb + 8 it + lane / 8,
+//    column n0 + 64 wn + 8 (lane % 8) — epilogue_wave's mapping.  The descriptor is there for the addressing form (no 64-bit
+//    vector arithmetic), NOT as a guard: the range check of a raw buffer covers the per-lane offset only, never the scalar
+//    offset that carries the row multiple, so nothing clamps a wrong row.  The stores are in range by arithmetic: the caller
+//    takes this path only for a tile whose 32 H rows and 256 columns lie inside the matrix.  All byte offsets are 32-bit: the
+//    caller also requires N <= 2^22, which keeps the largest one, (32 H - 17) rows + 128 bytes at H = 8, below 2^31.
+//  - A wave's LDS operations execute in issue order, so the only waits are the counted ones before a block's rows are stored:
+//        W(0) W(1) R(0) | R(1) W(2) [R(0) landed] S(0) | R(2) W(3) [R(1) landed] S(1) | ...
+//    R(mb + 1) is issued before the stores of block mb and reads what W(mb + 1) wrote a block earlier; W(mb + 2) goes into
+//    the slice of block mb behind R(mb).  The waits are the compiler's own (all these are plain LDS accesses it counts; no
+//    scalar load is outstanding here: the next schedule entry was consumed by the last k-steps): lgkmcnt(11) and (10) in
+//    the steady state — the second read of the block, W(mb + 1), R(mb + 1) and W(mb + 2) are younger than the row being stored —
+//    instead of a full drain, and the read latency of a block is covered by the conversion of the block after next.
+//    The rows of one more block live in registers that the accumulators already written out gave up.
+template <typename YT, int H, bool GELU>
+__device__ __forceinline__ void epilogue_wave_full(char* scratch, const f32x4_t (&acc)[4][H], YT* yw, int N, int lane) {
+    static_assert(sizeof(YT) == 2, "16-bit outputs");
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
+    constexpr int BLK = 16 * 128;                // one slice: 16 rows of 128 bytes
+    asm volatile("" : "+v"(lane));               // offsets recomputed per tile, not hoisted into the k-loop's registers
+    int wr_off[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) wr_off[nb] = epi16_wr_off(lane & 15, lane >> 4, nb);
+    // read side: instruction it covers rows 8 it + lane / 8, chunk lane % 8
+    const int rr = lane >> 3, rc = lane & 7;
+    int rd_off[2];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) rd_off[it] = epi16_rd_off(it * 8 + rr, rc);
+    const unsigned row_bytes = (unsigned)N * 2u;
+    const unsigned voff = (unsigned)rr * row_bytes + (unsigned)rc * 16u;
+    const __amdgpu_buffer_rsrc_t dsc =
+        __builtin_amdgcn_make_buffer_rsrc(yw, 0, (int)((unsigned)(32 * H - 17) * row_bytes + 128u), 0x00020000);
+    auto write_block = [&](int mb) {
+        char* R = scratch + (mb & 1) * BLK;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            const f32x4_t v = GELU ? bf_apply_act<true>(acc[nb][mb], BF_ACT_GELU) : acc[nb][mb];
+            if constexpr (__is_same(YT, __bf16))
+                *reinterpret_cast<bf16x4_t*>(R + wr_off[nb]) = __builtin_convertvector(v, bf16x4_t);
+            else
+                *reinterpret_cast<f16x4_t*>(R + wr_off[nb]) = __builtin_convertvector(v, f16x4_t);
+        }
+    };
+    u32x4_t rows[2][2];
+    auto read_block = [&](int mb) {
+        const char* R = scratch + (mb & 1) * BLK;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) rows[mb & 1][it] = *reinterpret_cast<const u32x4_t*>(R + rd_off[it]);
+    };
+    static_assert(H >= 2, "two blocks in flight");
+    write_block(0);
+    write_block(1);
+    read_block(0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int mb = 0; mb < H; ++mb) {
+        if (mb + 1 < H) read_block(mb + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (mb + 2 < H) write_block(mb + 2);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int it = 0; it < 2; ++it)  // rows (2 mb + wm) 16 + 8 it + rr: nontemporal, 8 whole lines per instruction
+            __builtin_amdgcn_raw_buffer_store_b128(rows[mb & 1][it], dsc, (int)voff, (int)((unsigned)(4 * mb + it) * 8u * row_bytes), 2);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 }  // namespace

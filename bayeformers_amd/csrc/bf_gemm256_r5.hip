@@ -302,6 +302,21 @@ __global__ __launch_bounds__(512, 2) void gemm256_ring5_kernel(const GemmParams 
             YT* y2 = p.y2 ? reinterpret_cast<YT*>(p.y2) + (long long)s * M * N : nullptr;
             const int m_end = min(M, m0 + h * UNIT);
             char* scratch = smem + sc * SLOT_BYTES + wid * 4096;
+            if constexpr (!TRW && !SEG && !AG && sizeof(YT) == 2) {
+                // a full tile (wave-uniform test: every row of the template height and all 256 columns inside the matrix, whole
+                // aligned 16-byte chunks, one output) takes the epilogue without predicates; everything ragged the general one.
+                // N <= 2^22: that epilogue addresses its part of the tile by 32-bit byte offsets, the largest of which is
+                // (32 H - 17) rows of 2 N bytes + 128 (descriptor size; voffset + scalar offset (32 H - 24) rows come to 16 less):
+                // below 2^31 at H = 8 for every such N
+                const bool full = !y2 && h == H && m0 + H * UNIT <= M && n0 + TN <= N && (N & 7) == 0 && N <= (1 << 22) &&
+                                  ((uintptr_t)y & 15) == 0;
+                if (full) {
+                    YT* yw = y + ((long long)(m0 + wm * 16) * N + n0 + wn * 64);
+                    if (p.act == BF_ACT_GELU) epilogue_wave_full<YT, H, true>(scratch, acc, yw, N, lane);
+                    else epilogue_wave_full<YT, H, false>(scratch, acc, yw, N, lane);
+                    return;
+                }
+            }
             const YT* gpre = AG ? reinterpret_cast<const YT*>(p.gpre) + (long long)s * M * N : nullptr;
             epilogue_wave<YT, H, sizeof(YT) == 2 ? 2 : 1>(scratch, acc, y, y2, m0, m_end, n0, N, wm, wn, lane, p.act, gpre);
         };
