@@ -192,6 +192,15 @@ SOFTCAP_SYMBOLS = {
                                              ctypes.c_float, _vp]),
 }
 
+# what include/bayeformers_amd_family_blocks.h declares (the decoder-block entries of the Gemma and Qwen3 families):
+# bf_add_rmsnorm with a second gamma, a weight offset and a second eps; bf_rope_qk with (gamma_q, gamma_k, param_dtype,
+# weight_offset, eps) behind cs_dtype; bf_swiglu's arguments
+FAMILY_BLOCK_SYMBOLS = {
+    "bf_norm_add_rmsnorm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i64, _i, ctypes.c_float, ctypes.c_float, _vp]),
+    "bf_qknorm_rope": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp, _i, _vp, _vp]),
+    "bf_geglu": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -215,6 +224,14 @@ def lib():
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SYMBOLS.items()) + list(SOFTCAP_SYMBOLS.items()):
             fn = getattr(l, name)  # AttributeError here = header/library drift
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in FAMILY_BLOCK_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # a library from before these entries reports the version these bindings expect
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the Gemma / Qwen3 decoder-block entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args
         if l.bf_version() != ABI_VERSION:  # a stale .so called through newer signatures corrupts the stack: refuse it

@@ -1086,33 +1086,278 @@ def _swiglu_mlp_forward(self, x):
     return self.down_proj(ops.SwiGLUFn.apply(gate, up) if rec else ops.swiglu(gate, up))
 
 
-def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False) -> int:
+# ---- the Gemma 1 / 2 / 3 and Qwen3 families (fuse_decoder_blocks(families=...)): inference-time forwards only
+# family -> (decoder layer class, attention class, weight offset of its norms, has q / k norms, sandwich of four norms)
+_FAMILY_LAYERS = {"qwen3": ("Qwen3DecoderLayer", "Qwen3Attention", 0, True, False),
+                  "gemma": ("GemmaDecoderLayer", "GemmaAttention", 1, False, False),
+                  "gemma2": ("Gemma2DecoderLayer", "Gemma2Attention", 1, False, True),
+                  "gemma3": ("Gemma3DecoderLayer", "Gemma3Attention", 1, True, True)}
+_DEFAULT_FAMILIES = ("llama", "mistral", "qwen2")
+_CLASSIC_FAMILIES = {"llama": "LlamaDecoderLayer", "mistral": "MistralDecoderLayer", "qwen2": "Qwen2DecoderLayer"}
+
+
+def _is_gemma_rmsnorm(m) -> bool:
+    """An HF Gemma*RMSNorm: `weight` [N] and `eps`, y = x rsqrt(mean(x^2) + eps) (1 + weight) rounded once."""
+    return (isinstance(m, torch.nn.Module) and type(m).__name__.endswith("RMSNorm") and type(m).__name__.startswith("Gemma")
+            and isinstance(getattr(m, "weight", None), torch.Tensor) and m.weight.dim() == 1
+            and isinstance(getattr(m, "eps", None), (int, float)) and not hasattr(m, "variance_epsilon"))
+
+
+def _is_gelu_tanh(fn) -> bool:
+    if isinstance(fn, torch.nn.GELU):
+        return fn.approximate == "tanh"
+    return type(fn).__name__ in ("GELUTanh", "PytorchGELUTanh")
+
+
+def _norm_eps(norm) -> float:
+    return norm.eps if hasattr(norm, "eps") else norm.variance_epsilon
+
+
+def _gemma_rmsnorm_forward(self, hidden_states):
+    """forward of an HF Gemma*RMSNorm on bf_norm_add_rmsnorm (no first norm, no residual, offset 1).  A hidden state that
+    the fused layer in front of this norm produced carries this norm's output already (`_bf_normed`, as _rmsnorm_forward
+    describes): it is handed out as it is.  Inference only: under recorded gradients the module's own forward runs."""
+    from . import ops
+
+    x = hidden_states
+    if (not isinstance(x, torch.Tensor) or _records_grad(x, self) or not x.is_cuda
+            or not ops.norm_add_rmsnorm_supported(x, None, None, self)):
+        return self._bf_plain_rmsnorm_forward(hidden_states)
+    ready = x.__dict__.pop("_bf_normed", None)
+    if ready is not None and ready[1] is self:
+        return ready[0]
+    return ops.norm_add_rmsnorm(x, None, None, self.weight, 0.0, self.eps, 1, want_sum=False)[1]
+
+
+def _gemma_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
+                         use_cache=False, position_embeddings=None, **kwargs):
+    """forward of an HF GemmaDecoderLayer: _decoder_layer_forward's structure (each residual add folded into the norm that
+    follows it, the second one's output travelling on the hidden state as `_bf_normed`) through bf_norm_add_rmsnorm with the
+    (1 + weight) convention.  Inference only: gradients recorded, training mode, tensors off the device or a hook on the
+    norm whose forward is skipped send the layer to its own forward."""
+    from . import ops
+
+    h = hidden_states
+    post, nxt = self.post_attention_layernorm, self._bf_next_norm[0]
+    if (not isinstance(h, torch.Tensor) or self.training or _records_grad(h, self, nxt) or _hooked(post)
+            or not ops.norm_add_rmsnorm_supported(h, None, None, post)
+            or not ops.norm_add_rmsnorm_supported(h, None, None, nxt)):
+        return self._bf_plain_layer_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
+                                            past_key_values=past_key_values, use_cache=use_cache,
+                                            position_embeddings=position_embeddings, **kwargs)
+    a, _ = self.self_attn(hidden_states=self.input_layernorm(h), attention_mask=attention_mask, position_ids=position_ids,
+                          past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings,
+                          **kwargs)
+    if ops.norm_add_rmsnorm_supported(a, None, h, post):
+        h1, y1 = ops.norm_add_rmsnorm(a, None, h, post.weight, 0.0, post.eps, 1)
+    else:
+        h1 = h + a
+        y1 = post(h1)
+    m = self.mlp(y1)
+    if not ops.norm_add_rmsnorm_supported(m, None, h1, nxt):
+        return h1 + m
+    h2, y2 = ops.norm_add_rmsnorm(m, None, h1, nxt.weight, 0.0, nxt.eps, 1)
+    h2._bf_normed = (y2, nxt)
+    return h2
+
+
+def _sandwich_layer_forward(self, hidden_states, position_embeddings=None, attention_mask=None, position_ids=None,
+                            past_key_values=None, **kwargs):
+    """forward of an HF Gemma2DecoderLayer / Gemma3DecoderLayer, whose four norms sandwich the two residual adds:
+        (h1, y1) = K(attn_out, post_attention_layernorm, h, pre_feedforward_layernorm)
+        (h2, y2) = K(mlp_out, post_feedforward_layernorm, h1, the next layer's input_layernorm or the final norm)
+    with K = bf_norm_add_rmsnorm: norm, add, norm in one launch each, so a layer makes four launches with its rotary and
+    GeGLU ones.  y2 travels on the returned hidden state as `_bf_normed`; the returned tensor is always the true hidden
+    state.  Inference only: gradients recorded, training mode, tensors off the device or a hook on one of the three norms
+    whose forward is skipped send the layer to its own forward."""
+    from . import ops
+
+    h = hidden_states
+    post, pre_ff, post_ff = self.post_attention_layernorm, self.pre_feedforward_layernorm, self.post_feedforward_layernorm
+    nxt = self._bf_next_norm[0]
+    if (not isinstance(h, torch.Tensor) or self.training or _records_grad(h, self, nxt)
+            or _hooked(post) or _hooked(pre_ff) or _hooked(post_ff)
+            or not ops.norm_add_rmsnorm_supported(h, post, h, pre_ff)
+            or not ops.norm_add_rmsnorm_supported(h, post_ff, h, nxt)):
+        return self._bf_plain_layer_forward(hidden_states, position_embeddings=position_embeddings,
+                                            attention_mask=attention_mask, position_ids=position_ids,
+                                            past_key_values=past_key_values, **kwargs)
+    a, _ = self.self_attn(hidden_states=self.input_layernorm(h), position_embeddings=position_embeddings,
+                          attention_mask=attention_mask, position_ids=position_ids, past_key_values=past_key_values,
+                          **kwargs)
+    if ops.norm_add_rmsnorm_supported(a, post, h, pre_ff):
+        h1, y1 = ops.norm_add_rmsnorm(a, post.weight, h, pre_ff.weight, post.eps, pre_ff.eps, 1)
+    else:  # an attention output in another dtype: the framework's ops on what is already computed
+        h1 = h + post(a)
+        y1 = pre_ff(h1)
+    m = self.mlp(y1)
+    if not ops.norm_add_rmsnorm_supported(m, post_ff, h1, nxt):
+        return h1 + post_ff(m)
+    h2, y2 = ops.norm_add_rmsnorm(m, post_ff.weight, h1, nxt.weight, post_ff.eps, nxt.eps, 1)
+    h2._bf_normed = (y2, nxt)
+    return h2
+
+
+def _family_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
+                              **kwargs):
+    """forward of an HF Qwen3 / Gemma / Gemma2 / Gemma3 attention module with the per-head q_norm / k_norm (Qwen3, Gemma 3)
+    and apply_rotary_pos_emb as one launch (bf_qknorm_rope: head size 64, 128 or 256), in place on the projections' outputs
+    in the [B, T, heads * head_dim] layout the attention kernels read through strides.  The cache update, the attention
+    interface lookup and o_proj are the module's own code path, and the interface gets exactly the keyword arguments that
+    class's own forward passes.  Inference only: gradients recorded, training mode, tensors off the device or a hook on
+    q_norm / k_norm send the module to its own forward."""
+    import sys
+
+    from . import ops
+
+    x = hidden_states
+    pe = position_embeddings
+    name = type(self).__name__
+    offset, has_qk = self._bf_family[0], self._bf_family[1]
+    qn, kn = (self.q_norm, self.k_norm) if has_qk else (None, None)
+    fast = (pe is not None and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 3 and x.dtype in ops._TORCH2BF
+            and self.head_dim in (64, 128, 256) and not self.training and not _records_grad(x, self)
+            and not (has_qk and (_hooked(qn) or _hooked(kn))))
+    if fast:
+        cos, sin = pe
+        fast = (cos.dim() == 3 and sin.shape == cos.shape and cos.shape[-1] == self.head_dim and cos.shape[1] == x.shape[1]
+                and cos.shape[0] in (1, x.shape[0]))
+    if not fast:
+        return self._bf_plain_attn_forward(hidden_states, position_embeddings=position_embeddings,
+                                           attention_mask=attention_mask, past_key_values=past_key_values, **kwargs)
+    mod = sys.modules[type(self).__module__]
+    input_shape = x.shape[:-1]
+    hidden_shape = (*input_shape, -1, self.head_dim)
+    query_states = self.q_proj(x).view(hidden_shape).transpose(1, 2)
+    key_states = self.k_proj(x).view(hidden_shape).transpose(1, 2)
+    value_states = self.v_proj(x).view(hidden_shape).transpose(1, 2)
+    cos, sin = (t if t.is_contiguous() else t.contiguous() for t in (cos, sin))
+    gq, gk = (qn.weight, kn.weight) if has_qk else (None, None)
+    if ops.qknorm_rope_supported(query_states, key_states, cos, sin, gq, gk):
+        query_states, key_states = ops.qknorm_rope(query_states, key_states, cos, sin, gq, gk,
+                                                   eps=_norm_eps(qn) if has_qk else 0.0, weight_offset=offset, inplace=True)
+    else:  # a projection that came back in another dtype or layout: the framework's ops on what is already computed
+        if has_qk:
+            query_states, key_states = qn(query_states), kn(key_states)
+        query_states, key_states = mod.apply_rotary_pos_emb(query_states, key_states, cos, sin)
+    if past_key_values is not None:
+        key_states, value_states = past_key_values.update(key_states, value_states, self.layer_idx)
+    attention_interface = mod.ALL_ATTENTION_FUNCTIONS.get_interface(self.config._attn_implementation,
+                                                                    mod.eager_attention_forward)
+    # what each class's own forward hands the interface (transformers' modeling_qwen3 / gemma / gemma2 / gemma3)
+    if name == "Gemma2Attention":
+        kwargs = dict(sliding_window=self.sliding_window, softcap=self.attn_logit_softcapping, **kwargs)
+    elif name in ("Gemma3Attention", "Qwen3Attention"):
+        kwargs = dict(sliding_window=self.sliding_window, **kwargs)
+    attn_output, attn_weights = attention_interface(self, query_states, key_states, value_states, attention_mask,
+                                                    dropout=self.attention_dropout if self.training else 0.0,
+                                                    scaling=self.scaling, **kwargs)
+    attn_output = attn_output.reshape(*input_shape, -1).contiguous()
+    return self.o_proj(attn_output), attn_weights
+
+
+def _geglu_mlp_forward(self, x):
+    """forward of an HF Gemma-style MLP — down_proj(gelu_tanh(gate_proj(x)) * up_proj(x)) — with the activation and the
+    product as one launch (bf_geglu).  Inference only."""
+    from . import ops
+
+    if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in ops._TORCH2BF or _hooked(self.act_fn)
+            or self.training or _records_grad(x, self)):
+        return self._bf_plain_mlp_forward(x)
+    gate, up = self.gate_proj(x), self.up_proj(x)
+    if not ops.geglu_supported(gate, up):
+        return self.down_proj(self.act_fn(gate) * up)
+    return self.down_proj(ops.geglu(gate, up))
+
+
+def _fuse_family_layer(layer, nxt, family) -> bool:
+    """Rewrite one layer of a family of _FAMILY_LAYERS; False (and nothing changed) when it lacks the attribute shape."""
+    layer_cls, attn_cls, offset, has_qk, sandwich = _FAMILY_LAYERS[family]
+    attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
+    is_norm = _is_gemma_rmsnorm if offset else _is_rmsnorm
+    norms = ["input_layernorm", "post_attention_layernorm"] + (["pre_feedforward_layernorm", "post_feedforward_layernorm"]
+                                                               if sandwich else [])
+    act = getattr(mlp, "act_fn", None)
+    if (type(attn).__name__ != attn_cls or not all(is_norm(getattr(layer, n, None)) for n in norms) or not is_norm(nxt)
+            or not all(isinstance(getattr(mlp, n, None), torch.nn.Module) for n in ("gate_proj", "up_proj", "down_proj"))
+            or not (_is_gelu_tanh(act) if offset else _is_silu(act))
+            or not all(isinstance(getattr(attn, n, None), torch.nn.Module) for n in ("q_proj", "k_proj", "v_proj", "o_proj"))
+            or getattr(attn, "head_dim", None) not in (64, 128, 256)
+            or (has_qk and not (is_norm(getattr(attn, "q_norm", None)) and is_norm(getattr(attn, "k_norm", None))))):
+        return False
+    layer._bf_next_norm = (nxt,)  # (in a tuple: not a child module of this layer)
+    layer._bf_plain_layer_forward = layer.forward
+    layer.forward = types.MethodType(_sandwich_layer_forward if sandwich else _gemma_layer_forward if offset
+                                     else _decoder_layer_forward, layer)
+    attn._bf_family = (offset, has_qk)
+    attn._bf_plain_attn_forward = attn.forward
+    attn.forward = types.MethodType(_family_attention_forward, attn)
+    mlp._bf_plain_mlp_forward = mlp.forward
+    mlp.forward = types.MethodType(_geglu_mlp_forward if offset else _swiglu_mlp_forward, mlp)
+    for norm in (layer.input_layernorm, nxt):
+        if not hasattr(norm, "_bf_plain_rmsnorm_forward"):
+            norm._bf_plain_rmsnorm_forward = norm.forward
+            norm.forward = types.MethodType(_gemma_rmsnorm_forward if offset else _rmsnorm_forward, norm)
+    return True
+
+
+def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False, families=_DEFAULT_FAMILIES) -> int:
     """Run the memory-bound ops of HuggingFace Llama, Mistral and Qwen2 decoder layers — the two RMSNorms with the
     residual adds in front of them, the rotary embedding of q and k, SiLU(gate) * up — as four launches per layer
     (bf_add_rmsnorm twice, bf_rope_qk, bf_swiglu) instead of the framework's thirty or so elementwise kernels.  A layer is
     rewritten when its class is exactly LlamaDecoderLayer, MistralDecoderLayer or Qwen2DecoderLayer with the attribute
     shape those have (RMSNorm modules with `weight` and `variance_epsilon`, an MLP of gate / up / down projections around
-    a SiLU, an attention module with q / k / v / o projections and head_dim 64 or 128); Qwen3 (q / k norms), Gemma
-    (1 + weight), OLMo and mixture-of-experts layers are left alone.  By default an inference-time rewrite like the
-    other fuse_* functions: with gradients recorded, in training mode, off the device or on shapes the kernels refuse, the
-    modules' own forwards run.  backward=True: the fast forms also run under recorded gradients and in training mode,
-    through autograd functions whose backward is one launch each (bf_add_rmsnorm_bwd, bf_rope_qk_bwd, bf_swiglu_bwd) — a
-    training step's decoder glue on the kernels in both directions; an attention module whose dropout would be active
-    still runs its own forward.  Returns the number of layers rewritten; calling it again rewrites nothing twice (a second
-    call with backward=True turns the backward on for the layers already rewritten, and counts none of them)."""
+    a SiLU, an attention module with q / k / v / o projections and head_dim 64 or 128); with the default `families`, Qwen3
+    (q / k norms), Gemma (1 + weight), OLMo and mixture-of-experts layers are left alone.  By default an inference-time
+    rewrite like the other fuse_* functions: with gradients recorded, in training mode, off the device or on shapes the
+    kernels refuse, the modules' own forwards run.  backward=True: the fast forms also run under recorded gradients and in
+    training mode, through autograd functions whose backward is one launch each (bf_add_rmsnorm_bwd, bf_rope_qk_bwd,
+    bf_swiglu_bwd) — a training step's decoder glue on the kernels in both directions; an attention module whose dropout
+    would be active still runs its own forward.
+
+    families: the model families whose layers are rewritten, a name or an iterable of names out of "llama", "mistral",
+    "qwen2" (the default three), "qwen3", "gemma", "gemma2", "gemma3" (Gemma3 text decoder layers), or "all".  The four
+    further families are opt-in and matched by exact class name as well:
+      qwen3   the layer and the MLP as above (bf_add_rmsnorm, bf_swiglu); the attention module's q_norm, k_norm and
+              rotary embedding are one launch (bf_qknorm_rope).
+      gemma   Llama's structure with the (1 + weight) norms (bf_norm_add_rmsnorm), the rotary embedding at head size
+              256 (bf_qknorm_rope without gammas) and gelu_tanh(gate) * up (bf_geglu).
+      gemma2, gemma3   the four norms around the two residual adds as two norm -> add -> norm launches
+              (bf_norm_add_rmsnorm), bf_qknorm_rope (with Gemma 3's q_norm / k_norm), bf_geglu: four launches a layer.
+              A Gemma whose activation is not the tanh GELU is declined.
+    For these four the rewrite is inference-only: under recorded gradients or in training mode the modules' own forwards
+    run, and backward=True sets no backward flag on them.  A hook on a module whose forward a fast form skips (the three
+    further norms, q_norm, k_norm, act_fn) sends that module, or its layer, to its own forward.
+
+    Returns the number of layers rewritten; calling it again rewrites nothing twice (a second call with backward=True
+    turns the backward on for the Llama / Mistral / Qwen2 layers already rewritten, and counts none of them)."""
+    names = (families,) if isinstance(families, str) else tuple(families)
+    if "all" in names:
+        names = tuple(_CLASSIC_FAMILIES) + tuple(_FAMILY_LAYERS)
+    unknown = [n for n in names if n not in _CLASSIC_FAMILIES and n not in _FAMILY_LAYERS]
+    if unknown:
+        raise ValueError(f"fuse_decoder_blocks: unknown families {unknown}; known: "
+                         f"{sorted(_CLASSIC_FAMILIES) + sorted(_FAMILY_LAYERS)} and 'all'")
+    classic = {_CLASSIC_FAMILIES[n] for n in names if n in _CLASSIC_FAMILIES}
+    further = {_FAMILY_LAYERS[n][0]: n for n in names if n in _FAMILY_LAYERS}
     fused = 0
     for parent in model.modules():
         layers, final = getattr(parent, "layers", None), getattr(parent, "norm", None)
-        if not isinstance(layers, torch.nn.ModuleList) or not _is_rmsnorm(final):
+        if not isinstance(layers, torch.nn.ModuleList) or not (_is_rmsnorm(final) or _is_gemma_rmsnorm(final)):
             continue
         for i, layer in enumerate(layers):
             attn, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
             nxt = getattr(layers[i + 1], "input_layernorm", None) if i + 1 < len(layers) else final
-            if backward and hasattr(layer, "_bf_plain_layer_forward"):
+            cls = type(layer).__name__
+            if cls in further:
+                if not hasattr(layer, "_bf_plain_layer_forward") and _fuse_family_layer(layer, nxt, further[cls]):
+                    fused += 1
+                continue
+            if backward and hasattr(layer, "_bf_plain_layer_forward") and cls in _DECODER_LAYERS:
                 for m in (layer, attn, mlp, layer.input_layernorm, nxt):
                     m._bf_blocks_backward = True
-            if (type(layer).__name__ not in _DECODER_LAYERS or hasattr(layer, "_bf_plain_layer_forward")
-                    or type(attn).__name__ != _DECODER_LAYERS[type(layer).__name__]
+            if (cls not in _DECODER_LAYERS or cls not in classic or hasattr(layer, "_bf_plain_layer_forward")
+                    or type(attn).__name__ != _DECODER_LAYERS[cls]
                     or not _is_rmsnorm(getattr(layer, "input_layernorm", None))
                     or not _is_rmsnorm(getattr(layer, "post_attention_layernorm", None)) or not _is_rmsnorm(nxt)
                     or not all(isinstance(getattr(mlp, n, None), torch.nn.Module) for n in ("gate_proj", "up_proj", "down_proj"))
@@ -1147,7 +1392,8 @@ def fuse_attention(model: torch.nn.Module) -> bool:
     attention sinks (gpt-oss) goes to the framework.  Logit soft-capping (Gemma 2) runs the soft-cap entries
     (bf_attention_fwd_gqa_softcap and its backward and decode siblings) once `softcap_attention()` or BF_SOFTCAP_ATTENTION
     switches them on; with that switch off, the default, such a call goes to the framework's scaled-dot-product attention,
-    which ignores the cap — the model then computes another function than its `eager` attention.  Returns False (and changes
+    which ignores the cap — the model then computes another function than its `eager` attention.  The ops around the
+    attention of those families (norms, rotary embedding, gate) are fuse_decoder_blocks's, opt-in by its `families`.  Returns False (and changes
     nothing) when the model has no HuggingFace config or transformers lacks the interface.
     A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation
     forwards that ask for neither hidden states nor attentions, everything behind the last layer's key / value

@@ -1566,6 +1566,131 @@ def swiglu(gate: Tensor, up: Tensor) -> Tensor:
     return out
 
 
+# ---- the Gemma 1 / 2 / 3 and Qwen3 siblings (bf_family_blocks.hip): norm -> add -> norm, q / k norm + RoPE, GeGLU
+# launches of bf_norm_add_rmsnorm / bf_qknorm_rope / bf_geglu from this process (BLOCK_CALLS keeps its three keys)
+FAMILY_BLOCK_CALLS = {"norm_add_norm": 0, "qknorm_rope": 0, "geglu": 0}
+
+
+def _gamma_ok(w, n: int, dtype) -> bool:
+    return (isinstance(w, Tensor) and w.is_cuda and w.dim() == 1 and w.shape[0] == n and w.dtype in (torch.float32, dtype)
+            and w.is_contiguous() and w.data_ptr() % 16 == 0)
+
+
+def norm_add_rmsnorm_supported(x: Tensor, pre, residual: Optional[Tensor], out_norm) -> bool:
+    """Does bf_norm_add_rmsnorm take x (and the residual) under the norm modules `pre` (or None) and `out_norm` (modules
+    with `weight` [N], of one dtype)?"""
+    n = x.shape[-1]
+    return (x.is_cuda and x.dtype in _TORCH2BF and x.dim() >= 1 and n % 8 == 0 and n <= 8192 and x.numel() > 0 and
+            (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype and residual.is_cuda)) and
+            _gamma_ok(out_norm.weight, n, x.dtype) and
+            (pre is None or (_gamma_ok(pre.weight, n, x.dtype) and pre.weight.dtype == out_norm.weight.dtype)))
+
+
+def norm_add_rmsnorm(x: Tensor, gamma_pre: Optional[Tensor], residual: Optional[Tensor], gamma_out: Tensor,
+                     eps_pre: float, eps_out: float, weight_offset: int = 1, want_sum: bool = True):
+    """(z, y) of one pass (bf_norm_add_rmsnorm): u = x normalised under gamma_pre and rounded (x itself without one),
+    z = residual + u rounded (u itself without a residual), y = z normalised under gamma_out; both norms multiply by
+    (weight_offset + gamma): 1 for Gemma's modules, 0 for Llama's.  want_sum=False: z is not written and None is returned
+    in its place; without gamma_pre and residual z is x itself."""
+    _require_device(x, "norm_add_rmsnorm input")
+    N = x.shape[-1]
+    x2 = _rows_of(x, N)
+    r2 = None
+    if residual is not None:
+        if residual.shape != x.shape or residual.dtype != x.dtype:
+            raise _C.BayeFormersAMDError("norm_add_rmsnorm: residual must match the input's shape and dtype")
+        r2 = _rows_of(residual, N)
+    for g in (gamma_pre, gamma_out):
+        if g is not None and (g.dtype != gamma_out.dtype or g.dtype not in (torch.float32, x.dtype) or g.numel() != N):
+            raise _C.BayeFormersAMDError("norm_add_rmsnorm: the gammas must be [N], of one dtype: float32 or the input's")
+    out = torch.empty_like(x2)
+    changed = r2 is not None or gamma_pre is not None
+    z = torch.empty_like(x2) if (want_sum and changed) else None
+    _C.check(_C.lib().bf_norm_add_rmsnorm(
+        x2.data_ptr(), gamma_pre.data_ptr() if gamma_pre is not None else None, r2.data_ptr() if r2 is not None else None,
+        gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype], int(weight_offset), z.data_ptr() if z is not None else None,
+        out.data_ptr(), _TORCH2BF[x.dtype], x2.shape[0], N, float(eps_pre), float(eps_out), _stream_ptr()),
+        "bf_norm_add_rmsnorm")
+    FAMILY_BLOCK_CALLS["norm_add_norm"] += 1
+    if z is not None:
+        z = z.view(x.shape)
+    elif want_sum and not changed:
+        z = x
+    return z, out.view(x.shape)
+
+
+def qknorm_rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, gamma_q: Optional[Tensor] = None,
+                          gamma_k: Optional[Tensor] = None) -> bool:
+    """rope_supported's layouts at head size 64, 128 or 256; the gammas (each may be None) [D] contiguous tensors of one
+    dtype, q's or fp32: what bf_qknorm_rope takes."""
+    if not (q.is_cuda and q.dtype in _TORCH2BF and k.dtype == q.dtype and k.is_cuda and q.dim() == 4 and k.dim() == 4):
+        return False
+    B, H, T, D = q.shape
+    if D not in (64, 128, 256) or k.shape[0] != B or k.shape[2] != T or k.shape[3] != D or q.numel() == 0 or k.numel() == 0:
+        return False
+    if B * T * (H + k.shape[1]) * (D // 16) >= 2 ** 31:
+        return False
+    for c in (cos, sin):
+        if not (c.is_cuda and c.dtype in (torch.float32, q.dtype) and c.dim() == 3 and c.shape[0] in (1, B)
+                and tuple(c.shape[1:]) == (T, D) and c.is_contiguous() and c.data_ptr() % 16 == 0):
+            return False
+    if cos.shape != sin.shape or cos.dtype != sin.dtype:
+        return False
+    gs = [g for g in (gamma_q, gamma_k) if g is not None]
+    if not all(_gamma_ok(g, D, q.dtype) and g.dtype == gs[0].dtype for g in gs):
+        return False
+    return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (q, k))
+
+
+def qknorm_rope(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, gamma_q: Optional[Tensor] = None,
+                gamma_k: Optional[Tensor] = None, eps: float = 1e-6, weight_offset: int = 0, inplace: bool = False):
+    """rope_qk at head size 64, 128 or 256 with an RMSNorm of every head in front of the rotation, in one launch
+    (bf_qknorm_rope): n = x rsqrt(mean_D(x^2) + eps) (weight_offset + gamma) kept in fp32, then n cos + rotate_half(n) sin,
+    rounded once.  A tensor whose gamma is None is only rotated.  Shapes as qknorm_rope_supported describes; inplace and
+    the returned layouts as rope_qk's."""
+    _require_device(q, "qknorm_rope input")
+    if not qknorm_rope_supported(q, k, cos, sin, gamma_q, gamma_k):
+        raise _C.BayeFormersAMDError("qknorm_rope: unsupported shapes, strides or dtypes (see ops.qknorm_rope_supported)")
+    B, H, T, D = q.shape
+    Hkv = k.shape[1]
+    if inplace:
+        qo, ko = q, k
+    else:
+        qo = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device).transpose(1, 2)
+        ko = torch.empty((B, T, Hkv, D), dtype=k.dtype, device=k.device).transpose(1, 2)
+    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
+    for name, t in (("q_stride", q), ("k_stride", k), ("q_out_stride", qo), ("k_out_stride", ko)):
+        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    g = gamma_q if gamma_q is not None else gamma_k
+    _C.check(_C.lib().bf_qknorm_rope(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
+                                     gamma_q.data_ptr() if gamma_q is not None else None,
+                                     gamma_k.data_ptr() if gamma_k is not None else None,
+                                     _TORCH2BF[g.dtype] if g is not None else _C.BF_DT_F32, int(weight_offset), float(eps),
+                                     qo.data_ptr(), ko.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()),
+             "bf_qknorm_rope")
+    FAMILY_BLOCK_CALLS["qknorm_rope"] += 1
+    return qo, ko
+
+
+def geglu_supported(gate: Tensor, up: Tensor) -> bool:
+    """What bf_geglu takes: what bf_swiglu takes (swiglu_supported)."""
+    return swiglu_supported(gate, up)
+
+
+def geglu(gate: Tensor, up: Tensor) -> Tensor:
+    """gelu(gate, approximate="tanh") * up in one launch (bf_geglu): one rounding, against the framework's two."""
+    _require_device(gate, "geglu input")
+    if not geglu_supported(gate, up):
+        raise _C.BayeFormersAMDError("geglu: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
+    N = gate.shape[-1]
+    out = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
+    _C.check(_C.lib().bf_geglu(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), out.data_ptr(), N,
+                               _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()), "bf_geglu")
+    FAMILY_BLOCK_CALLS["geglu"] += 1
+    return out
+
+
 # ---- their backward: bf_add_rmsnorm_bwd / bf_rope_qk_bwd / bf_swiglu_bwd, and the autograd functions over both directions
 # launches of the three backward entries from this process (the forwards of a training step count in BLOCK_CALLS)
 BLOCK_BWD_CALLS = {"rmsnorm": 0, "rope": 0, "swiglu": 0}
