@@ -201,6 +201,18 @@ FAMILY_BLOCK_SYMBOLS = {
     "bf_geglu": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
 }
 
+# what include/bayeformers_amd_family_blocks_bwd.h declares, their backward entries: the forwards' arguments with the gradients, the parameter gradients
+# (fp32) and a workspace
+FAMILY_BLOCK_BWD_SYMBOLS = {
+    "bf_norm_add_rmsnorm_bwd_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "bf_norm_add_rmsnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i64, _i,
+                                     ctypes.c_float, ctypes.c_float, _vp]),
+    "bf_qknorm_rope_bwd_workspace_bytes": (_sz, [_vp, _i]),
+    "bf_qknorm_rope_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,
+                                _sz, _i, _vp, _vp]),
+    "bf_geglu_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -226,7 +238,7 @@ def lib():
             fn = getattr(l, name)  # AttributeError here = header/library drift
             fn.restype = res
             fn.argtypes = args
-        for name, (res, args) in FAMILY_BLOCK_SYMBOLS.items():
+        for name, (res, args) in list(FAMILY_BLOCK_SYMBOLS.items()) + list(FAMILY_BLOCK_BWD_SYMBOLS.items()):
             fn = getattr(l, name, None)
             if fn is None:  # a library from before these entries reports the version these bindings expect
                 raise BayeFormersAMDError(

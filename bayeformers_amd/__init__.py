@@ -10,7 +10,7 @@ import os
 import threading
 import types
 from copy import deepcopy
-from typing import Optional
+from typing import Optional, Union
 
 import torch.nn
 
@@ -1086,7 +1086,8 @@ def _swiglu_mlp_forward(self, x):
     return self.down_proj(ops.SwiGLUFn.apply(gate, up) if rec else ops.swiglu(gate, up))
 
 
-# ---- the Gemma 1 / 2 / 3 and Qwen3 families (fuse_decoder_blocks(families=...)): inference-time forwards only
+# ---- the Gemma 1 / 2 / 3 and Qwen3 families (fuse_decoder_blocks(families=...)): inference-time forwards, and with
+# backward="all" the training-time ones through ops.NormAddRMSNormFn / QKNormRopeFn / GeGLUFn
 # family -> (decoder layer class, attention class, weight offset of its norms, has q / k norms, sandwich of four norms)
 _FAMILY_LAYERS = {"qwen3": ("Qwen3DecoderLayer", "Qwen3Attention", 0, True, False),
                   "gemma": ("GemmaDecoderLayer", "GemmaAttention", 1, False, False),
@@ -1116,16 +1117,21 @@ def _norm_eps(norm) -> float:
 def _gemma_rmsnorm_forward(self, hidden_states):
     """forward of an HF Gemma*RMSNorm on bf_norm_add_rmsnorm (no first norm, no residual, offset 1).  A hidden state that
     the fused layer in front of this norm produced carries this norm's output already (`_bf_normed`, as _rmsnorm_forward
-    describes): it is handed out as it is.  Inference only: under recorded gradients the module's own forward runs."""
+    describes): it is handed out as it is.  Under recorded gradients the module's own forward runs, unless the norm was
+    rewritten with backward="all": then _rmsnorm_forward's rules for the attached tensor hold and the norm runs through
+    ops.NormAddRMSNormFn."""
     from . import ops
 
     x = hidden_states
-    if (not isinstance(x, torch.Tensor) or _records_grad(x, self) or not x.is_cuda
+    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
+    if (not isinstance(x, torch.Tensor) or (rec and not _blocks_backward(self)) or not x.is_cuda
             or not ops.norm_add_rmsnorm_supported(x, None, None, self)):
         return self._bf_plain_rmsnorm_forward(hidden_states)
-    ready = x.__dict__.pop("_bf_normed", None)
-    if ready is not None and ready[1] is self:
+    ready = x.__dict__.get("_bf_normed") if rec else x.__dict__.pop("_bf_normed", None)
+    if ready is not None and ready[1] is self and not (rec and ready[0].grad_fn is None):
         return ready[0]
+    if rec:
+        return ops.NormAddRMSNormFn.apply(x, None, None, self.weight, 0.0, self.eps, 1)
     return ops.norm_add_rmsnorm(x, None, None, self.weight, 0.0, self.eps, 1, want_sum=False)[1]
 
 
@@ -1133,13 +1139,15 @@ def _gemma_layer_forward(self, hidden_states, attention_mask=None, position_ids=
                          use_cache=False, position_embeddings=None, **kwargs):
     """forward of an HF GemmaDecoderLayer: _decoder_layer_forward's structure (each residual add folded into the norm that
     follows it, the second one's output travelling on the hidden state as `_bf_normed`) through bf_norm_add_rmsnorm with the
-    (1 + weight) convention.  Inference only: gradients recorded, training mode, tensors off the device or a hook on the
-    norm whose forward is skipped send the layer to its own forward."""
+    (1 + weight) convention.  Tensors off the device or a hook on the norm whose forward is skipped send the layer to its
+    own forward; gradients recorded or training mode as well, unless the layer was rewritten with backward="all" — then the
+    two passes run through ops.NormAddRMSNormFn, whose backward is bf_norm_add_rmsnorm_bwd."""
     from . import ops
 
     h = hidden_states
     post, nxt = self.post_attention_layernorm, self._bf_next_norm[0]
-    if (not isinstance(h, torch.Tensor) or self.training or _records_grad(h, self, nxt) or _hooked(post)
+    rec = isinstance(h, torch.Tensor) and _records_grad(h, self, nxt)
+    if (not isinstance(h, torch.Tensor) or ((self.training or rec) and not _blocks_backward(self)) or _hooked(post)
             or not ops.norm_add_rmsnorm_supported(h, None, None, post)
             or not ops.norm_add_rmsnorm_supported(h, None, None, nxt)):
         return self._bf_plain_layer_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
@@ -1148,15 +1156,16 @@ def _gemma_layer_forward(self, hidden_states, attention_mask=None, position_ids=
     a, _ = self.self_attn(hidden_states=self.input_layernorm(h), attention_mask=attention_mask, position_ids=position_ids,
                           past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings,
                           **kwargs)
+    norm_add_rmsnorm = ops.NormAddRMSNormFn.apply if rec else ops.norm_add_rmsnorm
     if ops.norm_add_rmsnorm_supported(a, None, h, post):
-        h1, y1 = ops.norm_add_rmsnorm(a, None, h, post.weight, 0.0, post.eps, 1)
+        h1, y1 = norm_add_rmsnorm(a, None, h, post.weight, 0.0, post.eps, 1)
     else:
         h1 = h + a
         y1 = post(h1)
     m = self.mlp(y1)
     if not ops.norm_add_rmsnorm_supported(m, None, h1, nxt):
         return h1 + m
-    h2, y2 = ops.norm_add_rmsnorm(m, None, h1, nxt.weight, 0.0, nxt.eps, 1)
+    h2, y2 = norm_add_rmsnorm(m, None, h1, nxt.weight, 0.0, nxt.eps, 1)
     h2._bf_normed = (y2, nxt)
     return h2
 
@@ -1168,14 +1177,16 @@ def _sandwich_layer_forward(self, hidden_states, position_embeddings=None, atten
         (h2, y2) = K(mlp_out, post_feedforward_layernorm, h1, the next layer's input_layernorm or the final norm)
     with K = bf_norm_add_rmsnorm: norm, add, norm in one launch each, so a layer makes four launches with its rotary and
     GeGLU ones.  y2 travels on the returned hidden state as `_bf_normed`; the returned tensor is always the true hidden
-    state.  Inference only: gradients recorded, training mode, tensors off the device or a hook on one of the three norms
-    whose forward is skipped send the layer to its own forward."""
+    state.  Tensors off the device or a hook on one of the three norms whose forward is skipped send the layer to its own
+    forward; gradients recorded or training mode as well, unless the layer was rewritten with backward="all" — then K is
+    ops.NormAddRMSNormFn, whose backward is one bf_norm_add_rmsnorm_bwd for both norms and the add."""
     from . import ops
 
     h = hidden_states
     post, pre_ff, post_ff = self.post_attention_layernorm, self.pre_feedforward_layernorm, self.post_feedforward_layernorm
     nxt = self._bf_next_norm[0]
-    if (not isinstance(h, torch.Tensor) or self.training or _records_grad(h, self, nxt)
+    rec = isinstance(h, torch.Tensor) and _records_grad(h, self, nxt)
+    if (not isinstance(h, torch.Tensor) or ((self.training or rec) and not _blocks_backward(self))
             or _hooked(post) or _hooked(pre_ff) or _hooked(post_ff)
             or not ops.norm_add_rmsnorm_supported(h, post, h, pre_ff)
             or not ops.norm_add_rmsnorm_supported(h, post_ff, h, nxt)):
@@ -1185,15 +1196,16 @@ def _sandwich_layer_forward(self, hidden_states, position_embeddings=None, atten
     a, _ = self.self_attn(hidden_states=self.input_layernorm(h), position_embeddings=position_embeddings,
                           attention_mask=attention_mask, position_ids=position_ids, past_key_values=past_key_values,
                           **kwargs)
+    norm_add_rmsnorm = ops.NormAddRMSNormFn.apply if rec else ops.norm_add_rmsnorm
     if ops.norm_add_rmsnorm_supported(a, post, h, pre_ff):
-        h1, y1 = ops.norm_add_rmsnorm(a, post.weight, h, pre_ff.weight, post.eps, pre_ff.eps, 1)
+        h1, y1 = norm_add_rmsnorm(a, post.weight, h, pre_ff.weight, post.eps, pre_ff.eps, 1)
     else:  # an attention output in another dtype: the framework's ops on what is already computed
         h1 = h + post(a)
         y1 = pre_ff(h1)
     m = self.mlp(y1)
     if not ops.norm_add_rmsnorm_supported(m, post_ff, h1, nxt):
         return h1 + post_ff(m)
-    h2, y2 = ops.norm_add_rmsnorm(m, post_ff.weight, h1, nxt.weight, post_ff.eps, nxt.eps, 1)
+    h2, y2 = norm_add_rmsnorm(m, post_ff.weight, h1, nxt.weight, post_ff.eps, nxt.eps, 1)
     h2._bf_normed = (y2, nxt)
     return h2
 
@@ -1204,8 +1216,9 @@ def _family_attention_forward(self, hidden_states, position_embeddings=None, att
     and apply_rotary_pos_emb as one launch (bf_qknorm_rope: head size 64, 128 or 256), in place on the projections' outputs
     in the [B, T, heads * head_dim] layout the attention kernels read through strides.  The cache update, the attention
     interface lookup and o_proj are the module's own code path, and the interface gets exactly the keyword arguments that
-    class's own forward passes.  Inference only: gradients recorded, training mode, tensors off the device or a hook on
-    q_norm / k_norm send the module to its own forward."""
+    class's own forward passes.  Tensors off the device or a hook on q_norm / k_norm send the module to its own forward;
+    gradients recorded or training mode as well, unless it was rewritten with backward="all": then it runs out of place
+    through ops.QKNormRopeFn (unless attention dropout would be active), whose outputs have the same layout."""
     import sys
 
     from . import ops
@@ -1215,8 +1228,10 @@ def _family_attention_forward(self, hidden_states, position_embeddings=None, att
     name = type(self).__name__
     offset, has_qk = self._bf_family[0], self._bf_family[1]
     qn, kn = (self.q_norm, self.k_norm) if has_qk else (None, None)
+    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
     fast = (pe is not None and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 3 and x.dtype in ops._TORCH2BF
-            and self.head_dim in (64, 128, 256) and not self.training and not _records_grad(x, self)
+            and self.head_dim in (64, 128, 256) and (_blocks_backward(self) or not (self.training or rec))
+            and not (self.training and self.attention_dropout > 0)
             and not (has_qk and (_hooked(qn) or _hooked(kn))))
     if fast:
         cos, sin = pe
@@ -1234,8 +1249,12 @@ def _family_attention_forward(self, hidden_states, position_embeddings=None, att
     cos, sin = (t if t.is_contiguous() else t.contiguous() for t in (cos, sin))
     gq, gk = (qn.weight, kn.weight) if has_qk else (None, None)
     if ops.qknorm_rope_supported(query_states, key_states, cos, sin, gq, gk):
-        query_states, key_states = ops.qknorm_rope(query_states, key_states, cos, sin, gq, gk,
-                                                   eps=_norm_eps(qn) if has_qk else 0.0, weight_offset=offset, inplace=True)
+        eps = _norm_eps(qn) if has_qk else 0.0
+        if rec:  # the in-place form would overwrite what the projections' backward reads
+            query_states, key_states = ops.QKNormRopeFn.apply(query_states, key_states, cos, sin, gq, gk, eps, offset)
+        else:
+            query_states, key_states = ops.qknorm_rope(query_states, key_states, cos, sin, gq, gk, eps=eps,
+                                                       weight_offset=offset, inplace=True)
     else:  # a projection that came back in another dtype or layout: the framework's ops on what is already computed
         if has_qk:
             query_states, key_states = qn(query_states), kn(key_states)
@@ -1258,16 +1277,18 @@ def _family_attention_forward(self, hidden_states, position_embeddings=None, att
 
 def _geglu_mlp_forward(self, x):
     """forward of an HF Gemma-style MLP — down_proj(gelu_tanh(gate_proj(x)) * up_proj(x)) — with the activation and the
-    product as one launch (bf_geglu).  Inference only."""
+    product as one launch (bf_geglu); rewritten with backward="all", under recorded gradients and in training mode too,
+    through ops.GeGLUFn."""
     from . import ops
 
+    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
     if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in ops._TORCH2BF or _hooked(self.act_fn)
-            or self.training or _records_grad(x, self)):
+            or ((self.training or rec) and not _blocks_backward(self))):
         return self._bf_plain_mlp_forward(x)
     gate, up = self.gate_proj(x), self.up_proj(x)
     if not ops.geglu_supported(gate, up):
         return self.down_proj(self.act_fn(gate) * up)
-    return self.down_proj(ops.geglu(gate, up))
+    return self.down_proj(ops.GeGLUFn.apply(gate, up) if rec else ops.geglu(gate, up))
 
 
 def _fuse_family_layer(layer, nxt, family) -> bool:
@@ -1301,7 +1322,7 @@ def _fuse_family_layer(layer, nxt, family) -> bool:
     return True
 
 
-def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False, families=_DEFAULT_FAMILIES) -> int:
+def fuse_decoder_blocks(model: torch.nn.Module, backward: Union[bool, str] = False, families=_DEFAULT_FAMILIES) -> int:
     """Run the memory-bound ops of HuggingFace Llama, Mistral and Qwen2 decoder layers — the two RMSNorms with the
     residual adds in front of them, the rotary embedding of q and k, SiLU(gate) * up — as four launches per layer
     (bf_add_rmsnorm twice, bf_rope_qk, bf_swiglu) instead of the framework's thirty or so elementwise kernels.  A layer is
@@ -1325,12 +1346,18 @@ def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False, families
       gemma2, gemma3   the four norms around the two residual adds as two norm -> add -> norm launches
               (bf_norm_add_rmsnorm), bf_qknorm_rope (with Gemma 3's q_norm / k_norm), bf_geglu: four launches a layer.
               A Gemma whose activation is not the tanh GELU is declined.
-    For these four the rewrite is inference-only: under recorded gradients or in training mode the modules' own forwards
-    run, and backward=True sets no backward flag on them.  A hook on a module whose forward a fast form skips (the three
-    further norms, q_norm, k_norm, act_fn) sends that module, or its layer, to its own forward.
+    For these four backward=True sets no backward flag: under recorded gradients or in training mode the modules' own
+    forwards run.  backward="all" turns the backward on for them as well as for the default three: the fast forms then run
+    under recorded gradients and in training mode through autograd functions whose backward is bf_norm_add_rmsnorm_bwd (one
+    launch for a norm -> add -> norm, and a small one for the two weights' gradients), bf_qknorm_rope_bwd and bf_geglu_bwd
+    (Qwen3's layer and MLP: bf_add_rmsnorm_bwd, bf_swiglu_bwd).  A hook on a module whose forward a fast form skips (the
+    three further norms, q_norm, k_norm, act_fn) sends that module, or its layer, to its own forward.
 
     Returns the number of layers rewritten; calling it again rewrites nothing twice (a second call with backward=True
-    turns the backward on for the Llama / Mistral / Qwen2 layers already rewritten, and counts none of them)."""
+    turns the backward on for the Llama / Mistral / Qwen2 layers already rewritten, one with backward="all" for the layers
+    of every family, and counts none of them).  Any other value of `backward` that is no bool is a ValueError."""
+    if not isinstance(backward, bool) and backward != "all":
+        raise ValueError(f"fuse_decoder_blocks: backward={backward!r} must be False, True or 'all'")
     names = (families,) if isinstance(families, str) else tuple(families)
     if "all" in names:
         names = tuple(_CLASSIC_FAMILIES) + tuple(_FAMILY_LAYERS)
@@ -1352,6 +1379,9 @@ def fuse_decoder_blocks(model: torch.nn.Module, backward: bool = False, families
             if cls in further:
                 if not hasattr(layer, "_bf_plain_layer_forward") and _fuse_family_layer(layer, nxt, further[cls]):
                     fused += 1
+                if backward == "all" and hasattr(layer, "_bf_plain_layer_forward"):
+                    for m in (layer, attn, mlp, layer.input_layernorm, nxt):
+                        m._bf_blocks_backward = True
                 continue
             if backward and hasattr(layer, "_bf_plain_layer_forward") and cls in _DECODER_LAYERS:
                 for m in (layer, attn, mlp, layer.input_layernorm, nxt):

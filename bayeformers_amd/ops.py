@@ -1841,6 +1841,191 @@ class SwiGLUFn(torch.autograd.Function):
         return swiglu_backward(gate, up, grad_out)
 
 
+# ---- the backward of the Gemma / Qwen3 siblings: bf_norm_add_rmsnorm_bwd / bf_qknorm_rope_bwd / bf_geglu_bwd
+# launches of the three backward entries from this process (the forwards of a training step count in FAMILY_BLOCK_CALLS)
+FAMILY_BLOCK_BWD_CALLS = {"norm_add_norm": 0, "qknorm_rope": 0, "geglu": 0}
+
+
+def norm_add_rmsnorm_backward(x: Optional[Tensor], z: Tensor, gamma_pre: Optional[Tensor], gamma_out: Tensor,
+                              grad_out: Optional[Tensor], eps_pre: float, eps_out: float, weight_offset: int = 1,
+                              grad_sum: Optional[Tensor] = None, want_dz: bool = True):
+    """Gradients of norm_add_rmsnorm (bf_norm_add_rmsnorm_bwd) from the sum z it returned (x itself when nothing changed
+    it) and, with gamma_pre, its input x: (dx, dz, dgamma_pre, dgamma_out).  dz is the gradient of the residual; without
+    gamma_pre dx is dz and dgamma_pre None.  The dgammas are fp32.  grad_sum: the gradient that reached z through its
+    other consumer, added inside the kernel; grad_out None: only the sum was consumed (dgamma_out is then zero).
+    want_dz=False (with gamma_pre, no residual): dz is not written and None is returned in its place."""
+    _require_device(z, "norm_add_rmsnorm_backward input")
+    N = z.shape[-1]
+    if grad_out is None and grad_sum is None:
+        raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: no gradient")
+    for g in (gamma_pre, gamma_out):
+        if g is not None and (g.dtype != gamma_out.dtype or g.dtype not in (torch.float32, z.dtype) or g.numel() != N):
+            raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: the gammas must be [N], of one dtype: float32 or the input's")
+    if any(t is not None and t.shape != z.shape for t in (grad_out, grad_sum, x if gamma_pre is not None else None)):
+        raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: the gradients and x must have z's shape")
+    pre = gamma_pre is not None
+    if pre and (x is None or x.dtype != z.dtype):
+        raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: gamma_pre needs the forward's input x")
+    z2 = _rows_of(z, N)
+    x2 = _rows_of(x, N) if pre else None
+    g2 = _grad_rows(grad_out, z, N) if grad_out is not None else None
+    h2 = _grad_rows(grad_sum, z, N) if grad_sum is not None else None
+    dz = torch.empty_like(z2) if (want_dz or not pre) else None
+    dx = torch.empty_like(z2) if pre else None
+    dg_out = torch.empty(N, dtype=torch.float32, device=z.device)
+    dg_pre = torch.empty(N, dtype=torch.float32, device=z.device) if pre else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    lib = _C.lib()
+    ws = workspace(z.device, lib.bf_norm_add_rmsnorm_bwd_workspace_bytes(z2.shape[0], N, int(pre)))
+    _C.check(lib.bf_norm_add_rmsnorm_bwd(ptr(x2), z2.data_ptr(), ptr(gamma_pre), gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype],
+                                         int(weight_offset), ptr(g2), ptr(h2), ptr(dz), ptr(dx), ptr(dg_pre), dg_out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _TORCH2BF[z.dtype], z2.shape[0], N, float(eps_pre),
+                                         float(eps_out), _stream_ptr()), "bf_norm_add_rmsnorm_bwd")
+    FAMILY_BLOCK_BWD_CALLS["norm_add_norm"] += 1
+    dz = dz.view(z.shape) if dz is not None else None
+    return (dx.view(z.shape) if pre else dz), dz, dg_pre, dg_out
+
+
+class NormAddRMSNormFn(torch.autograd.Function):
+    """norm_add_rmsnorm with both directions in the HIP kernels.  It returns (z, y), the two outputs of one launch, or y
+    alone when z is x (no gamma_pre, no residual); backward receives their gradients separately and hands z's to the
+    kernel, which adds it on load, as AddRMSNormFn does.  Saves x (only with gamma_pre), z (an output, or x) and the gammas."""
+
+    @staticmethod
+    def forward(ctx, x, gamma_pre, residual, gamma_out, eps_pre, eps_out, weight_offset):
+        ctx.eps_pre, ctx.eps_out, ctx.woff = eps_pre, eps_out, weight_offset
+        ctx.has_pre, ctx.has_res = gamma_pre is not None, residual is not None
+        z, y = norm_add_rmsnorm(x, gamma_pre, residual, gamma_out, eps_pre, eps_out, weight_offset)
+        ctx.save_for_backward(x if ctx.has_pre else None, z, gamma_pre, gamma_out)
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, not as a tensor of zeros
+        return (z, y) if (ctx.has_pre or ctx.has_res) else y
+
+    @staticmethod
+    def backward(ctx, *grads):
+        x, z, gamma_pre, gamma_out = ctx.saved_tensors
+        grad_z, grad_y = grads if (ctx.has_pre or ctx.has_res) else (None, grads[0])
+        need = ctx.needs_input_grad
+        if grad_y is None and grad_z is None:
+            return None, None, None, None, None, None, None
+        if grad_y is None and not ctx.has_pre:  # only the sum was used: the add's own backward
+            return grad_z if need[0] else None, None, grad_z if need[2] else None, None, None, None, None
+        dx, dz, dg_pre, dg_out = norm_add_rmsnorm_backward(x, z, gamma_pre, gamma_out, grad_y, ctx.eps_pre, ctx.eps_out, ctx.woff,
+                                                           grad_sum=grad_z, want_dz=ctx.has_res and need[2])
+        if grad_y is None:
+            dg_out = None  # the second norm's output was not used
+        elif need[3] and dg_out.dtype != gamma_out.dtype:
+            dg_out = dg_out.to(gamma_out.dtype)  # the kernel emits fp32
+        if ctx.has_pre and need[1] and dg_pre.dtype != gamma_pre.dtype:
+            dg_pre = dg_pre.to(gamma_pre.dtype)
+        return (dx if need[0] else None, dg_pre if (ctx.has_pre and need[1]) else None,
+                dz if (ctx.has_res and need[2]) else None, dg_out if need[3] else None, None, None, None)
+
+
+def _bthd(t: Tensor) -> Tensor:
+    """t [B, heads, T, D] laid out [B, T, heads, D] back to back (the projections' layout): t itself, or a copy."""
+    if t.transpose(1, 2).is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    return t.transpose(1, 2).contiguous().transpose(1, 2)
+
+
+def qknorm_rope_backward(grad_q: Tensor, grad_k: Tensor, cos: Tensor, sin: Tensor, q: Optional[Tensor] = None,
+                         k: Optional[Tensor] = None, gamma_q: Optional[Tensor] = None, gamma_k: Optional[Tensor] = None,
+                         eps: float = 1e-6, weight_offset: int = 0):
+    """Gradients of qknorm_rope (bf_qknorm_rope_bwd): grad_q [B, H, T, D] / grad_k [B, Hkv, T, D] in any layout
+    qknorm_rope_supported takes (read where the attention backward left them) -> (dq, dk, dgamma_q, dgamma_k): dq / dk new
+    tensors laid out [B, T, heads, D] — what the backward of the projections reads — returned as their [B, heads, T, D]
+    views, the dgammas fp32 [D] (None for a tensor without a gamma).  q / k: the forward's inputs, needed for a tensor that
+    has a gamma."""
+    _require_device(grad_q, "qknorm_rope_backward input")
+    grad_q, grad_k = _rope_grad(grad_q, grad_q), _rope_grad(grad_k, grad_q)
+    if not qknorm_rope_supported(grad_q, grad_k, cos, sin, gamma_q, gamma_k):
+        raise _C.BayeFormersAMDError("qknorm_rope_backward: unsupported shapes, strides or dtypes (see ops.qknorm_rope_supported)")
+    for g, x, like in ((gamma_q, q, grad_q), (gamma_k, k, grad_k)):
+        if g is not None and (x is None or x.shape != like.shape or x.dtype != like.dtype or not x.is_cuda):
+            raise _C.BayeFormersAMDError("qknorm_rope_backward: a gamma needs the forward's input of the gradient's shape and dtype")
+    B, H, T, D = grad_q.shape
+    Hkv = grad_k.shape[1]
+    xq = _bthd(q) if gamma_q is not None else None
+    xk = _bthd(k) if gamma_k is not None else None
+    dq = torch.empty((B, T, H, D), dtype=grad_q.dtype, device=grad_q.device).transpose(1, 2)
+    dk = torch.empty((B, T, Hkv, D), dtype=grad_k.dtype, device=grad_k.device).transpose(1, 2)
+    dgq = torch.empty(D, dtype=torch.float32, device=grad_q.device) if gamma_q is not None else None
+    dgk = torch.empty(D, dtype=torch.float32, device=grad_q.device) if gamma_k is not None else None
+    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
+    for name, t in (("q_stride", grad_q), ("k_stride", grad_k), ("q_out_stride", dq), ("k_out_stride", dk)):
+        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
+    g = gamma_q if gamma_q is not None else gamma_k
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    lib = _C.lib()
+    nbytes = lib.bf_qknorm_rope_bwd_workspace_bytes(ctypes.byref(s), int(g is not None))
+    ws = workspace(grad_q.device, nbytes) if nbytes else None
+    _C.check(lib.bf_qknorm_rope_bwd(grad_q.data_ptr(), grad_k.data_ptr(), ptr(xq), ptr(xk), cos.data_ptr(), sin.data_ptr(),
+                                    _TORCH2BF[cos.dtype], ptr(gamma_q), ptr(gamma_k),
+                                    _TORCH2BF[g.dtype] if g is not None else _C.BF_DT_F32, int(weight_offset), float(eps),
+                                    dq.data_ptr(), dk.data_ptr(), ptr(dgq), ptr(dgk), ptr(ws), ws.numel() if ws is not None else 0,
+                                    _TORCH2BF[grad_q.dtype], ctypes.byref(s), _stream_ptr()), "bf_qknorm_rope_bwd")
+    FAMILY_BLOCK_BWD_CALLS["qknorm_rope"] += 1
+    return dq, dk, dgq, dgk
+
+
+class QKNormRopeFn(torch.autograd.Function):
+    """qknorm_rope (out of place) with both directions in the HIP kernels; saves the two tables, the gammas, and q / k only
+    when a gamma is present."""
+
+    @staticmethod
+    def forward(ctx, q, k, cos, sin, gamma_q, gamma_k, eps, weight_offset):
+        ctx.eps, ctx.woff = eps, weight_offset
+        ctx.save_for_backward(cos, sin, gamma_q, gamma_k, q if gamma_q is not None else None, k if gamma_k is not None else None)
+        return qknorm_rope(q, k, cos, sin, gamma_q, gamma_k, eps=eps, weight_offset=weight_offset)
+
+    @staticmethod
+    def backward(ctx, grad_q, grad_k):
+        cos, sin, gamma_q, gamma_k, q, k = ctx.saved_tensors
+        dq, dk, dgq, dgk = qknorm_rope_backward(grad_q, grad_k, cos, sin, q, k, gamma_q, gamma_k, ctx.eps, ctx.woff)
+        need = ctx.needs_input_grad
+        if dgq is not None and need[4] and dgq.dtype != gamma_q.dtype:
+            dgq = dgq.to(gamma_q.dtype)  # the kernel emits fp32
+        if dgk is not None and need[5] and dgk.dtype != gamma_k.dtype:
+            dgk = dgk.to(gamma_k.dtype)
+        return dq, dk, None, None, dgq if need[4] else None, dgk if need[5] else None, None, None
+
+
+def geglu_backward(gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool = False):
+    """Gradients of geglu (bf_geglu_bwd): (dgate, dup) from the forward's inputs; stacked as swiglu_backward's."""
+    _require_device(gate, "geglu_backward input")
+    if not geglu_supported(gate, up) or grad_out.shape != gate.shape:
+        raise _C.BayeFormersAMDError("geglu_backward: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
+    g = grad_out if grad_out.dtype == gate.dtype else grad_out.to(gate.dtype)
+    if not g.is_cuda or _row_stride(g) is None:
+        g = g.contiguous()
+    N = gate.shape[-1]
+    if stacked:
+        both = torch.empty((*gate.shape[:-1], 2 * N), dtype=gate.dtype, device=gate.device)
+        dgate, dup = both[..., :N], both[..., N:]
+    else:
+        dgate, dup = (torch.empty(gate.shape, dtype=gate.dtype, device=gate.device) for _ in range(2))
+    _C.check(_C.lib().bf_geglu_bwd(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), g.data_ptr(),
+                                   _row_stride(g), dgate.data_ptr(), 2 * N if stacked else N, dup.data_ptr(),
+                                   2 * N if stacked else N, _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()),
+             "bf_geglu_bwd")
+    FAMILY_BLOCK_BWD_CALLS["geglu"] += 1
+    return dgate, dup
+
+
+class GeGLUFn(torch.autograd.Function):
+    """geglu with both directions in the HIP kernels; saves gate and up (the projections' outputs), nothing new."""
+
+    @staticmethod
+    def forward(ctx, gate, up):
+        ctx.save_for_backward(gate, up)
+        return geglu(gate, up)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gate, up = ctx.saved_tensors
+        return geglu_backward(gate, up, grad_out)
+
+
 # ------------------------------------------------------------------------------------- Monte-Carlo predictive statistics
 _PREDICTIVE_WS = {}
 

@@ -57,4 +57,7 @@ int bf_geglu(const void* d_gate, int64_t gate_row_stride, const void* d_up, int6
 #ifdef __cplusplus
 }
 #endif
+
+#include "bayeformers_amd_family_blocks_bwd.h" /* the backward of the three: a header and a ctypes table of their own */
+
 #endif /* BAYEFORMERS_AMD_FAMILY_BLOCKS_H */
