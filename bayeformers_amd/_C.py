@@ -213,6 +213,14 @@ FAMILY_BLOCK_BWD_SYMBOLS = {
     "bf_geglu_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i64, _i, _vp]),
 }
 
+# what include/bayeformers_amd_packed.h declares (banded causal attention for packed sequences): the plain entries'
+# arguments with the int32 bounds d_lo (and d_hi in the backward) in place of the key mask and its flag
+PACKED_SYMBOLS = {
+    "bf_attention_fwd_gqa_band": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float, _vp]),
+    "bf_attention_bwd_gqa_band": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, ctypes.c_float,
+                                       _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -243,6 +251,14 @@ def lib():
             if fn is None:  # a library from before these entries reports the version these bindings expect
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the Gemma / Qwen3 decoder-block entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in PACKED_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise: a library from before these entries reports the same version
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the packed-sequence attention entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

@@ -352,7 +352,8 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     # when nothing is padded); an explicit is_causal wins over the module flag, as in the framework's sdpa_attention_forward
     explicit = kwargs.get("is_causal", None)
     causal = bool(getattr(attention_mask, "_bf_causal", False) or getattr(attention_mask, "_bf_decode", False)
-                  or getattr(attention_mask, "_bf_window", None) is not None) or (
+                  or getattr(attention_mask, "_bf_window", None) is not None
+                  or getattr(attention_mask, "_bf_band", None) is not None) or (
         bool(explicit) if explicit is not None else (attention_mask is None and bool(getattr(module, "is_causal", False))))
     if causal:
         return _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs)
@@ -406,6 +407,9 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
 
     from . import ops
 
+    band = getattr(attention_mask, "_bf_band", None) if attention_mask is not None else None
+    if band is not None and kwargs.get("softcap", None) is None:
+        return _packed_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, band, **kwargs)
     window = getattr(attention_mask, "_bf_window", None) if attention_mask is not None else None
     if (window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window) \
             or kwargs.get("s_aux", None) is not None \
@@ -465,6 +469,33 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     if need_grad:
         return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True), None
     return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off), None
+
+
+def _packed_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, band, **kwargs):
+    """_causal_attention for a packed-sequence mask (`_bf_band = (lo, hi)`, `_bf_band_window`: `_packed_mask`), without
+    soft-capping: bf_attention_fwd_gqa_band (bf_attention_bwd_gqa_band behind it when a gradient is needed) under
+    `packed_attention()`, for equal query and key lengths of any size (subject to `ragged_attention`) and the shapes
+    ops.attention_supported takes.  Attention sinks (`s_aux`), a `sliding_window` argument that disagrees with the mask's
+    window, attention dropout, unsupported shapes and the classes ops.prefill_kernel_wins sends there run the framework's
+    scaled-dot-product attention over the dense mask, as every such call did before."""
+    from transformers.integrations.sdpa_attention import sdpa_attention_forward
+
+    from . import ops
+
+    window = getattr(attention_mask, "_bf_band_window", None)
+    B, H, T, D = query.shape
+    usable = (packed_attention_enabled() and kwargs.get("s_aux", None) is None
+              and not ("sliding_window" in kwargs and kwargs["sliding_window"] != window)
+              and dropout == 0.0 and T == key.shape[2] and (T % 128 == 0 or ragged_attention_enabled())
+              and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1])
+              and tuple(band[0].shape) == (B, T) and tuple(band[1].shape) == (B, T)
+              and ops.prefill_kernel_wins(H, key.shape[1], T, D, need_grad, window, masked=True))
+    if not usable:
+        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
+    scale = scaling if scaling is not None else D ** -0.5
+    if need_grad:
+        return ops.AttentionGqaBandFn.apply(query, key, value, band[0], band[1], scale), None
+    return ops.attention_forward_gqa_band(query, key, value, band[0], scale), None
 
 
 def _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window, softcap):
@@ -532,17 +563,67 @@ def _softcap_eager(module, query, key, value, attention_mask, dropout, scaling, 
     return torch.matmul(w, value).transpose(1, 2).contiguous()
 
 
+def _closure_cell(fn, name):
+    """What the closure of `fn` holds under the free variable `name` (None: not a closure over it)."""
+    code = getattr(fn, "__code__", None)
+    if code is None or name not in code.co_freevars or fn.__closure__ is None:
+        return None
+    return fn.__closure__[code.co_freevars.index(name)].cell_contents
+
+
+def _packed_sequence_of(mask_function):
+    """(ids, W) when mask_function is exactly the composition transformers builds for packed sequences
+    (masking_utils._preprocess_mask_arguments: position_ids that restart, no attention mask) — and_masks(f,
+    packed_sequence_mask_function(ids)) over exactly two functions, f being causal_mask_function (W = None) or
+    sliding_window_causal_mask_function(W) — else None.  `ids` is the [B, T] tensor of document indices, non-decreasing
+    along T as find_packed_sequence_indices returns it (a cumulative sum)."""
+    from transformers import masking_utils as mu
+
+    if getattr(mask_function, "__code__", None) is not mu.and_masks(mu.causal_mask_function).__code__:
+        return None
+    fns = _closure_cell(mask_function, "mask_functions")
+    if not isinstance(fns, tuple) or len(fns) != 2:
+        return None
+    if getattr(fns[1], "__code__", None) is not mu.packed_sequence_mask_function(None).__code__:
+        return None
+    ids = _closure_cell(fns[1], "packed_sequence_mask")
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
+        return None
+    if fns[0] is mu.causal_mask_function:
+        return ids, None
+    window = _sliding_window_of(fns[0])
+    return (ids, window) if window is not None else None
+
+
+def _packed_mask(batch_size, q_length, kv_length, q_offset, kv_offset, ids, window, attention_mask, **kwargs):
+    """The packed-sequence mask _padding_mask_interface builds on the device (NotImplemented: not the case it takes): the
+    cache-free sequence, no padding mask, ids [batch_size, kv_length].  Query i sees key j iff j <= i, both lie in one
+    document and — with a window — i - j < window: sdpa_mask's [B, 1, T, T] bool mask, carrying the bounds of banded
+    causal attention `_bf_band = (lo, hi)` (ops.band_bounds) and `_bf_band_window` for the band entries."""
+    from . import ops
+
+    local_size = kwargs.get("local_size", None)
+    if (kwargs.get("use_vmap", False) or attention_mask is not None or q_length is None or q_length != kv_length
+            or not (isinstance(q_offset, int) and isinstance(kv_offset, int) and q_offset == 0 and kv_offset == 0)
+            or tuple(ids.shape) != (batch_size, kv_length)
+            or (local_size is not None and local_size != window)):
+        return NotImplemented
+    pos = torch.arange(kv_length, device=ids.device)
+    seen = (pos[None, :] <= pos[:, None])[None, :, :] & (ids[:, :, None] == ids[:, None, :])
+    if window is not None:
+        seen = seen & (pos[None, :] > pos[:, None] - window)[None, :, :]
+    out = seen[:, None, :, :]
+    out._bf_band = ops.band_bounds(ids, window)
+    out._bf_band_window = window
+    return out
+
+
 def _sliding_window_of(mask_function):
     """W when mask_function is exactly transformers' sliding_window_causal_mask_function(W) — and_masks over the two
     functions (sliding_window_overlay(W)'s inner function, causal_mask_function) and nothing else — else None."""
     from transformers import masking_utils as mu
 
-    def cell(fn, name):
-        code = getattr(fn, "__code__", None)
-        if code is None or name not in code.co_freevars or fn.__closure__ is None:
-            return None
-        return fn.__closure__[code.co_freevars.index(name)].cell_contents
-
+    cell = _closure_cell
     if getattr(mask_function, "__code__", None) is not mu.and_masks(mu.causal_mask_function).__code__:
         return None
     fns = cell(mask_function, "mask_functions")
@@ -633,10 +714,19 @@ def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=
     ways — the cache-free sequence, a step against a cache (a DynamicSlidingWindowLayer's kv_offset > 0 included: its
     key mask is the 2-D mask's slice at kv_offset) and a fixed-capacity cache — and carries `_bf_window = W` for the
     window entries; it is never None when the window hides something.
+    Packed sequences (exactly and_masks(causal_mask_function or sliding_window_causal_mask_function(W),
+    packed_sequence_mask_function(ids)), the cache-free sequence, no padding mask: `_packed_mask`) get the same dense bool
+    mask carrying `_bf_band = (lo, hi)` and `_bf_band_window` for the band entries — and none of the other markers.
     Anything else (4-D masks, extra mask functions, other offsets) goes to the framework's scaled-dot-product mask."""
     from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
 
     window = _sliding_window_of(mask_function) if mask_function is not causal_mask_function else None
+    packed = _packed_sequence_of(mask_function) if mask_function is not causal_mask_function and window is None else None
+    if packed is not None:
+        out = _packed_mask(batch_size, q_length, kv_length, q_offset, kv_offset, packed[0], packed[1], attention_mask,
+                           **kwargs)
+        if out is not NotImplemented:
+            return out
     if window is not None:
         out = _sliding_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, attention_mask, **kwargs)
         if out is not NotImplemented:
@@ -731,6 +821,22 @@ def ragged_attention(enable: bool = True) -> None:
 
 def ragged_attention_enabled() -> bool:
     return _RAGGED_ATTENTION[0] and os.environ.get("BF_NO_RAGGED_ATTENTION") is None
+
+
+_PACKED_ATTENTION = [True]
+
+
+def packed_attention(enable: bool = True) -> None:
+    """Switch the band attention kernels for packed sequences (bf_attention_fwd_gqa_band / bf_attention_bwd_gqa_band:
+    position ids that restart at each document, no attention mask) on or off for this process; BF_NO_PACKED_ATTENTION in
+    the environment switches them off too.  Off: such a prefill or training step runs the framework's scaled-dot-product
+    attention over the dense [B, 1, T, T] mask, as it did before.  The switch is part of what a captured forward bakes in
+    (graphs.baked_state): a replayed forward is captured again after a flip."""
+    _PACKED_ATTENTION[0] = bool(enable)
+
+
+def packed_attention_enabled() -> bool:
+    return _PACKED_ATTENTION[0] and os.environ.get("BF_NO_PACKED_ATTENTION") is None
 
 
 _SOFTCAP_ATTENTION = [False]
@@ -1422,7 +1528,10 @@ def fuse_attention(model: torch.nn.Module) -> bool:
     attention sinks (gpt-oss) goes to the framework.  Logit soft-capping (Gemma 2) runs the soft-cap entries
     (bf_attention_fwd_gqa_softcap and its backward and decode siblings) once `softcap_attention()` or BF_SOFTCAP_ATTENTION
     switches them on; with that switch off, the default, such a call goes to the framework's scaled-dot-product attention,
-    which ignores the cap — the model then computes another function than its `eager` attention.  The ops around the
+    which ignores the cap — the model then computes another function than its `eager` attention.  Packed sequences
+    (position ids that restart at each document, no attention mask, no cache) run the band entries
+    (bf_attention_fwd_gqa_band / bf_attention_bwd_gqa_band) unless `packed_attention(False)` or BF_NO_PACKED_ATTENTION
+    sends them to the framework's attention over the dense mask.  The ops around the
     attention of those families (norms, rotary embedding, gate) are fuse_decoder_blocks's, opt-in by its `families`.  Returns False (and changes
     nothing) when the model has no HuggingFace config or transformers lacks the interface.
     A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation

@@ -85,8 +85,17 @@ struct GqaParams {
 struct GqaCapParams : GqaParams {
     float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
 };
-template <bool CAP>
-using ParamsOf = std::conditional_t<CAP, GqaCapParams, GqaParams>;
+// The BAND instantiations run banded causal attention (packed sequences: include/bayeformers_amd_packed.h): query i sees
+// key j iff lo[b][i] <= j <= i, and key j is seen by the queries j .. hi[b][j]; both bounds are non-decreasing along T, so
+// a block's first row holds its least bound and its last row its greatest.  The forward and the dq kernel read lo, the
+// dk/dv kernel hi: LOCAL with a bound that varies per row, and like it a compile-time flag with a parameter block and
+// branches of its own (no key mask, no cap).  Rows >= T of a TAIL launch read the bound of row T - 1.
+struct GqaBandParams : GqaParams {
+    const int* lo;  // [B][T]
+    const int* hi;  // [B][T], backward only
+};
+template <bool CAP, bool BAND = false>
+using ParamsOf = std::conditional_t<BAND, GqaBandParams, std::conditional_t<CAP, GqaCapParams, GqaParams>>;
 
 // The TAIL instantiations run a sequence whose length is no multiple of TQ (any T >= 1): the last tile's missing rows are
 // never read or written.  A load of row >= T re-reads row T - 1 (finite values of the caller's, no branch), keys >= T get
@@ -103,9 +112,43 @@ __device__ __forceinline__ void stage_rows(const T* base, long long stride, int 
     else stage<T, HD, NR, NT>(base, stride, row0, swz, pad, tid);
 }
 
+// A wave's bounds over its NB blocks of 16 rows (queries with lo, keys with hi): each lane's own row's (rows >= T of a TAIL
+// launch: row T - 1's), wave-uniform copies of each block's first and last row's — the least and the greatest, the bounds
+// being monotone — and whether the tile in hand crosses some row's bound.  The kernels touch it behind `BAND &&` or
+// `if constexpr (BAND)` alone: in their other instantiations it is an object nobody reads or writes.
+template <int NB>
+struct Band {
+    int row[NB], first[NB], last[NB];
+    bool edge;
+    template <bool TAIL>
+    __device__ __forceinline__ void load(const int* bound, int r0, int li, int T) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            row[i] = bound[tail_row<TAIL>(r0 + i * 16 + li, T)];
+            first[i] = __builtin_amdgcn_readlane(row[i], 0);
+            last[i] = __builtin_amdgcn_readlane(row[i], 15);
+        }
+    }
+};
+// the first key tile of query tile qt: its first row's bound (clamped: the range stays inside the sequence)
+template <int KT, typename P>
+__device__ __forceinline__ int band_first_key(const P& p, int b, int qt) {
+    if constexpr (std::is_same_v<P, GqaBandParams>)
+        return max(0, __builtin_amdgcn_readfirstlane(p.lo[(long long)b * p.T + qt * TQ])) / KT * KT;
+    else return 0;
+}
+// the end of the query tiles of a key tile whose last key is `key`: after the tile of the last query that sees it
+template <int QT, typename P>
+__device__ __forceinline__ int band_query_end(const P& p, int b, int key) {
+    if constexpr (std::is_same_v<P, GqaBandParams>) {
+        const int last = min(p.T - 1, __builtin_amdgcn_readfirstlane(p.hi[(long long)b * p.T + min(key, p.T - 1)]));
+        return min(p.T, last / QT * QT + QT);
+    } else return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------- forward
-template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, int MINB>
-__global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> p) {
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, int MINB, bool BAND = false>
+__global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP, BAND> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
@@ -140,7 +183,10 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> 
     float run_max[2] = {-INFINITY, -INFINITY}, run_sum[2] = {0.f, 0.f};
 
     const int kend = CAUSAL ? (TAIL ? min((qt + 1) * TQ, p.T) : (qt + 1) * TQ) : p.T;
-    const int kbeg = LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;  // the tile of the tile's first window key
+    Band<2> lo;  // BAND: the lower bounds of the wave's queries
+    if constexpr (BAND) lo.template load<TAIL>(p.lo + (long long)b * p.T, q0, li, p.T);
+    // the tile of the tile's first window key (BAND: of its first visible key)
+    const int kbeg = BAND ? band_first_key<KT>(p, b, qt) : LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;
     for (int key0 = kbeg; key0 < kend; key0 += KT) {
         if (key0 != kbeg) __syncthreads();
         stage_rows<TAIL, T, HD, KT, 256>(kb, p.ks[2], key0, p.T, ks, nullptr, tid);
@@ -158,6 +204,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> 
             if (TAIL && qr0 >= p.T) continue;  // no query of the block exists (after the barriers: every wave stages)
             if (CAUSAL && key0 > qr0 + 15) continue;  // the tile lies wholly above the diagonal for these 16 queries
             if (LOCAL && key0 + KT - 1 < qr0 - p.window + 1) continue;  // ... or wholly before their windows
+            if (BAND && key0 + KT - 1 < lo.first[qi]) continue;         // ... or wholly before their bounds
             f32x4_t s[NKB];
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -167,6 +214,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> 
             }
             const bool diag = CAUSAL && key0 + KT - 1 > qr0;
             const bool edge = LOCAL && key0 < qr0 + 16 - p.window;  // the tile crosses a window's lower edge
+            if constexpr (BAND) lo.edge = key0 < lo.last[qi];       // ... or some row's lower bound
             const bool past = TAIL && key0 + KT > p.T;              // the tile crosses the sequence's end
             float mx = -INFINITY;
 #pragma unroll
@@ -179,6 +227,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> 
                     else s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) s[kbk][j] = -INFINITY;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) s[kbk][j] = -INFINITY;
+                    if (BAND && lo.edge && key0 + kbk * 16 + lg * 4 + j < lo.row[qi]) s[kbk][j] = -INFINITY;
                     if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) s[kbk][j] = -INFINITY;
                     mx = fmaxf(mx, s[kbk][j]);
                 }
@@ -227,8 +276,8 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP> 
 }
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
-template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP>
-__global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(const ParamsOf<CAP> p) {
+template <typename T, int HD, int KT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, bool BAND = false>
+__global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(const ParamsOf<CAP, BAND> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
@@ -280,7 +329,9 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
         for (int j = 0; j < NDB; ++j) dq[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int kend = CAUSAL ? (TAIL ? min((qt + 1) * TQ, p.T) : (qt + 1) * TQ) : p.T;
-    const int kbeg = LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;
+    Band<2> lo;  // BAND: as in the forward
+    if constexpr (BAND) lo.template load<TAIL>(p.lo + (long long)b * p.T, q0, li, p.T);
+    const int kbeg = BAND ? band_first_key<KT>(p, b, qt) : LOCAL ? max(0, qt * TQ - p.window + 1) / KT * KT : 0;
     for (int key0 = kbeg; key0 < kend; key0 += KT) {
         if (key0 != kbeg) __syncthreads();
         stage_rows<TAIL, T, HD, KT, 256>(kb, p.ks[2], key0, p.T, ks, kp, tid);
@@ -297,6 +348,7 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
             if (TAIL && qr0 >= p.T) continue;
             if (CAUSAL && key0 > qr0 + 15) continue;
             if (LOCAL && key0 + KT - 1 < qr0 - p.window + 1) continue;
+            if (BAND && key0 + KT - 1 < lo.first[qi]) continue;
             f32x4_t s[NKB], dp[NKB];
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -309,6 +361,7 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
             }
             const bool diag = CAUSAL && key0 + KT - 1 > qr0;
             const bool edge = LOCAL && key0 < qr0 + 16 - p.window;
+            if constexpr (BAND) lo.edge = key0 < lo.last[qi];
             const bool past = TAIL && key0 + KT > p.T;
 #pragma unroll
             for (int kbk = 0; kbk < NKB; ++kbk) {
@@ -328,6 +381,7 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
+                    if (BAND && lo.edge && key0 + kbk * 16 + lg * 4 + j < lo.row[qi]) pr = 0.f;
                     if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
                     s[kbk][j] = pr * (dp[kbk][j] - delta[qi]);  // dS^T
                 }
@@ -352,8 +406,8 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
 }
 
 // ---------------------------------------------------------------------------------------------------- dK, dV
-template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, int MINB>
-__global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_kernel(const ParamsOf<CAP> p) {
+template <typename T, int HD, int QT, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, int MINB, bool BAND = false>
+__global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_kernel(const ParamsOf<CAP, BAND> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     constexpr int NDH = HD / 32, NDB = HD / 16, NQB = QT / 16;
@@ -390,8 +444,12 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
     for (int j = 0; j < NDB; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     const int qbeg = CAUSAL ? kt * KEYS : 0;
-    // LOCAL: up to the query tile of the last query that sees the tile's last key
-    const int qend = LOCAL ? min(p.T, (kt * KEYS + KEYS - 1 + p.window - 1) / QT * QT + QT) : p.T;
+    Band<1> hi;  // BAND: the upper bounds of the wave's keys
+    if constexpr (BAND) hi.template load<TAIL>(p.hi + (long long)b * p.T, wkey0, li, p.T);
+    // LOCAL, BAND: up to the query tile of the last query that sees the tile's last key
+    const int qend = BAND    ? band_query_end<QT>(p, b, kt * KEYS + KEYS - 1)
+                     : LOCAL ? min(p.T, (kt * KEYS + KEYS - 1 + p.window - 1) / QT * QT + QT)
+                             : p.T;
     bool first = true;
     for (int h = g * p.group; h < (g + 1) * p.group; ++h) {  // the group's query heads, in order: a fixed summation order
         const T* qb = reinterpret_cast<const T*>(p.q) + b * p.qs[0] + h * p.qs[1];
@@ -417,6 +475,7 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
             if (TAIL && wkey0 >= p.T) continue;  // no key of the wave exists (after the barriers: every wave stages)
             if (CAUSAL && q0 + QT - 1 < wkey0) continue;  // every query of the tile precedes the wave's keys
             if (LOCAL && q0 > wkey0 + 15 + p.window - 1) continue;  // ... or lies past all their windows
+            if (BAND && q0 > hi.last[0]) continue;                    // ... or past all their bounds
             f32x4_t s[NQB], dp[NQB];
 #pragma unroll
             for (int qbk = 0; qbk < NQB; ++qbk) {
@@ -429,6 +488,7 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
             }
             const bool diag = CAUSAL && q0 < wkey0 + 15;
             const bool edge = LOCAL && q0 + QT - 1 > wkey0 + p.window - 1;  // some query lies past a key's window
+            if constexpr (BAND) hi.edge = q0 + QT - 1 > hi.first[0];        // ... or past a key's bound
             const bool past = TAIL && q0 + QT > p.T;                        // the tile crosses the sequence's end
 #pragma unroll
             for (int qbk = 0; qbk < NQB; ++qbk) {
@@ -449,6 +509,7 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
                     float pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
                     if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
                     if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
+                    if (BAND && hi.edge && q0 + qbk * 16 + lg * 4 + j > hi.row[0]) pr = 0.f;
                     if (past && q0 + qbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
                     s[qbk][j] = pr;                          // P
                     dp[qbk][j] = pr * (dp[qbk][j] - d4[j]);  // dS
@@ -481,20 +542,39 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
 // the tiles fastest (as the BERT kernels order them) every XCD would get the tiles of one position — under a causal mask one
 // XCD all the heaviest — while tiles-slowest issues the heavy tiles of every (head, sequence) first, spread over all XCDs.
 // TAIL (T % TQ != 0): one more tile, whose rows >= T the kernels neither read nor write.
-template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP>
-void launch_fwd(const ParamsOf<CAP>& p, hipStream_t stream) {
+template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, bool BAND = false>
+void launch_fwd(const ParamsOf<CAP, BAND>& p, hipStream_t stream) {
     const dim3 grid(p.H, p.B, (p.T + TQ - 1) / TQ);
-    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, TAIL, CAP, Shape<HD>::FWD_MINB>), grid, dim3(256), 0,
-                       stream, p);
+    hipLaunchKernelGGL((gqa_fwd_kernel<T, HD, Shape<HD>::FWD_KT, CAUSAL, LOCAL, TAIL, CAP, Shape<HD>::FWD_MINB, BAND>), grid,
+                       dim3(256), 0, stream, p);
 }
 
-template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP>
-void launch_bwd(const ParamsOf<CAP>& p, hipStream_t stream) {
+template <typename T, int HD, bool CAUSAL, bool LOCAL, bool TAIL, bool CAP, bool BAND = false>
+void launch_bwd(const ParamsOf<CAP, BAND>& p, hipStream_t stream) {
     constexpr int KEYS = Shape<HD>::DKV_KEYS;  // keys per dk/dv workgroup: its own tile count
-    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL, CAP>), dim3(p.H, p.B, (p.T + TQ - 1) / TQ),
-                       dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, TAIL, CAP, Shape<HD>::DKV_MINB>),
+    hipLaunchKernelGGL((gqa_bwd_dq_kernel<T, HD, Shape<HD>::DQ_KT, CAUSAL, LOCAL, TAIL, CAP, BAND>),
+                       dim3(p.H, p.B, (p.T + TQ - 1) / TQ), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((gqa_bwd_dkv_kernel<T, HD, Shape<HD>::DKV_QT, CAUSAL, LOCAL, TAIL, CAP, Shape<HD>::DKV_MINB, BAND>),
                        dim3(p.Hkv, p.B, (p.T + KEYS - 1) / KEYS), dim3(KEYS * 4), 0, stream, p);
+}
+
+// the band instantiations: causal only, no cap, with or without a tail
+template <typename T, int HD>
+void launch_band(const GqaBandParams& p, bool bwd, hipStream_t stream) {
+    if (p.T % TQ) {
+        if (bwd) launch_bwd<T, HD, true, false, true, false, true>(p, stream);
+        else launch_fwd<T, HD, true, false, true, false, true>(p, stream);
+    } else {
+        if (bwd) launch_bwd<T, HD, true, false, false, false, true>(p, stream);
+        else launch_fwd<T, HD, true, false, false, false, true>(p, stream);
+    }
+}
+
+template <typename T>
+void launch_band(const GqaBandParams& p, int D, bool bwd, hipStream_t stream) {
+    if (D == 64) launch_band<T, 64>(p, bwd, stream);
+    else if (D == 128) launch_band<T, 128>(p, bwd, stream);
+    else launch_band<T, 256>(p, bwd, stream);
 }
 
 template <typename T, int HD, bool CAUSAL, bool LOCAL = false, bool CAP = false>
@@ -673,7 +753,71 @@ int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     return 0;
 }
 
+// The band entries' shape: what fill_shape takes, causal only (the bounds sit under the diagonal)
+int fill_band(const char* what, GqaBandParams& p, const bf_attn_gqa_t* s, int dtype, float scaling) {
+    if (fill_shape(what, p, s, dtype, scaling)) return 1;
+    if (s->causal != 1) BF_FAIL("%s: the band kernels need a causal shape (causal=%d)", what, s->causal);
+    return 0;
+}
+
+void dispatch_band(const GqaBandParams& p, int dtype, int D, bool bwd, hipStream_t stream) {
+    if (dtype == BF_DT_BF16) launch_band<__bf16>(p, D, bwd, stream);
+    else launch_band<_Float16>(p, D, bwd, stream);
+}
+
 }  // namespace
+
+int bf_attention_fwd_gqa_band(const void* d_q, const void* d_k, const void* d_v, const int32_t* d_lo, void* d_out, float* d_lse,
+                              int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
+    const char* what = "bf_attention_fwd_gqa_band";
+    if (!d_lo) BF_FAIL("%s: d_lo is NULL", what);
+    if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
+    GqaBandParams p = {};
+    if (fill_band(what, p, shape, dtype, scaling)) return 1;
+    if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if (d_lse && ((uintptr_t)d_lse & 15)) BF_FAIL("%s: lse must be 16-byte aligned", what);
+    if ((uintptr_t)d_lo & 3) BF_FAIL("%s: d_lo must be 4-byte aligned", what);
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.out = d_out;
+    p.lse = d_lse;
+    p.lo = d_lo;
+    dispatch_band(p, dtype, shape->head_dim, false, (hipStream_t)stream);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int bf_attention_bwd_gqa_band(const void* d_q, const void* d_k, const void* d_v, const int32_t* d_lo, const int32_t* d_hi,
+                              const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                              void* d_dv, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {
+    const char* what = "bf_attention_bwd_gqa_band";
+    if (!d_lo) BF_FAIL("%s: d_lo is NULL", what);
+    if (!d_hi) BF_FAIL("%s: d_hi is NULL", what);
+    if (!d_q || !d_k || !d_v || !d_out || !d_dout || !d_lse || !d_delta || !d_dq || !d_dk || !d_dv)
+        BF_FAIL("%s: NULL argument", what);
+    GqaBandParams p = {};
+    if (fill_band(what, p, shape, dtype, scaling)) return 1;
+    const uintptr_t al = (uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_dout |
+                         (uintptr_t)d_dq | (uintptr_t)d_dk | (uintptr_t)d_dv | (uintptr_t)d_lse | (uintptr_t)d_delta;
+    if (al & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if (((uintptr_t)d_lo | (uintptr_t)d_hi) & 3) BF_FAIL("%s: d_lo / d_hi must be 4-byte aligned", what);
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.o = d_out;
+    p.dout = d_dout;
+    p.lse = const_cast<float*>(d_lse);
+    p.delta = d_delta;
+    p.dq = d_dq;
+    p.dk = d_dk;
+    p.dv = d_dv;
+    p.lo = d_lo;
+    p.hi = d_hi;
+    dispatch_band(p, dtype, shape->head_dim, true, (hipStream_t)stream);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 int bf_attention_fwd_gqa(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
                          void* d_out, float* d_lse, int dtype, const bf_attn_gqa_t* shape, float scaling, void* stream) {

@@ -878,6 +878,74 @@ def attention_backward_gqa(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[T
     return dq, dkv[0], dkv[1]
 
 
+# launches of the band entries (bf_attention_fwd_gqa_band / bf_attention_bwd_gqa_band: packed sequences); they count here
+# alone
+PACKED_CALLS = {"fwd": 0, "bwd": 0}
+
+
+def band_bounds(doc_ids: Tensor, window: Optional[int] = None):
+    """The bounds of banded causal attention (include/bayeformers_amd_packed.h) for packed documents: doc_ids [B, T] (or
+    [T]) integers, non-decreasing along T, equal within a document (transformers' find_packed_sequence_indices).  Returns
+    (lo, hi), int32 of doc_ids' shape on its device, without a host synchronisation: query i sees the keys lo[i] .. i and
+    key j is seen by the queries j .. hi[j], where lo[i] = max(doc_start(i), i - window + 1) and
+    hi[j] = min(doc_end(j), j + window - 1) (window None: the documents alone)."""
+    if window is not None and window < 1:
+        raise ValueError(f"band_bounds: window={window} must be at least 1")
+    ids = doc_ids.contiguous()
+    pos = torch.arange(ids.shape[-1], device=ids.device)
+    lo = torch.searchsorted(ids, ids, right=False)     # the first token of each token's document
+    hi = torch.searchsorted(ids, ids, right=True) - 1  # ... and the last
+    if window is not None:
+        lo = torch.maximum(lo, pos - (window - 1))
+        hi = torch.minimum(hi, pos + (window - 1))
+    return lo.to(torch.int32), hi.to(torch.int32)
+
+
+def attention_forward_gqa_band(q: Tensor, k: Tensor, v: Tensor, lo: Tensor, scaling: float, want_lse: bool = False):
+    """Banded causal grouped-query attention (bf_attention_fwd_gqa_band): q, k, v as attention_forward_gqa takes them, lo
+    [B, T] int32 as band_bounds returns it — query i sees the keys lo[b, i] .. i; no key mask.  Returns [B, T, H, D]
+    contiguous and, with want_lse, the [B, H, T] fp32 log-sum-exp rows of the backward."""
+    B, H, T, D = q.shape
+    _check_bound(lo, "lo", B, T, q.device)
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device) if want_lse else None
+    shape = _gqa_shape(q, k, v, True)
+    _C.check(_C.lib().bf_attention_fwd_gqa_band(q.data_ptr(), k.data_ptr(), v.data_ptr(), lo.data_ptr(), out.data_ptr(),
+                                                lse.data_ptr() if lse is not None else None, _TORCH2BF[q.dtype],
+                                                ctypes.byref(shape), float(scaling), _stream_ptr()),
+             "bf_attention_fwd_gqa_band")
+    PACKED_CALLS["fwd"] += 1
+    return (out, lse) if want_lse else out
+
+
+def attention_backward_gqa_band(q: Tensor, k: Tensor, v: Tensor, lo: Tensor, hi: Tensor, out: Tensor, grad_out: Tensor,
+                                lse: Tensor, scaling: float):
+    """Gradients of attention_forward_gqa_band (bf_attention_bwd_gqa_band; hi: band_bounds' second result):
+    (dq [B, T, H, D], dk [B, T, Hkv, D], dv [B, T, Hkv, D]), contiguous, as attention_backward_gqa returns them."""
+    B, H, T, D = q.shape
+    Hkv = k.shape[1]
+    _check_bound(lo, "lo", B, T, q.device)
+    _check_bound(hi, "hi", B, T, q.device)
+    go = grad_out if (grad_out.dtype == q.dtype and grad_out.is_contiguous()) else grad_out.to(q.dtype).contiguous()
+    dq = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    dkv = torch.empty((2, B, T, Hkv, D), dtype=q.dtype, device=q.device)
+    delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    shape = _gqa_shape(q, k, v, True)
+    _C.check(_C.lib().bf_attention_bwd_gqa_band(q.data_ptr(), k.data_ptr(), v.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                                out.data_ptr(), go.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                                                dq.data_ptr(), dkv[0].data_ptr(), dkv[1].data_ptr(), _TORCH2BF[q.dtype],
+                                                ctypes.byref(shape), float(scaling), _stream_ptr()),
+             "bf_attention_bwd_gqa_band")
+    PACKED_CALLS["bwd"] += 1
+    return dq, dkv[0], dkv[1]
+
+
+def _check_bound(t: Tensor, name: str, B: int, T: int, device) -> None:
+    if t.dtype != torch.int32 or tuple(t.shape) != (B, T) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"band attention: {name} must be a contiguous int32 [{B}, {T}] tensor on {device}, got "
+                         f"{t.dtype} {tuple(t.shape)} on {t.device}")
+
+
 # launches of bf_attention_decode_gqa from this process (a test can assert that a cached decode step ran on the kernel);
 # "len": of bf_attention_decode_gqa_len (a step against a fixed-capacity cache, attention_forward_decode_len);
 # "window" / "len_window": of their sliding-window siblings
@@ -933,7 +1001,12 @@ def prefill_kernel_wins(H: int, Hkv: int, T: int, D: int, backward: bool, window
         (0.40x .. 0.86x) and ties it, inside the spread, in three (8 / 4 at T 256: 0.95x, 16 / 16 at 512: 1.00x, 8 / 1 at
         2048: 0.97x) whose neighbours in T on either side lose: the ties go with their neighbours, so the whole class is on
         SDPA and the rule stays monotone in T.
-    T 512 verdicts hold up to 1024, the midpoint (in ratio) to the next measured length; nothing below 256 was timed."""
+    T 512 verdicts hold up to 1024, the midpoint (in ratio) to the next measured length; nothing below 256 was timed.
+    Packed rows (`_packed_attention`: masked=True, the fallback being SDPA over the dense document mask) follow the same
+    rule.  profiles/packed_attention.md timed head size 256 for them at H / Hkv 8 / 4, T 2048 and 8192 (documents of 512,
+    mixed, one document; with and without W 1024): every class wins (forward 1.37x .. 12.9x, forward + backward 2.64x ..
+    29x, spreads under 5 %), so none is sent to SDPA on that account; the two masked classes above (T <= 1024) were not
+    timed with documents and keep their padding-mask verdicts."""
     if D != 256 or (window is not None and window < T):
         return True
     if backward:
@@ -1197,6 +1270,24 @@ class AttentionGqaFn(torch.autograd.Function):
         dq, dk, dv = attention_backward_gqa(q, k, v, ctx.key_mask, ctx.mask_off, out, grad_out, lse, ctx.scaling, ctx.causal,
                                             ctx.window, **ctx.cap)
         return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None, None, None
+
+
+class AttentionGqaBandFn(torch.autograd.Function):
+    """attention_forward_gqa_band with attention_backward_gqa_band as its backward.  Keeps q, k, v, the output, one fp32
+    row statistic per query and the two bounds."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, lo, hi, scaling):
+        out, lse = attention_forward_gqa_band(q, k, v, lo, scaling, want_lse=True)
+        ctx.save_for_backward(q, k, v, out, lse, lo, hi)
+        ctx.scaling = scaling
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, k, v, out, lse, lo, hi = ctx.saved_tensors
+        dq, dk, dv = attention_backward_gqa_band(q, k, v, lo, hi, out, grad_out, lse, ctx.scaling)
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None
 
 
 def attention_forward(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,

@@ -833,5 +833,6 @@ int bf_mc_predictive_finish(const void* d_partial, int64_t R, int64_t C, int S_t
 /* the soft-cap attention entries (Gemma 2), a part of this ABI kept in a file of its own */
 #include "bayeformers_amd_softcap.h"
 #include "bayeformers_amd_family_blocks.h" /* the Gemma / Qwen3 decoder-block entries, likewise */
+#include "bayeformers_amd_packed.h"        /* banded causal attention for packed sequences, likewise */
 
 #endif /* BAYEFORMERS_AMD_H */
