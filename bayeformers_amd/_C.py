@@ -221,6 +221,15 @@ PACKED_SYMBOLS = {
                                        _vp]),
 }
 
+# what include/bayeformers_amd_fp8.h declares (the centred FP8 rows of Model.pinned_samples(keep_weights="fp8")): quantise,
+# dequantise, and bf_gemm_nt_skinny's arguments with (q, scale, center) in place of (w, w_dtype)
+FP8_SYMBOLS = {
+    "bf_fp8_rows_quantize": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "bf_fp8_rows_dequantize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "bf_gemm_nt_skinny_fp8": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_gemm_nt_skinny_fp8_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -259,6 +268,14 @@ def lib():
             if fn is None:  # likewise: a library from before these entries reports the same version
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the packed-sequence attention entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in FP8_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the FP8 kept-weight entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

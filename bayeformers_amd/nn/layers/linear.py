@@ -293,17 +293,26 @@ class Linear(KernelLayer):
         return y.view(*input.shape[:-1], self.out_features)
 
     def _kept_forward(self, ctx, x2: Tensor, S: int, slot: Tensor, want_act: bool) -> Tensor:
-        """A forward inside Model.pinned_samples(keep_weights=True) (no gradient): the weights were sampled by the block's
-        first forward.  A few rows per sample: bf_gemm_nt_skinny; otherwise the tiled GEMM (or the stacked query/key/value
+        """A forward inside Model.pinned_samples(keep_weights=True or "fp8") (no gradient): the weights were sampled by the
+        block's first forward.  A few rows per sample: bf_gemm_nt_skinny; otherwise the tiled GEMM (or the stacked query/key/value
         launch), as a planned forward runs it.  Leaves `_small_m` alone: Model._plan is not this block's."""
-        w_s, b_s = ctx.plan.views[id(self)]
         N, K = self.out_features, self.in_features
         act = 1 if want_act else 0
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
-        if ops.skinny_supported(x2, w_s, S, K):
-            y = ops.skinny_linear_forward(x2, w_s, b_s, S, N, K, act)
+        y = None
+        if ctx.kept.fp8:
+            # keep_weights="fp8": a few rows per sample multiply the quantised rows directly; every other launch reads the
+            # same weights W^, dequantised into the plan's ring (unless the arena still holds this layer's group)
+            center, q, scale, b_s = ctx.kept.store[id(self)]
+            if ops.skinny_fp8_supported(x2, q, center, S, K):
+                y = ops.skinny_linear_forward_fp8(x2, q, scale, center, b_s, S, N, K, act)
+            else:
+                w_s, b_s = ctx.kept.weights16(self)
         else:
-            y = None
+            w_s, b_s = ctx.plan.views[id(self)]
+            if ops.skinny_supported(x2, w_s, S, K):
+                y = ops.skinny_linear_forward(x2, w_s, b_s, S, N, K, act)
+        if y is None:
             if self._shared_input is not None and not want_act:
                 y = self._stacked_forward(ctx, x2, S)
             if y is None:

@@ -14,7 +14,7 @@ Additions for the MI355X path (all optional; with S = 1 the behaviour is the ref
 import contextlib
 import itertools
 import warnings
-from typing import Any, Iterator, List, Optional
+from typing import Any, Iterator, List, Optional, Union
 
 import torch
 from torch import Tensor
@@ -89,6 +89,9 @@ class _KeptWeights:
     one arena per group (plan.SamplePlan keep=True), sampled by one launch in the block's first forward and read by every
     later one.  Belongs to the block: Model._plan and its rebuilds never see it."""
 
+    mode = "keep_weights=True"
+    fp8 = False
+
     def __init__(self, S: int, cdt: torch.dtype):
         self.S, self.cdt = S, cdt
         self.plan: Optional[SamplePlan] = None
@@ -98,22 +101,21 @@ class _KeptWeights:
         """The plan of the block; in its first forward also the one sampling launch over all groups."""
         S, cdt = ctx.S, bfr.get_compute_dtype()
         if (S, cdt) != (self.S, self.cdt):
-            raise RuntimeError(f"pinned_samples(keep_weights=True): entered for S={self.S} at {self.cdt}, a forward runs "
+            raise RuntimeError(f"pinned_samples({self.mode}): entered for S={self.S} at {self.cdt}, a forward runs "
                                f"with S={S} at {cdt}")
         if torch.is_grad_enabled() or model.training:
-            raise RuntimeError("pinned_samples(keep_weights=True): forwards inside must run in eval mode without gradients")
+            raise RuntimeError(f"pinned_samples({self.mode}): forwards inside must run in eval mode without gradients")
         if self.plan is not None:
             for t, ptr, ver in self.watch:
                 if t.data_ptr() != ptr or t._version != ver:
-                    raise RuntimeError("pinned_samples(keep_weights=True): a posterior mu / rho changed inside the block; "
+                    raise RuntimeError(f"pinned_samples({self.mode}): a posterior mu / rho changed inside the block; "
                                        "the kept samples no longer match it (leave the block to draw new ones)")
             return self.plan
         linears = [(i, l) for i, l in enumerate(layers) if isinstance(l, Linear)]
         pl = [l for _, l in linears]
         shared = tuple(sorted({id(l._shared_input): l._shared_input for l in pl
                                if l._shared_input is not None}.values(), key=lambda t: t[0].layer_id))
-        self.plan = SamplePlan(pl, S, cdt, pl[0].weight.mu.device, index=[i for i, _ in linears], shared=shared, keep=True)
-        self.plan._sample_groups(0, len(self.plan.groups) - 1, ctx.token, bfr.STATE.seed, ctx.sample_base)
+        self.plan = self._draw(pl, [i for i, _ in linears], shared, ctx)
         from .parameters.gaussian import Gaussian
 
         for l in pl:
@@ -121,6 +123,72 @@ class _KeptWeights:
                 if isinstance(g, Gaussian):
                     self.watch += [(t, t.data_ptr(), t._version) for t in (g.mu, g.rho)]
         return self.plan
+
+    def _draw(self, pl, index, shared, ctx) -> SamplePlan:
+        plan = SamplePlan(pl, self.S, self.cdt, pl[0].weight.mu.device, index=index, shared=shared, keep=True)
+        plan._sample_groups(0, len(plan.groups) - 1, ctx.token, bfr.STATE.seed, ctx.sample_base)
+        return plan
+
+
+class _KeptFp8Weights(_KeptWeights):
+    """The sampled weights of a `pinned_samples(keep_weights="fp8")` block as centred FP8 rows
+    (include/bayeformers_amd_fp8.h): per layer one bf16 copy of the posterior mean shared by the S samples, and per sample
+    the draw's deviation from it in e4m3 with a power-of-two scale per output row (and the fp32 biases as they are).  The
+    plan is an ordinary ring plan: the block's first forward samples it a ringful of groups at a time and quantises each
+    into the store, so the 16-bit draws never exist all at once; later the ring only holds the dequantised weights W^ of
+    the groups whose layers run a GEMM that reads 16-bit weights."""
+    mode = 'keep_weights="fp8"'
+    fp8 = True
+
+    def __init__(self, S: int, cdt: torch.dtype):
+        super().__init__(S, cdt)
+        self.store = {}     # id(layer) -> (center [N, K] bf16, q [S, N, K] uint8, scale [S, N] fp32, bias [S, N] fp32 or None)
+        self.resident = []  # per ring arena: the group whose W^ (and biases) it holds
+
+    def _draw(self, pl, index, shared, ctx) -> SamplePlan:
+        S, dev = self.S, pl[0].weight.mu.device
+        plan = SamplePlan(pl, S, self.cdt, dev, index=index, shared=shared)
+        for l in pl:
+            N, K = l.out_features, l.in_features
+            _, b_s = plan.views[id(l)]
+            self.store[id(l)] = (l.weight.mu.detach().to(torch.bfloat16, copy=True).contiguous(),  # (a copy even of a bf16 mu)
+                                 torch.empty((S, N, K), dtype=torch.uint8, device=dev),
+                                 torch.empty((S, N), dtype=torch.float32, device=dev),
+                                 torch.empty((S, N), dtype=torch.float32, device=dev) if b_s is not None else None)
+        ring, first = len(plan.arenas), 0
+        while first < len(plan.groups):  # everything runs on one stream: a launch overwrites an arena after its quantisation
+            last = min(len(plan.groups), first + ring) - 1
+            plan._sample_groups(first, last, ctx.token, bfr.STATE.seed, ctx.sample_base)
+            for gi in range(first, last + 1):
+                for l in plan.groups[gi]:
+                    center, q, scale, bias = self.store[id(l)]
+                    w_s, b_s = plan.views[id(l)]
+                    ops.quantize_rows_fp8(w_s, center, q, scale)
+                    if bias is not None:
+                        bias.copy_(b_s)
+            first = last + 1
+        # the arenas hold unrounded draws now: no layer may read them as they are
+        plan.arena_owner = [None] * ring
+        self.resident = [None] * ring
+        return plan
+
+    def store_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for entry in self.store.values() for t in entry if t is not None)
+
+    def weights16(self, layer):
+        """(W^ [S, N, K] bf16, bias) of `layer` in the ring: its group is dequantised unless the arena still holds it."""
+        plan = self.plan
+        gi = plan.group_of[id(layer)]
+        slot = gi % len(plan.arenas)
+        if self.resident[slot] != gi:
+            for l in plan.groups[gi]:
+                center, q, scale, bias = self.store[id(l)]
+                w_s, b_s = plan.views[id(l)]
+                ops.dequantize_rows_fp8(q, scale, center, out=w_s)
+                if bias is not None:
+                    b_s.copy_(bias)
+            self.resident[slot] = gi
+        return plan.views[id(layer)]
 
 
 class _KLFn(torch.autograd.Function):
@@ -294,7 +362,7 @@ class Model(Module):
             self._mc_harness -= 1
 
     @contextlib.contextmanager
-    def pinned_samples(self, keep_weights: bool = False, max_bytes: Optional[int] = None):
+    def pinned_samples(self, keep_weights: Union[bool, str] = False, max_bytes: Optional[int] = None):
         """Run every forward inside on ONE reservation of Monte-Carlo sample indices: reserved when the block is entered
         (for the span of the `monte_carlo` setting in force then), committed once when it is left.  Each of the S samples
         is then one fixed draw of the weights across the forwards — e.g. the steps of a generation that reuse a KV cache
@@ -308,12 +376,22 @@ class Model(Module):
         tiled GEMM (fp32 compute: the fp32 GEMM).  The draws and log-probs are the bits the cross-layer plan gives.  Costs
         plan.kept_weight_bytes(model, S, compute dtype) bytes — S * P * 2 in bf16 for P Linear weights — checked before
         anything is allocated against max_bytes (default plan.ARENA_BYTES): above it, ValueError.  A forward after a
-        posterior mu / rho was changed inside the block raises.  bnn.Embedding layers keep their own path."""
+        posterior mu / rho was changed inside the block raises.  bnn.Embedding layers keep their own path.
+
+        keep_weights="fp8" (bf16 compute only): the same block on fewer bytes.  One bf16 copy of each layer's posterior mean is
+        kept for all samples, and of each draw only its deviation from that mean, in e4m3 with a power-of-two scale per output
+        row (include/bayeformers_amd_fp8.h) — plan.kept_weight_bytes(model, S, bfloat16, fp8=True) bytes, about (2 + S) * P
+        instead of 2 * S * P, plus a transient 16-bit ring of at most plan.ARENA_BYTES.  Every forward of the block, prefill and
+        decode alike, multiplies by the dequantised weights W^, which differ from the bf16 draws by 2^-4 of the DEVIATION (0.3 %
+        of |mu| at MOPED delta = 0.05), not of the weight.  Decode steps run bf_gemm_nt_skinny_fp8 on the bytes; the other
+        GEMMs read W^ dequantised into the ring.  log_prob_samples() is that of the unrounded draws, bitwise keep_weights=True's."""
         if self.__dict__.get("_pinned") is not None:
             raise RuntimeError("pinned_samples: already pinned")
+        if keep_weights != "fp8" and (isinstance(keep_weights, str) or keep_weights not in (True, False)):
+            raise ValueError(f"pinned_samples: keep_weights={keep_weights!r} (False, True or \"fp8\")")
         kept = None
         if keep_weights:
-            kept = self._keep_weights_check(max_bytes)
+            kept = self._keep_weights_check(max_bytes, fp8=keep_weights == "fp8")
         elif max_bytes is not None:
             raise ValueError("pinned_samples: max_bytes is the budget of keep_weights=True")
         start, total = self._mc_span
@@ -326,27 +404,31 @@ class Model(Module):
             self._pinned = self._pinned_lp = self._kept = None  # (the kept samples' arenas go with the last reference)
             bfr.commit_samples(total)
 
-    def _keep_weights_check(self, max_bytes: Optional[int]) -> "_KeptWeights":
-        """Everything pinned_samples(keep_weights=True) refuses, checked before anything is reserved or allocated."""
+    def _keep_weights_check(self, max_bytes: Optional[int], fp8: bool = False) -> "_KeptWeights":
+        """Everything pinned_samples(keep_weights=True or "fp8") refuses, checked before anything is reserved or allocated."""
         from .. import plan as bplan
 
+        mode = _KeptFp8Weights.mode if fp8 else _KeptWeights.mode
         if torch.is_grad_enabled():
-            raise RuntimeError("pinned_samples(keep_weights=True) is inference only: enter it under torch.no_grad()")
+            raise RuntimeError(f"pinned_samples({mode}) is inference only: enter it under torch.no_grad()")
         if self.training:
-            raise RuntimeError("pinned_samples(keep_weights=True) is inference only: put the model in eval mode (model.eval())")
+            raise RuntimeError(f"pinned_samples({mode}) is inference only: put the model in eval mode (model.eval())")
         S, cdt = self._mc_samples, bfr.get_compute_dtype()
+        if fp8 and cdt != torch.bfloat16:
+            raise ValueError(f"pinned_samples({mode}) needs bfloat16 compute (set_compute_dtype): at {cdt} the dequantised "
+                             "weights are not the exact bf16 values the format defines")
         limit = bplan.ARENA_BYTES if max_bytes is None else int(max_bytes)
-        need = bplan.kept_weight_bytes(self, S, cdt)
+        need = bplan.kept_weight_bytes(self, S, cdt, fp8=fp8)
         if need > limit:
-            raise ValueError(f"pinned_samples(keep_weights=True): the kept samples need {need} bytes (S={S}, {cdt}), "
+            raise ValueError(f"pinned_samples({mode}): the kept samples need {need} bytes (S={S}, {cdt}), "
                              f"above max_bytes={limit}")
         linears = [l for l in self.fused_children() if isinstance(l, Linear)]
         if not linears:
-            raise ValueError("pinned_samples(keep_weights=True): the model has no Bayesian Linear layer")
+            raise ValueError(f"pinned_samples({mode}): the model has no Bayesian Linear layer")
         if not SamplePlan.plannable(linears):
-            raise ValueError("pinned_samples(keep_weights=True) needs every Bayesian Linear on one ROCm device, with built-in "
+            raise ValueError(f"pinned_samples({mode}) needs every Bayesian Linear on one ROCm device, with built-in "
                              "priors and the global compute dtype (SamplePlan.plannable)")
-        return _KeptWeights(S, cdt)
+        return (_KeptFp8Weights if fp8 else _KeptWeights)(S, cdt)
 
     def fused_children(self) -> List[KernelLayer]:
         """The kernel-backed children (bnn.Linear, bnn.Embedding) in registration order; their layer_id (Philox

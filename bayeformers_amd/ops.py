@@ -444,6 +444,86 @@ def skinny_linear_forward(x: Tensor, w_s: Tensor, b_s: Optional[Tensor], S: int,
     return y
 
 
+SKINNY_FP8_CALLS = [0]  # launches of bf_gemm_nt_skinny_fp8 through skinny_linear_forward_fp8 (tests, diagnostics)
+
+
+def _fp8_rows_check(what: str, S: int, N: int, K: int, **tensors) -> None:
+    """Dtype, shape, device and contiguity of the operands of the FP8 row entries (include/bayeformers_amd_fp8.h)."""
+    want = {"w": (torch.bfloat16, (S, N, K)), "center": (torch.bfloat16, (N, K)), "q": (torch.uint8, (S, N, K)),
+            "scale": (torch.float32, (S, N))}
+    for name, t in tensors.items():
+        _require_device(t, name)
+        dt, shape = want[name]
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _C.BayeFormersAMDError(f"{what}: {name} must be a contiguous {dt} tensor of shape {shape} (got {t.dtype} "
+                                         f"{tuple(t.shape)}; fp16 and fp32 weights are not taken)")
+
+
+def quantize_rows_fp8(w: Tensor, center: Tensor, q: Optional[Tensor] = None, scale: Optional[Tensor] = None):
+    """Centred FP8 rows of sampled weights (bf_fp8_rows_quantize): w [S, N, K] bf16 draws, center [N, K] bf16 ->
+    (q [S, N, K] uint8 holding e4m3fn bytes of w - center over a power-of-two scale per row, scale [S, N] fp32)."""
+    S, N, K = w.shape
+    q = torch.empty((S, N, K), dtype=torch.uint8, device=w.device) if q is None else q
+    scale = torch.empty((S, N), dtype=torch.float32, device=w.device) if scale is None else scale
+    _fp8_rows_check("quantize_rows_fp8", S, N, K, w=w, center=center, q=q, scale=scale)
+    _C.check(_C.lib().bf_fp8_rows_quantize(w.data_ptr(), _C.BF_DT_BF16, center.data_ptr(), q.data_ptr(), scale.data_ptr(),
+                                           S, N, K, _stream_ptr()), "bf_fp8_rows_quantize")
+    return q, scale
+
+
+def dequantize_rows_fp8(q: Tensor, scale: Tensor, center: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """W^ = bf16(fp32(q * scale + center)) [S, N, K] (bf_fp8_rows_dequantize): the weights every layer of a
+    keep_weights="fp8" block multiplies by, written out for the GEMMs that read 16-bit weights."""
+    S, N, K = q.shape
+    out = torch.empty((S, N, K), dtype=torch.bfloat16, device=q.device) if out is None else out
+    _fp8_rows_check("dequantize_rows_fp8", S, N, K, w=out, center=center, q=q, scale=scale)
+    _C.check(_C.lib().bf_fp8_rows_dequantize(q.data_ptr(), scale.data_ptr(), center.data_ptr(), out.data_ptr(),
+                                             _C.BF_DT_BF16, S, N, K, _stream_ptr()), "bf_fp8_rows_dequantize")
+    return out
+
+
+def skinny_fp8_supported(x: Tensor, q: Tensor, center: Tensor, S: int, K: int) -> bool:
+    """Does skinny_linear_forward_fp8 take x ([S*M, K]) with these quantised rows?  skinny_supported's conditions at bf16."""
+    if x.dtype != torch.bfloat16 or center.dtype != torch.bfloat16 or K % 32 or S > 65535:
+        return False
+    rows = x.shape[0]
+    if rows % S or not 1 <= rows // S <= min(SKINNY_ROWS, _C.lib().bf_gemm_nt_skinny_max_rows()):
+        return False
+    return x.is_contiguous() and (x.data_ptr() | q.data_ptr() | center.data_ptr()) % 16 == 0
+
+
+def skinny_linear_forward_fp8(x: Tensor, q: Tensor, scale: Tensor, center: Tensor, b_s: Optional[Tensor], S: int, N: int,
+                              K: int, act: int = 0, x_sample_stride: Optional[int] = None,
+                              out: Optional[Tensor] = None) -> Tensor:
+    """y[s] = act(x[s] W^_s^T + b_s) for a few rows per sample on centred FP8 rows (bf_gemm_nt_skinny_fp8): x [S*M, K] bf16
+    (or any storage with `x_sample_stride` elements between samples), q [S, N, K] uint8, scale [S, N] fp32, center [N, K]
+    bf16, b_s [S, N] fp32 or None; returns [S*M, N] bf16.  The split-K scratch comes from the stream's workspace."""
+    _require_device(x, "input")
+    lib = _C.lib()
+    if x.dtype not in _TORCH2BF:
+        raise _C.BayeFormersAMDError(f"unsupported input dtype {x.dtype}")
+    if x_sample_stride is None:
+        if not x.is_contiguous():
+            x = x.contiguous()
+        rows = x.numel() // K
+        if rows % S:
+            raise _C.BayeFormersAMDError(f"input rows ({rows}) are not a multiple of the sample count S={S}")
+        M = rows // S
+        x_sample_stride = M * K
+    else:
+        M = x.shape[-2]
+    y = out if out is not None else torch.empty((S * M, N), dtype=x.dtype, device=x.device)
+    need = lib.bf_gemm_nt_skinny_fp8_workspace_bytes(S, M, N, K)
+    ws = workspace(x.device, need) if need else None
+    _C.check(lib.bf_gemm_nt_skinny_fp8(x.data_ptr(), _TORCH2BF[x.dtype], int(x_sample_stride), q.data_ptr(), scale.data_ptr(),
+                                       center.data_ptr(), b_s.data_ptr() if b_s is not None else None, y.data_ptr(),
+                                       _TORCH2BF[y.dtype], S, M, N, K, int(act),
+                                       ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                       _stream_ptr()), "bf_gemm_nt_skinny_fp8")
+    SKINNY_FP8_CALLS[0] += 1
+    return y
+
+
 # launches of the row-subset entries from this process (tests, diagnostics): bf_gemm_nt_rows, bf_attention_fwd_rows,
 # bf_add_layernorm_rows — what the last encoder layer under a pooled head runs (bayeformers_amd._pooled_last_layer_forward)
 ROWS_CALLS = {"gemm": 0, "attention": 0, "layernorm": 0}

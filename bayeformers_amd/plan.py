@@ -292,15 +292,21 @@ class SamplePlan:
         self.pending.clear()
 
 
-def kept_weight_bytes(model, S: int, dtype) -> int:
+def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
     """Device bytes Model.pinned_samples(keep_weights=True) keeps for `S` samples at compute dtype `dtype` (torch.float32,
     torch.bfloat16 or torch.float16): S * sum(N * K) * element size over the model's Bayesian Linear layers, plus S * N fp32 per
-    bias.  (The arenas round each slice up to 256 bytes.)  Needs no GPU."""
+    bias.  (The arenas round each slice up to 256 bytes.)  Needs no GPU.
+
+    fp8=True: what keep_weights="fp8" keeps (bf16 compute only) — per layer the 16-bit centre N * K * 2 shared by the samples,
+    and per sample N * K bytes of e4m3 deviations with N fp32 row scales; the fp32 biases as above.  Exactly the bytes of the
+    block's store: each piece is a tensor of its own, nothing is padded."""
     from .nn.layers.linear import Linear
     from .nn.parameters.base import NoneParameter
 
     if dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise ValueError(f"kept_weight_bytes: dtype {dtype} (float32, bfloat16 or float16)")
+    if fp8 and dtype != torch.bfloat16:
+        raise ValueError(f"kept_weight_bytes: fp8 kept weights need bfloat16 compute (got {dtype})")
     S = int(S)
     if S < 1:
         raise ValueError(f"kept_weight_bytes: S={S} (at least 1)")
@@ -308,7 +314,8 @@ def kept_weight_bytes(model, S: int, dtype) -> int:
     total = 0
     for l in model.fused_children():
         if isinstance(l, Linear):
-            total += S * l.out_features * l.in_features * esz
+            N, K = l.out_features, l.in_features
+            total += N * K * 2 + S * (N * K + N * 4) if fp8 else S * N * K * esz
             if not isinstance(l.bias, NoneParameter):
-                total += S * l.out_features * 4
+                total += S * N * 4
     return total

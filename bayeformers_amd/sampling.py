@@ -760,7 +760,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     max_new_tokens: int = 1, do_sample: bool = False, temperature: float = 1.0,
                     eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, group: Optional["dist.ProcessGroup"] = None,
-                    keep_weights: bool = False, max_bytes: Optional[int] = None, static_cache: bool = False,
+                    keep_weights: Union[bool, str] = False, max_bytes: Optional[int] = None, static_cache: bool = False,
                     graph: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
                     min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                     no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None) -> Generation:
@@ -797,6 +797,10 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     keep_weights / max_bytes go to `model.pinned_samples`: with keep_weights=True the prefill samples every Bayesian Linear's
     S weight draws once and the decode steps run on them (bf_gemm_nt_skinny) instead of drawing them again per token, at the
     cost of plan.kept_weight_bytes(model, S, compute dtype) bytes of device memory; the result is the same Generation.
+    keep_weights="fp8" (bf16 compute) keeps them as centred FP8 rows instead — one bf16 posterior mean per layer and one
+    e4m3 byte per sampled weight for its deviation from it, plan.kept_weight_bytes(..., fp8=True) bytes — and decodes on
+    bf_gemm_nt_skinny_fp8; prefill and decode multiply by the same dequantised weights, which are not bitwise the bf16 draws
+    (Model.pinned_samples).  Any other value raises ValueError.
 
     static_cache=True decodes on a transformers StaticCache of capacity T0 + max_new_tokens - 1, filled from the (unchanged)
     prefill: every step has the same shapes, the attention runs on bf_attention_decode_gqa_len (the fill is a device
@@ -1004,7 +1008,7 @@ def _static_cache(model: Model, capacity: int):
 
 def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, do_sample: bool,
                      temperature: float, eos_token_id: Optional[int], pad_token_id: int,
-                     generator: Optional[torch.Generator], keep_weights: bool, max_bytes: Optional[int],
+                     generator: Optional[torch.Generator], keep_weights: Union[bool, str], max_bytes: Optional[int],
                      graph: bool, truncation=None, processors=None) -> Generation:
     """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
     static one), then decode steps of one shape whose bookkeeping is bf_generate_step (after bf_probs_truncate with a
