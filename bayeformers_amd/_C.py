@@ -230,6 +230,16 @@ FP8_SYMBOLS = {
     "bf_gemm_nt_skinny_fp8_workspace_bytes": (_sz, [_i, _i, _i, _i]),
 }
 
+# what include/bayeformers_amd_kv8.h declares (the FP8 KV cache of sample_generate(kv_cache="fp8")): append (K and V with
+# their strides, the four cache buffers, the device fill pointer), dequantise, and bf_attention_decode_gqa_softcap's
+# arguments with (kq, vq, k_scale, v_scale) in place of (k, v)
+KV8_SYMBOLS = {
+    "bf_kv8_append": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "bf_kv8_dequantize": (_i, [_vp, _vp, _vp, _i, _i64, _i, _vp]),
+    "bf_attention_decode_gqa_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, ctypes.c_float,
+                                         ctypes.c_float, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -276,6 +286,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the FP8 kept-weight entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in KV8_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the FP8 KV-cache entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

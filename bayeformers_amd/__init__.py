@@ -22,12 +22,12 @@ from .nn.parameters.base import Parameter
 from .nn.parameters.gaussian import DEFAULT_SCALED_GAUSSIAN_MIXTURE
 from .nn.parameters.initializations import DEFAULT_UNIFORM, Initialization
 from .ops import invalidate_caches  # noqa: F401
-from .plan import kept_weight_bytes  # noqa: F401
+from .plan import kept_weight_bytes, kv_cache_bytes  # noqa: F401
 from .random import (get_compute_dtype, manual_seed, set_compute_dtype, set_kl_gradient,  # noqa: F401
                      use_device_counter)
 
 __all__ = ["to_bayesian", "invalidate_caches", "fuse_activations", "fuse_residual_layernorm", "fuse_shared_inputs", "fuse_ffn_pairs", "fuse_attention", "fuse_embeddings", "fuse_decoder_blocks", "enable_embedding", "nn", "manual_seed", "set_compute_dtype", "get_compute_dtype",
-           "use_device_counter", "set_kl_gradient", "kept_weight_bytes"]
+           "use_device_counter", "set_kl_gradient", "kept_weight_bytes", "kv_cache_bytes"]
 
 
 def to_bayesian(model: torch.nn.Module, initialization: Optional[Initialization] = DEFAULT_UNIFORM,
@@ -346,6 +346,8 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
 
     from . import ops
 
+    if getattr(key, "_bf_kv8_scale", None) is not None:  # an FP8 cache (kv_cache.Fp8StaticLayer): key / value are e4m3 rows
+        return _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs)
     need_grad = torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad)
     # causal: a mask _padding_mask_interface marked causal (the mask itself carries the structure), else what the caller
     # says with is_causal, else — with no mask — the module's own flag (HF decoders set module.is_causal and pass no mask
@@ -386,6 +388,41 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     if need_grad:  # training: the same kernel, with bf_attention_bwd behind it
         return ops.AttentionFn.apply(query, key, value, key_mask, mask_off, scale, drop), None
     return ops.attention_forward(query, key, value, key_mask, scale, mask_off, drop=drop), None
+
+
+def _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs):
+    """_attention_interface for a call against an FP8 cache: `key` and `value` are the uint8 e4m3 rows of a
+    kv_cache.Fp8StaticLayer, carrying their fp32 row scales as `_bf_kv8_scale`.  A decode step — the mask carries the fill
+    `_bf_kv_len`, at most 16 queries, no gradient, no dropout, no attention sinks, no key mask or a [B, capacity] one, the
+    module's `sliding_window` agreeing with the mask's — runs bf_attention_decode_gqa_kv8 on the rows as they are, with the
+    mask's window and, under `softcap_attention()`, the call's soft-cap.  ops.decode_kernel_wins is not consulted: the FP8
+    cache is a memory option and no other attention reads it.  Every other call dequantises the cache into bf16 first
+    (ops.kv8_dequantize, the whole capacity: correct but slow) and then takes the path the bf16 tensors would have taken;
+    the framework never sees the uint8 tensors."""
+    from . import ops
+
+    k_scale, v_scale = key._bf_kv8_scale, getattr(value, "_bf_kv8_scale", None)
+    if v_scale is None:
+        raise ValueError("bayeformers_amd: the keys of this call are FP8 cache rows but its values carry no scales")
+    marked = attention_mask is not None
+    kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
+    window = getattr(attention_mask, "_bf_window", None) if marked else None
+    key_mask = getattr(attention_mask, "_bf_key_mask", None) if marked else None
+    softcap = kwargs.get("softcap", None)
+    need_grad = torch.is_grad_enabled() and query.requires_grad
+    if (kv_len is not None and query.shape[2] <= ops.DECODE_MAX_QUERIES and not need_grad and dropout == 0.0
+            and kwargs.get("s_aux", None) is None
+            and not (window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window)
+            and (softcap is None or softcap_attention_enabled())
+            and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2]))
+            and ops.attention_decode_kv8_supported(query, key, value)):
+        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+        return ops.attention_forward_decode_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
+                                                window=window,
+                                                softcap=float(softcap) if softcap is not None else None), None
+    return _attention_interface(module, query, ops.kv8_dequantize(key, k_scale), ops.kv8_dequantize(value, v_scale),
+                                attention_mask, dropout, scaling, **kwargs)
 
 
 def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):

@@ -20,7 +20,13 @@
 // serves at every step): Tk is the capacity, the filled length L comes from a device scalar.  The grid and the workspace
 // follow the capacity; the split boundaries follow the keys-per-split rule applied to L, computed in the kernel (splits
 // past L write an empty partial the merge skips), so at L == Tk the launch is bitwise bf_attention_decode_gqa's.
+//
+// bf_attention_decode_gqa_kv8 (include/bayeformers_amd_kv8.h) runs them over an FP8 cache: K and V rows of D e4m3fn bytes
+// with one fp32 power-of-two scale each (bf_kv8.hip writes them).  Only the fetch differs: a key row is HD / 16 16-byte
+// chunks plus its scale, and the dequantised bf16 values — exact — are written into the same LDS images, so everything
+// behind the fetch is the bf16 kernel's and the result is bitwise that kernel's on the dequantised cache.
 #include "bf_attention_tiles.h"
+#include "bf_fp8.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -54,8 +60,14 @@ struct DecodeParams {
 struct DecodeCapParams : DecodeParams {
     float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
 };
-template <bool CAP>
-using ParamsOf = std::conditional_t<CAP, DecodeCapParams, DecodeParams>;
+// KV8: k and v are e4m3fn rows (ks / vs in bytes), with one scale per (sequence, K/V head, key); again a compile-time flag
+// with a parameter block of its own
+struct DecodeKv8Params : DecodeCapParams {
+    const float* k_scale;  // [N][Hkv][Tk]
+    const float* v_scale;
+};
+template <bool CAP, bool KV8>
+using ParamsOf = std::conditional_t<KV8, DecodeKv8Params, std::conditional_t<CAP, DecodeCapParams, DecodeParams>>;
 
 struct Split {
     int n, keys;  // splits, keys per split (a multiple of KT; the last split ends at Tk)
@@ -81,12 +93,14 @@ Split decode_split(const bf_attn_decode_t* s) {
     return Split{(tiles + per - 1) / per, per * KT};
 }
 
-template <typename T, int HD, bool LOCAL, bool CAP>
-__global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP> p) {
+template <typename T, int HD, bool LOCAL, bool CAP, bool KV8 = false>
+__global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
+    using KV = std::conditional_t<KV8, uint8_t, T>;          // what the cache holds
+    using chunk = std::conditional_t<KV8, u32x4_t, f32x4_t>;  // 16 bytes of it in flight
     constexpr int NDH = HD / 32, NDB = HD / 16, NKB = KT / 16;
-    constexpr int CPR = HD / 8, NLD = KT * CPR / 256;  // 16-byte chunks per key row; per thread and tile
+    constexpr int CPR = HD * (int)sizeof(KV) / 16, NLD = KT * CPR / 256;  // 16-byte chunks per key row; per thread and tile
     constexpr int K_BYTES = KT * Rows<HD>::SWZ, V_BYTES = KT * Rows<HD>::PAD;
     __shared__ __attribute__((aligned(16))) char smem[K_BYTES + V_BYTES + KT * 4];
     char* const ks = smem;
@@ -113,8 +127,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP> p) {
     const bool wave_live = (int)blockIdx.z * ROWS + wid * 16 < p.R, row_ok = r < p.R;
     const int qi = row_ok ? r % p.Tq : 0, h = g * p.group + (row_ok ? r / p.Tq : 0);
     const int lim = L - p.Tq + qi;  // the last key query qi sees
-    const T* kb = reinterpret_cast<const T*>(p.k) + n * p.ks[0] + g * p.ks[1];
-    const T* vb = reinterpret_cast<const T*>(p.v) + n * p.vs[0] + g * p.vs[1];
+    const KV* kb = reinterpret_cast<const KV*>(p.k) + n * p.ks[0] + g * p.ks[1];
+    const KV* vb = reinterpret_cast<const KV*>(p.v) + n * p.vs[0] + g * p.vs[1];
 
     frag qf[NDH];
     const T* qrow = reinterpret_cast<const T*>(p.q) + n * p.qs[0] + h * p.qs[1] + qi * p.qs[2];
@@ -130,16 +144,24 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP> p) {
     float run_max = -INFINITY, run_sum = 0.f;
 
     // the next tile travels in registers while the current one is computed; keys past the split read as 0
-    f32x4_t kr[NLD], vr[NLD];
+    // (KV8: with the rows' scales; a key past the split has scale 0 too)
+    chunk kr[NLD], vr[NLD];
+    float ksc[KV8 ? NLD : 1], vsc[KV8 ? NLD : 1];
     float mr = 0.f;
     auto fetch = [&](int key0) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int c = tid + 256 * i, key = key0 + c / CPR, c8 = c % CPR;
-            kr[i] = vr[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            kr[i] = vr[i] = chunk{};
+            if constexpr (KV8) ksc[i] = vsc[i] = 0.f;
             if (key < k_hi) {
-                kr[i] = *reinterpret_cast<const f32x4_t*>(kb + (long long)key * p.ks[2] + c8 * 8);
-                vr[i] = *reinterpret_cast<const f32x4_t*>(vb + (long long)key * p.vs[2] + c8 * 8);
+                kr[i] = *reinterpret_cast<const chunk*>(kb + (long long)key * p.ks[2] + c8 * (16 / (int)sizeof(KV)));
+                vr[i] = *reinterpret_cast<const chunk*>(vb + (long long)key * p.vs[2] + c8 * (16 / (int)sizeof(KV)));
+                if constexpr (KV8) {
+                    const long long srow = ((long long)n * p.Hkv + g) * p.Tk + key;
+                    ksc[i] = p.k_scale[srow];
+                    vsc[i] = p.v_scale[srow];
+                }
             }
         }
         if (mask && tid < KT && key0 + tid < k_hi) mr = mask[(long long)n * p.Tk + key0 + tid] * LOG2E;
@@ -150,8 +172,19 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP> p) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int c = tid + 256 * i, row = c / CPR, c8 = c % CPR;
-            *reinterpret_cast<f32x4_t*>(ks + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = kr[i];
-            *reinterpret_cast<f32x4_t*>(vs + row * Rows<HD>::PAD + (c8 << 4)) = vr[i];
+            if constexpr (KV8) {  // 16 bytes are 16 features: two 16-byte chunks of the bf16 images
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int d8 = 2 * c8 + h;
+                    *reinterpret_cast<bf16x8_t*>(ks + row * Rows<HD>::SWZ + ((d8 ^ (row & 7)) << 4)) =
+                        fp8_rows_value(u32x2_t{kr[i][2 * h], kr[i][2 * h + 1]}, ksc[i]);
+                    *reinterpret_cast<bf16x8_t*>(vs + row * Rows<HD>::PAD + (d8 << 4)) =
+                        fp8_rows_value(u32x2_t{vr[i][2 * h], vr[i][2 * h + 1]}, vsc[i]);
+                }
+            } else {
+                *reinterpret_cast<f32x4_t*>(ks + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = kr[i];
+                *reinterpret_cast<f32x4_t*>(vs + row * Rows<HD>::PAD + (c8 << 4)) = vr[i];
+            }
         }
         if (mask && tid < KT) ms[tid] = mr;
         __syncthreads();
@@ -269,6 +302,22 @@ void launch(const DecodeCapParams& cp, bool cap, hipStream_t stream) {
     }
 }
 
+// the KV8 instantiations (bf16 only)
+template <int HD>
+void launch_kv8(const DecodeKv8Params& kp, bool cap, hipStream_t stream) {
+    const DecodeParams& p = kp;
+    const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
+    if (cap) {
+        if (p.window) decode_kernel<__bf16, HD, true, true, true><<<grid, 256, 0, stream>>>(kp);
+        else decode_kernel<__bf16, HD, false, true, true><<<grid, 256, 0, stream>>>(kp);
+    } else if (p.window) decode_kernel<__bf16, HD, true, false, true><<<grid, 256, 0, stream>>>(kp);
+    else decode_kernel<__bf16, HD, false, false, true><<<grid, 256, 0, stream>>>(kp);
+    if (p.nsplit > 1) {
+        const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
+        decode_merge_kernel<__bf16, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
+    }
+}
+
 // Validates the shape; returns 0 or the BF_FAIL status
 int check_shape(const char* what, const bf_attn_decode_t* s, int dtype) {
     if (!s) BF_FAIL("%s: shape is NULL", what);
@@ -305,13 +354,24 @@ int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
 
 namespace {
 
-// window 0: the plain entries; >= 1: the sliding-window ones.  softcap 0: no cap
+// window 0: the plain entries; >= 1: the sliding-window ones.  softcap 0: no cap.  kv8: d_k / d_v are e4m3fn rows with the
+// scales d_k_scale / d_v_scale (bf16 compute)
 int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
            const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
-           const bf_attn_decode_t* shape, int window, float softcap, float scaling, hipStream_t stream) {
+           const bf_attn_decode_t* shape, int window, float softcap, float scaling, hipStream_t stream, bool kv8 = false,
+           const float* d_k_scale = nullptr, const float* d_v_scale = nullptr) {
     if (window < 0) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    if (kv8 && dtype != BF_DT_BF16)
+        BF_FAIL("%s: dtype must be bf16 (bfloat16: the dequantised rows are exact in it alone)", what);
     if (check_shape(what, shape, dtype)) return 1;
     if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
+    if (kv8) {
+        if (!d_k_scale || !d_v_scale) BF_FAIL("%s: NULL scale", what);
+        if (((uintptr_t)d_k_scale | (uintptr_t)d_v_scale) & 3) BF_FAIL("%s: the scales must be 4-byte aligned", what);
+        for (int i = 0; i < 3; ++i)
+            if (shape->k_stride[i] % 16 || shape->v_stride[i] % 16)
+                BF_FAIL("%s: the K / V strides (bytes) must be multiples of 16", what);
+    }
     if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_workspace) & 15)
         BF_FAIL("%s: pointers must be 16-byte aligned", what);
     if (d_mask && ((uintptr_t)d_mask & 3)) BF_FAIL("%s: mask must be 4-byte aligned", what);
@@ -362,7 +422,15 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
         if (!(p.cap_log2e < INFINITY) || !(fabsf(p.cap_x) < INFINITY))
             BF_FAIL("%s: softcap=%g: scaling / softcap or softcap * log2(e) is not finite", what, (double)softcap);
     }
-    if (dtype == BF_DT_BF16) {
+    if (kv8) {
+        DecodeKv8Params kp = {};
+        static_cast<DecodeCapParams&>(kp) = p;
+        kp.k_scale = d_k_scale;
+        kp.v_scale = d_v_scale;
+        if (shape->head_dim == 64) launch_kv8<64>(kp, softcap != 0.f, stream);
+        else if (shape->head_dim == 128) launch_kv8<128>(kp, softcap != 0.f, stream);
+        else launch_kv8<256>(kp, softcap != 0.f, stream);
+    } else if (dtype == BF_DT_BF16) {
         if (shape->head_dim == 64) launch<__bf16, 64>(p, softcap != 0.f, stream);
         else if (shape->head_dim == 128) launch<__bf16, 128>(p, softcap != 0.f, stream);
         else launch<__bf16, 256>(p, softcap != 0.f, stream);
@@ -423,4 +491,16 @@ int bf_attention_decode_gqa_softcap(const void* d_q, const void* d_k, const void
     if (d_kv_len && ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
     return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, softcap, scaling,
                   (hipStream_t)stream);
+}
+
+int bf_attention_decode_gqa_kv8(const void* d_q, const void* d_kq, const void* d_vq, const float* d_k_scale,
+                                const float* d_v_scale, const float* d_mask, const uint8_t* d_mask_off,
+                                const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
+                                const bf_attn_decode_t* shape, int32_t window, float softcap, float scaling, void* stream) {
+    const char* what = "bf_attention_decode_gqa_kv8";
+    if (!(softcap >= 0.f) || !(softcap < INFINITY)) BF_FAIL("%s: softcap=%g must be finite and at least 0 (0: no cap)", what, (double)softcap);
+    if (window < 0) BF_FAIL("%s: window=%d must be at least 0 (0: no window)", what, window);
+    if (d_kv_len && ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
+    return decode(what, d_q, d_kq, d_vq, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, softcap,
+                  scaling, (hipStream_t)stream, true, d_k_scale, d_v_scale);
 }

@@ -13,58 +13,21 @@
 // No host synchronisation or allocation: capturable.
 #include "bf_common.h"
 #include "bf_device.h"
+#include "bf_fp8.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
 
 constexpr int NW = 4;       // waves per workgroup
 constexpr int NB = 2;       // 16-feature blocks per workgroup
 constexpr int kMaxRows = 64;
-constexpr int kExpClamp = 64;  // |e| of a row's scale 2^e
-
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((uint32_t)(127 + e) << 23); }
-
-// The row's exponent: the smallest e with a 2^-e <= 448 for the row's amax a (a = m 2^x, m in [0.5, 1): x - 9 when
-// m <= 0.875, else x - 8), 0 for a = 0, clamped to +-64.  A denormal a has x <= -126: the clamp decides.
-__device__ __forceinline__ int fp8_row_exponent(float amax) {
-    const uint32_t bits = __float_as_uint(amax);
-    if (bits == 0) return 0;
-    const int field = (int)(bits >> 23);
-    if (field == 0) return -kExpClamp;
-    const int e = field - 126 - ((bits & 0x7fffffu) <= 0x600000u ? 9 : 8);
-    return e < -kExpClamp ? -kExpClamp : (e > kExpClamp ? kExpClamp : e);
-}
-
-// 8 deviations times 2^-e (exact), clamped to +-448 (a no-op unless e hit its clamp), to 8 e4m3fn bytes, RNE
-__device__ __forceinline__ u32x2_t fp8_rows_encode(const float (&d)[8], float inv_scale) {
-    float a[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a[i] = fmaxf(-448.f, fminf(448.f, d[i] * inv_scale));
-    u32x2_t r;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        int v = __builtin_amdgcn_cvt_pk_fp8_f32(a[4 * h], a[4 * h + 1], 0, false);
-        v = __builtin_amdgcn_cvt_pk_fp8_f32(a[4 * h + 2], a[4 * h + 3], v, true);
-        r[h] = (uint32_t)v;
-    }
-    return r;
-}
-
 // W^ of 8 consecutive k: bf16(fp32(q * scale + c)).  q * scale is exact (a power of two, no underflow at |e| <= 64), so
 // the fma rounds once to fp32, then once to bf16.
 __device__ __forceinline__ bf16x8_t fp8_rows_weight(u32x2_t q, bf16x8_t c, float scale) {
+    float f[8];
+    fp8_rows_decode(q, f);
     bf16x8_t w;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[h], false);
-        const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[h], true);
-        w[4 * h + 0] = (__bf16)fmaf(lo[0], scale, (float)c[4 * h + 0]);
-        w[4 * h + 1] = (__bf16)fmaf(lo[1], scale, (float)c[4 * h + 1]);
-        w[4 * h + 2] = (__bf16)fmaf(hi[0], scale, (float)c[4 * h + 2]);
-        w[4 * h + 3] = (__bf16)fmaf(hi[1], scale, (float)c[4 * h + 3]);
-    }
+    for (int i = 0; i < 8; ++i) w[i] = (__bf16)fmaf(f[i], scale, (float)c[i]);
     return w;
 }
 

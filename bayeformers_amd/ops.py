@@ -1195,6 +1195,159 @@ def attention_forward_decode_len(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor
                              softcap)
 
 
+# launches of the FP8 KV-cache entries (include/bayeformers_amd_kv8.h) from this process: bf_kv8_append, bf_attention_decode_gqa_kv8,
+# bf_kv8_dequantize.  The kv8 decode bumps neither DECODE_CALLS nor SOFTCAP_CALLS.
+KV8_CALLS = {"append": 0, "decode": 0, "dequantize": 0}
+KV8_HEAD_SIZES = (64, 128, 256)
+
+
+def _kv8_cache_check(what: str, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor) -> None:
+    """The four tensors of an FP8 cache: kq / vq [N, Hkv, capacity, D] uint8 and k_scale / v_scale [N, Hkv, capacity] fp32 on
+    one ROCm device."""
+    for name, t in (("kq", kq), ("vq", vq), ("k_scale", k_scale), ("v_scale", v_scale)):
+        _require_device(t, f"{what}: {name}")
+    if kq.dtype != torch.uint8 or vq.dtype != torch.uint8 or kq.dim() != 4 or tuple(vq.shape) != tuple(kq.shape):
+        raise _C.BayeFormersAMDError(f"{what}: kq and vq must be uint8 [N, Hkv, capacity, D] of one shape (got {kq.dtype} "
+                                     f"{tuple(kq.shape)}, {vq.dtype} {tuple(vq.shape)})")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t.dtype != torch.float32 or tuple(t.shape) != tuple(kq.shape[:3]) or not t.is_contiguous():
+            raise _C.BayeFormersAMDError(f"{what}: {name} must be contiguous fp32 {tuple(kq.shape[:3])} (got {t.dtype} "
+                                         f"{tuple(t.shape)})")
+    if len({t.device for t in (kq, vq, k_scale, v_scale)}) != 1:
+        raise _C.BayeFormersAMDError(f"{what}: the cache tensors must share one device")
+
+
+def kv8_append(k: Tensor, v: Tensor, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor) -> None:
+    """Quantise the new K and V rows of a forward into an FP8 cache (bf_kv8_append): k, v [N, Hkv, Tq, D] bf16 with any
+    (batch, head, token) strides that are multiples of 8 and a contiguous feature dimension (HF's transposed projections
+    as they come); kq, vq [N, Hkv, capacity, D] uint8 and k_scale, v_scale [N, Hkv, capacity] fp32, contiguous.  Row i goes
+    to slot pos + i, pos a one-element int64 device tensor the kernel reads (a slot outside the capacity is skipped).  Each
+    row is D e4m3fn bytes over a power-of-two scale: include/bayeformers_amd_kv8.h."""
+    what = "kv8_append"
+    _require_device(k, f"{what}: k")
+    _require_device(v, f"{what}: v")
+    if k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise _C.BayeFormersAMDError(f"{what}: k and v must be bfloat16 (got {k.dtype}, {v.dtype}): the FP8 cache's "
+                                     "dequantised rows are exact in bfloat16 alone")
+    _kv8_cache_check(what, kq, vq, k_scale, v_scale)
+    if k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or tuple(k.shape[:2]) != tuple(kq.shape[:2]) \
+            or k.shape[3] != kq.shape[3]:
+        raise _C.BayeFormersAMDError(f"{what}: k {tuple(k.shape)}, v {tuple(v.shape)} are not [N, Hkv, Tq, D] rows of the "
+                                     f"cache {tuple(kq.shape)}")
+    N, Hkv, Tq, D = k.shape
+    if D not in KV8_HEAD_SIZES:
+        raise _C.BayeFormersAMDError(f"{what}: head size {D} (64, 128 or 256)")
+    if Tq < 1:
+        raise _C.BayeFormersAMDError(f"{what}: Tq={Tq} new rows (at least 1)")
+    if not (kq.is_contiguous() and vq.is_contiguous()):
+        raise _C.BayeFormersAMDError(f"{what}: kq and vq must be contiguous")
+    if k.stride(3) != 1 or v.stride(3) != 1 or any(st < 0 or st % 8 for t in (k, v) for st in t.stride()[:3]):
+        raise _C.BayeFormersAMDError(f"{what}: k and v need a contiguous feature dimension and (batch, head, token) strides "
+                                     "that are non-negative multiples of 8")
+    if pos.dtype != torch.int64 or pos.numel() != 1 or pos.device != k.device or kq.device != k.device:
+        raise _C.BayeFormersAMDError(f"{what}: pos must be one int64 on the device of k and of the cache")
+    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (k, v)]
+    _C.check(_C.lib().bf_kv8_append(k.data_ptr(), v.data_ptr(), _C.BF_DT_BF16, strides[0], strides[1], kq.data_ptr(),
+                                    vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), pos.data_ptr(), N, Hkv, Tq, D,
+                                    int(kq.shape[2]), _stream_ptr()), "bf_kv8_append")
+    KV8_CALLS["append"] += 1
+
+
+def kv8_dequantize(q: Tensor, scale: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """bf16 rows of an FP8 cache (bf_kv8_dequantize): q [..., D] uint8 contiguous, scale [...] fp32 contiguous -> [..., D]
+    bfloat16, float(q) * scale, exact.  For the callers that read a 16-bit cache (every attention route but the kv8 decode
+    kernel) and for the tests."""
+    what = "kv8_dequantize"
+    _require_device(q, f"{what}: q")
+    _require_device(scale, f"{what}: scale")
+    if q.dtype != torch.uint8 or scale.dtype != torch.float32 or q.dim() < 1 or tuple(scale.shape) != tuple(q.shape[:-1]) \
+            or not q.is_contiguous() or not scale.is_contiguous() or scale.device != q.device:
+        raise _C.BayeFormersAMDError(f"{what}: q must be contiguous uint8 [..., D] and scale contiguous fp32 [...] on its "
+                                     f"device (got {q.dtype} {tuple(q.shape)}, {scale.dtype} {tuple(scale.shape)})")
+    D = q.shape[-1]
+    if D < 16 or D % 16:
+        raise _C.BayeFormersAMDError(f"{what}: D={D} must be a positive multiple of 16")
+    if out is None:
+        out = torch.empty(q.shape, dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != tuple(q.shape) or not out.is_contiguous() or out.device != q.device:
+        raise _C.BayeFormersAMDError(f"{what}: out must be contiguous bfloat16 {tuple(q.shape)} on the device of q")
+    rows = q.numel() // D
+    if rows:
+        _C.check(_C.lib().bf_kv8_dequantize(q.data_ptr(), scale.data_ptr(), out.data_ptr(), _C.BF_DT_BF16, rows, D,
+                                            _stream_ptr()), "bf_kv8_dequantize")
+        KV8_CALLS["dequantize"] += 1
+    return out
+
+
+def attention_decode_kv8_supported(q: Tensor, kq: Tensor, vq: Tensor, check_device: bool = True) -> bool:
+    """What bf_attention_decode_gqa_kv8 takes: attention_decode_supported's shapes with q bfloat16 and kq / vq uint8
+    [N, Hkv, Tk, D] whose (batch, head, token) strides are multiples of 16 bytes."""
+    if check_device and not (q.is_cuda and kq.is_cuda and vq.is_cuda):
+        return False
+    if q.dtype != torch.bfloat16 or kq.dtype != torch.uint8 or vq.dtype != torch.uint8:
+        return False
+    if q.dim() != 4 or kq.dim() != 4 or kq.shape != vq.shape:
+        return False
+    N, H, Tq, D = q.shape
+    Hkv, Tk = kq.shape[1], kq.shape[2]
+    if kq.shape[0] != N or kq.shape[3] != D or Hkv < 1 or H % Hkv or D not in KV8_HEAD_SIZES:
+        return False
+    if not (1 <= Tq <= DECODE_MAX_QUERIES and Tq <= Tk) or N * Hkv > 65535:
+        return False
+    if q.stride(3) != 1 or any(st < 0 or st % 8 for st in q.stride()[:3]) or q.data_ptr() % 16:
+        return False
+    return all(t.stride(3) == 1 and all(st >= 0 and st % 16 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (kq, vq))
+
+
+def attention_forward_decode_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor,
+                                 kv_len: Optional[Tensor], key_mask: Optional[Tensor], scaling: float,
+                                 mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+                                 window: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
+    """attention_forward_decode (kv_len None) / attention_forward_decode_len on an FP8 cache (bf_attention_decode_gqa_kv8):
+    q [N, H, Tq, D] bfloat16, kq / vq [N, Hkv, Tk, D] uint8 (e4m3fn rows), k_scale / v_scale [N, Hkv, Tk] fp32 contiguous.
+    key_mask, mask_off, workspace (attention_decode_workspace_bytes of the shape), window and softcap as there.  The rows
+    are dequantised in registers on their way to LDS; the result is bitwise that of the bf16 entry on
+    kv8_dequantize(kq, k_scale), kv8_dequantize(vq, v_scale)."""
+    name = "attention_forward_decode_kv8"
+    _require_device(q, f"{name}: q")
+    if q.dtype != torch.bfloat16:
+        raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
+                                     "exact in bfloat16 alone")
+    _kv8_cache_check(name, kq, vq, k_scale, v_scale)
+    if q.dim() != 4 or kq.shape[0] != q.shape[0] or kq.shape[3] != q.shape[3]:
+        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, kq {tuple(kq.shape)} are not [N, H, Tq, D], "
+                                     "[N, Hkv, Tk, D]")
+    if kq.device != q.device:
+        raise _C.BayeFormersAMDError(f"{name}: q and the cache must share one device")
+    if q.stride(3) != 1 or kq.stride(3) != 1 or vq.stride(3) != 1:
+        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q, kq and vq must be contiguous")
+    if kv_len is not None and (kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device):
+        raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
+    N, H, Tq, D = q.shape
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
+    shape = _decode_shape(q, kq, vq)
+    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
+    if nbytes < 0:
+        _C.check(1, "bf_attention_decode_workspace_bytes")
+    ws = None
+    if nbytes:
+        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+            raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
+    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, kq.shape[2])
+                                 or not key_mask.is_contiguous()):
+        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk]")
+    _C.check(_C.lib().bf_attention_decode_gqa_kv8(
+        q.data_ptr(), kq.data_ptr(), vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+        key_mask.data_ptr() if key_mask is not None else None, mask_off.data_ptr() if mask_off is not None else None,
+        kv_len.data_ptr() if kv_len is not None else None, out.data_ptr(), ws.data_ptr() if ws is not None else None,
+        _C.BF_DT_BF16, ctypes.byref(shape), int(window or 0), float(softcap or 0.0), float(scaling), _stream_ptr()),
+        "bf_attention_decode_gqa_kv8")
+    KV8_CALLS["decode"] += 1
+    return out
+
+
 GENERATE_CALLS = [0]  # launches of bf_generate_step through generate_step (tests, diagnostics)
 
 

@@ -319,3 +319,29 @@ def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
             if not isinstance(l.bias, NoneParameter):
                 total += S * N * 4
     return total
+
+
+def kv_cache_bytes(model, samples: int, batch: int, capacity: int, dtype=torch.bfloat16, fp8: bool = False) -> int:
+    """Device bytes the static KV cache of sample_generate(static_cache=True) holds for `samples` Monte-Carlo samples of
+    `batch` rows at `capacity` slots, counted from the decoder's config (layers, K/V heads, head size): per layer, K/V head
+    and slot one K row and one V row of D elements of `dtype` for each of the samples * batch sequences.  Needs no GPU.
+
+    fp8=True: what kv_cache="fp8" holds (bf16 compute only) — D e4m3 bytes and one fp32 scale per row, 2 D + 8 bytes a row
+    pair against 4 D in bf16."""
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"kv_cache_bytes: dtype {dtype} (float32, bfloat16 or float16)")
+    if fp8 and dtype != torch.bfloat16:
+        raise ValueError(f"kv_cache_bytes: the FP8 KV cache needs bfloat16 compute (got {dtype})")
+    samples, batch, capacity = int(samples), int(batch), int(capacity)
+    if samples < 1 or batch < 1 or capacity < 1:
+        raise ValueError(f"kv_cache_bytes: samples={samples}, batch={batch}, capacity={capacity} (each at least 1)")
+    inner = getattr(model, "model", None)
+    config = getattr(inner if inner is not None else model, "config", None)
+    if config is None:
+        raise ValueError("kv_cache_bytes: the model has no config to count layers and heads from")
+    config = config.get_text_config(decoder=True) if hasattr(config, "get_text_config") else config
+    layers, heads = int(config.num_hidden_layers), int(config.num_attention_heads)
+    kv_heads = int(getattr(config, "num_key_value_heads", None) or heads)
+    D = int(getattr(config, "head_dim", None) or config.hidden_size // heads)
+    row_pair = 2 * D + 8 if fp8 else 2 * D * (4 if dtype == torch.float32 else 2)
+    return layers * samples * batch * kv_heads * capacity * row_pair

@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 from torch import Tensor
 
+from . import random as bfr
 from .nn.model import Model
 
 
@@ -763,7 +764,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     keep_weights: Union[bool, str] = False, max_bytes: Optional[int] = None, static_cache: bool = False,
                     graph: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
                     min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
-                    no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None) -> Generation:
+                    no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
+                    kv_cache: Optional[str] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -812,7 +814,17 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     static_cache=True returns.  With eos_token_id the all-finished check runs every 8 replays (rows past EOS emit pad with
     zero statistics either way).  Both need a model routed by fuse_attention, a single process and no sliding-window
     layers — except in Mistral, Qwen2 and Qwen3 models, whose sliding layers get full-capacity static layers (capacity
-    slots each, not W) and decode on bf_attention_decode_gqa_len_window."""
+    slots each, not W) and decode on bf_attention_decode_gqa_len_window.
+
+    kv_cache="fp8" (implies static_cache; bf16 compute only) keeps that static cache as e4m3 rows — per cached K or V row D
+    bytes and one fp32 power-of-two scale (include/bayeformers_amd_kv8.h), plan.kv_cache_bytes(..., fp8=True) bytes, 0.52x
+    the bf16 cache at head size 128 — and decodes on bf_attention_decode_gqa_kv8, which reads the rows as they are: half
+    the bytes kept and half the bytes every step reads.  The prompt's cache is bf16 until it is handed over (one
+    bf_kv8_append per layer, each dynamic layer released as it goes); every later step appends its row with the same
+    entry.  It composes with graph=True, keep_weights in any form, truncation, the logits processors, the sliding-window
+    families and soft-capping.  The cached rows carry e4m3's rounding (at most 2^-4 relative per element), so the
+    Generation is close to, not bitwise, the bf16 cache's.  None (the default) changes nothing; any other value, or a
+    compute dtype other than bfloat16, raises ValueError."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -822,7 +834,9 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         raise ValueError(f"sample_generate: temperature={temperature} (must be positive)")
     truncation = _truncation(top_k, top_p, min_p, do_sample)
     processors = _processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id)
-    static_cache = bool(static_cache) or bool(graph)
+    if kv_cache is not None and not (isinstance(kv_cache, str) and kv_cache == "fp8"):
+        raise ValueError(f"sample_generate: kv_cache={kv_cache!r} (None or \"fp8\")")
+    static_cache = bool(static_cache) or bool(graph) or kv_cache is not None
     if static_cache and group is not None:
         raise ValueError("sample_generate: static_cache / graph generation runs in a single process (group must be None)")
     if group is not None:
@@ -841,10 +855,13 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
 
     if pad_token_id is None:
         pad_token_id = eos_token_id if eos_token_id is not None else 0
+    if kv_cache is not None and bfr.get_compute_dtype() != torch.bfloat16:
+        raise ValueError(f"sample_generate: kv_cache=\"fp8\" needs bfloat16 compute (set_compute_dtype): at "
+                         f"{bfr.get_compute_dtype()} the dequantised cache rows are not exact")
     if static_cache:
         return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
                                 eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph),
-                                truncation, processors)
+                                truncation, processors, kv_cache)
     S, n = samples, max_new_tokens
     B, T0 = input_ids.shape
     dev = input_ids.device
@@ -977,11 +994,15 @@ _FINISHED_EVERY = 8  # graph replays between two all-finished checks (host synch
 _SLIDING_STATIC_FAMILIES = ("mistral", "qwen2", "qwen3", "gemma2")
 
 
-def _static_cache(model: Model, capacity: int):
+_STATIC_LAYER_HOOK = None  # tests: a StaticLayer subclass every layer of _static_cache's cache is built from instead
+
+
+def _static_cache(model: Model, capacity: int, kv_cache: Optional[str] = None):
     """A transformers StaticCache of `capacity` tokens for the wrapped decoder, or the reason it cannot serve.  For the
     families of _SLIDING_STATIC_FAMILIES the sliding-window layers get plain full-capacity StaticLayers too (transformers'
     StaticSlidingWindowLayer branches on a host count and rolls its buffer, so one captured graph could not serve every
-    step): the mask carries the window and the decode kernel applies it.  Such a layer holds `capacity` slots, not W."""
+    step): the mask carries the window and the decode kernel applies it.  Such a layer holds `capacity` slots, not W.
+    kv_cache="fp8": every layer is a kv_cache.Fp8StaticLayer of the same capacity (after the same refusals)."""
     from transformers import StaticCache
     from transformers.cache_utils import StaticLayer
 
@@ -1003,13 +1024,20 @@ def _static_cache(model: Model, capacity: int):
     if any(type(layer) is not StaticLayer or getattr(layer, "is_sliding", False) for layer in cache.layers):
         raise ValueError("sample_generate: static_cache / graph take full-attention decoders only (this config has "
                          "sliding-window or other non-static cache layers)")
+    if kv_cache is not None and kv_cache != "fp8":
+        raise ValueError(f"sample_generate: kv_cache={kv_cache!r} (None or \"fp8\")")
+    cls = _STATIC_LAYER_HOOK
+    if cls is None and kv_cache == "fp8":
+        from .kv_cache import Fp8StaticLayer as cls
+    if cls is not None:
+        cache.layers = [cls(max_cache_len=int(capacity)) for _ in cache.layers]
     return cache
 
 
 def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, do_sample: bool,
                      temperature: float, eos_token_id: Optional[int], pad_token_id: int,
                      generator: Optional[torch.Generator], keep_weights: Union[bool, str], max_bytes: Optional[int],
-                     graph: bool, truncation=None, processors=None) -> Generation:
+                     graph: bool, truncation=None, processors=None, kv_cache: Optional[str] = None) -> Generation:
     """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
     static one), then decode steps of one shape whose bookkeeping is bf_generate_step (after bf_probs_truncate with a
     truncation: the step's inverse-CDF draw over the filtered, unnormalised row samples the renormalised kept set; with
@@ -1022,7 +1050,7 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
 
     B, T0 = input_ids.shape
     dev = input_ids.device
-    static = _static_cache(model, T0 + n - 1)
+    static = _static_cache(model, T0 + n - 1, kv_cache)
     inner = model.model if model.model is not None else model
     seed = None
     if do_sample:  # the generation's own Philox key: one draw from the caller's generator per call
@@ -1073,6 +1101,7 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
         lp = model.log_prob_samples().clone()
         for i, layer in enumerate(dynamic.layers):  # the prompt's keys and values fill the static cache's first T0 slots
             static.update(layer.keys, layer.values, i)
+            layer.keys = layer.values = None  # released as it goes: the peak is the prompt's cache plus the static one so far
         del dynamic
         epilogue(out, 0)
         del out

@@ -21,6 +21,10 @@ paths named by --mode (default all three, alternated): dynamic (the default Dyna
 alternated: without the truncation (`..._sample`) and with it (`..._truncated`).  With --repetition-penalty /
 --no-repeat-ngram / --min-new-tokens every decode path runs twice, alternated: without the logits processors (`..._plain`)
 and with them (`..._processed`), both with the truncation when one is given.
+e2e --kv-cache fp8: the FP8 KV cache instead — graph=True with the bf16 static cache and with kv_cache="fp8", alternated, each
+without and with keep_weights=True (`runs` each), tokens/s; then the bytes the caching allocator holds for each static cache
+of that generation (torch.cuda.memory_allocated before and after the hand-over's updates) beside plan.kv_cache_bytes.
+--prompt / --batch / --samples size it (default 512 / 4 / 4, as above).
 trace: a prefill-only generation, a 2 s pause, then a generation of `new-tokens`; analyze splits a kernel trace of it at the
 pause and attributes (second - first) to the decode steps: GPU time per kernel class and the host gaps between kernels.
 """
@@ -198,6 +202,60 @@ def e2e(runs, new_tokens, paths=("dynamic", "static", "graph"), truncation=None,
     return res
 
 
+def e2e_kv_cache(runs, new_tokens, prompt=512, batch=4, samples=4):
+    import bayeformers_amd as bf
+    from bayeformers_amd.sampling import _static_cache, sample_generate
+
+    bmodel = _decoder()
+    S, B = samples, batch
+    ids = torch.randint(0, 32000, (B, prompt), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    configs = [(keep, kv) for keep in (False, True) for kv in (None, "fp8")]
+    name = lambda keep, kv: ("keep_weights" if keep else "draw_per_step") + "_graph" + ("_kv_fp8" if kv else "_kv_bf16")
+    res = {name(*c): [] for c in configs}
+    res.update(samples=S, batch=B, prompt=prompt, new_tokens=new_tokens)
+    seqs = {}
+    with torch.no_grad():
+        for keep, kv in configs:  # warm-up
+            sample_generate(bmodel, ids, samples=S, max_new_tokens=8, keep_weights=keep, graph=True, kv_cache=kv)
+        for _ in range(runs):
+            for keep, kv in configs:
+                bf.manual_seed(0x5EED)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                gen = sample_generate(bmodel, ids, samples=S, max_new_tokens=new_tokens, keep_weights=keep, graph=True,
+                                      kv_cache=kv)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                res[name(keep, kv)].append(round(B * new_tokens / dt, 1))
+                seqs[keep, kv] = gen.sequences
+                print(json.dumps({"keep_weights": keep, "kv_cache": kv, "seconds": round(dt, 3),
+                                  "tokens_per_s": round(B * new_tokens / dt, 1)}), flush=True)
+        # tokens of the two caches: equal up to the first step at which e4m3's rounding flips an argmax
+        diff = (seqs[True, None] != seqs[True, "fp8"]).any(0).nonzero()
+        res["first_differing_position"] = int(diff[0]) - prompt if diff.numel() else None
+        # the allocator's view of each static cache at this generation's capacity
+        cap, cfg = prompt + new_tokens - 1, bmodel.model.config
+        k = torch.randn(S * B, prompt, cfg.num_key_value_heads * cfg.head_dim, device="cuda", dtype=torch.bfloat16)
+        k = k.view(S * B, prompt, cfg.num_key_value_heads, cfg.head_dim).transpose(1, 2)
+        for kv in (None, "fp8"):
+            torch.cuda.synchronize()
+            before = torch.cuda.memory_allocated()
+            cache = _static_cache(bmodel, cap, kv_cache=kv)
+            for i in range(len(cache.layers)):
+                cache.update(k, k, i)
+            torch.cuda.synchronize()
+            res["cache_bytes_allocated" + ("_fp8" if kv else "_bf16")] = torch.cuda.memory_allocated() - before
+            res["kv_cache_bytes" + ("_fp8" if kv else "_bf16")] = bf.kv_cache_bytes(bmodel, S, B, cap, fp8=kv is not None)
+            del cache
+    for key in [key for key in res if isinstance(res[key], list)]:
+        v = res[key]
+        res[key + "_summary"] = {"median": statistics.median(v), "min": min(v), "max": max(v)}
+    for keep in (False, True):
+        res[("keep_weights" if keep else "draw_per_step") + "_fp8_over_bf16"] = round(
+            res[name(keep, "fp8") + "_summary"]["median"] / res[name(keep, None) + "_summary"]["median"], 3)
+    return res
+
+
 def trace(mode, new_tokens, path="dynamic", processors=None, fuse_blocks=False):
     from bayeformers_amd.sampling import sample_generate
 
@@ -267,6 +325,10 @@ def main():
     ap.add_argument("--min-new-tokens", type=int, default=None)
     ap.add_argument("--eos-token-id", type=int, default=None)
     ap.add_argument("--fuse-blocks", action="store_true")
+    ap.add_argument("--kv-cache", choices=["fp8"], default=None)
+    ap.add_argument("--prompt", type=int, default=512)
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--samples", type=int, default=4)
     a = ap.parse_args()
     processors = {k: v for k, v in (("repetition_penalty", a.repetition_penalty), ("no_repeat_ngram_size", a.no_repeat_ngram),
                                     ("min_new_tokens", a.min_new_tokens), ("eos_token_id", a.eos_token_id))
@@ -279,6 +341,8 @@ def main():
         paths = [m for m in modes if m in PATHS] or None
         if a.what == "kernels":
             res = block_kernels() if a.fuse_blocks else kernels(tuple(int(v) for v in a.only.split(",")) if a.only else None)
+        elif a.what == "e2e" and a.kv_cache:
+            res = e2e_kv_cache(a.runs, a.new_tokens, a.prompt, a.batch, a.samples)
         elif a.what == "e2e":
             truncation = {k: v for k, v in (("top_k", a.top_k), ("top_p", a.top_p), ("min_p", a.min_p)) if v is not None}
             res = e2e(a.runs, a.new_tokens, paths or ("dynamic", "static", "graph"), truncation, processors, a.fuse_blocks)
