@@ -240,6 +240,16 @@ KV8_SYMBOLS = {
                                          ctypes.c_float, _vp]),
 }
 
+# what include/bayeformers_amd_chunk.h declares (the cached-chunk attention of sample_generate(prefill_chunk=...)):
+# (q, k, v, mask, mask_off, kv_len, out, dtype, shape, window, key_origin, softcap, scaling, stream), and the same on an FP8 cache with
+# (kq, vq, k_scale, v_scale) in place of (k, v)
+CHUNK_SYMBOLS = {
+    "bf_attention_chunk_gqa": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, ctypes.c_float, ctypes.c_float,
+                                    _vp]),
+    "bf_attention_chunk_gqa_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, ctypes.c_float,
+                                        ctypes.c_float, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -294,6 +304,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the FP8 KV-cache entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in CHUNK_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the cached-chunk attention entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

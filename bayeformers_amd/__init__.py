@@ -396,7 +396,8 @@ def _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, 
     `_bf_kv_len`, at most 16 queries, no gradient, no dropout, no attention sinks, no key mask or a [B, capacity] one, the
     module's `sliding_window` agreeing with the mask's — runs bf_attention_decode_gqa_kv8 on the rows as they are, with the
     mask's window and, under `softcap_attention()`, the call's soft-cap.  ops.decode_kernel_wins is not consulted: the FP8
-    cache is a memory option and no other attention reads it.  Every other call dequantises the cache into bf16 first
+    cache is a memory option and no other attention reads it.  Under `chunked_attention()` a cached chunk of more than 16
+    queries (`_cached_chunk`) runs bf_attention_chunk_gqa_kv8 on the rows as they are, likewise.  Every other call dequantises the cache into bf16 first
     (ops.kv8_dequantize, the whole capacity: correct but slow) and then takes the path the bf16 tensors would have taken;
     the framework never sees the uint8 tensors."""
     from . import ops
@@ -421,8 +422,38 @@ def _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, 
         return ops.attention_forward_decode_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
                                                 window=window,
                                                 softcap=float(softcap) if softcap is not None else None), None
+    if (_cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs)
+            and (softcap is None or softcap_attention_enabled()) and ops.attention_chunk_kv8_supported(query, key, value)):
+        # a chunk of the chunked prefill: the rows as they are, no capacity-wide dequantise
+        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+        return ops.attention_forward_chunk_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
+                                               window=window, softcap=float(softcap) if softcap is not None else None,
+                                               key_origin=getattr(attention_mask, "_bf_key_origin", 0)), None
     return _attention_interface(module, query, ops.kv8_dequantize(key, k_scale), ops.kv8_dequantize(value, v_scale),
                                 attention_mask, dropout, scaling, **kwargs)
+
+
+def _cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs) -> bool:
+    """Whether a call is a cached chunk for the chunk entries (bf_attention_chunk_gqa and its kv8 sibling), under
+    `chunked_attention()`: more than 16 new queries (fewer run the decode kernels) and no more than the keys, no gradient,
+    no dropout, no attention sinks, one of _padding_mask_interface's cached-step masks (`_bf_decode`, or `_bf_kv_len` on a
+    fixed-capacity cache — the first chunk into a static cache included) whose window, if any, the module's
+    `sliding_window` agrees with, and no key mask or a [N, Tk] one.  The callers read the mask's fields themselves."""
+    from . import ops
+
+    if not chunked_attention_enabled() or attention_mask is None or need_grad or dropout != 0.0 \
+            or kwargs.get("s_aux", None) is not None:
+        return False
+    if not ops.DECODE_MAX_QUERIES < query.shape[2] <= key.shape[2]:
+        return False
+    if not (bool(getattr(attention_mask, "_bf_decode", False)) or getattr(attention_mask, "_bf_kv_len", None) is not None):
+        return False
+    window = getattr(attention_mask, "_bf_window", None)
+    if window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window:
+        return False
+    key_mask = getattr(attention_mask, "_bf_key_mask", None)
+    return key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])
 
 
 def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):
@@ -439,7 +470,9 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
     (`_softcap_attention`) when `softcap_attention()` is on; with the switch off (the default) such a call goes to the
     framework's scaled-dot-product attention too, which does NOT apply the cap.  Head size 256 (Gemma): a full-attention
     forward without gradients and without a mask stays on the framework's attention too, whose is_causal form measured
-    faster (ops.prefill_kernel_wins)."""
+    faster (ops.prefill_kernel_wins).  Under `chunked_attention()` (off by default) a cached chunk of more than 16 queries
+    (`_cached_chunk`) runs bf_attention_chunk_gqa instead of the framework's attention, on a dynamic or a fixed-capacity
+    cache, with or without a window."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
@@ -454,8 +487,17 @@ def _causal_attention(module, query, key, value, attention_mask, dropout, scalin
         return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
     if kwargs.get("softcap", None) is not None:
         return _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window,
-                                  float(kwargs["softcap"]))
+                                  float(kwargs["softcap"]), **{k: v for k, v in kwargs.items() if k != "softcap"})
     kv_len = getattr(attention_mask, "_bf_kv_len", None) if attention_mask is not None else None
+    if _cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs) \
+            and ops.attention_chunk_supported(query, key, value) \
+            and ops.chunk_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3], window):
+        # a chunk of the chunked prefill (chunked_attention(), off by default): bf_attention_chunk_gqa
+        key_mask = getattr(attention_mask, "_bf_key_mask", None)
+        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+        return ops.attention_forward_chunk(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
+                                           key_origin=getattr(attention_mask, "_bf_key_origin", 0)), None
     # the keys a decode step reads: all Tk, or with a window the ~W + Tq - 1 some query sees (decode_kernel_wins' Tk)
     read = key.shape[2] if window is None else min(key.shape[2], window + query.shape[2] - 1)
     if kv_len is not None:  # a step against a fixed-capacity cache: _padding_mask_interface's mask carries the fill
@@ -535,7 +577,7 @@ def _packed_attention(module, query, key, value, attention_mask, dropout, scalin
     return ops.attention_forward_gqa_band(query, key, value, band[0], scale), None
 
 
-def _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window, softcap):
+def _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window, softcap, **kwargs):
     """_causal_attention for a call with logit soft-capping (HF Gemma2Attention: softcap = attn_logit_softcapping), under
     `softcap_attention()`: the same cases on the soft-cap entries — bf_attention_fwd_gqa_softcap (with
     bf_attention_bwd_gqa_softcap behind it) for prefill and training at any length (subject to `ragged_attention`),
@@ -543,7 +585,8 @@ def _softcap_attention(module, query, key, value, attention_mask, dropout, scali
     with or without a window and a padding key mask.  The dispatch rules that weigh the kernels against the framework's
     attention are not consulted: that attention does not compute this function.  What the kernels do not take (attention
     dropout, a cached chunk of more than 16 queries, other masks, unsupported shapes or dtypes) runs `_softcap_eager`,
-    never the framework's scaled-dot-product attention."""
+    never the framework's scaled-dot-product attention.  Under `chunked_attention()` such a cached chunk (`_cached_chunk`)
+    runs bf_attention_chunk_gqa with the cap instead."""
     from . import ops
 
     scale = scaling if scaling is not None else query.shape[-1] ** -0.5
@@ -554,6 +597,12 @@ def _softcap_attention(module, query, key, value, attention_mask, dropout, scali
     keys_ok = key_mask is None or tuple(key_mask.shape) == (query.shape[0], Tk)
     kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
     plain = not need_grad and dropout == 0.0 and keys_ok
+    if _cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs) \
+            and ops.attention_chunk_supported(query, key, value):
+        # a chunk of the chunked prefill (chunked_attention()): bf_attention_chunk_gqa with the cap (kwargs: the call's other
+        # arguments, for the sinks and the module's own window, which _causal_attention sends to the framework before this)
+        return ops.attention_forward_chunk(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
+                                           softcap=softcap, key_origin=getattr(attention_mask, "_bf_key_origin", 0)), None
     if kv_len is not None:  # a step against a fixed-capacity cache
         if Tq < Tk and plain and ops.attention_decode_supported(query, key, value):
             return ops.attention_forward_decode_len(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
@@ -717,6 +766,7 @@ def _sliding_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, 
     if q_length < kv_length:
         out._bf_decode = True  # a step against a cache (bottom-right aligned)
     out._bf_window = window
+    out._bf_key_origin = kv_offset  # the sequence index of key 0 (a sliding cache kept its last keys): the chunk entries' tile grid
     return out
 
 
@@ -893,6 +943,24 @@ def softcap_attention(enable: bool = True) -> None:
 
 def softcap_attention_enabled() -> bool:
     return _SOFTCAP_ATTENTION[0] or os.environ.get("BF_SOFTCAP_ATTENTION") is not None
+
+
+_CHUNKED_ATTENTION = [False]
+
+
+def chunked_attention(enable: bool = True) -> None:
+    """Switch the cached-chunk attention kernels (bf_attention_chunk_gqa / bf_attention_chunk_gqa_kv8) on or off for this
+    process; BF_CHUNKED_ATTENTION in the environment switches them on too.  OFF by default.  On: a forward of more than 16
+    new tokens against a KV cache — a chunk of a chunked prefill — without gradient, dropout or attention sinks runs them
+    (`_cached_chunk`): on a dynamic cache, on a fixed-capacity one (the fill is a device scalar), on an FP8 cache without
+    dequantising it, with a sliding window, and with soft-capping under `softcap_attention()`.  Off: such a call goes
+    where it always went — the framework's scaled-dot-product attention over the dense mask, the capped eager chain, or a
+    capacity-wide dequantise first.  `sample_generate(prefill_chunk=...)` turns it on for its prefill and restores it."""
+    _CHUNKED_ATTENTION[0] = bool(enable)
+
+
+def chunked_attention_enabled() -> bool:
+    return _CHUNKED_ATTENTION[0] or os.environ.get("BF_CHUNKED_ATTENTION") is not None
 
 
 _POOLED_LAST_LAYER = [True]

@@ -40,19 +40,19 @@ template <int HD>
 struct Shape;
 template <>
 struct Shape<64> {
-    static constexpr int FWD_KT = 128, FWD_MINB = 3, DQ_KT = 128, DKV_QT = 128, DKV_MINB = 2;
+    static constexpr int FWD_KT = FwdShape<64>::KT, FWD_MINB = FwdShape<64>::MINB, DQ_KT = 128, DKV_QT = 128, DKV_MINB = 2;
     static constexpr int DQ_MINB = 2, DKV_KEYS = TQ;
 };
 // (the head-128 alternatives were measured: profiles/causal_attention.md)
 template <>
 struct Shape<128> {
-    static constexpr int FWD_KT = 128, FWD_MINB = 2, DQ_KT = 64, DKV_QT = 64, DKV_MINB = 1;
+    static constexpr int FWD_KT = FwdShape<128>::KT, FWD_MINB = FwdShape<128>::MINB, DQ_KT = 64, DKV_QT = 64, DKV_MINB = 1;
     static constexpr int DQ_MINB = 2, DKV_KEYS = TQ;
 };
 // (measured against the framework's attention: profiles/head256_attention.md)
 template <>
 struct Shape<256> {
-    static constexpr int FWD_KT = 64, FWD_MINB = 1, DQ_KT = 32, DKV_QT = 64, DKV_MINB = 1;
+    static constexpr int FWD_KT = FwdShape<256>::KT, FWD_MINB = FwdShape<256>::MINB, DQ_KT = 32, DKV_QT = 64, DKV_MINB = 1;
     static constexpr int DQ_MINB = 1, DKV_KEYS = 64;
 };
 

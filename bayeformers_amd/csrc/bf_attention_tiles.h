@@ -58,6 +58,23 @@ struct Rows {
     static constexpr int PAD = HD * 2 + 32;
 };
 
+// Key tile and workgroups per CU of the causal forward kernels, per head size: bf_attention_gqa.hip's forward (its Shape gives
+// the reasons) and bf_attention_chunk.hip's, whose rows are bitwise that forward's only while both walk the same key tiles.
+template <int HD>
+struct FwdShape;
+template <>
+struct FwdShape<64> {
+    static constexpr int KT = 128, MINB = 3;
+};
+template <>
+struct FwdShape<128> {
+    static constexpr int KT = 128, MINB = 2;
+};
+template <>
+struct FwdShape<256> {
+    static constexpr int KT = 64, MINB = 1;
+};
+
 // stage rows row0 .. row0 + NR - 1 of a [tokens][stride] tensor into the swizzled and / or the padded image
 template <typename T, int HD, int NR, int NT>
 __device__ __forceinline__ void stage(const T* base, long long stride, int row0, char* swz, char* pad, int tid) {

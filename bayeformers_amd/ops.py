@@ -5,6 +5,7 @@ step of the Monte-Carlo forward path runs in the HIP kernels of csrc/.  There is
 are not on a ROCm device raise.
 """
 import ctypes
+import math
 from typing import Optional, Union
 
 import torch
@@ -1096,6 +1097,24 @@ def prefill_kernel_wins(H: int, Hkv: int, T: int, D: int, backward: bool, window
     return False
 
 
+def chunk_kernel_wins(H: int, Hkv: int, Tq: int, Tk: int, D: int, window: Optional[int] = None) -> bool:
+    """The dispatch rule of cached chunks (more than 16 new queries against a cache, under `chunked_attention()`), beside
+    prefill_kernel_wins: True = bf_attention_chunk_gqa, False = the framework's SDPA over the dense [N, 1, Tq, Tk] mask.
+    From profiles/chunked_prefill.md (bf16, N 8, H / Hkv 16 / 4, Tq 512 and 2048 against L 4096 and 16384 cached keys, with
+    and without W 1024, both in one process; x = SDPA time / kernel time):
+      * head sizes 64 and 128 win every class: 2.1x .. 2.8x without a window, 5.2x .. 28x with one;
+      * head size 256 (one wave per SIMD, 64-key tiles) with a window wins 3.4x .. 16.1x; without one it wins at L 4096
+        (1.11x at Tq 512 inside the kernel's 19 % spread there, 1.63x at Tq 2048) and at L 16384 loses at Tq 512 (0.79x) and
+        ties at Tq 2048 (1.01x, spreads under 1.5 %): the tie goes with its neighbour, so head size 256 without a window goes
+        to SDPA from 8192 keys on, the midpoint (in ratio) of the two measured lengths.
+    The crossover itself was NOT measured: nothing between 4096 and 16384 keys was timed.
+    Tk is what the fallback would read: the capacity of a fixed-capacity cache.  The soft-cap and FP8-cache callers do not
+    consult it (the framework's attention does not compute the cap, and nothing else reads the FP8 rows)."""
+    if D != 256 or (window is not None and window < Tk):
+        return True
+    return Tk < 8192
+
+
 def _decode_shape(q: Tensor, k: Tensor, v: Tensor):
     N, H, Tq, D = q.shape
     s = _C.bf_attn_decode_t(N, Tq, k.shape[2], H, k.shape[1], D)
@@ -1345,6 +1364,143 @@ def attention_forward_decode_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Ten
         _C.BF_DT_BF16, ctypes.byref(shape), int(window or 0), float(softcap or 0.0), float(scaling), _stream_ptr()),
         "bf_attention_decode_gqa_kv8")
     KV8_CALLS["decode"] += 1
+    return out
+
+
+# launches of the cached-chunk attention entries (include/bayeformers_amd_chunk.h) from this process: "fwd" of
+# bf_attention_chunk_gqa, "kv8" of bf_attention_chunk_gqa_kv8.  They bump no other counter.
+CHUNK_CALLS = {"fwd": 0, "kv8": 0}
+
+
+def _chunk_shape_ok(q: Tensor, k: Tensor) -> bool:
+    N, H, Tq, D = q.shape
+    Hkv, Tk = k.shape[1], k.shape[2]
+    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in (64, 128, 256):
+        return False
+    return 1 <= Tq <= Tk and N <= 65535 and H <= 65535 and Tk < 2 ** 31
+
+
+def attention_chunk_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bool = True) -> bool:
+    """What bf_attention_chunk_gqa takes: q [N, H, Tq, D] with any 1 <= Tq <= Tk, k and v [N, Hkv, Tk, D], Hkv dividing H, D
+    64, 128 or 256, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8 elements) and a
+    contiguous feature dimension.  check_device=False judges the shapes, dtypes and strides alone (CPU or meta tensors)."""
+    if check_device and not (q.is_cuda and k.is_cuda and v.is_cuda):
+        return False
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        return False
+    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or not _chunk_shape_ok(q, k):
+        return False
+    return all(t.stride(3) == 1 and all(st >= 0 and st % 8 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (q, k, v))
+
+
+def attention_chunk_kv8_supported(q: Tensor, kq: Tensor, vq: Tensor, check_device: bool = True) -> bool:
+    """What bf_attention_chunk_gqa_kv8 takes: attention_chunk_supported's shapes with q bfloat16 and kq / vq uint8
+    [N, Hkv, Tk, D] whose (batch, head, token) strides are multiples of 16 bytes."""
+    if check_device and not (q.is_cuda and kq.is_cuda and vq.is_cuda):
+        return False
+    if q.dtype != torch.bfloat16 or kq.dtype != torch.uint8 or vq.dtype != torch.uint8:
+        return False
+    if q.dim() != 4 or kq.dim() != 4 or kq.shape != vq.shape or not _chunk_shape_ok(q, kq):
+        return False
+    if q.stride(3) != 1 or any(st < 0 or st % 8 for st in q.stride()[:3]) or q.data_ptr() % 16:
+        return False
+    return all(t.stride(3) == 1 and all(st >= 0 and st % 16 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t in (kq, vq))
+
+
+def _chunk_args_check(name: str, q: Tensor, k: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
+                      mask_off: Optional[Tensor], window: Optional[int], softcap: Optional[float], key_origin: int) -> None:
+    """What the two chunk wrappers check alike, after q and the cache tensors themselves."""
+    if q.stride(3) != 1 or k.stride(3) != 1:
+        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q and of the cache must be contiguous")
+    if not 1 <= q.shape[2] <= k.shape[2]:
+        raise _C.BayeFormersAMDError(f"{name}: Tq={q.shape[2]} new queries against Tk={k.shape[2]} cached keys "
+                                     "(1 <= Tq <= Tk)")
+    if kv_len is not None and (kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device):
+        raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
+    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (q.shape[0], k.shape[2])
+                                 or not key_mask.is_contiguous() or key_mask.device != q.device):
+        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk] on the device of q")
+    if mask_off is not None and (mask_off.numel() != 1 or mask_off.element_size() != 1 or mask_off.device != q.device):
+        raise _C.BayeFormersAMDError(f"{name}: mask_off must be one byte on the device of q")
+    if window is not None and (isinstance(window, bool) or not isinstance(window, int) or window < 1):
+        raise _C.BayeFormersAMDError(f"{name}: window={window!r} (None or an int >= 1)")
+    if softcap is not None and not (math.isfinite(softcap) and softcap > 0.0):
+        raise _C.BayeFormersAMDError(f"{name}: softcap={softcap!r} (None or finite and positive)")
+    if isinstance(key_origin, bool) or not isinstance(key_origin, int) or not 0 <= key_origin < 2 ** 31:
+        raise _C.BayeFormersAMDError(f"{name}: key_origin={key_origin!r} (an int >= 0)")
+
+
+def attention_forward_chunk(q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
+                            scaling: float, mask_off: Optional[Tensor] = None, window: Optional[int] = None,
+                            softcap: Optional[float] = None, key_origin: int = 0) -> Tensor:
+    """Causal attention of a chunk of Tq new queries against a KV cache (bf_attention_chunk_gqa): q [N, H, Tq, D], k / v
+    [N, Hkv, Tk, D] as described by attention_chunk_supported.  kv_len: None (L = Tk) or a one-element int64 device tensor
+    read by the kernel, the fill L of a fixed-capacity cache after this call's rows were appended (keys past it are never
+    read; one captured launch serves every L).  Query i has position L - Tq + i and sees the keys up to it — with `window`
+    the last `window` of them — that key_mask (additive fp32 [N, Tk] or None; mask_off: optional 1-element device flag,
+    true = the mask hides nothing) leaves visible.  softcap: soft-capped logits as attention_forward_gqa's.  key_origin: the
+    index in its sequence of k's key 0 (a sliding-window cache that kept its last keys only): the kernel lays its key tiles on
+    the sequence's tile grid, so the rows round as the same rows of attention_forward_gqa over the whole sequence.  Forward only.
+    Returns [N, Tq, H, D] contiguous (a query with no visible key gives 0)."""
+    name = "attention_forward_chunk"
+    _require_device(q, f"{name}: q")
+    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
+            or k.shape[3] != q.shape[3]:
+        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
+                                     "are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
+    if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
+            or v.device != q.device:
+        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one dtype and one device")
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise _C.BayeFormersAMDError(f"{name}: dtype {q.dtype} (bfloat16 or float16)")
+    if v.stride(3) != 1:
+        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q and of the cache must be contiguous")
+    _chunk_args_check(name, q, k, kv_len, key_mask, mask_off, window, softcap, key_origin)
+    N, H, Tq, D = q.shape
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
+    shape = _decode_shape(q, k, v)
+    _C.check(_C.lib().bf_attention_chunk_gqa(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+        mask_off.data_ptr() if mask_off is not None else None, kv_len.data_ptr() if kv_len is not None else None,
+        out.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(shape), int(window or 0), key_origin, float(softcap or 0.0), float(scaling),
+        _stream_ptr()), "bf_attention_chunk_gqa")
+    CHUNK_CALLS["fwd"] += 1
+    return out
+
+
+def attention_forward_chunk_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor,
+                                kv_len: Optional[Tensor], key_mask: Optional[Tensor], scaling: float,
+                                mask_off: Optional[Tensor] = None, window: Optional[int] = None,
+                                softcap: Optional[float] = None, key_origin: int = 0) -> Tensor:
+    """attention_forward_chunk on an FP8 cache (bf_attention_chunk_gqa_kv8): q [N, H, Tq, D] bfloat16, kq / vq
+    [N, Hkv, Tk, D] uint8 (e4m3fn rows), k_scale / v_scale [N, Hkv, Tk] fp32 contiguous; the other arguments as there.  The
+    rows are dequantised in registers on their way to LDS — rows and scales past the fill are never read — and the result
+    is bitwise that of attention_forward_chunk on kv8_dequantize(kq, k_scale), kv8_dequantize(vq, v_scale)."""
+    name = "attention_forward_chunk_kv8"
+    _require_device(q, f"{name}: q")
+    if q.dtype != torch.bfloat16:
+        raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
+                                     "exact in bfloat16 alone")
+    _kv8_cache_check(name, kq, vq, k_scale, v_scale)
+    if q.dim() != 4 or kq.shape[0] != q.shape[0] or kq.shape[3] != q.shape[3]:
+        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, kq {tuple(kq.shape)} are not [N, H, Tq, D], "
+                                     "[N, Hkv, Tk, D]")
+    if kq.device != q.device:
+        raise _C.BayeFormersAMDError(f"{name}: q and the cache must share one device")
+    if vq.stride(3) != 1:
+        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q and of the cache must be contiguous")
+    _chunk_args_check(name, q, kq, kv_len, key_mask, mask_off, window, softcap, key_origin)
+    N, H, Tq, D = q.shape
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
+    shape = _decode_shape(q, kq, vq)
+    _C.check(_C.lib().bf_attention_chunk_gqa_kv8(
+        q.data_ptr(), kq.data_ptr(), vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+        key_mask.data_ptr() if key_mask is not None else None, mask_off.data_ptr() if mask_off is not None else None,
+        kv_len.data_ptr() if kv_len is not None else None, out.data_ptr(), _C.BF_DT_BF16, ctypes.byref(shape),
+        int(window or 0), key_origin, float(softcap or 0.0), float(scaling), _stream_ptr()), "bf_attention_chunk_gqa_kv8")
+    CHUNK_CALLS["kv8"] += 1
     return out
 
 

@@ -765,7 +765,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     graph: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
                     min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                     no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                    kv_cache: Optional[str] = None) -> Generation:
+                    kv_cache: Optional[str] = None, prefill_chunk: Optional[int] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -824,7 +824,20 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     entry.  It composes with graph=True, keep_weights in any form, truncation, the logits processors, the sliding-window
     families and soft-capping.  The cached rows carry e4m3's rounding (at most 2^-4 relative per element), so the
     Generation is close to, not bitwise, the bf16 cache's.  None (the default) changes nothing; any other value, or a
-    compute dtype other than bfloat16, raises ValueError."""
+    compute dtype other than bfloat16, raises ValueError.
+
+    prefill_chunk=C (an int >= 17; needs a model routed by fuse_attention) feeds the prompt in spans of C tokens against the
+    cache instead of one forward over all of it: only C positions of activations exist at a time, only the last span's
+    last position goes through the lm_head (`logits_to_keep=1` where the wrapped model's forward takes it), and on the
+    static_cache / graph / kv_cache="fp8" paths the spans go straight into the static cache — no DynamicCache, no
+    hand-over, and with kv_cache="fp8" the prompt's cache never exists in bf16.  Each span's attention runs on
+    bf_attention_chunk_gqa (bf_attention_chunk_gqa_kv8 on the FP8 cache): `chunked_attention()` is switched on for the
+    prefill and restored afterwards; a last span of at most 16 tokens runs the decode kernels.  The decode steps, the
+    graph and the Generation's fields are unchanged; the values are those of another valid 16-bit route of the same
+    function (attention over cached, for FP8 quantised, keys), close to, not bitwise, the whole-prompt prefill's.  Without
+    keep_weights every span draws the same pinned weights again — S draws of every layer per span — so chunking is best
+    combined with keep_weights.  None, or C >= T0, is the whole-prompt prefill, bit for bit; any other value raises
+    ValueError."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -858,10 +871,11 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     if kv_cache is not None and bfr.get_compute_dtype() != torch.bfloat16:
         raise ValueError(f"sample_generate: kv_cache=\"fp8\" needs bfloat16 compute (set_compute_dtype): at "
                          f"{bfr.get_compute_dtype()} the dequantised cache rows are not exact")
+    chunk = _checked_prefill_chunk(model, prefill_chunk, input_ids.shape[1])
     if static_cache:
         return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
                                 eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph),
-                                truncation, processors, kv_cache)
+                                truncation, processors, kv_cache, chunk)
     S, n = samples, max_new_tokens
     B, T0 = input_ids.shape
     dev = input_ids.device
@@ -878,8 +892,12 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     lengths = torch.zeros(B, dtype=torch.long, device=dev)
     finished = torch.zeros(B, dtype=torch.bool, device=dev)
     with model.monte_carlo(S), model.pinned_samples(keep_weights=keep_weights, max_bytes=max_bytes):
-        out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
-        lp = model.log_prob_samples().clone()
+        if chunk is None:
+            out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
+            lp = model.log_prob_samples().clone()
+        else:  # the prompt in spans against the DynamicCache, each under the mask up to its end
+            out, lp = _chunked_prefill(model, ids, pos, (lambda b: mask[:, :b]) if mask is not None else (lambda b: None),
+                                       cache, _prefill_spans(T0, chunk))
         for t in range(n):
             logits = out.logits[:, -1, :].reshape(S, B, -1)
             if temperature != 1.0:
@@ -909,6 +927,65 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                 pos = pos[:, -1:] + 1
             out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=cache, use_cache=True)
     return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])
+
+
+def _prefill_spans(T0: int, C: int) -> List[Tuple[int, int]]:
+    """The [a, b) token spans a prompt of T0 tokens is fed in at prefill_chunk=C: C tokens each, the last one shorter."""
+    if T0 < 1 or C < 1:
+        raise ValueError(f"_prefill_spans: T0={T0}, C={C} (both at least 1)")
+    return [(a, min(a + C, T0)) for a in range(0, T0, C)]
+
+
+_MIN_PREFILL_CHUNK = 17  # (a span of at most 16 tokens is a decode step: the chunk kernels are for more)
+
+
+def _checked_prefill_chunk(model: Model, prefill_chunk, T0: int) -> Optional[int]:
+    """sample_generate's checked prefill_chunk: None when the prompt goes in one forward (None, or a chunk of at least T0
+    tokens), else the chunk — which needs the model's attention routed through the kernels."""
+    if prefill_chunk is None:
+        return None
+    if isinstance(prefill_chunk, bool) or not isinstance(prefill_chunk, numbers.Integral) \
+            or prefill_chunk < _MIN_PREFILL_CHUNK:
+        raise ValueError(f"sample_generate: prefill_chunk={prefill_chunk!r} (None or an int >= {_MIN_PREFILL_CHUNK})")
+    if prefill_chunk >= T0:
+        return None
+    from . import _ATTENTION_NAME
+
+    inner = model.model if model.model is not None else model
+    if getattr(getattr(inner, "config", None), "_attn_implementation", None) != _ATTENTION_NAME:
+        raise RuntimeError("sample_generate: prefill_chunk needs the model's attention routed through the HIP kernels "
+                           "— call bayeformers_amd.fuse_attention(model) first")
+    return int(prefill_chunk)
+
+
+def _chunked_prefill(model: Model, ids: Tensor, pos: Optional[Tensor], mask_to, cache, spans):
+    """The prefill of sample_generate(prefill_chunk=...): one forward per span [a, b) of the prompt against `cache`, with
+    input_ids[:, a:b], position_ids[:, a:b] and the attention mask mask_to(b), under `chunked_attention()` (restored
+    afterwards, also on an exception).  A span's output is dropped as soon as its forward has updated the cache; only the
+    last span's is returned, with one position of logits where the wrapped model's forward takes `logits_to_keep`.
+    Returns (out, lp): lp the log-probs of the pinned draws, read after the first span (every span draws the same)."""
+    import inspect
+
+    from . import _CHUNKED_ATTENTION
+
+    inner = model.model if model.model is not None else model
+    try:
+        keep = {"logits_to_keep": 1} if "logits_to_keep" in inspect.signature(inner.forward).parameters else {}
+    except (TypeError, ValueError):
+        keep = {}
+    before = _CHUNKED_ATTENTION[0]
+    _CHUNKED_ATTENTION[0] = True
+    try:
+        out = lp = None
+        for a, b in spans:
+            out = None  # the span before: nothing of it is read
+            out = model(input_ids=ids[:, a:b], attention_mask=mask_to(b), position_ids=pos[:, a:b] if pos is not None else None,
+                        past_key_values=cache, use_cache=True, **keep)
+            if lp is None:
+                lp = model.log_prob_samples().clone()
+    finally:
+        _CHUNKED_ATTENTION[0] = before
+    return out, lp
 
 
 def _truncation(top_k, top_p, min_p, do_sample: bool) -> Optional[Tuple[Optional[int], Optional[float], Optional[float]]]:
@@ -1037,12 +1114,14 @@ def _static_cache(model: Model, capacity: int, kv_cache: Optional[str] = None):
 def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, do_sample: bool,
                      temperature: float, eos_token_id: Optional[int], pad_token_id: int,
                      generator: Optional[torch.Generator], keep_weights: Union[bool, str], max_bytes: Optional[int],
-                     graph: bool, truncation=None, processors=None, kv_cache: Optional[str] = None) -> Generation:
+                     graph: bool, truncation=None, processors=None, kv_cache: Optional[str] = None,
+                     prefill_chunk: Optional[int] = None) -> Generation:
     """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
     static one), then decode steps of one shape whose bookkeeping is bf_generate_step (after bf_probs_truncate with a
     truncation: the step's inverse-CDF draw over the filtered, unnormalised row samples the renormalised kept set; with
     logits processors, bf_logits_process at the device step and a second mc_predictive choose the token, and
-    bf_generate_step_stat_probs reads its probability from the unprocessed row)."""
+    bf_generate_step_stat_probs reads its probability from the unprocessed row).  prefill_chunk (checked: smaller than
+    T0): the prompt goes in spans straight into the static cache instead, under the full-capacity mask — no DynamicCache."""
     from transformers import DynamicCache
     from transformers.cache_utils import DynamicLayer
 
@@ -1094,15 +1173,25 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
         return eos_token_id is not None and bool(finished.all())
 
     with model.monte_carlo(S), model.pinned_samples(keep_weights=keep_weights, max_bytes=max_bytes):
-        dynamic = DynamicCache(config=getattr(inner, "config", None))
-        # (a sliding layer of the prefill keeps every key: they go to their own slots of the full-capacity static layer)
-        dynamic.layers = [DynamicLayer() if getattr(layer, "is_sliding", False) else layer for layer in dynamic.layers]
-        out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=dynamic, use_cache=True)
-        lp = model.log_prob_samples().clone()
-        for i, layer in enumerate(dynamic.layers):  # the prompt's keys and values fill the static cache's first T0 slots
-            static.update(layer.keys, layer.values, i)
-            layer.keys = layer.values = None  # released as it goes: the peak is the prompt's cache plus the static one so far
-        del dynamic
+        if prefill_chunk is not None:  # each span is appended at the static cache's fill pointer by its own forward
+            # the layers are allocated before the first span: its mask is then built from the fill (a device scalar, 0) like
+            # every later one's, and its attention reads the first `chunk` slots and not the whole capacity
+            config = inner.config.get_text_config(decoder=True) if hasattr(inner.config, "get_text_config") else inner.config
+            heads = int(config.num_attention_heads)
+            static.early_initialization(S * B, int(getattr(config, "num_key_value_heads", None) or heads),
+                                        int(getattr(config, "head_dim", None) or config.hidden_size // heads),
+                                        bfr.get_compute_dtype(), dev)
+            out, lp = _chunked_prefill(model, ids, pos, lambda b: full_mask, static, _prefill_spans(T0, prefill_chunk))
+        else:
+            dynamic = DynamicCache(config=getattr(inner, "config", None))
+            # (a sliding layer of the prefill keeps every key: they go to their own slots of the full-capacity static layer)
+            dynamic.layers = [DynamicLayer() if getattr(layer, "is_sliding", False) else layer for layer in dynamic.layers]
+            out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=dynamic, use_cache=True)
+            lp = model.log_prob_samples().clone()
+            for i, layer in enumerate(dynamic.layers):  # the prompt's keys and values fill the static cache's first T0 slots
+                static.update(layer.keys, layer.values, i)
+                layer.keys = layer.values = None  # released as it goes: the peak is the prompt's cache plus the static one so far
+            del dynamic
         epilogue(out, 0)
         del out
         t = 1
