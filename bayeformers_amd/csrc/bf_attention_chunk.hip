@@ -7,9 +7,10 @@
 //   out[n,i,h,:] = sum_j softmax_j(scale q[n,h,i] . k[n,g,j] + mask[n,j]) v[n,g,j,:],  g = h / (H / Hkv).
 //   Keys at or past L are never read; a query with p_i < 0, or with every key hidden, gives 0.
 //
-// A sibling of bf_attention_gqa.hip's forward, with its work split, tiles, LDS images, fragment layouts and online softmax
-// (bf_attention_tiles.h): one 256-thread workgroup per (128 queries, head, sequence), 4 waves x 32 queries, walking key
-// tiles of KT; the heaviest query tiles first on the grid's slowest dimension.  What differs:
+// Shares with bf_attention_gqa.hip's forward the tiles, LDS images, fragment layouts, staging and the online-softmax step
+// (bf_attention_tiles.h: FwdShape, stage_clamped, softmax_pv_step), and has its work split: one 256-thread workgroup per
+// (128 queries, head, sequence), 4 waves x 32 queries, walking key tiles of KT; the heaviest query tiles first on the
+// grid's slowest dimension.  Its own is what a query sees:
 //   * the diagonal sits at key = off + query, which is aligned to no tile: every comparison carries off;
 //   * the query tail (Tq % 128) and the key end (L, any value, a device scalar) are independent bounds.  A load of query
 //     row >= Tq re-reads row Tq - 1, a load of key row >= L re-reads row L - 1 (finite values of the caller's, no branch);
@@ -23,11 +24,10 @@
 // CAP: the soft-capped logits of the CAP forward there (softcap * tanh(scale q.k / softcap), then the mask and the -inf's).
 // KV8: k and v are the e4m3 rows of an FP8 cache (include/bayeformers_amd_kv8.h) with one fp32 scale per row.  Only the
 // staging differs — 16 bytes are 16 features, dequantised in registers (bf_fp8.h: exact in bf16) into the same two LDS
-// images, as bf_attention_decode.hip's kv8 kernel does — so everything behind it is the bf16 kernel's and the result is
-// bitwise that kernel's on the dequantised cache.
+// images by the write it shares with bf_attention_decode.hip's kv8 kernel (write_fp8) — so everything behind it is the
+// bf16 kernel's and the result is bitwise that kernel's on the dequantised cache.
 // Head size 256 keeps one wave per SIMD and 64-key tiles, as the forward there (its header gives the reasons).
 #include "bf_attention_tiles.h"
-#include "bf_fp8.h"
 
 #include "../../include/bayeformers_amd_chunk.h"
 
@@ -55,9 +55,7 @@ struct ChunkParams {
     int origin;                     // key 0's index in its sequence (tile alignment only)
     float scale_log2e;
 };
-struct ChunkCapParams : ChunkParams {
-    float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
-};
+struct ChunkCapParams : ChunkParams, SoftCap {};
 struct ChunkKv8Params : ChunkCapParams {
     const float* k_scale;  // [N][Hkv][Tk]
     const float* v_scale;
@@ -75,30 +73,8 @@ __device__ __forceinline__ void stage_kv8(const uint8_t* base, long long stride,
 #pragma unroll
     for (int i = 0; i < NR * CPR / NT; ++i) {
         const int c = tid + NT * i, row = c / CPR, c16 = c % CPR, src = max(0, min(row0 + row, last));
-        const u32x4_t x = *reinterpret_cast<const u32x4_t*>(base + (long long)src * stride + c16 * 16);
-        const float sc = scale[src];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int d8 = 2 * c16 + h;
-            const bf16x8_t w = fp8_rows_value(u32x2_t{x[2 * h], x[2 * h + 1]}, sc);
-            if (swz) *reinterpret_cast<bf16x8_t*>(swz + row * Rows<HD>::SWZ + ((d8 ^ (row & 7)) << 4)) = w;
-            if (pad) *reinterpret_cast<bf16x8_t*>(pad + row * Rows<HD>::PAD + (d8 << 4)) = w;
-        }
-    }
-}
-
-// ... of a 16-bit cache head: stage_clamped (bf_attention_tiles.h) with the lower clamp as well
-template <typename T, int HD, int NR, int NT>
-__device__ __forceinline__ void stage_between(const T* base, long long stride, int row0, int last, char* swz, char* pad,
-                                              int tid) {
-    constexpr int CPR = HD / 8;
-    static_assert((NR * CPR) % NT == 0, "whole passes");
-#pragma unroll
-    for (int i = 0; i < NR * CPR / NT; ++i) {
-        const int c = tid + NT * i, row = c / CPR, c8 = c % CPR;
-        const f32x4_t x = *reinterpret_cast<const f32x4_t*>(base + (long long)max(0, min(row0 + row, last)) * stride + c8 * 8);
-        if (swz) *reinterpret_cast<f32x4_t*>(swz + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = x;
-        if (pad) *reinterpret_cast<f32x4_t*>(pad + row * Rows<HD>::PAD + (c8 << 4)) = x;
+        write_fp8<HD>(*reinterpret_cast<const u32x4_t*>(base + (long long)src * stride + c16 * 16), scale[src], row, c16, swz,
+                      pad);
     }
 }
 
@@ -118,11 +94,7 @@ __global__ __launch_bounds__(256, MINB) void chunk_fwd_kernel(const ParamsOf<CAP
     const int li = lane & 15, lg = lane >> 4;
     const int qt = (int)gridDim.z - 1 - (int)blockIdx.z;  // heavy query tiles first
     const int q0 = qt * TQ + wid * 32, h = blockIdx.x, n = blockIdx.y, g = h / p.group;
-    int L = p.Tk;
-    if (p.kv_len) {  // a fixed-capacity cache filled to L
-        const int64_t len = *p.kv_len;
-        L = len < 0 ? 0 : (len > p.Tk ? p.Tk : (int)len);
-    }
+    const int L = filled_keys(p.kv_len, p.Tk);
     // Everything below counts keys and positions from `shift` slots before the cache's key 0, where a tile of the sequence
     // begins: key j is slot j + shift, the cache holds the slots [shift, end)
     const int shift = p.origin % KT, end = L + shift;
@@ -142,7 +114,7 @@ __global__ __launch_bounds__(256, MINB) void chunk_fwd_kernel(const ParamsOf<CAP
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < NDB; ++j) o[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float run_max[2] = {-INFINITY, -INFINITY}, run_sum[2] = {0.f, 0.f};
+    SoftmaxRow run[2];
 
     // the tile's keys: up to its last query's position (and the fill), from the tile of its first query's first window key
     const int kend = min(end, off + min((qt + 1) * TQ, p.Tq));
@@ -156,10 +128,10 @@ __global__ __launch_bounds__(256, MINB) void chunk_fwd_kernel(const ParamsOf<CAP
             stage_kv8<HD, KT, 256>(reinterpret_cast<const uint8_t*>(p.v) + n * p.vs[0] + g * p.vs[1], p.vs[2],
                                    p.v_scale + srow, key0 - shift, L - 1, nullptr, vs, tid);
         } else {
-            stage_between<T, HD, KT, 256>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + g * p.ks[1], p.ks[2], key0 - shift,
-                                          L - 1, ks, nullptr, tid);
-            stage_between<T, HD, KT, 256>(reinterpret_cast<const T*>(p.v) + n * p.vs[0] + g * p.vs[1], p.vs[2], key0 - shift,
-                                          L - 1, nullptr, vs, tid);
+            stage_clamped<T, HD, KT, 256>(reinterpret_cast<const T*>(p.k) + n * p.ks[0] + g * p.ks[1], p.ks[2], key0 - shift,
+                                          0, L - 1, ks, nullptr, tid);
+            stage_clamped<T, HD, KT, 256>(reinterpret_cast<const T*>(p.v) + n * p.vs[0] + g * p.vs[1], p.vs[2], key0 - shift,
+                                          0, L - 1, nullptr, vs, tid);
         }
         // the dense [N][Tk] rows are not 16-byte aligned: element-wise, with a bound
         if (mask && tid < KT) {
@@ -201,38 +173,14 @@ __global__ __launch_bounds__(256, MINB) void chunk_fwd_kernel(const ParamsOf<CAP
                     mx = fmaxf(mx, s[kbk][j]);
                 }
             }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float new_max = fmaxf(run_max[qi], mx);
-            const float ref = new_max == -INFINITY ? 0.f : new_max;  // nothing visible yet: every term is 0
-            const float corr = __builtin_amdgcn_exp2f(run_max[qi] - ref);
-            float sum = 0.f;
-#pragma unroll
-            for (int kbk = 0; kbk < NKB; ++kbk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    s[kbk][j] = __builtin_amdgcn_exp2f(s[kbk][j] - ref);
-                    sum += s[kbk][j];
-                }
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
-            run_sum[qi] = run_sum[qi] * corr + sum;
-            run_max[qi] = new_max;
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) o[qi][db] *= corr;
-#pragma unroll
-            for (int c = 0; c < KT / 32; ++c) {
-                const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) o[qi][db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[qi][db]);
-            }
+            softmax_pv_step<T, HD, KT>(s, mx, run[qi], o[qi], (lds_image)vs, li, lg);
         }
     }
 
     T* ob = reinterpret_cast<T*>(p.out) + ((long long)n * p.Tq * p.H + h) * HD;
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
-        const float inv = run_sum[qi] > 0.f ? 1.0f / run_sum[qi] : 0.f;
+        const float inv = run[qi].sum > 0.f ? 1.0f / run[qi].sum : 0.f;
         if (q0 + qi * 16 + li >= p.Tq) continue;  // rows >= Tq are never written
         T* orow = ob + (long long)(q0 + qi * 16 + li) * p.H * HD;
 #pragma unroll
@@ -243,51 +191,32 @@ __global__ __launch_bounds__(256, MINB) void chunk_fwd_kernel(const ParamsOf<CAP
 
 // The query tiles are the grid's SLOWEST dimension, last tile first: the heavy tiles of every (head, sequence) are
 // dispatched first, spread over the XCDs (bf_attention_gqa.hip: launch_fwd)
-template <typename T, int HD, bool LOCAL, bool CAP, bool KV8>
-void launch_one(const ParamsOf<CAP, KV8>& p, hipStream_t stream) {
+// kv8: the FP8 instantiations (bf16 compute); each dtype and head size with and without a window and a cap
+void launch(const ChunkKv8Params& p, int dtype, int D, bool cap, bool kv8, hipStream_t stream) {
     const dim3 grid(p.H, p.N, (p.Tq + TQ - 1) / TQ);
-    hipLaunchKernelGGL((chunk_fwd_kernel<T, HD, Shape<HD>::KT, LOCAL, CAP, KV8, Shape<HD>::MINB>), grid, dim3(256), 0, stream, p);
-}
-
-template <typename T, int HD, bool KV8>
-void launch_hd(const ChunkKv8Params& kp, bool cap, hipStream_t stream) {
-    if (cap) {
-        if (kp.window) launch_one<T, HD, true, true, KV8>(kp, stream);
-        else launch_one<T, HD, false, true, KV8>(kp, stream);
-    } else if (kp.window) launch_one<T, HD, true, false, KV8>(kp, stream);
-    else launch_one<T, HD, false, false, KV8>(kp, stream);
-}
-
-template <typename T, bool KV8>
-void launch(const ChunkKv8Params& kp, int D, bool cap, hipStream_t stream) {
-    if (D == 64) launch_hd<T, 64, KV8>(kp, cap, stream);
-    else if (D == 128) launch_hd<T, 128, KV8>(kp, cap, stream);
-    else launch_hd<T, 256, KV8>(kp, cap, stream);
+    with_head_size(D, [&](auto hd) {
+        with_flag(p.window != 0, [&](auto local) {
+            with_flag(cap, [&](auto capped) {
+                auto run = [&](auto tag, auto fp8) {
+                    using T = typename decltype(tag)::type;
+                    constexpr int HD = decltype(hd)::value;
+                    constexpr bool LOCAL = decltype(local)::value, CAP = decltype(capped)::value, KV8 = decltype(fp8)::value;
+                    const ParamsOf<CAP, KV8>& kp = p;
+                    hipLaunchKernelGGL((chunk_fwd_kernel<T, HD, Shape<HD>::KT, LOCAL, CAP, KV8, Shape<HD>::MINB>), grid,
+                                       dim3(256), 0, stream, kp);
+                };
+                if (kv8) run(TypeTag<__bf16>{}, std::true_type{});
+                else with_dtype(dtype, [&](auto tag) { run(tag, std::false_type{}); });
+            });
+        });
+    });
 }
 
 // Validates the shape; returns 0 or the BF_FAIL status
 int check_shape(const char* what, const bf_attn_decode_t* s, int dtype, bool kv8) {
-    if (!s) BF_FAIL("%s: shape is NULL", what);
-    if (kv8 && dtype != BF_DT_BF16)
-        BF_FAIL("%s: dtype must be bf16 (bfloat16: the dequantised rows are exact in it alone)", what);
-    if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
-    if (s->head_dim != 64 && s->head_dim != 128 && s->head_dim != 256)
-        BF_FAIL("%s: head size %d (64, 128 or 256)", what, s->head_dim);
-    if (s->Tq < 1) BF_FAIL("%s: Tq=%d new queries (at least 1)", what, s->Tq);
-    if (s->Tk < s->Tq) BF_FAIL("%s: Tk=%d cached keys, fewer than Tq=%d", what, s->Tk, s->Tq);
-    if (s->Tk > 0x7fffff00) BF_FAIL("%s: Tk=%d cached keys exceeds the key index", what, s->Tk);
-    if (s->N < 1 || s->H < 1 || s->Hkv < 1) BF_FAIL("%s: N=%d, H=%d, Hkv=%d must be positive", what, s->N, s->H, s->Hkv);
-    if (s->H % s->Hkv) BF_FAIL("%s: %d query heads do not divide into %d K/V head groups", what, s->H, s->Hkv);
+    if (check_decode_dims(what, s, dtype, 0, kv8 ? 16 : 8)) return 1;
     if (s->N > 65535 || s->H > 65535 || (s->Tq + TQ - 1) / TQ > 65535) BF_FAIL("%s: N, H or Tq / 128 exceeds the grid", what);
-    for (int i = 0; i < 3; ++i) {
-        if (s->q_stride[i] < 0 || s->q_stride[i] % 8) BF_FAIL("%s: strides must be non-negative multiples of 8 elements", what);
-        const int64_t st[2] = {s->k_stride[i], s->v_stride[i]};
-        for (int t = 0; t < 2; ++t) {
-            if (kv8 && (st[t] < 0 || st[t] % 16)) BF_FAIL("%s: the K / V strides (bytes) must be non-negative multiples of 16", what);
-            if (st[t] < 0 || st[t] % 8) BF_FAIL("%s: strides must be non-negative multiples of 8 elements", what);
-        }
-    }
-    return 0;
+    return check_decode_strides(what, s, kv8 ? 16 : 8);
 }
 
 // window 0: none.  softcap 0: no cap.  kv8: d_k / d_v are e4m3fn rows with the scales d_k_scale / d_v_scale (bf16 compute)
@@ -330,17 +259,10 @@ int chunk(const char* what, const void* d_q, const void* d_k, const void* d_v, c
         p.vs[i] = shape->v_stride[i];
     }
     p.scale_log2e = scaling * LOG2E;
-    if (softcap != 0.f) {
-        p.cap_x = scaling / softcap;
-        p.cap_log2e = softcap * LOG2E;
-        if (!(p.cap_log2e < INFINITY) || !(fabsf(p.cap_x) < INFINITY))
-            BF_FAIL("%s: softcap=%g: scaling / softcap or softcap * log2(e) is not finite", what, (double)softcap);
-    }
+    if (softcap != 0.f && p.fill(what, softcap, scaling)) return 1;
     p.k_scale = d_k_scale;
     p.v_scale = d_v_scale;
-    if (kv8) launch<__bf16, true>(p, shape->head_dim, softcap != 0.f, stream);
-    else if (dtype == BF_DT_BF16) launch<__bf16, false>(p, shape->head_dim, softcap != 0.f, stream);
-    else launch<_Float16, false>(p, shape->head_dim, softcap != 0.f, stream);
+    launch(p, dtype, shape->head_dim, softcap != 0.f, kv8, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }

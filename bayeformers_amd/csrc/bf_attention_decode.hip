@@ -12,8 +12,9 @@
 // shape only (decode_split), and with more than one split a second launch merges the partial (max, sum, output) rows in
 // split order — bitwise the same result on every run, no atomics, no host synchronisation, no allocation (the partials
 // live in the caller's workspace: bf_attention_decode_workspace_bytes).
-// Fragment layouts, LDS images and the online softmax are those of bf_attention_gqa.hip's forward: S^T = K Q^T, then
-// O^T = V^T P^T with P^T straight from the accumulators.  The next key tile is fetched into registers while the current
+// It shares the fragment layouts, LDS images and the online-softmax step with bf_attention_gqa.hip's forward
+// (bf_attention_tiles.h: softmax_pv_step, one 64-key block per wave and tile): S^T = K Q^T, then O^T = V^T P^T with P^T
+// straight from the accumulators.  The next key tile is fetched into registers while the current
 // one is computed.  A query with no visible key returns 0.
 //
 // bf_attention_decode_gqa_len runs the same kernels over a fixed-capacity cache (a static cache that one captured graph
@@ -23,10 +24,9 @@
 //
 // bf_attention_decode_gqa_kv8 (include/bayeformers_amd_kv8.h) runs them over an FP8 cache: K and V rows of D e4m3fn bytes
 // with one fp32 power-of-two scale each (bf_kv8.hip writes them).  Only the fetch differs: a key row is HD / 16 16-byte
-// chunks plus its scale, and the dequantised bf16 values — exact — are written into the same LDS images, so everything
-// behind the fetch is the bf16 kernel's and the result is bitwise that kernel's on the dequantised cache.
+// chunks plus its scale, and the dequantised bf16 values — exact — are written into the same LDS images (write_fp8, shared
+// with bf_attention_chunk.hip), so everything behind the fetch is the bf16 kernel's and the result is bitwise that kernel's on the dequantised cache.
 #include "bf_attention_tiles.h"
-#include "bf_fp8.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -56,10 +56,8 @@ struct DecodeParams {
 };
 
 // CAP: the soft-capped logits of bf_attention_gqa.hip's CAP forward (softcap * tanh(scale q.k / softcap), then the mask): a
-// compile-time flag with a parameter block of its own; the instantiations without it compile to the code they had.
-struct DecodeCapParams : DecodeParams {
-    float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
-};
+// compile-time flag with a parameter block of its own (SoftCap: bf_attention_tiles.h)
+struct DecodeCapParams : DecodeParams, SoftCap {};
 // KV8: k and v are e4m3fn rows (ks / vs in bytes), with one scale per (sequence, K/V head, key); again a compile-time flag
 // with a parameter block of its own
 struct DecodeKv8Params : DecodeCapParams {
@@ -111,11 +109,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p)
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int li = lane & 15, lg = lane >> 4;
     const int split = blockIdx.x, nk = blockIdx.y, n = nk / p.Hkv, g = nk % p.Hkv;
-    int L = p.Tk, split_keys = p.split_keys;
-    if (p.kv_len) {  // a fixed-capacity cache filled to L
-        const int64_t len = *p.kv_len;
-        L = len < 0 ? 0 : (len > p.Tk ? p.Tk : (int)len);
-    }
+    const int L = filled_keys(p.kv_len, p.Tk);
+    int split_keys = p.split_keys;
     // LOCAL: the keys some query sees start at lo (the first query's window); the splits are laid over [lo, L)
     const int lo = LOCAL ? max(0, L - p.Tq - p.window + 1) : 0;
     if (p.kv_len) {  // the range's own split rule, within the grid's nsplit splits
@@ -141,7 +136,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p)
     f32x4_t o[NDB];
 #pragma unroll
     for (int j = 0; j < NDB; ++j) o[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float run_max = -INFINITY, run_sum = 0.f;
+    SoftmaxRow run;
 
     // the next tile travels in registers while the current one is computed; keys past the split read as 0
     // (KV8: with the rows' scales; a key past the split has scale 0 too)
@@ -173,14 +168,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p)
         for (int i = 0; i < NLD; ++i) {
             const int c = tid + 256 * i, row = c / CPR, c8 = c % CPR;
             if constexpr (KV8) {  // 16 bytes are 16 features: two 16-byte chunks of the bf16 images
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int d8 = 2 * c8 + h;
-                    *reinterpret_cast<bf16x8_t*>(ks + row * Rows<HD>::SWZ + ((d8 ^ (row & 7)) << 4)) =
-                        fp8_rows_value(u32x2_t{kr[i][2 * h], kr[i][2 * h + 1]}, ksc[i]);
-                    *reinterpret_cast<bf16x8_t*>(vs + row * Rows<HD>::PAD + (d8 << 4)) =
-                        fp8_rows_value(u32x2_t{vr[i][2 * h], vr[i][2 * h + 1]}, vsc[i]);
-                }
+                write_fp8<HD>(kr[i], ksc[i], row, c8, ks, nullptr);
+                write_fp8<HD>(vr[i], vsc[i], row, c8, nullptr, vs);
             } else {
                 *reinterpret_cast<f32x4_t*>(ks + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = kr[i];
                 *reinterpret_cast<f32x4_t*>(vs + row * Rows<HD>::PAD + (c8 << 4)) = vr[i];
@@ -212,36 +201,12 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p)
                 mx = fmaxf(mx, s[kbk][j]);
             }
         }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float new_max = fmaxf(run_max, mx);
-        const float ref = new_max == -INFINITY ? 0.f : new_max;  // nothing visible yet: every term is 0
-        const float corr = __builtin_amdgcn_exp2f(run_max - ref);
-        float sum = 0.f;
-#pragma unroll
-        for (int kbk = 0; kbk < NKB; ++kbk)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                s[kbk][j] = __builtin_amdgcn_exp2f(s[kbk][j] - ref);
-                sum += s[kbk][j];
-            }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        run_sum = run_sum * corr + sum;
-        run_max = new_max;
-#pragma unroll
-        for (int db = 0; db < NDB; ++db) o[db] *= corr;
-#pragma unroll
-        for (int c = 0; c < KT / 32; ++c) {
-            const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) o[db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[db]);
-        }
+        softmax_pv_step<T, HD, KT>(s, mx, run, o, (lds_image)vs, li, lg);
     }
     if (!row_ok) return;
 
     if (p.nsplit == 1) {  // one split: the final rows
-        const float inv = run_sum > 0.f ? 1.0f / run_sum : 0.f;
+        const float inv = run.sum > 0.f ? 1.0f / run.sum : 0.f;
         T* orow = reinterpret_cast<T*>(p.out) + (((long long)n * p.Tq + qi) * p.H + h) * HD;
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
@@ -252,8 +217,8 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p)
 #pragma unroll
     for (int db = 0; db < NDB; ++db) *reinterpret_cast<f32x4_t*>(p.part_o + prow * HD + db * 16 + lg * 4) = o[db];
     if (lg == 0) {
-        p.part_ml[2 * prow] = run_max;
-        p.part_ml[2 * prow + 1] = run_sum;
+        p.part_ml[2 * prow] = run.max;
+        p.part_ml[2 * prow + 1] = run.sum;
     }
 }
 
@@ -287,55 +252,38 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(const DecodeParams p)
     *reinterpret_cast<half4*>(reinterpret_cast<T*>(p.out) + row * HD + c4 * 4) = __builtin_convertvector(acc * inv, half4);
 }
 
-template <typename T, int HD>
-void launch(const DecodeCapParams& cp, bool cap, hipStream_t stream) {
-    const DecodeParams& p = cp;
+// kv8: the FP8 instantiations (bf16 compute); each dtype and head size with and without a window and a cap
+void launch(const DecodeKv8Params& p, int dtype, int D, bool cap, bool kv8, hipStream_t stream) {
     const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
-    if (cap) {
-        if (p.window) decode_kernel<T, HD, true, true><<<grid, 256, 0, stream>>>(cp);
-        else decode_kernel<T, HD, false, true><<<grid, 256, 0, stream>>>(cp);
-    } else if (p.window) decode_kernel<T, HD, true, false><<<grid, 256, 0, stream>>>(p);
-    else decode_kernel<T, HD, false, false><<<grid, 256, 0, stream>>>(p);
-    if (p.nsplit > 1) {
-        const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
-        decode_merge_kernel<T, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
-    }
-}
-
-// the KV8 instantiations (bf16 only)
-template <int HD>
-void launch_kv8(const DecodeKv8Params& kp, bool cap, hipStream_t stream) {
-    const DecodeParams& p = kp;
-    const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
-    if (cap) {
-        if (p.window) decode_kernel<__bf16, HD, true, true, true><<<grid, 256, 0, stream>>>(kp);
-        else decode_kernel<__bf16, HD, false, true, true><<<grid, 256, 0, stream>>>(kp);
-    } else if (p.window) decode_kernel<__bf16, HD, true, false, true><<<grid, 256, 0, stream>>>(kp);
-    else decode_kernel<__bf16, HD, false, false, true><<<grid, 256, 0, stream>>>(kp);
-    if (p.nsplit > 1) {
-        const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
-        decode_merge_kernel<__bf16, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
-    }
+    with_head_size(D, [&](auto hd) {
+        constexpr int HD = decltype(hd)::value;
+        with_flag(p.window != 0, [&](auto local) {
+            with_flag(cap, [&](auto capped) {
+                auto run = [&](auto tag, auto fp8) {
+                    using T = typename decltype(tag)::type;
+                    constexpr bool LOCAL = decltype(local)::value, CAP = decltype(capped)::value, KV8 = decltype(fp8)::value;
+                    const ParamsOf<CAP, KV8>& kp = p;
+                    decode_kernel<T, HD, LOCAL, CAP, KV8><<<grid, 256, 0, stream>>>(kp);
+                };
+                if (kv8) run(TypeTag<__bf16>{}, std::true_type{});
+                else with_dtype(dtype, [&](auto tag) { run(tag, std::false_type{}); });
+            });
+        });
+        if (p.nsplit > 1) {
+            const long long threads = (long long)p.N * p.Tq * p.H * (HD / 4);
+            with_dtype(dtype, [&](auto tag) {
+                decode_merge_kernel<typename decltype(tag)::type, HD><<<(unsigned)((threads + 255) / 256), 256, 0, stream>>>(p);
+            });
+        }
+    });
 }
 
 // Validates the shape; returns 0 or the BF_FAIL status
 int check_shape(const char* what, const bf_attn_decode_t* s, int dtype) {
-    if (!s) BF_FAIL("%s: shape is NULL", what);
-    if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
-    if (s->head_dim != 64 && s->head_dim != 128 && s->head_dim != 256)
-        BF_FAIL("%s: head size %d (64, 128 or 256)", what, s->head_dim);
-    if (s->Tq < 1 || s->Tq > 16) BF_FAIL("%s: Tq=%d new queries (1 .. 16)", what, s->Tq);
-    if (s->Tk < s->Tq) BF_FAIL("%s: Tk=%d cached keys, fewer than Tq=%d", what, s->Tk, s->Tq);
-    if (s->N < 1 || s->H < 1 || s->Hkv < 1) BF_FAIL("%s: N=%d, H=%d, Hkv=%d must be positive", what, s->N, s->H, s->Hkv);
-    if (s->H % s->Hkv) BF_FAIL("%s: %d query heads do not divide into %d K/V head groups", what, s->H, s->Hkv);
+    if (check_decode_dims(what, s, dtype, 16, 8)) return 1;
     const long long rows = (long long)(s->H / s->Hkv) * s->Tq;
     if ((long long)s->N * s->Hkv > 65535 || (rows + ROWS - 1) / ROWS > 65535) BF_FAIL("%s: N * Hkv or H / Hkv * Tq exceeds the grid", what);
-    for (int i = 0; i < 3; ++i) {
-        const int64_t st[3] = {s->q_stride[i], s->k_stride[i], s->v_stride[i]};
-        for (int t = 0; t < 3; ++t)
-            if (st[t] < 0 || st[t] % 8) BF_FAIL("%s: strides must be non-negative multiples of 8 elements", what);
-    }
-    return 0;
+    return check_decode_strides(what, s, 8);
 }
 
 int64_t workspace_bytes(const bf_attn_decode_t* s) {
@@ -378,7 +326,7 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
     const Split sp = decode_split(shape);
     if (sp.n > 1 && !d_workspace) BF_FAIL("%s: %d key splits need a workspace of %lld bytes", what, sp.n,
                                           (long long)workspace_bytes(shape));
-    DecodeCapParams p = {};
+    DecodeKv8Params p = {};
     p.q = d_q;
     p.k = d_k;
     p.v = d_v;
@@ -416,29 +364,10 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
         p.vs[i] = shape->v_stride[i];
     }
     p.scale_log2e = scaling * LOG2E;
-    if (softcap != 0.f) {
-        p.cap_x = scaling / softcap;
-        p.cap_log2e = softcap * LOG2E;
-        if (!(p.cap_log2e < INFINITY) || !(fabsf(p.cap_x) < INFINITY))
-            BF_FAIL("%s: softcap=%g: scaling / softcap or softcap * log2(e) is not finite", what, (double)softcap);
-    }
-    if (kv8) {
-        DecodeKv8Params kp = {};
-        static_cast<DecodeCapParams&>(kp) = p;
-        kp.k_scale = d_k_scale;
-        kp.v_scale = d_v_scale;
-        if (shape->head_dim == 64) launch_kv8<64>(kp, softcap != 0.f, stream);
-        else if (shape->head_dim == 128) launch_kv8<128>(kp, softcap != 0.f, stream);
-        else launch_kv8<256>(kp, softcap != 0.f, stream);
-    } else if (dtype == BF_DT_BF16) {
-        if (shape->head_dim == 64) launch<__bf16, 64>(p, softcap != 0.f, stream);
-        else if (shape->head_dim == 128) launch<__bf16, 128>(p, softcap != 0.f, stream);
-        else launch<__bf16, 256>(p, softcap != 0.f, stream);
-    } else {
-        if (shape->head_dim == 64) launch<_Float16, 64>(p, softcap != 0.f, stream);
-        else if (shape->head_dim == 128) launch<_Float16, 128>(p, softcap != 0.f, stream);
-        else launch<_Float16, 256>(p, softcap != 0.f, stream);
-    }
+    if (softcap != 0.f && p.fill(what, softcap, scaling)) return 1;
+    p.k_scale = d_k_scale;
+    p.v_scale = d_v_scale;
+    launch(p, dtype, shape->head_dim, softcap != 0.f, kv8, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -80,11 +80,9 @@ struct GqaParams {
 // scale q.k, in log2 units th * cap_log2e with th = tanh(s * cap_x); the mask and the -inf of the diagonal, the window
 // edge, the tail and the unseen keys come after the cap, and the online softmax is the same.  The backward recomputes th
 // with P and multiplies dS by d tanh = 1 - th^2 (the dk/dv kernel's P for dv goes without).  A compile-time flag with a
-// parameter block and branches of its own: the instantiations without it take the block, keep the statements and compile
-// to the code they had.
-struct GqaCapParams : GqaParams {
-    float cap_x, cap_log2e;  // scale / softcap and softcap * log2(e)
-};
+// parameter block of its own (SoftCap: bf_attention_tiles.h); `if constexpr (CAP)` stands where the score is formed and
+// where that factor is applied, nowhere else.
+struct GqaCapParams : GqaParams, SoftCap {};
 // The BAND instantiations run banded causal attention (packed sequences: include/bayeformers_amd_packed.h): query i sees
 // key j iff lo[b][i] <= j <= i, and key j is seen by the queries j .. hi[b][j]; both bounds are non-decreasing along T, so
 // a block's first row holds its least bound and its last row its greatest.  The forward and the dq kernel read lo, the
@@ -108,7 +106,7 @@ __device__ __forceinline__ int tail_row(int row, int T) {
 
 template <bool TAIL, typename T, int HD, int NR, int NT>
 __device__ __forceinline__ void stage_rows(const T* base, long long stride, int row0, int rows, char* swz, char* pad, int tid) {
-    if (TAIL) stage_clamped<T, HD, NR, NT>(base, stride, row0, rows - 1, swz, pad, tid);
+    if (TAIL) stage_clamped<T, HD, NR, NT>(base, stride, row0, 0, rows - 1, swz, pad, tid);
     else stage<T, HD, NR, NT>(base, stride, row0, swz, pad, tid);
 }
 
@@ -180,7 +178,7 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP, 
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < NDB; ++j) o[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    float run_max[2] = {-INFINITY, -INFINITY}, run_sum[2] = {0.f, 0.f};
+    SoftmaxRow run[2];
 
     const int kend = CAUSAL ? (TAIL ? min((qt + 1) * TQ, p.T) : (qt + 1) * TQ) : p.T;
     Band<2> lo;  // BAND: the lower bounds of the wave's queries
@@ -232,42 +230,18 @@ __global__ __launch_bounds__(256, MINB) void gqa_fwd_kernel(const ParamsOf<CAP, 
                     mx = fmaxf(mx, s[kbk][j]);
                 }
             }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            const float new_max = fmaxf(run_max[qi], mx);
-            const float ref = new_max == -INFINITY ? 0.f : new_max;  // nothing visible yet: every term is 0
-            const float corr = __builtin_amdgcn_exp2f(run_max[qi] - ref);
-            float sum = 0.f;
-#pragma unroll
-            for (int kbk = 0; kbk < NKB; ++kbk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    s[kbk][j] = __builtin_amdgcn_exp2f(s[kbk][j] - ref);
-                    sum += s[kbk][j];
-                }
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
-            run_sum[qi] = run_sum[qi] * corr + sum;
-            run_max[qi] = new_max;
-#pragma unroll
-            for (int db = 0; db < NDB; ++db) o[qi][db] *= corr;
-#pragma unroll
-            for (int c = 0; c < KT / 32; ++c) {
-                const frag pf = pack2<T>(s[2 * c], s[2 * c + 1]);
-#pragma unroll
-                for (int db = 0; db < NDB; ++db) o[qi][db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[qi][db]);
-            }
+            softmax_pv_step<T, HD, KT>(s, mx, run[qi], o[qi], (lds_image)vs, li, lg);
         }
     }
 
     T* ob = reinterpret_cast<T*>(p.out) + ((long long)b * p.T * p.H + h) * HD;
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
-        const float inv = run_sum[qi] > 0.f ? 1.0f / run_sum[qi] : 0.f;
+        const float inv = run[qi].sum > 0.f ? 1.0f / run[qi].sum : 0.f;
         if (TAIL && q0 + qi * 16 + li >= p.T) continue;  // rows >= T are never written
         if (p.lse && lg == 0)
             p.lse[((long long)b * p.H + h) * p.T + q0 + qi * 16 + li] =
-                run_sum[qi] > 0.f ? run_max[qi] + __builtin_amdgcn_logf(run_sum[qi]) : INFINITY;
+                run[qi].sum > 0.f ? run[qi].max + __builtin_amdgcn_logf(run[qi].sum) : INFINITY;
         T* orow = ob + (long long)(q0 + qi * 16 + li) * p.H * HD;
 #pragma unroll
         for (int db = 0; db < NDB; ++db)
@@ -369,21 +343,18 @@ __global__ __launch_bounds__(256, Shape<HD>::DQ_MINB) void gqa_bwd_dq_kernel(con
                 if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if constexpr (CAP) {  // (a branch of its own: the plain form below keeps the statements, and the code, it had)
-                        const float th = softcap_tanh(s[kbk][j] * p.cap_x);
-                        float pr = __builtin_amdgcn_exp2f(fmaf(th, p.cap_log2e, mk[j]) - lse[qi]);
-                        if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
-                        if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
-                        if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
-                        s[kbk][j] = pr * (dp[kbk][j] - delta[qi]) * fmaf(-th, th, 1.0f);  // dS^T through the cap
-                        continue;
-                    }
-                    float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
+                    [[maybe_unused]] float th = 0.f;  // CAP: tanh(scale q.k / softcap)
+                    float pr;
+                    if constexpr (CAP) {
+                        th = softcap_tanh(s[kbk][j] * p.cap_x);
+                        pr = __builtin_amdgcn_exp2f(fmaf(th, p.cap_log2e, mk[j]) - lse[qi]);
+                    } else pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
                     if (diag && key0 + kbk * 16 + lg * 4 + j > qr0 + li) pr = 0.f;
                     if (edge && qr0 + li - (key0 + kbk * 16 + lg * 4 + j) >= p.window) pr = 0.f;
                     if (BAND && lo.edge && key0 + kbk * 16 + lg * 4 + j < lo.row[qi]) pr = 0.f;
                     if (past && key0 + kbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
                     s[kbk][j] = pr * (dp[kbk][j] - delta[qi]);  // dS^T
+                    if constexpr (CAP) s[kbk][j] *= fmaf(-th, th, 1.0f);  // ... through the cap
                 }
             }
 #pragma unroll
@@ -496,23 +467,19 @@ __global__ __launch_bounds__(Shape<HD>::DKV_KEYS * 4, MINB) void gqa_bwd_dkv_ker
                 const f32x4_t d4 = *reinterpret_cast<const f32x4_t*>(del_s + qbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    if constexpr (CAP) {  // (a branch of its own: the plain form below keeps the statements, and the code, it had)
-                        const float th = softcap_tanh(s[qbk][j] * p.cap_x);
-                        float pr = __builtin_amdgcn_exp2f(fmaf(th, p.cap_log2e, mk) - l4[j]);
-                        if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
-                        if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
-                        if (past && q0 + qbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
-                        s[qbk][j] = pr;                                                   // P (for dv: without the factor)
-                        dp[qbk][j] = pr * (dp[qbk][j] - d4[j]) * fmaf(-th, th, 1.0f);  // dS through the cap
-                        continue;
-                    }
-                    float pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
+                    [[maybe_unused]] float th = 0.f;  // CAP: tanh(scale q.k / softcap)
+                    float pr;
+                    if constexpr (CAP) {
+                        th = softcap_tanh(s[qbk][j] * p.cap_x);
+                        pr = __builtin_amdgcn_exp2f(fmaf(th, p.cap_log2e, mk) - l4[j]);
+                    } else pr = __builtin_amdgcn_exp2f(fmaf(s[qbk][j], p.scale_log2e, mk) - l4[j]);
                     if (diag && q0 + qbk * 16 + lg * 4 + j < key) pr = 0.f;
                     if (edge && q0 + qbk * 16 + lg * 4 + j - key >= p.window) pr = 0.f;
                     if (BAND && hi.edge && q0 + qbk * 16 + lg * 4 + j > hi.row[0]) pr = 0.f;
                     if (past && q0 + qbk * 16 + lg * 4 + j >= p.T) pr = 0.f;
-                    s[qbk][j] = pr;                          // P
+                    s[qbk][j] = pr;                          // P (CAP: for dv, without the factor)
                     dp[qbk][j] = pr * (dp[qbk][j] - d4[j]);  // dS
+                    if constexpr (CAP) dp[qbk][j] *= fmaf(-th, th, 1.0f);  // ... through the cap
                 }
             }
 #pragma unroll
@@ -558,76 +525,30 @@ void launch_bwd(const ParamsOf<CAP, BAND>& p, hipStream_t stream) {
                        dim3(p.Hkv, p.B, (p.T + KEYS - 1) / KEYS), dim3(KEYS * 4), 0, stream, p);
 }
 
-// the band instantiations: causal only, no cap, with or without a tail
-template <typename T, int HD>
-void launch_band(const GqaBandParams& p, bool bwd, hipStream_t stream) {
-    if (p.T % TQ) {
-        if (bwd) launch_bwd<T, HD, true, false, true, false, true>(p, stream);
-        else launch_fwd<T, HD, true, false, true, false, true>(p, stream);
-    } else {
-        if (bwd) launch_bwd<T, HD, true, false, false, false, true>(p, stream);
-        else launch_fwd<T, HD, true, false, false, false, true>(p, stream);
-    }
-}
-
-template <typename T>
-void launch_band(const GqaBandParams& p, int D, bool bwd, hipStream_t stream) {
-    if (D == 64) launch_band<T, 64>(p, bwd, stream);
-    else if (D == 128) launch_band<T, 128>(p, bwd, stream);
-    else launch_band<T, 256>(p, bwd, stream);
-}
-
-template <typename T, int HD, bool CAUSAL, bool LOCAL = false, bool CAP = false>
-void launch(const ParamsOf<CAP>& p, bool bwd, hipStream_t stream) {
-    if (p.T % TQ) {
-        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, true, CAP>(p, stream);
-        else launch_fwd<T, HD, CAUSAL, LOCAL, true, CAP>(p, stream);
-    } else {
-        if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, false, CAP>(p, stream);
-        else launch_fwd<T, HD, CAUSAL, LOCAL, false, CAP>(p, stream);
-    }
-}
-
-// the soft-cap instantiations: causal only, with or without a window
-template <typename T, int HD>
-void launch_cap(const GqaCapParams& p, bool local, bool bwd, hipStream_t stream) {
-    if (local) launch<T, HD, true, true, true>(p, bwd, stream);
-    else launch<T, HD, true, false, true>(p, bwd, stream);
-}
-
-template <typename T>
-void launch_cap(const GqaCapParams& p, int D, bool local, bool bwd, hipStream_t stream) {
-    if (D == 64) launch_cap<T, 64>(p, local, bwd, stream);
-    else if (D == 128) launch_cap<T, 128>(p, local, bwd, stream);
-    else launch_cap<T, 256>(p, local, bwd, stream);
-}
-
-// local: the sliding-window instantiations (causal only); the others are the kernels the plain entries always ran
-template <typename T>
-void launch(const GqaParams& p, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
-    if (D == 64) {
-        if (local) launch<T, 64, true, true>(p, bwd, stream);
-        else if (causal) launch<T, 64, true>(p, bwd, stream);
-        else launch<T, 64, false>(p, bwd, stream);
-    } else if (D == 128) {
-        if (local) launch<T, 128, true, true>(p, bwd, stream);
-        else if (causal) launch<T, 128, true>(p, bwd, stream);
-        else launch<T, 128, false>(p, bwd, stream);
-    } else {
-        if (local) launch<T, 256, true, true>(p, bwd, stream);
-        else if (causal) launch<T, 256, true>(p, bwd, stream);
-        else launch<T, 256, false>(p, bwd, stream);
-    }
-}
-
-// cap: the soft-cap instantiations with their parameter block (fill_softcap: causal shapes only); else the plain block
-void dispatch(const GqaCapParams& cp, bool cap, int dtype, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
-    const GqaParams& p = cp;
-    if (cap) {
-        if (dtype == BF_DT_BF16) launch_cap<__bf16>(cp, D, local, bwd, stream);
-        else launch_cap<_Float16>(cp, D, local, bwd, stream);
-    } else if (dtype == BF_DT_BF16) launch<__bf16>(p, D, causal, local, bwd, stream);
-    else launch<_Float16>(p, D, causal, local, bwd, stream);
+// The instantiations, by the parameter block: the plain one runs non-causal, causal and (local) sliding-window causal
+// kernels, the soft-cap one causal kernels with or without a window, the band one causal kernels alone; each with and
+// without a tail, at every dtype and head size.
+template <typename P>
+void launch(const P& p, int dtype, int D, bool causal, bool local, bool bwd, hipStream_t stream) {
+    constexpr bool CAP = std::is_same_v<P, GqaCapParams>, BAND = std::is_same_v<P, GqaBandParams>;
+    with_dtype(dtype, [&](auto tag) {
+        with_head_size(D, [&](auto hd) {
+            with_flag(p.T % TQ != 0, [&](auto tail) {
+                auto run = [&](auto is_causal, auto is_local) {
+                    using T = typename decltype(tag)::type;
+                    constexpr int HD = decltype(hd)::value;
+                    constexpr bool CAUSAL = decltype(is_causal)::value, LOCAL = decltype(is_local)::value;
+                    constexpr bool TAIL = decltype(tail)::value;
+                    if (bwd) launch_bwd<T, HD, CAUSAL, LOCAL, TAIL, CAP, BAND>(p, stream);
+                    else launch_fwd<T, HD, CAUSAL, LOCAL, TAIL, CAP, BAND>(p, stream);
+                };
+                if constexpr (BAND) run(std::true_type{}, std::false_type{});
+                else if (local) run(std::true_type{}, std::true_type{});
+                else if (CAP || causal) run(std::true_type{}, std::false_type{});
+                else if constexpr (!CAP) run(std::false_type{}, std::false_type{});
+            });
+        });
+    });
 }
 
 // Validates the shape and fills the parameters' shape part; returns 0 or the BF_FAIL status
@@ -684,11 +605,7 @@ int fill_window(const char* what, GqaParams& p, const bf_attn_gqa_t* s, int wind
 // The soft-cap entries' extra argument (finite and > 0: the entries checked it): causal shapes only
 int fill_softcap(const char* what, GqaCapParams& p, const bf_attn_gqa_t* s, float softcap, float scaling) {
     if (s->causal != 1) BF_FAIL("%s: the soft-cap kernels need a causal shape (causal=%d)", what, s->causal);
-    p.cap_x = scaling / softcap;
-    p.cap_log2e = softcap * LOG2E;
-    if (!(p.cap_log2e < INFINITY) || !(fabsf(p.cap_x) < INFINITY))
-        BF_FAIL("%s: softcap=%g: scaling / softcap or softcap * log2(e) is not finite", what, (double)softcap);
-    return 0;
+    return p.fill(what, softcap, scaling);
 }
 
 // window 0: the plain entries; >= 1: the sliding-window ones.  softcap 0: no cap
@@ -713,7 +630,8 @@ int fwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     p.mask_off = d_mask_off;
     p.out = d_out;
     p.lse = d_lse;
-    dispatch(p, softcap != 0.f, dtype, shape->head_dim, shape->causal, window > 0, false, stream);
+    if (softcap != 0.f) launch(p, dtype, shape->head_dim, true, window > 0, false, stream);
+    else launch<GqaParams>(p, dtype, shape->head_dim, shape->causal, window > 0, false, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -748,7 +666,8 @@ int bwd_gqa(const char* what, const void* d_q, const void* d_k, const void* d_v,
     p.dq = d_dq;
     p.dk = d_dk;
     p.dv = d_dv;
-    dispatch(p, softcap != 0.f, dtype, shape->head_dim, shape->causal, window > 0, true, stream);
+    if (softcap != 0.f) launch(p, dtype, shape->head_dim, true, window > 0, true, stream);
+    else launch<GqaParams>(p, dtype, shape->head_dim, shape->causal, window > 0, true, stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -758,11 +677,6 @@ int fill_band(const char* what, GqaBandParams& p, const bf_attn_gqa_t* s, int dt
     if (fill_shape(what, p, s, dtype, scaling)) return 1;
     if (s->causal != 1) BF_FAIL("%s: the band kernels need a causal shape (causal=%d)", what, s->causal);
     return 0;
-}
-
-void dispatch_band(const GqaBandParams& p, int dtype, int D, bool bwd, hipStream_t stream) {
-    if (dtype == BF_DT_BF16) launch_band<__bf16>(p, D, bwd, stream);
-    else launch_band<_Float16>(p, D, bwd, stream);
 }
 
 }  // namespace
@@ -783,7 +697,7 @@ int bf_attention_fwd_gqa_band(const void* d_q, const void* d_k, const void* d_v,
     p.out = d_out;
     p.lse = d_lse;
     p.lo = d_lo;
-    dispatch_band(p, dtype, shape->head_dim, false, (hipStream_t)stream);
+    launch(p, dtype, shape->head_dim, true, false, false, (hipStream_t)stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -814,7 +728,7 @@ int bf_attention_bwd_gqa_band(const void* d_q, const void* d_k, const void* d_v,
     p.dv = d_dv;
     p.lo = d_lo;
     p.hi = d_hi;
-    dispatch_band(p, dtype, shape->head_dim, true, (hipStream_t)stream);
+    launch(p, dtype, shape->head_dim, true, false, true, (hipStream_t)stream);
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
