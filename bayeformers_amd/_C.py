@@ -250,6 +250,16 @@ CHUNK_SYMBOLS = {
                                         ctypes.c_float, _vp]),
 }
 
+# what include/bayeformers_amd_encoder_any.h declares (the encoder attention at any sequence length): each entry takes the
+# arguments of its sibling above (bf_attention_fwd, _fwd_dropout, _fwd_rows, bf_attention_bwd, _bwd_dropout)
+ENCODER_ANY_SYMBOLS = {
+    "bf_attention_fwd_any": SYMBOLS["bf_attention_fwd"],
+    "bf_attention_fwd_any_dropout": SYMBOLS["bf_attention_fwd_dropout"],
+    "bf_attention_fwd_any_rows": SYMBOLS["bf_attention_fwd_rows"],
+    "bf_attention_bwd_any": SYMBOLS["bf_attention_bwd"],
+    "bf_attention_bwd_any_dropout": SYMBOLS["bf_attention_bwd_dropout"],
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -312,6 +322,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the cached-chunk attention entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in ENCODER_ANY_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the any-length encoder attention entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

@@ -341,7 +341,8 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     it applies (head size 64, T a multiple of 128, no mask or a key-padding mask; attention_probs_dropout runs inside the
     kernels on the Philox keep-mask of csrc/bf_philox.h); anything else goes to the
     framework's scaled-dot-product attention.  Causal calls (decoders) go to `_causal_attention`, whose kernels take any
-    sequence length; the T % 128 limit here is the encoder kernels' alone."""
+    sequence length; the T % 128 limit here is the encoder kernels' alone, and `encoder_ragged_attention()` (off by default)
+    lifts it: other lengths then run bf_attention_fwd_any / bf_attention_bwd_any, the same kernels' tail forms."""
     from transformers.integrations.sdpa_attention import sdpa_attention_forward
 
     from . import ops
@@ -361,6 +362,10 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
         return _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs)
     # attention_probs_dropout (training mode) runs inside the kernels, forward and backward, for any supported length
     usable = ops.attention_supported(query, key, value)
+    # under encoder_ragged_attention() (off by default): a length the kernels above refuse runs their tail forms
+    # (bf_attention_fwd_any and its siblings) — the same masks, the same dropout contract, inference and training alike
+    any_length = (not usable and encoder_ragged_attention_enabled() and ops.attention_any_supported(query, key, value))
+    usable = usable or any_length
     key_mask = mask_off = None
     ready = getattr(attention_mask, "_bf_key_mask", None) if attention_mask is not None else None
     if usable and ready is not None and ready.shape == (query.shape[0], query.shape[2]):
@@ -385,6 +390,10 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     scale = scaling if scaling is not None else query.shape[-1] ** -0.5
     drop = ops.Dropout(dropout, bfr.STATE.seed, bfr.dropout_call(), bfr.dropout_site(module), bfr.dropout_origin(),
                        bfr.dropout_counter()) if dropout > 0.0 else None
+    if any_length:
+        if need_grad:
+            return ops.AttentionAnyFn.apply(query, key, value, key_mask, mask_off, scale, drop), None
+        return ops.attention_forward_any(query, key, value, key_mask, scale, mask_off, drop=drop), None
     if need_grad:  # training: the same kernel, with bf_attention_bwd behind it
         return ops.AttentionFn.apply(query, key, value, key_mask, mask_off, scale, drop), None
     return ops.attention_forward(query, key, value, key_mask, scale, mask_off, drop=drop), None
@@ -963,6 +972,26 @@ def chunked_attention_enabled() -> bool:
     return _CHUNKED_ATTENTION[0] or os.environ.get("BF_CHUNKED_ATTENTION") is not None
 
 
+_ENCODER_RAGGED_ATTENTION = [False]
+
+
+def encoder_ragged_attention(enable: bool = True) -> None:
+    """Switch the any-length encoder attention kernels (bf_attention_fwd_any / bf_attention_bwd_any and their dropout and
+    rows siblings: the tail forms of the encoder kernels) on or off for this process; BF_ENCODER_RAGGED_ATTENTION in the
+    environment switches them on too.  OFF by default.  On: a non-causal attention call of head size 64 whose length is
+    no multiple of 128 (a batch padded to its longest sentence, a ViT's 197 tokens) runs them — inference, training with
+    attention_probs_dropout on the Philox keep-masks (the dropout contract of csrc/bf_philox.h then holds at every
+    length), and the [CLS] row of a pooled head's last layer — with the masks `_attention_interface` takes.  Off: such
+    a call runs the framework's scaled-dot-product attention over the dense mask, dropout from the framework's generator.
+    The switch is part of what a captured forward bakes in (graphs.baked_state): a replayed forward is captured again
+    after a flip.  profiles/encoder_ragged_attention.md says when it pays."""
+    _ENCODER_RAGGED_ATTENTION[0] = bool(enable)
+
+
+def encoder_ragged_attention_enabled() -> bool:
+    return _ENCODER_RAGGED_ATTENTION[0] or os.environ.get("BF_ENCODER_RAGGED_ATTENTION") is not None
+
+
 _POOLED_LAST_LAYER = [True]
 _POOLED_ACTIVE = threading.local()  # .layers: ids of the last layers whose head said "narrow" for the call running on this thread
 
@@ -1092,6 +1121,8 @@ def _pooled_last_layer_forward(self, hidden_states, attention_mask=None, encoder
     v = sa.value(h).view(Bt, T, H, D).transpose(1, 2)
     key_mask = mask_off = None
     rows_attention = ops.attention_supported(q, k, v)
+    rows_any = not rows_attention and encoder_ragged_attention_enabled() and ops.attention_any_supported(q, k, v)
+    rows_attention = rows_attention or rows_any
     if rows_attention and attention_mask is not None:
         ready = getattr(attention_mask, "_bf_key_mask", None)
         if ready is not None and ready.shape == (Bt, T):
@@ -1099,7 +1130,8 @@ def _pooled_last_layer_forward(self, hidden_states, attention_mask=None, encoder
         else:
             rows_attention = False
     if rows_attention:
-        a = ops.attention_forward_rows(q, k, v, key_mask, sa.scaling, mask_off, q_rows=1).view(Bt, Hd)
+        rows_fn = ops.attention_forward_rows_any if rows_any else ops.attention_forward_rows
+        a = rows_fn(q, k, v, key_mask, sa.scaling, mask_off, q_rows=1).view(Bt, Hd)
         a_row_stride = Hd
     else:
         # the attention this length or mask needs, on every query; its [CLS] rows are read where they lie

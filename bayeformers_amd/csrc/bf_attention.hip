@@ -13,6 +13,7 @@
 // Algorithmic HBM bytes: (3 reads + 1 write) * B*T*H*64 * 2 B.
 #include "bf_attention_tiles.h"
 #include "bf_philox.h"
+#include "../../include/bayeformers_amd_encoder_any.h"
 
 namespace {
 
@@ -46,8 +47,13 @@ struct AttnParams {
     // keep_bits (nullable): the decisions as one 32-bit word per (b, h, q, tile, lg), bit c * 8 + e * 4 + j — 1 bit per
     // probability, 3 % of the layer's q/k/v/o traffic — for the backward kernel, whose lanes own 4 QUERIES of one key and
     // would have to evaluate eight Philox blocks per group of eight to regenerate them.
+    // TAIL instantiation (any T >= 1, the bf_attention_fwd_any entries): with Tp = 128 * ceil(T / 128) the key tiles are
+    // those of a sequence of Tp keys, so
+    //   group index g = (((b * H + h) * T + q) * (Tp / 32) + tile * 4 + c) * 4 + lg,   keep_bits [B][H][T][Tp / 32]
+    // — at T % 128 == 0 the contract above, bit for bit.  Bits drawn for keys >= T are meaningless and unread; a query
+    // >= T stores no word.
     bf_dropout_t drop;
-    uint32_t* keep_bits;  // [B][H][T][T / 32]
+    uint32_t* keep_bits;  // [B][H][T][T / 32] (TAIL: [B][H][T][Tp / 32])
     // ROWS instantiation: only queries 0 .. q_rows - 1 (<= 16) of each (sequence, head) are computed, against all T keys;
     // out is the compact [B][q_rows][H][64]
     int q_rows;
@@ -59,7 +65,11 @@ struct AttnParams {
 // ROWS: the first q_rows <= 16 queries only — the block (wave 0, qi 0) of the full kernel that owns them, run as it is (the
 // lanes past q_rows repeat the last row and store nothing), so those rows come out bit for bit as the full kernel's; the other
 // three waves only stage the key / value tiles, which is what the launch costs.
-template <typename T, bool DROP = false, bool ROWS = false>
+// TAIL: any T >= 1 on the same tiles.  Rows of q / k / v past T - 1 re-read row T - 1 (never what lies around the tensor);
+// a key >= T scores -inf through the tile's mask row in LDS — into which the mask, when there is one, goes by bounded 4-byte
+// reads (its row b * T is 16-byte aligned only when T % 4 == 0) — so its probability is exactly 0 and the rows < T come
+// out bit for bit as the plain kernel's on a sequence padded to Tp with -inf on the pad keys; a query >= T stores nothing.
+template <typename T, bool DROP = false, bool ROWS = false, bool TAIL = false>
 __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams p) {
     static_assert(!(DROP && ROWS), "the query-subset form is an inference kernel");
     using frag = typename Mfma<T>::frag;
@@ -85,7 +95,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh)
             qf[qb_i][dh] = *reinterpret_cast<const frag*>(
-                qb + (long long)(ROWS ? min(li, p.q_rows - 1) : q0 + qb_i * 16 + li) * p.tok_stride + dh * 32 + lg * 8);
+                qb + (long long)(ROWS ? min(li, p.q_rows - 1) : (TAIL ? min(q0 + qb_i * 16 + li, p.T - 1) : q0 + qb_i * 16 + li)) *
+                         p.tok_stride + dh * 32 + lg * 8);
 
     f32x4_t o[2][4];
 #pragma unroll
@@ -100,12 +111,20 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int c = tid + 256 * i, row = c >> 3, c8 = c & 7;
-            const f32x4_t kv = *reinterpret_cast<const f32x4_t*>(kb + (long long)(key0 + row) * p.tok_stride + c8 * 8);
+            const int krow = TAIL ? min(key0 + row, p.T - 1) : key0 + row;
+            const f32x4_t kv = *reinterpret_cast<const f32x4_t*>(kb + (long long)krow * p.tok_stride + c8 * 8);
             *reinterpret_cast<f32x4_t*>(ks + row * Rows<HD>::SWZ + ((c8 ^ (row & 7)) << 4)) = kv;
-            const f32x4_t vv = *reinterpret_cast<const f32x4_t*>(vb + (long long)(key0 + row) * p.tok_stride + c8 * 8);
+            const f32x4_t vv = *reinterpret_cast<const f32x4_t*>(vb + (long long)krow * p.tok_stride + c8 * 8);
             *reinterpret_cast<f32x4_t*>(vs + row * Rows<HD>::PAD + (c8 << 4)) = vv;
         }
-        if (mask && tid < TKEY / 4)
+        // (uniform) TAIL: the last tile always has a mask row, -inf on the keys >= T
+        const bool masked = TAIL ? mask || key0 + TKEY > p.T : mask != nullptr;
+        if constexpr (TAIL) {
+            if (masked && tid < TKEY) {
+                const int key = key0 + tid;
+                ms[tid] = key < p.T ? (mask ? mask[(long long)b * p.T + key] * LOG2E : 0.f) : -INFINITY;
+            }
+        } else if (mask && tid < TKEY / 4)
             *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
                 *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
         __syncthreads();
@@ -127,7 +146,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 #pragma unroll
             for (int kbk = 0; kbk < 8; ++kbk) {
                 f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
-                if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
+                if (TAIL ? masked : mask != nullptr) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     s[kbk][j] = fmaf(s[kbk][j], p.scale_log2e, mk[j]);
@@ -155,7 +174,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
             if constexpr (DROP) {
                 // drop probabilities (the sum above saw all of them); the 1 / (1 - p) factor joins the final normalisation
                 const unsigned long long qrow = ((unsigned long long)b * p.H + h) * p.T + (q0 + qi * 16 + li);
-                const unsigned long long g0 = (qrow * (unsigned)(p.T >> 5) + (unsigned)(key0 >> 7) * 4u) * 4u + lg +
+                const unsigned tiles = TAIL ? (unsigned)(p.T + TKEY - 1) >> 7 : (unsigned)(p.T >> 7);  // Tp / 128
+                const unsigned long long g0 = (qrow * (TAIL ? tiles * 4u : (unsigned)(p.T >> 5)) + (unsigned)(key0 >> 7) * 4u) * 4u + lg +
                                               (((unsigned long long)p.drop.g0_hi << 32) | p.drop.g0_lo);
                 uint32_t word = 0;
 #pragma unroll
@@ -170,7 +190,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
                         for (int j = 0; j < 4; ++j)
                             if (!((keep >> (e * 4 + j)) & 1u)) s[2 * c + e][j] = 0.f;
                 }
-                if (p.keep_bits) p.keep_bits[(qrow * (unsigned)(p.T >> 7) + (unsigned)(key0 >> 7)) * 4u + lg] = word;
+                if (p.keep_bits && (!TAIL || q0 + qi * 16 + li < p.T))
+                    p.keep_bits[(qrow * tiles + (unsigned)(key0 >> 7)) * 4u + lg] = word;
             }
 #pragma unroll
             for (int db = 0; db < 4; ++db) o[qi][db] *= corr;
@@ -181,6 +202,8 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 #pragma unroll
                 for (int db = 0; db < 4; ++db) o[qi][db] = Mfma<T>::run(tr_frag<T, HD>(vs, c, db, li, lg), pf, o[qi][db]);
             }
+            // (TAIL: keeps the two query blocks' scores from being live at once)
+            if constexpr (TAIL) __builtin_amdgcn_sched_barrier(0);
         }
     }
 
@@ -199,6 +222,7 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
     T* ob = reinterpret_cast<T*>(p.out) + ((long long)b * p.T * p.H + h) * HD;
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
+        if (TAIL && q0 + qi * 16 + li >= p.T) continue;
         const float inv = run_sum[qi] > 0.f ? (DROP ? p.drop.inv_keep : 1.0f) / run_sum[qi] : 0.f;
         // a fully masked query has no probabilities: +inf makes exp2(score - lse) = 0 in the backward kernels
         if (p.lse && lg == 0)
@@ -214,9 +238,10 @@ __global__ __launch_bounds__(256, 3) void attention_fwd_kernel(const AttnParams 
 }
 
 // ROWS: one workgroup per (sequence, head)
-template <typename T, bool DROP, bool ROWS>
+template <typename T, bool DROP, bool ROWS, bool TAIL = false>
 void launch(const AttnParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL((attention_fwd_kernel<T, DROP, ROWS>), dim3(ROWS ? 1 : p.T / TQ, p.H, p.B), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attention_fwd_kernel<T, DROP, ROWS, TAIL>), dim3(ROWS ? 1 : (p.T + TQ - 1) / TQ, p.H, p.B), dim3(256), 0,
+                       stream, p);
 }
 
 }  // namespace
@@ -293,4 +318,85 @@ int bf_attention_fwd_dropout(const void* d_q, const void* d_k, const void* d_v, 
     const bf_dropout_t d = bf_make_dropout(p_drop, seed, call, site, first_group, d_call);
     return attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim, token_stride, scaling,
                          (hipStream_t)stream, &d, d_keep_bits);
+}
+
+// ------------------------------------------------------------------------------- any T >= 1 (bayeformers_amd_encoder_any.h)
+// T % 128 == 0: the sibling's own worker, kernel and bits.  Otherwise the TAIL instantiations; their mask reads are 4 bytes
+// wide, so the mask needs no more than its type's alignment.
+static int attention_fwd_any(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                             const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim,
+                             long long token_stride, float scaling, hipStream_t stream, const bf_dropout_t* drop = nullptr,
+                             uint32_t* d_keep_bits = nullptr, int q_rows = 0) {
+    if (T >= TKEY && T % TKEY == 0)
+        return attention_fwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim, token_stride, scaling,
+                             stream, drop, d_keep_bits, q_rows);
+    if (!d_q || !d_k || !d_v || !d_out) BF_FAIL("%s: NULL argument", what);
+    if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
+    if (head_dim != HD) BF_FAIL("%s: head size %d (only %d)", what, head_dim, HD);
+    if (B < 1 || H < 1 || T < 1) BF_FAIL("%s: B=%d, H=%d, T=%d must be positive", what, B, H, T);
+    if (T > 0x7fffff00) BF_FAIL("%s: T=%d exceeds the key index", what, T);
+    if (B > 65535 || H > 65535) BF_FAIL("%s: B or H exceeds the grid", what);
+    if (token_stride < (long long)H * HD || token_stride % 8) BF_FAIL("%s: bad token stride %lld", what, token_stride);
+    if (((uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out) & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if (d_mask && ((uintptr_t)d_mask & 3)) BF_FAIL("%s: mask must be 4-byte aligned", what);
+    if (d_lse && ((uintptr_t)d_lse & 3)) BF_FAIL("%s: lse must be 4-byte aligned", what);
+    AttnParams p;
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.mask = d_mask;
+    p.mask_off = d_mask_off;
+    p.out = d_out;
+    p.lse = d_lse;
+    p.tok_stride = token_stride;
+    p.B = B;
+    p.T = T;
+    p.H = H;
+    p.scale_log2e = scaling * LOG2E;
+    p.keep_bits = nullptr;
+    p.drop = bf_dropout_t{0, 0, 0, 0, 0, 1.0f, 0, 0, nullptr};
+    p.q_rows = q_rows;
+    const bool bf16 = dtype == BF_DT_BF16;
+    if (q_rows) {
+        if (q_rows > T) BF_FAIL("%s: q_rows=%d exceeds T=%d", what, q_rows, T);
+        if (bf16) launch<__bf16, false, true, true>(p, stream);
+        else launch<_Float16, false, true, true>(p, stream);
+    } else if (drop && drop->thresh) {
+        if (d_keep_bits && ((uintptr_t)d_keep_bits & 3)) BF_FAIL("%s: keep bits must be 4-byte aligned", what);
+        p.drop = *drop;
+        p.keep_bits = d_keep_bits;
+        if (bf16) launch<__bf16, true, false, true>(p, stream);
+        else launch<_Float16, true, false, true>(p, stream);
+    } else {
+        if (bf16) launch<__bf16, false, false, true>(p, stream);
+        else launch<_Float16, false, false, true>(p, stream);
+    }
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int bf_attention_fwd_any(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         void* d_out, float* d_lse, int dtype, int B, int T, int H, int head_dim, int64_t token_stride,
+                         float scaling, void* stream) {
+    return attention_fwd_any("bf_attention_fwd_any", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H, head_dim,
+                             token_stride, scaling, (hipStream_t)stream);
+}
+
+int bf_attention_fwd_any_rows(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                              void* d_out, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, int q_rows,
+                              float scaling, void* stream) {
+    if (q_rows < 1 || q_rows > 16) BF_FAIL("bf_attention_fwd_any_rows: q_rows=%d (1 .. 16)", q_rows);
+    return attention_fwd_any("bf_attention_fwd_any_rows", d_q, d_k, d_v, d_mask, d_mask_off, d_out, nullptr, dtype, B, T, H,
+                             head_dim, token_stride, scaling, (hipStream_t)stream, nullptr, nullptr, q_rows);
+}
+
+int bf_attention_fwd_any_dropout(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                 const uint8_t* d_mask_off, void* d_out, float* d_lse, int dtype, int B, int T, int H,
+                                 int head_dim, int64_t token_stride, float scaling, float p_drop, uint64_t seed, uint32_t call,
+                                 uint32_t site, uint64_t first_group, uint32_t* d_keep_bits, const uint32_t* d_call,
+                                 void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_fwd_any_dropout: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, seed, call, site, first_group, d_call);
+    return attention_fwd_any("bf_attention_fwd_any_dropout", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_lse, dtype, B, T, H,
+                             head_dim, token_stride, scaling, (hipStream_t)stream, &d, d_keep_bits);
 }

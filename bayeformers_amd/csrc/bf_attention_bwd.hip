@@ -17,6 +17,7 @@
 #include "bf_attention_tiles.h"
 #include "bf_device.h"
 #include "bf_philox.h"
+#include "../../include/bayeformers_amd_encoder_any.h"
 
 namespace {
 
@@ -53,7 +54,13 @@ struct BwdParams {
 };
 
 // ---------------------------------------------------------------------------------------------------- dQ (+ delta)
-template <typename T, bool DROP = false>
+// TAIL (both kernels; any T >= 1, the bf_attention_bwd_any entries; Tp = 128 * ceil(T / 128)): rows of q / k / v / o / dO
+// past T - 1 re-read row T - 1, never what lies around the tensor.  A key >= T scores -inf through the mask row in LDS (dq
+// kernel) and stores no dk / dv row (dk/dv kernel); a query >= T has lse = +inf — its probabilities are exactly 0, so it
+// adds exactly 0 to dk and dv — and stores no delta and no dq row.  The mask, lse and delta rows start at b * T or
+// (b * H + h) * T floats, 16-byte aligned only when T % 4 == 0: bounded 4-byte reads.  The keep words are the TAIL
+// forward's, [B][H][T][Tp / 32].
+template <typename T, bool DROP = false, bool TAIL = false>
 __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -80,7 +87,8 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
     float delta[2], lse[2];
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
-        const long long q = q0 + qi * 16 + li;
+        const bool live = !TAIL || q0 + qi * 16 + li < p.T;  // (TAIL: a query >= T repeats row T - 1 and stores nothing)
+        const long long q = TAIL ? min(q0 + qi * 16 + li, p.T - 1) : q0 + qi * 16 + li;
         float part = 0.f;
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh) {
@@ -93,8 +101,8 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
         part += __shfl_xor(part, 16);
         part += __shfl_xor(part, 32);
         delta[qi] = part;
-        lse[qi] = p.lse[((long long)b * p.H + h) * p.T + q];
-        if (lg == 0) p.delta[((long long)b * p.H + h) * p.T + q] = part;
+        lse[qi] = live ? p.lse[((long long)b * p.H + h) * p.T + q] : INFINITY;
+        if (lg == 0 && live) p.delta[((long long)b * p.H + h) * p.T + q] = part;
     }
 
     f32x4_t dq[2][4];
@@ -105,18 +113,32 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
 
     for (int key0 = 0; key0 < p.T; key0 += TT) {
         if (key0) __syncthreads();
-        stage<T, HD, TT, 256>(kb, p.tok_stride, key0, ks, kp, tid);
-        stage<T, HD, TT, 256>(vb, p.tok_stride, key0, vs, nullptr, tid);
-        if (mask && tid < TT / 4)
-            *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
-                *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
+        // (uniform) TAIL: the last tile always has a mask row, -inf on the keys >= T
+        const bool masked = TAIL ? mask || key0 + TT > p.T : mask != nullptr;
+        if constexpr (TAIL) {
+            stage_clamped<T, HD, TT, 256>(kb, p.tok_stride, key0, 0, p.T - 1, ks, kp, tid);
+            stage_clamped<T, HD, TT, 256>(vb, p.tok_stride, key0, 0, p.T - 1, vs, nullptr, tid);
+            if (masked && tid < TT) {
+                const int key = key0 + tid;
+                ms[tid] = key < p.T ? (mask ? mask[(long long)b * p.T + key] * LOG2E : 0.f) : -INFINITY;
+            }
+        } else {
+            stage<T, HD, TT, 256>(kb, p.tok_stride, key0, ks, kp, tid);
+            stage<T, HD, TT, 256>(vb, p.tok_stride, key0, vs, nullptr, tid);
+            if (mask && tid < TT / 4)
+                *reinterpret_cast<f32x4_t*>(ms + tid * 4) =
+                    *reinterpret_cast<const f32x4_t*>(mask + (long long)b * p.T + key0 + tid * 4) * LOG2E;
+        }
         __syncthreads();
 #pragma unroll
         for (int qi = 0; qi < 2; ++qi) {
             // DROP: the lane's 32 probabilities of this (query, key tile) are the 32 bits of ONE keep word, in the
             // forward's own layout (word (query, key tile, lg), bit 4 kbk + j) — loaded ahead of the products
             uint32_t kw = 0;
-            if constexpr (DROP)
+            if constexpr (DROP && TAIL)
+                kw = p.keep_bits[((((long long)b * p.H + h) * p.T + min(q0 + qi * 16 + li, p.T - 1)) * ((p.T + TT - 1) / TT) +
+                                  key0 / TT) * 4 + lg];
+            else if constexpr (DROP)
                 kw = p.keep_bits[((((long long)b * p.H + h) * p.T + (q0 + qi * 16 + li)) * (p.T / TT) + key0 / TT) * 4 + lg];
             // S^T and dP^T [key][query]: lane (query li, group lg) holds keys kbk*16 + 4 lg + 0..3 of each block
             f32x4_t s[8], dp[8];
@@ -132,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
 #pragma unroll
             for (int kbk = 0; kbk < 8; ++kbk) {
                 f32x4_t mk = {0.f, 0.f, 0.f, 0.f};
-                if (mask) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
+                if (TAIL ? masked : mask != nullptr) mk = *reinterpret_cast<const f32x4_t*>(ms + kbk * 16 + lg * 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float pr = __builtin_amdgcn_exp2f(fmaf(s[kbk][j], p.scale_log2e, mk[j]) - lse[qi]);
@@ -157,6 +179,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
     T* dqb = reinterpret_cast<T*>(p.dq) + (long long)b * p.T * ostride + hoff;
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
+        if (TAIL && q0 + qi * 16 + li >= p.T) continue;
         T* row = dqb + (long long)(q0 + qi * 16 + li) * ostride;
 #pragma unroll
         for (int db = 0; db < 4; ++db)
@@ -166,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq_kernel(const BwdParam
 
 // ---------------------------------------------------------------------------------------------------- dK, dV
 // 8 waves, each owning 16 keys of the workgroup's 128 (32 keys per wave need 117 spilled registers).
-template <typename T, bool DROP = false>
+template <typename T, bool DROP = false, bool TAIL = false>
 __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdParams p) {
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
@@ -197,27 +220,41 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
     const float* del_g = p.delta + ((long long)b * p.H + h) * p.T;
 
     // column operands: lane (key li, k group lg) holds 8 consecutive features of its key
+    const long long key_r = TAIL ? (key < p.T ? key : p.T - 1) : key;  // (TAIL: a key >= T repeats row T - 1 and stores nothing)
     frag kf[2], vf[2];
 #pragma unroll
     for (int dh = 0; dh < 2; ++dh) {
-        kf[dh] = *reinterpret_cast<const frag*>(kb + key * p.tok_stride + dh * 32 + lg * 8);
-        vf[dh] = *reinterpret_cast<const frag*>(vb + key * p.tok_stride + dh * 32 + lg * 8);
+        kf[dh] = *reinterpret_cast<const frag*>(kb + key_r * p.tok_stride + dh * 32 + lg * 8);
+        vf[dh] = *reinterpret_cast<const frag*>(vb + key_r * p.tok_stride + dh * 32 + lg * 8);
     }
-    const float mk = mask ? mask[(long long)b * p.T + key] * LOG2E : 0.f;
+    const float mk = mask ? mask[(long long)b * p.T + key_r] * LOG2E : 0.f;
     f32x4_t dk[4], dv[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) dk[j] = dv[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     for (int q0 = 0; q0 < p.T; q0 += TT) {
         if (q0) __syncthreads();
-        stage<T, HD, TT, 512>(qb, p.tok_stride, q0, qs, qp, tid);
-        stage<T, HD, TT, 512>(dob, ostride, q0, dos, dop, tid);
-        if (tid < TT / 4) {
-            *reinterpret_cast<f32x4_t*>(lse_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(lse_g + q0 + tid * 4);
-            *reinterpret_cast<f32x4_t*>(del_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(del_g + q0 + tid * 4);
+        if constexpr (TAIL) {
+            stage_clamped<T, HD, TT, 512>(qb, p.tok_stride, q0, 0, p.T - 1, qs, qp, tid);
+            stage_clamped<T, HD, TT, 512>(dob, ostride, q0, 0, p.T - 1, dos, dop, tid);
+            if (tid < TT) {  // a query >= T: lse = +inf, every probability exactly 0
+                const bool live = q0 + tid < p.T;
+                lse_s[tid] = live ? lse_g[q0 + tid] : INFINITY;
+                del_s[tid] = live ? del_g[q0 + tid] : 0.f;
+            }
+            if constexpr (DROP)
+                keep_s[tid] = p.keep_bits[((((long long)b * p.H + h) * p.T + min(q0 + (tid >> 2), p.T - 1)) * ((p.T + TT - 1) / TT) +
+                                           blockIdx.x) * 4 + (tid & 3)];
+        } else {
+            stage<T, HD, TT, 512>(qb, p.tok_stride, q0, qs, qp, tid);
+            stage<T, HD, TT, 512>(dob, ostride, q0, dos, dop, tid);
+            if (tid < TT / 4) {
+                *reinterpret_cast<f32x4_t*>(lse_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(lse_g + q0 + tid * 4);
+                *reinterpret_cast<f32x4_t*>(del_s + tid * 4) = *reinterpret_cast<const f32x4_t*>(del_g + q0 + tid * 4);
+            }
+            if constexpr (DROP)  // 512 words = 128 queries x 4 groups of this tile pair
+                keep_s[tid] = p.keep_bits[((((long long)b * p.H + h) * p.T + q0 + (tid >> 2)) * (p.T / TT) + blockIdx.x) * 4 + (tid & 3)];
         }
-        if constexpr (DROP)  // 512 words = 128 queries x 4 groups of this tile pair
-            keep_s[tid] = p.keep_bits[((((long long)b * p.H + h) * p.T + q0 + (tid >> 2)) * (p.T / TT) + blockIdx.x) * 4 + (tid & 3)];
         __syncthreads();
         // S and dP [query][key]: lane (key li, group lg) holds queries qbk*16 + 4 lg + 0..3 of each block
         f32x4_t s[8], dp[8];
@@ -262,6 +299,7 @@ __global__ __launch_bounds__(512, 2) void attention_bwd_dkv_kernel(const BwdPara
     }
     T* dkb = reinterpret_cast<T*>(p.dk) + (long long)b * p.T * ostride + hoff;
     T* dvb = reinterpret_cast<T*>(p.dv) + (long long)b * p.T * ostride + hoff;
+    if (TAIL && key >= p.T) return;
 #pragma unroll
     for (int db = 0; db < 4; ++db) {
         *reinterpret_cast<half4*>(dkb + key * ostride + db * 16 + lg * 4) = __builtin_convertvector(dk[db] * p.scale, half4);
@@ -486,6 +524,14 @@ void launch(const BwdParams& p, bool one_tile, hipStream_t stream) {
     }
 }
 
+// T % 128 != 0: the TAIL forms of the dq kernel and of the dk/dv kernel that reads its delta, over ceil(T / 128) tiles
+template <typename T, bool DROP>
+void launch_tail(const BwdParams& p, hipStream_t stream) {
+    const dim3 grid((p.T + TT - 1) / TT, p.H, p.B);
+    hipLaunchKernelGGL((attention_bwd_dq_kernel<T, DROP, true>), grid, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attention_bwd_dkv_kernel<T, DROP, true>), grid, dim3(512), 0, stream, p);
+}
+
 }  // namespace
 
 // the three entries' shared worker: d_keep_bits / inv_keep for the dropout entries, the rest for the column sums
@@ -575,4 +621,83 @@ int bf_attention_bwd_colsum(const void* d_q, const void* d_k, const void* d_v, c
     return attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, B, T, H,
                          head_dim, token_stride, scaling, (hipStream_t)stream, d.thresh ? d_keep_bits : nullptr, d.inv_keep,
                          samples, d_partial, d_colsum);
+}
+
+// ------------------------------------------------------------------------------- any T >= 1 (bayeformers_amd_encoder_any.h)
+// T % 128 == 0: the sibling's own worker, kernels and bits (T = 128: the one-tile kernel).  Otherwise the TAIL forms of the
+// dq and dk/dv kernels; their mask, lse and delta accesses are 4 bytes wide.
+static int attention_bwd_any(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                             const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                             float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, int B, int T, int H, int head_dim,
+                             long long token_stride, float scaling, hipStream_t stream, const uint32_t* d_keep_bits = nullptr,
+                             float inv_keep = 1.0f) {
+    if (T >= TT && T % TT == 0)
+        return attention_bwd(d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq, d_dk, d_dv, dtype, B, T, H,
+                             head_dim, token_stride, scaling, stream, d_keep_bits, inv_keep);
+    if (!d_q || !d_k || !d_v || !d_out || !d_dout || !d_lse || !d_delta || !d_dq || !d_dk || !d_dv)
+        BF_FAIL("%s: NULL argument", what);
+    if (dtype != BF_DT_BF16 && dtype != BF_DT_F16) BF_FAIL("%s: dtype must be bf16 or fp16", what);
+    if (head_dim != HD) BF_FAIL("%s: head size %d (only %d)", what, head_dim, HD);
+    if (B < 1 || H < 1 || T < 1) BF_FAIL("%s: B=%d, H=%d, T=%d must be positive", what, B, H, T);
+    if (T > 0x7fffff00) BF_FAIL("%s: T=%d exceeds the key index", what, T);
+    if (B > 65535 || H > 65535) BF_FAIL("%s: B or H exceeds the grid", what);
+    if (token_stride < (long long)H * HD || token_stride % 8) BF_FAIL("%s: bad token stride %lld", what, token_stride);
+    const uintptr_t al = (uintptr_t)d_q | (uintptr_t)d_k | (uintptr_t)d_v | (uintptr_t)d_out | (uintptr_t)d_dout |
+                         (uintptr_t)d_dq | (uintptr_t)d_dk | (uintptr_t)d_dv;
+    if (al & 15) BF_FAIL("%s: pointers must be 16-byte aligned", what);
+    if (((uintptr_t)d_lse | (uintptr_t)d_delta) & 3) BF_FAIL("%s: lse and delta must be 4-byte aligned", what);
+    if (d_mask && ((uintptr_t)d_mask & 3)) BF_FAIL("%s: mask must be 4-byte aligned", what);
+    if (d_keep_bits && ((uintptr_t)d_keep_bits & 3)) BF_FAIL("%s: keep bits must be 4-byte aligned", what);
+    BwdParams p;
+    p.q = d_q;
+    p.k = d_k;
+    p.v = d_v;
+    p.mask = d_mask;
+    p.mask_off = d_mask_off;
+    p.o = d_out;
+    p.dout = d_dout;
+    p.lse = d_lse;
+    p.delta = d_delta;
+    p.dq = d_dq;
+    p.dk = d_dk;
+    p.dv = d_dv;
+    p.tok_stride = token_stride;
+    p.B = B;
+    p.T = T;
+    p.H = H;
+    p.scale = scaling;
+    p.scale_log2e = scaling * LOG2E;
+    p.keep_bits = d_keep_bits;
+    p.inv_keep = inv_keep;
+    p.cs_partial = nullptr;
+    if (dtype == BF_DT_BF16) {
+        if (d_keep_bits) launch_tail<__bf16, true>(p, stream);
+        else launch_tail<__bf16, false>(p, stream);
+    } else {
+        if (d_keep_bits) launch_tail<_Float16, true>(p, stream);
+        else launch_tail<_Float16, false>(p, stream);
+    }
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int bf_attention_bwd_any(const void* d_q, const void* d_k, const void* d_v, const float* d_mask, const uint8_t* d_mask_off,
+                         const void* d_out, const void* d_dout, const float* d_lse, float* d_delta, void* d_dq, void* d_dk,
+                         void* d_dv, int dtype, int B, int T, int H, int head_dim, int64_t token_stride, float scaling,
+                         void* stream) {
+    return attention_bwd_any("bf_attention_bwd_any", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta, d_dq,
+                             d_dk, d_dv, dtype, B, T, H, head_dim, token_stride, scaling, (hipStream_t)stream);
+}
+
+int bf_attention_bwd_any_dropout(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                 const uint8_t* d_mask_off, const void* d_out, const void* d_dout, const float* d_lse,
+                                 float* d_delta, void* d_dq, void* d_dk, void* d_dv, int dtype, int B, int T, int H,
+                                 int head_dim, int64_t token_stride, float scaling, float p_drop, const uint32_t* d_keep_bits,
+                                 void* stream) {
+    if (!(p_drop >= 0.f) || !(p_drop < 1.f)) BF_FAIL("bf_attention_bwd_any_dropout: p must be in [0, 1) (got %g)", p_drop);
+    const bf_dropout_t d = bf_make_dropout(p_drop, 0, 0, 0);
+    if (d.thresh && !d_keep_bits) BF_FAIL("bf_attention_bwd_any_dropout: the forward's keep bits are needed");
+    return attention_bwd_any("bf_attention_bwd_any_dropout", d_q, d_k, d_v, d_mask, d_mask_off, d_out, d_dout, d_lse, d_delta,
+                             d_dq, d_dk, d_dv, dtype, B, T, H, head_dim, token_stride, scaling, (hipStream_t)stream,
+                             d.thresh ? d_keep_bits : nullptr, d.inv_keep);
 }

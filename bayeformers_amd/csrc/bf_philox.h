@@ -95,6 +95,11 @@ static inline void bf_normal4_host(uint64_t group, uint32_t sample, uint32_t str
 // forward (one number per bnn.Model forward), `site` the module the dropout belongs to.  The group index is GLOBAL over the
 // step's Monte-Carlo samples: a kernel that sees the slabs of samples [s0, s0 + S_local) numbers its groups from
 // first_group = s0 * (groups per sample) — masks are a function of the global sample, like epsilon.
+// Encoder attention at any length (bf_attention_fwd_any_dropout, T >= 1, Tp = 128 * ceil(T / 128)): the group of
+// probability (b, h, q, key) is ((((b*H + h)*T + q) * (Tp/32)) + (key/128)*4 + c) * 4 + lg — the key tiles of a sequence
+// of Tp keys under T real queries — so a (sequence, head) has T * (Tp/32) * 4 groups and a sample's first group is
+// s0 * (sequences per sample) * H * T * (Tp/32) * 4.  At T % 128 == 0 this is bf_attention_fwd_dropout's numbering, bit for
+// bit; the fields drawn for keys >= T are meaningless and unread.
 #define BF_DROPOUT_STREAM 0x80000000u
 
 // ---- generation contract --------------------------------------------------------------------------------------------

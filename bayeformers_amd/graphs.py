@@ -58,27 +58,29 @@ def plan_key(model):
 
 def baked_state(model):
     """The host state a captured forward of `model` bakes into its launches."""
-    from . import (chunked_attention_enabled, packed_attention_enabled, pooled_last_layer_enabled,
-                   ragged_attention_enabled, softcap_attention_enabled)
+    from . import (chunked_attention_enabled, encoder_ragged_attention_enabled, packed_attention_enabled,
+                   pooled_last_layer_enabled, ragged_attention_enabled, softcap_attention_enabled)
 
     plan = getattr(model, "_plan", None)
     # (the last entries: whether a pooled head's last encoder layer may run on the [CLS] rows alone, and whether causal
     # attention of a length that is no multiple of 128 runs the kernels or the framework's, and whether soft-capped
     # attention runs the soft-cap kernels, and whether packed sequences run the band kernels, and whether a cached chunk
-    # runs the chunk kernels — other sets of launches)
+    # runs the chunk kernels, and whether encoder attention of such a length runs the any-length kernels — other sets of
+    # launches)
     return (bfr.STATE.seed, bfr.get_compute_dtype(), plan, (plan.key if plan is not None else None), bfr.STATE.stale_epoch,
             pooled_last_layer_enabled(), ragged_attention_enabled(), softcap_attention_enabled(), packed_attention_enabled(),
-            chunked_attention_enabled())
+            chunked_attention_enabled(), encoder_ragged_attention_enabled())
 
 
 def still_valid(model, baked) -> bool:
     from . import ops
 
     ops.refresh_stale_epoch()  # (a replay whose kernels found a stale prior bumped the library's counter)
-    seed, cdt, plan, key, epoch, pooled, ragged, softcap, packed, chunked = baked
+    seed, cdt, plan, key, epoch, pooled, ragged, softcap, packed, chunked, encoder_ragged = baked
     now = baked_state(model)
     if not (now[0] == seed and now[1] == cdt and now[2] is plan and now[4] == epoch and now[5] == pooled
-            and now[6] == ragged and now[7] == softcap and now[8] == packed and now[9] == chunked):
+            and now[6] == ragged and now[7] == softcap and now[8] == packed and now[9] == chunked
+            and now[10] == encoder_ragged):
         return False
     # the plan's key as it would be built now: a parameter whose storage moved (`p.data = ...`, `.to()`) voids the capture
     return plan is None or (plan.alias_valid() and plan_key(model) == key)

@@ -1806,6 +1806,129 @@ class AttentionFn(torch.autograd.Function):
         return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None
 
 
+# launches of the any-length encoder attention entries (include/bayeformers_amd_encoder_any.h) from this process: "fwd" of
+# bf_attention_fwd_any / bf_attention_fwd_any_dropout, "bwd" of bf_attention_bwd_any / bf_attention_bwd_any_dropout, "rows"
+# of bf_attention_fwd_any_rows
+ENCODER_ANY_CALLS = {"fwd": 0, "bwd": 0, "rows": 0}
+
+
+def attention_any_supported(q: Tensor, k: Tensor, v: Tensor) -> bool:
+    """attention_supported's non-causal checks without the conditions on T (any T >= 1): what the bf_attention_*_any
+    entries take — [B, H, T, 64] views of contiguous [B, T, H, 64] projections, bf16 or fp16, 16-byte aligned."""
+    if not (q.is_cuda and q.dtype in (torch.bfloat16, torch.float16) and k.dtype == q.dtype and v.dtype == q.dtype):
+        return False
+    if q.dim() != 4 or q.shape != k.shape or q.shape != v.shape:
+        return False
+    B, H, T, D = q.shape
+    if D != 64 or T < 1 or B < 1 or H < 1 or B > 65535 or H > 65535:
+        return False
+    st = (T * H * D, D, H * D, 1)  # BHTD view of a contiguous [B, T, H, D] tensor
+    return all(t.stride() == st and t.data_ptr() % 16 == 0 for t in (q, k, v))
+
+
+def _keep_words_any(T: int) -> int:
+    """Keep words per query of the any-length entries: Tp / 32 with Tp = T rounded up to the key tile of 128."""
+    return 4 * ((T + 127) // 128)
+
+
+def attention_forward_any(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
+                          mask_off: Optional[Tensor] = None, want_lse: bool = False, drop: Optional[Dropout] = None,
+                          want_keep: bool = False):
+    """attention_forward at any sequence length T >= 1 (bf_attention_fwd_any / bf_attention_fwd_any_dropout): operands as
+    attention_any_supported describes them, key_mask additive fp32 [B, T] contiguous.  With want_keep the dropout
+    decisions come back as [B, H, T, Tp/32] int32 words, Tp = T rounded up to 128.  At T % 128 == 0 the entries launch
+    attention_forward's kernels: the same bits."""
+    B, H, T, D = q.shape
+    out = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((B, H, T), dtype=torch.float32, device=q.device) if want_lse else None
+    mask_ptr = key_mask.data_ptr() if key_mask is not None else None
+    off_ptr = mask_off.data_ptr() if mask_off is not None else None
+    lse_ptr = lse.data_ptr() if lse is not None else None
+    if drop is not None and drop.p > 0.0:
+        words = _keep_words_any(T)
+        keep = torch.empty((B, H, T, words), dtype=torch.int32, device=q.device) if want_keep else None
+        _C.check(_C.lib().bf_attention_fwd_any_dropout(q.data_ptr(), k.data_ptr(), v.data_ptr(), mask_ptr, off_ptr,
+                                                       out.data_ptr(), lse_ptr, _TORCH2BF[q.dtype], B, T, H, D, H * D,
+                                                       float(scaling), drop.p, drop.seed, drop.call, drop.site,
+                                                       drop.first_group(B, H * T * words * 4),
+                                                       keep.data_ptr() if keep is not None else None, drop.d_call,
+                                                       _stream_ptr()), "bf_attention_fwd_any_dropout")
+        ENCODER_ANY_CALLS["fwd"] += 1
+        res = (out,) + ((lse,) if want_lse else ()) + ((keep,) if want_keep else ())
+        return res if len(res) > 1 else out
+    _C.check(_C.lib().bf_attention_fwd_any(q.data_ptr(), k.data_ptr(), v.data_ptr(), mask_ptr, off_ptr, out.data_ptr(),
+                                           lse_ptr, _TORCH2BF[q.dtype], B, T, H, D, H * D, float(scaling), _stream_ptr()),
+             "bf_attention_fwd_any")
+    ENCODER_ANY_CALLS["fwd"] += 1
+    return (out, lse) if want_lse else out
+
+
+def attention_forward_rows_any(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], scaling: float,
+                               mask_off: Optional[Tensor] = None, q_rows: int = 1) -> Tensor:
+    """attention_forward_rows at any sequence length T >= q_rows (bf_attention_fwd_any_rows): the compact
+    [B, q_rows, H, 64], bit for bit rows 0 .. q_rows - 1 of attention_forward_any's output."""
+    B, H, T, D = q.shape
+    if not 1 <= int(q_rows) <= min(ATTENTION_MAX_Q_ROWS, T):
+        raise _C.BayeFormersAMDError(f"attention_forward_rows_any: q_rows={q_rows} (1 .. {min(ATTENTION_MAX_Q_ROWS, T)})")
+    out = torch.empty((B, int(q_rows), H, D), dtype=q.dtype, device=q.device)
+    _C.check(_C.lib().bf_attention_fwd_any_rows(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                                key_mask.data_ptr() if key_mask is not None else None,
+                                                mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(),
+                                                _TORCH2BF[q.dtype], B, T, H, D, H * D, int(q_rows), float(scaling),
+                                                _stream_ptr()), "bf_attention_fwd_any_rows")
+    ENCODER_ANY_CALLS["rows"] += 1
+    return out
+
+
+def attention_backward_any(q: Tensor, k: Tensor, v: Tensor, key_mask: Optional[Tensor], mask_off: Optional[Tensor],
+                           out: Tensor, grad_out: Tensor, lse: Tensor, scaling: float, drop_p: float = 0.0,
+                           keep: Optional[Tensor] = None):
+    """Gradients of attention_forward_any (bf_attention_bwd_any / bf_attention_bwd_any_dropout).  Returns (dq, dk, dv), each
+    [B, T, H, 64] contiguous; keep: the forward's [B, H, T, Tp/32] words.  No column-sum fold: that is a T = 128 launch."""
+    B, H, T, D = q.shape
+    go = grad_out if (grad_out.dtype == q.dtype and grad_out.is_contiguous()) else grad_out.to(q.dtype).contiguous()
+    dqkv = torch.empty((3, B, T, H, D), dtype=q.dtype, device=q.device)
+    dq, dk, dv = dqkv[0], dqkv[1], dqkv[2]
+    delta = torch.empty((B, H, T), dtype=torch.float32, device=q.device)
+    head = (q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+            mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), go.data_ptr(), lse.data_ptr(),
+            delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), _TORCH2BF[q.dtype], B, T, H, D, H * D,
+            float(scaling))
+    if drop_p > 0.0:
+        _C.check(_C.lib().bf_attention_bwd_any_dropout(*head, float(drop_p), keep.data_ptr(), _stream_ptr()),
+                 "bf_attention_bwd_any_dropout")
+    else:
+        _C.check(_C.lib().bf_attention_bwd_any(*head, _stream_ptr()), "bf_attention_bwd_any")
+    ENCODER_ANY_CALLS["bwd"] += 1
+    return dq, dk, dv
+
+
+class AttentionAnyFn(torch.autograd.Function):
+    """AttentionFn on the any-length entries: attention_forward_any with attention_backward_any as its backward; keeps
+    q, k, v, the output, one fp32 row statistic per query and, with dropout, the [B, H, T, Tp/32] keep words."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_mask, mask_off, scaling, drop=None):
+        ctx.drop_p = drop.p if drop is not None else 0.0
+        if ctx.drop_p > 0.0:
+            out, lse, keep = attention_forward_any(q, k, v, key_mask, scaling, mask_off, want_lse=True, drop=drop,
+                                                   want_keep=True)
+            ctx.save_for_backward(q, k, v, out, lse, keep)
+        else:
+            out, lse = attention_forward_any(q, k, v, key_mask, scaling, mask_off, want_lse=True)
+            ctx.save_for_backward(q, k, v, out, lse)
+        ctx.key_mask, ctx.mask_off, ctx.scaling = key_mask, mask_off, scaling
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q, k, v, out, lse = ctx.saved_tensors[:5]
+        keep = ctx.saved_tensors[5] if ctx.drop_p > 0.0 else None
+        dq, dk, dv = attention_backward_any(q, k, v, ctx.key_mask, ctx.mask_off, out, grad_out, lse, ctx.scaling, ctx.drop_p,
+                                            keep)
+        return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None, None, None, None
+
+
 def add_layernorm_backward(x: Tensor, residual: Optional[Tensor], gamma: Tensor, grad_out: Tensor, eps: float,
                            drop: Optional[Dropout] = None, grad_out2: Optional[Tensor] = None):
     """Gradients of add_layernorm (bf_add_layernorm_bwd): returns (dz, dgamma, dbeta); dz is the gradient of both x
