@@ -260,6 +260,17 @@ ENCODER_ANY_SYMBOLS = {
     "bf_attention_bwd_any_dropout": SYMBOLS["bf_attention_bwd_dropout"],
 }
 
+# what include/bayeformers_amd_lora.h declares (the rank-r terms of bnn.LoRALinear): forward (x, A_s, B, y, h, scale, dtype, S, M,
+# N, K, r, workspace, bytes, stream), backward (x, dy, A_s, B, h, dx, dA, dB, scale, dtype, ...), and the reduction of dA to
+# (dmu, drho) with bf_param_grad_table's arithmetic
+LORA_SYMBOLS = {
+    "bf_lora_fwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "bf_lora_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_lora_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "bf_lora_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_lora_reduce_da": (_i, [_vp, _vp, _u64, _i, _u64, _u32, _u32, _vp, _vp, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -330,6 +341,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the any-length encoder attention entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in LORA_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the Bayesian LoRA entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

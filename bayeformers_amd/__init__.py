@@ -26,7 +26,7 @@ from .plan import kept_weight_bytes, kv_cache_bytes  # noqa: F401
 from .random import (get_compute_dtype, manual_seed, set_compute_dtype, set_kl_gradient,  # noqa: F401
                      use_device_counter)
 
-__all__ = ["to_bayesian", "invalidate_caches", "fuse_activations", "fuse_residual_layernorm", "fuse_shared_inputs", "fuse_ffn_pairs", "fuse_attention", "fuse_embeddings", "fuse_decoder_blocks", "enable_embedding", "nn", "manual_seed", "set_compute_dtype", "get_compute_dtype",
+__all__ = ["to_bayesian", "to_bayesian_lora", "lora_state_dict", "invalidate_caches", "fuse_activations", "fuse_residual_layernorm", "fuse_shared_inputs", "fuse_ffn_pairs", "fuse_attention", "fuse_embeddings", "fuse_decoder_blocks", "enable_embedding", "nn", "manual_seed", "set_compute_dtype", "get_compute_dtype",
            "use_device_counter", "set_kl_gradient", "kept_weight_bytes", "kv_cache_bytes"]
 
 
@@ -50,6 +50,58 @@ def to_bayesian(model: torch.nn.Module, initialization: Optional[Initialization]
     new_model = deepcopy(model)
     swap(new_model)
     return Model(model=new_model)
+
+
+LORA_TARGET_MODULES = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+
+
+def to_bayesian_lora(model: torch.nn.Module, r: int = 16, alpha: float = 32, target_modules=LORA_TARGET_MODULES,
+                     initialization: Optional[Initialization] = DEFAULT_UNIFORM,
+                     prior: Optional[Parameter] = DEFAULT_SCALED_GAUSSIAN_MIXTURE) -> Model:
+    """Deep-copy `model`, put a Bayesian rank-`r` adapter (bnn.LoRALinear: a Gaussian posterior on the LoRA A factor, a plain
+    B factor starting at zero, scale alpha / r) on every child whose exact class is nn.Linear and whose name ends with one of
+    `target_modules`, freeze everything else and wrap the result in `bnn.Model`.  The pretrained weights stay where they are,
+    shared by all Monte-Carlo samples; a freshly converted model computes the pretrained function.  Only `lora_A.mu`,
+    `lora_A.rho` and `lora_B` of the adapters require gradients afterwards (`lora_state_dict` returns exactly those).
+
+    Not covered: LoRA dropout, a Bayesian B, DoRA / rsLoRA scaling, adapters on nn.Embedding or fused-QKV modules, merging
+    adapters into the base."""
+    if isinstance(r, bool) or not isinstance(r, int) or r < 1:
+        raise ValueError(f"to_bayesian_lora: r={r!r} (a positive int)")
+    targets = (target_modules,) if isinstance(target_modules, str) else tuple(target_modules)
+    swapped = []
+
+    def swap(module):
+        for name, child in module.named_children():
+            if child.__class__ is torch.nn.Linear and name.endswith(targets):
+                setattr(module, name, nn.LoRALinear.from_frequentist(child, r, alpha, initialization, prior))
+                swapped.append(name)
+            else:
+                swap(child)
+
+    new_model = deepcopy(model)
+    swap(new_model)
+    if not swapped:
+        raise ValueError(f"to_bayesian_lora: no nn.Linear child is named like one of target_modules={targets}")
+    adapters = {id(p) for m in new_model.modules() if isinstance(m, nn.LoRALinear)
+                for p in (m.lora_A.mu, m.lora_A.rho, m.lora_B)}
+    for p in new_model.parameters():
+        p.requires_grad = id(p) in adapters
+    return Model(model=new_model)
+
+
+def lora_state_dict(model: torch.nn.Module) -> dict:
+    """The adapter tensors of a `to_bayesian_lora` model alone — `<layer>.lora_A.mu`, `<layer>.lora_A.rho`, `<layer>.lora_B`
+    under their state-dict keys (detached, not copied): what a fine-tuning run has to save.  Load it back with
+    `model.load_state_dict(sd, strict=False)`."""
+    out = {}
+    for name, m in model.named_modules():
+        if isinstance(m, nn.LoRALinear):
+            prefix = name + "." if name else ""
+            out[prefix + "lora_A.mu"] = m.lora_A.mu.detach()
+            out[prefix + "lora_A.rho"] = m.lora_A.rho.detach()
+            out[prefix + "lora_B"] = m.lora_B.detach()
+    return out
 
 
 def enable_embedding(enable: bool = True) -> None:

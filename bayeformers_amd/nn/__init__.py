@@ -8,12 +8,13 @@ import torch.nn as _torch_nn
 
 from .layers.embedding import Embedding
 from .layers.linear import Linear
+from .layers.lora import LoRALinear
 from .model import Model, is_module_bayesian
 from .parameters.base import NoneParameter, Parameter
 from .parameters.gaussian import DEFAULT_SCALED_GAUSSIAN_MIXTURE, Gaussian, ScaledGaussianMixture
 from .parameters.initializations import DEFAULT_UNIFORM, Initialization, Uniform
 
-__all__ = ["Linear", "Embedding", "Model", "is_module_bayesian", "Parameter", "NoneParameter", "Gaussian",
+__all__ = ["Linear", "LoRALinear", "Embedding", "Model", "is_module_bayesian", "Parameter", "NoneParameter", "Gaussian",
            "ScaledGaussianMixture", "DEFAULT_SCALED_GAUSSIAN_MIXTURE", "Initialization", "Uniform", "DEFAULT_UNIFORM",
            "TORCH2BAYE"]
 

@@ -53,6 +53,16 @@ class KernelLayer(Module):
         self._parameters["log_prior"].data = v[0]
         self._parameters["log_variational_posterior"].data = v[1]
 
+    def gaussians(self):
+        """(Gaussian posterior, its prior, Philox stream) of every sampled tensor of the layer, in stream order: what the
+        model-level code (device lookup, the KL gradient) needs to know of a kernel layer.  Default: `weight`, then `bias`
+        when it is a Gaussian (bnn.Linear, bnn.Embedding)."""
+        from ..parameters.gaussian import Gaussian
+
+        yield self.weight, self.weight_prior, 2 * self.layer_id
+        if isinstance(self.bias, Gaussian):
+            yield self.bias, self.bias_prior, 2 * self.layer_id + 1
+
     @property
     def log_prob_samples(self) -> Optional[Tensor]:
         """[S, 2] float64 {log_prior, log_variational_posterior} of each sample of the last forward."""

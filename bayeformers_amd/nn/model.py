@@ -96,6 +96,8 @@ class _KeptWeights:
         self.S, self.cdt = S, cdt
         self.plan: Optional[SamplePlan] = None
         self.watch = []  # (tensor, data_ptr, _version) of every mu / rho the samples were drawn from
+        self.ready = False  # the block's first forward has run prepare()
+        self.lora = {}  # id(bnn.LoRALinear) -> its 16-bit A_s [S, r, K], drawn by the layer's first forward of the block
 
     def prepare(self, model, layers, ctx) -> SamplePlan:
         """The plan of the block; in its first forward also the one sampling launch over all groups."""
@@ -105,7 +107,7 @@ class _KeptWeights:
                                f"with S={S} at {cdt}")
         if torch.is_grad_enabled() or model.training:
             raise RuntimeError(f"pinned_samples({self.mode}): forwards inside must run in eval mode without gradients")
-        if self.plan is not None:
+        if self.ready:
             for t, ptr, ver in self.watch:
                 if t.data_ptr() != ptr or t._version != ver:
                     raise RuntimeError(f"pinned_samples({self.mode}): a posterior mu / rho changed inside the block; "
@@ -115,6 +117,9 @@ class _KeptWeights:
         pl = [l for _, l in linears]
         shared = tuple(sorted({id(l._shared_input): l._shared_input for l in pl
                                if l._shared_input is not None}.values(), key=lambda t: t[0].layer_id))
+        self.ready = True
+        if not pl:  # only LoRA layers are Bayesian: nothing to plan, each keeps its own A_s (lora_sample)
+            return None
         self.plan = self._draw(pl, [i for i, _ in linears], shared, ctx)
         from .parameters.gaussian import Gaussian
 
@@ -123,6 +128,15 @@ class _KeptWeights:
                 if isinstance(g, Gaussian):
                     self.watch += [(t, t.data_ptr(), t._version) for t in (g.mu, g.rho)]
         return self.plan
+
+    def lora_sample(self, layer, S: int, seed: int, base: int, slot: Tensor, x_dtype: torch.dtype) -> Tensor:
+        """The kept A_s of a bnn.LoRALinear: drawn (with its log-probs, into `slot`) at the layer's first forward of the block,
+        read by every later one.  Always the 16-bit (or fp32-compute) draw, never FP8: the tensor is tiny."""
+        a_s = self.lora.get(id(layer))
+        if a_s is None:
+            a_s = self.lora[id(layer)] = layer.sample_a(S, seed, base, slot, x_dtype)
+            self.watch += [(t, t.data_ptr(), t._version) for t in (layer.lora_A.mu, layer.lora_A.rho)]
+        return a_s
 
     def _draw(self, pl, index, shared, ctx) -> SamplePlan:
         plan = SamplePlan(pl, self.S, self.cdt, pl[0].weight.mu.device, index=index, shared=shared, keep=True)
@@ -203,16 +217,12 @@ class _KLFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         from .. import ops
-        from .parameters.gaussian import Gaussian
 
         g = g.to(torch.float64).contiguous()
         grads = []
         with bfr.counter_override(ctx.counter):
             for layer in ctx.model.fused_children():
-                pairs = [(layer.weight, layer.weight_prior, 2 * layer.layer_id)]
-                if isinstance(layer.bias, Gaussian):
-                    pairs.append((layer.bias, layer.bias_prior, 2 * layer.layer_id + 1))
-                for gauss, prior, sid in pairs:
+                for gauss, prior, sid in layer.gaussians():
                     dmu, drho = ops.kl_grad(gauss, prior, sid, ctx.S, ctx.seed, ctx.base, g, gauss.mu.requires_grad)
                     grads += [dmu, drho if gauss.rho.requires_grad else None]
         return (None, None, None, None, None, None) + tuple(grads)
@@ -272,7 +282,7 @@ class Model(Module):
         ops._COLSUM_OFFERS.clear()  # (column sums a backward pass offered and nobody took)
         slots = {}
         if layers:
-            dev = layers[0].weight.mu.device
+            dev = next(layers[0].gaussians())[0].mu.device
             buf = self._lp_buf
             if buf is None or buf.shape[0] != len(layers) or buf.shape[1] != S or buf.device != dev:
                 with torch.inference_mode(False):  # (kept across forwards, written in place by forwards of any mode)
@@ -294,7 +304,7 @@ class Model(Module):
                 key = SamplePlan.make_key(pl, S, cdt, shared)
                 if (self._plan is None or self._plan.key != key or not self._plan.alias_valid()
                         or self._plan.epoch != bfr.STATE.stale_epoch):
-                    self._plan = SamplePlan(pl, S, cdt, layers[0].weight.mu.device, index=[i for i, _ in planned],
+                    self._plan = SamplePlan(pl, S, cdt, pl[0].weight.mu.device, index=[i for i, _ in planned],
                                             shared=shared)
                 plan = self._plan
         if plan is None and kept is None:
@@ -422,10 +432,12 @@ class Model(Module):
         if need > limit:
             raise ValueError(f"pinned_samples({mode}): the kept samples need {need} bytes (S={S}, {cdt}), "
                              f"above max_bytes={limit}")
+        from .layers.lora import LoRALinear
+
         linears = [l for l in self.fused_children() if isinstance(l, Linear)]
-        if not linears:
+        if not linears and not any(isinstance(l, LoRALinear) for l in self.fused_children()):
             raise ValueError(f"pinned_samples({mode}): the model has no Bayesian Linear layer")
-        if not SamplePlan.plannable(linears):
+        if linears and not SamplePlan.plannable(linears):
             raise ValueError(f"pinned_samples({mode}) needs every Bayesian Linear on one ROCm device, with built-in "
                              "priors and the global compute dtype (SamplePlan.plannable)")
         return (_KeptFp8Weights if fp8 else _KeptWeights)(S, cdt)
@@ -500,13 +512,10 @@ class Model(Module):
         return self._sum(1, "log_variational_posterior")
 
     def _kl_params(self):
-        from .parameters.gaussian import Gaussian
-
         params = []
         for layer in self.fused_children():
-            params += [layer.weight.mu, layer.weight.rho]
-            if isinstance(layer.bias, Gaussian):
-                params += [layer.bias.mu, layer.bias.rho]
+            for gauss, _, _ in layer.gaussians():
+                params += [gauss.mu, gauss.rho]
         return params
 
     def log_prob_samples(self) -> Tensor:

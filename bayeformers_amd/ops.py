@@ -2700,3 +2700,166 @@ def predictive_finish(partial: Tensor, R: int, C: int, S_total: int, labels: Opt
         partial.data_ptr(), int(R), int(C), int(S_total), labels.data_ptr() if labels is not None else None,
         int(ignore_index), ctypes.byref(o), ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_mc_predictive_finish")
     return out
+
+
+# ------------------------------------------------------------------------------------------------- Bayesian LoRA
+# bnn.LoRALinear (include/bayeformers_amd_lora.h): y[s] = x[s] W0^T + b0 + scale * (x[s] A_s^T) B^T on a frozen base.  The
+# base products run on the GEMMs above with S = 1 — one stream over W0 for all samples — and bf_lora_fwd / bf_lora_bwd add the
+# rank-r terms in place.  What lora_supported() refuses runs the same formula as framework ops on the same A_s.
+LORA_MAX_RANK = 64
+LORA_CALLS = {"fwd": 0, "bwd": 0, "composite_fwd": 0, "composite_bwd": 0, "base_skinny": 0, "base_gemm": 0}
+
+
+def lora_kernel_wins(r: int, backward: bool) -> bool:
+    """Where the kernels beat the framework composite on one MI355X (profiles/bayesian_lora.md; bf16, S 4, 4096 / 11008-wide
+    layers, 8 .. 16384 rows, r 16 and 64): bf_lora_fwd at r = 16 (0.62-0.93x the composite's time from 4096 rows on, a tie
+    within the spread below), not at r = 64 (1.3-2.0x from 4096 rows on); bf_lora_bwd nowhere yet (1.7-7.0x from 4096 rows on:
+    its row contractions gather their operands element by element).  Ranks between the two measured ones go with the nearer."""
+    return not backward and r <= 32
+
+
+def lora_supported(dtype: torch.dtype, N: int, K: int, r: int, *tensors: Tensor, backward: Optional[bool] = None) -> bool:
+    """Do bf_lora_fwd / bf_lora_bwd take this layer?  16-bit compute, K % 8 == 0, N % 8 == 0, r % 8 == 0 with
+    8 <= r <= LORA_MAX_RANK; `tensors` (optional): the operands, each on a ROCm device, contiguous and 16-byte aligned.
+    backward = False / True: also whether that direction's kernel is the faster route (lora_kernel_wins) — what
+    lora_forward / lora_backward ask; None: the kernels' class alone.
+    The one predicate that routes a call to the kernels or to the framework composite."""
+    if dtype not in (torch.bfloat16, torch.float16) or K % 8 or N % 8 or r % 8 or not 8 <= r <= LORA_MAX_RANK:
+        return False
+    if backward is not None and not lora_kernel_wins(r, backward):
+        return False
+    return all(t is None or (t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+def _lora_dims(x: Tensor, a_s: Tensor, b: Tensor, S: int):
+    r, K = a_s.shape[-2], a_s.shape[-1]
+    N = b.shape[0]
+    rows = x.numel() // K
+    if a_s.shape[0] != S or b.shape[1] != r or rows % S:
+        raise _C.BayeFormersAMDError(f"lora: x {tuple(x.shape)}, A_s {tuple(a_s.shape)}, B {tuple(b.shape)} do not fit S={S}")
+    return rows // S, N, K, r
+
+
+def lora_fwd(x: Tensor, a_s: Tensor, b: Tensor, y: Optional[Tensor], scale: float, S: int) -> Tensor:
+    """h = x A_s^T (returned, [S*M, r] of x's dtype) and y += scale * h B^T in place (bf_lora_fwd).  x: [S*M, K] 16-bit,
+    a_s: [S, r, K] of the same dtype, b: [N, r] fp32, y: [S*M, N] of x's dtype or None.  Refusals raise."""
+    _require_device(x, "x")
+    M, N, K, r = _lora_dims(x, a_s, b, S)
+    if a_s.dtype != x.dtype or b.dtype != torch.float32 or (y is not None and y.dtype != x.dtype):
+        raise _C.BayeFormersAMDError("lora_fwd: A_s and y must have x's dtype, B must be fp32")
+    if not all(t is None or t.is_contiguous() for t in (x, a_s, b, y)):
+        raise _C.BayeFormersAMDError("lora_fwd: operands must be contiguous")
+    h = torch.empty((S * M, r), dtype=x.dtype, device=x.device)
+    _C.check(_C.lib().bf_lora_fwd(x.data_ptr(), a_s.data_ptr(), b.data_ptr(), y.data_ptr() if y is not None else None,
+                                  h.data_ptr(), float(scale), _TORCH2BF.get(x.dtype, -1), S, M, N, K, r, None, 0, _stream_ptr()),
+             "bf_lora_fwd")
+    LORA_CALLS["fwd"] += 1
+    return h
+
+
+def lora_bwd(x: Tensor, dy: Tensor, a_s: Tensor, b: Tensor, h: Optional[Tensor], dx: Optional[Tensor], scale: float, S: int,
+             need_db: bool = True):
+    """(dA [S, r, K] fp32, dB [N, r] fp32 or None) and dx += scale * (dy B) A_s in place (bf_lora_bwd).  x: [S*M, K], dy: [S*M, N],
+    h: what lora_fwd returned (needed for dB), dx: [S*M, K] holding dy W0, or None.  Refusals raise."""
+    _require_device(x, "x")
+    M, N, K, r = _lora_dims(x, a_s, b, S)
+    if any(t is not None and t.dtype != x.dtype for t in (dy, a_s, h, dx)) or b.dtype != torch.float32:
+        raise _C.BayeFormersAMDError("lora_bwd: dy, A_s, h and dx must have x's dtype, B must be fp32")
+    if not all(t is None or t.is_contiguous() for t in (x, dy, a_s, b, h, dx)):
+        raise _C.BayeFormersAMDError("lora_bwd: operands must be contiguous")
+    if need_db and h is None:
+        raise _C.BayeFormersAMDError("lora_bwd: dB needs the forward's h")
+    lib = _C.lib()
+    dt = _TORCH2BF.get(x.dtype, -1)
+    da = torch.empty((S, r, K), dtype=torch.float32, device=x.device)
+    db = torch.empty((N, r), dtype=torch.float32, device=x.device) if need_db else None
+    need = lib.bf_lora_bwd_workspace_bytes(S, M, N, K, r, dt)
+    ws = workspace(x.device, need)
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _C.check(lib.bf_lora_bwd(x.data_ptr(), dy.data_ptr(), a_s.data_ptr(), b.data_ptr(), ptr(h), ptr(dx), da.data_ptr(), ptr(db),
+                             float(scale), dt, S, M, N, K, r, ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_lora_bwd")
+    LORA_CALLS["bwd"] += 1
+    return da, db
+
+
+def lora_reduce_da(da: Tensor, gaussian, stream_id: int, S: int, seed: int, sample_base: int, need_mu: bool = True):
+    """(dmu_A or None, drho_A) from the per-sample gradients dA [S, r, K] fp32 (bf_lora_reduce_da): dmu = sum_s dA_s,
+    drho = (sum_s dA_s o eps_s) o softplus'(rho), eps regenerated from the counter."""
+    rho = gaussian.rho
+    da = da.contiguous()
+    dmu = torch.empty_like(rho, dtype=torch.float32) if need_mu else None
+    drho = torch.empty_like(rho, dtype=torch.float32)
+    _C.check(_C.lib().bf_lora_reduce_da(da.data_ptr(), rho.data_ptr(), rho.numel(), S, seed, sample_base & 0xFFFFFFFF,
+                                        int(stream_id), dmu.data_ptr() if dmu is not None else None, drho.data_ptr(),
+                                        _stream_ptr()), "bf_lora_reduce_da")
+    return dmu, drho
+
+
+def _gemm_nn_takes(dtype: torch.dtype, M: int, N: int, K: int) -> bool:
+    # (bf_gemm_nn's own condition, restated: it fails rather than falls back)
+    return dtype in (torch.bfloat16, torch.float16) and N % 64 == 0 and K % 8 == 0 and M * K >= 16384
+
+
+def lora_base_forward(x: Tensor, w0: Tensor, bias32: Optional[Tensor]) -> Tensor:
+    """x W0^T + b0 for ALL samples' rows as one product (S = 1): bf_gemm_nt_skinny up to SKINNY_ROWS rows (a decode step:
+    W0 is streamed once whatever S is), the tiled GEMM otherwise.  x: [rows, K] 16-bit, w0: [N, K] of the same dtype,
+    bias32: [1, N] fp32 or None."""
+    rows, K = x.shape
+    N = w0.shape[0]
+    w = w0.view(1, N, K)
+    if K % 32 == 0 and skinny_supported(x, w, 1, K):
+        LORA_CALLS["base_skinny"] += 1
+        return skinny_linear_forward(x, w, bias32, 1, N, K)
+    LORA_CALLS["base_gemm"] += 1
+    return gemm_nt(x, w, bias32, 1, rows, N, K, rows * K, x.dtype).view(rows, N)
+
+
+def lora_forward(x: Tensor, a_s: Tensor, b: Tensor, w0: Tensor, b0: Optional[Tensor], scale: float, S: int,
+                 bias32: Optional[Tensor] = None):
+    """(y, h) of bnn.LoRALinear for S samples: y[s] = x[s] W0^T + b0 + scale * h[s] B^T, h[s] = x[s] A_s^T.  x: [S*M, K];
+    a_s: [S, r, K] as ops.sample_logprob drew it; b: [N, r] fp32; w0: [N, K]; b0: [N] or None (bias32: its fp32 [1, N]
+    copy, when the caller keeps one).  Kernels where lora_supported(), else the same formula as framework ops."""
+    _require_device(x, "input")
+    N, K, r = w0.shape[0], w0.shape[1], a_s.shape[1]
+    x = x if x.is_contiguous() else x.contiguous()
+    if a_s.dtype == x.dtype and w0.dtype == x.dtype and lora_supported(x.dtype, N, K, r, x, a_s, b, w0, backward=False):
+        if b0 is not None and bias32 is None:
+            bias32 = b0.detach().float().view(1, N)
+        y = lora_base_forward(x, w0, bias32)
+        h = lora_fwd(x, a_s, b, y, scale, S)
+        return y, h
+    LORA_CALLS["composite_fwd"] += 1
+    M = x.shape[0] // S
+    xd = x.dtype
+    h = torch.bmm(x.view(S, M, K), a_s.to(xd).transpose(1, 2))
+    y = torch.nn.functional.linear(x, w0.to(xd), b0.to(xd) if b0 is not None else None)
+    y = torch.baddbmm(y.view(S, M, N), h, b.to(xd).t().expand(S, r, N), alpha=float(scale))
+    return y.view(S * M, N), h.view(S * M, r)
+
+
+def lora_backward(x: Tensor, dy: Tensor, a_s: Tensor, b: Tensor, h: Tensor, w0: Tensor, scale: float, S: int,
+                  need_x: bool = True, need_b: bool = True):
+    """(dx or None, dA [S, r, K] fp32, dB [N, r] fp32 or None) of lora_forward: g = dy B, dx = dy W0 + scale * g A_s,
+    dA_s = scale * g[s]^T x[s], dB = scale * sum_s dy[s]^T h[s].  No gradient reaches W0."""
+    N, K, r = w0.shape[0], w0.shape[1], a_s.shape[1]
+    M = x.shape[0] // S
+    dy = dy.reshape(S * M, N)
+    dy = (dy if dy.dtype == x.dtype else dy.to(x.dtype)).contiguous()
+    if a_s.dtype == x.dtype and w0.dtype == x.dtype and lora_supported(x.dtype, N, K, r, x, dy, a_s, b, h, w0, backward=True):
+        dx = None
+        if need_x:
+            if _gemm_nn_takes(x.dtype, S * M, N, K):
+                dx = gemm_nn(dy.view(1, S * M, N), w0.view(1, N, K)).view(S * M, K)
+            else:
+                dx = torch.matmul(dy, w0)
+        da, db = lora_bwd(x, dy, a_s, b, h, dx, scale, S, need_b)
+        return dx, da, db
+    LORA_CALLS["composite_bwd"] += 1
+    xd = x.dtype
+    g = torch.matmul(dy.view(S, M, N), b.to(xd))
+    dx = None
+    if need_x:
+        dx = torch.baddbmm(torch.matmul(dy, w0.to(xd)).view(S, M, K), g, a_s.to(xd), alpha=float(scale)).view(S * M, K)
+    da = (float(scale) * torch.bmm(g.transpose(1, 2), x.view(S, M, K))).float()
+    db = (float(scale) * torch.matmul(dy.t(), h.reshape(S * M, r))).float() if need_b else None
+    return dx, da, db

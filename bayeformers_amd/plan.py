@@ -301,6 +301,7 @@ def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
     and per sample N * K bytes of e4m3 deviations with N fp32 row scales; the fp32 biases as above.  Exactly the bytes of the
     block's store: each piece is a tensor of its own, nothing is padded."""
     from .nn.layers.linear import Linear
+    from .nn.layers.lora import LoRALinear
     from .nn.parameters.base import NoneParameter
 
     if dtype not in (torch.float32, torch.bfloat16, torch.float16):
@@ -318,6 +319,8 @@ def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
             total += N * K * 2 + S * (N * K + N * 4) if fp8 else S * N * K * esz
             if not isinstance(l.bias, NoneParameter):
                 total += S * N * 4
+        elif isinstance(l, LoRALinear):
+            total += S * l.r * l.in_features * esz  # its A_s [S, r, K] in the compute dtype (never FP8): the base is shared
     return total
 
 

@@ -836,5 +836,6 @@ int bf_mc_predictive_finish(const void* d_partial, int64_t R, int64_t C, int S_t
 #include "bayeformers_amd_packed.h"        /* banded causal attention for packed sequences, likewise */
 #include "bayeformers_amd_fp8.h"           /* centred FP8 rows of kept weight samples and their skinny GEMM, likewise */
 #include "bayeformers_amd_kv8.h"           /* the FP8 KV cache: append, dequantise, decode attention on e4m3 rows, likewise */
+#include "bayeformers_amd_lora.h"          /* Bayesian low-rank adapters on a frozen base: the rank-r forward / backward, likewise */
 
 #endif /* BAYEFORMERS_AMD_H */
