@@ -240,6 +240,19 @@ KV8_SYMBOLS = {
                                          ctypes.c_float, _vp]),
 }
 
+# what include/bayeformers_amd_ring.h declares (the ring-buffer KV cache of sample_generate(sliding_cache="ring")): the
+# 16-bit append (K and V with their strides, the two cache buffers, the device fill pointer, N, Hkv, T, D, ring_slots),
+# bf_kv8_append's arguments with ring_slots in place of the capacity, and the decode entries: bf_attention_decode_gqa_softcap's
+# and bf_attention_decode_gqa_kv8's arguments with ring_slots in front of the window
+RING_SYMBOLS = {
+    "bf_kv_ring_append": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "bf_kv8_ring_append": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "bf_attention_decode_gqa_ring": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, ctypes.c_float,
+                                          ctypes.c_float, _vp]),
+    "bf_attention_decode_gqa_ring_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i,
+                                              ctypes.c_float, ctypes.c_float, _vp]),
+}
+
 # what include/bayeformers_amd_chunk.h declares (the cached-chunk attention of sample_generate(prefill_chunk=...)):
 # (q, k, v, mask, mask_off, kv_len, out, dtype, shape, window, key_origin, softcap, scaling, stream), and the same on an FP8 cache with
 # (kq, vq, k_scale, v_scale) in place of (k, v)
@@ -341,6 +354,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the any-length encoder attention entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in RING_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the ring-buffer KV-cache entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

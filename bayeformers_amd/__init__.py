@@ -399,6 +399,8 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
 
     from . import ops
 
+    if getattr(key, "_bf_ring", None) is not None:  # a ring-buffer cache (kv_cache.RingStaticLayer), 16-bit or e4m3 rows
+        return _ring_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs)
     if getattr(key, "_bf_kv8_scale", None) is not None:  # an FP8 cache (kv_cache.Fp8StaticLayer): key / value are e4m3 rows
         return _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs)
     need_grad = torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad)
@@ -449,6 +451,66 @@ def _attention_interface(module, query, key, value, attention_mask, dropout: flo
     if need_grad:  # training: the same kernel, with bf_attention_bwd behind it
         return ops.AttentionFn.apply(query, key, value, key_mask, mask_off, scale, drop), None
     return ops.attention_forward(query, key, value, key_mask, scale, mask_off, drop=drop), None
+
+
+def _ring_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs):
+    """_attention_interface for a call against a ring-buffer cache: `key` and `value` are the [N, Hkv, ring_slots, D] tensors
+    of a kv_cache.RingStaticLayer (Fp8RingStaticLayer: e4m3 rows with `_bf_kv8_scale`), marked `_bf_ring = (ring_slots,
+    capacity)`, the key with sequence index j in row j % ring_slots.  A decode step — the mask carries the fill `_bf_kv_len`
+    and the window `_bf_window`, at most 16 queries, no gradient, no dropout, no attention sinks, no key mask or a
+    [N, capacity] one, the module's `sliding_window` agreeing with the mask's, a soft-cap only under `softcap_attention()` —
+    runs bf_attention_decode_gqa_ring (bf_attention_decode_gqa_ring_kv8 on e4m3 rows).  ops.decode_kernel_wins is not
+    consulted: nothing else can read a ring.  Every other call raises RuntimeError with the reason: the framework's
+    attention would read the rows as if they lay in sequence order and be silently wrong."""
+    from . import ops
+
+    def refuse(why):
+        raise RuntimeError("bayeformers_amd: the keys of this call are a ring-buffer cache (sliding_cache=\"ring\"), which only "
+                           f"the ring decode kernels read, and {why}")
+
+    slots, capacity = key._bf_ring
+    if getattr(value, "_bf_ring", None) != key._bf_ring:
+        refuse("its values are not the same ring's")
+    k_scale, v_scale = getattr(key, "_bf_kv8_scale", None), getattr(value, "_bf_kv8_scale", None)
+    if (k_scale is None) != (v_scale is None):
+        refuse("only one of its keys and values carries FP8 scales")
+    marked = attention_mask is not None
+    kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
+    window = getattr(attention_mask, "_bf_window", None) if marked else None
+    key_mask = getattr(attention_mask, "_bf_key_mask", None) if marked else None
+    softcap = kwargs.get("softcap", None)
+    Tq = query.shape[2]
+    if Tq > ops.DECODE_MAX_QUERIES:
+        refuse(f"it carries {Tq} queries: a step takes at most {ops.DECODE_MAX_QUERIES} (a ring of window + "
+               f"{ops.DECODE_MAX_QUERIES - 1} slots holds no more live keys; prefill_chunk is not supported)")
+    if kv_len is None or window is None:
+        refuse("its mask is not the sliding-window mask of a fixed-capacity cache (no `_bf_kv_len` or no `_bf_window`)")
+    if torch.is_grad_enabled() and query.requires_grad:
+        refuse("it needs a gradient")
+    if dropout != 0.0:
+        refuse(f"it carries attention dropout ({dropout})")
+    if kwargs.get("s_aux", None) is not None:
+        refuse("it carries attention sinks (s_aux)")
+    if softcap is not None and not softcap_attention_enabled():
+        refuse("it carries a logit soft-cap with softcap_attention() off")
+    if "sliding_window" in kwargs and kwargs["sliding_window"] != window:
+        refuse(f"the module's sliding_window={kwargs['sliding_window']!r} disagrees with the mask's window {window}")
+    if window + Tq - 1 > slots:
+        refuse(f"window {window} with {Tq} queries needs {window + Tq - 1} slots, the ring has {slots}")
+    if key_mask is not None and tuple(key_mask.shape) != (query.shape[0], capacity):
+        refuse(f"its key mask is {tuple(key_mask.shape)}, not [N, capacity] = {(query.shape[0], capacity)}")
+    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
+    mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
+    cap = float(softcap) if softcap is not None else None
+    if k_scale is not None:
+        if not ops.attention_decode_kv8_supported(query, key, value):
+            refuse("bf_attention_decode_gqa_ring_kv8 does not take its shapes, dtypes or strides")
+        return ops.attention_forward_decode_ring_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
+                                                     None, window, slots, capacity, softcap=cap), None
+    if not ops.attention_decode_supported(query, key, value):
+        refuse("bf_attention_decode_gqa_ring does not take its shapes, dtypes or strides")
+    return ops.attention_forward_decode_ring(query, key, value, kv_len, key_mask, scale, mask_off, None, window, slots,
+                                             capacity, softcap=cap), None
 
 
 def _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs):

@@ -26,6 +26,13 @@
 // with one fp32 power-of-two scale each (bf_kv8.hip writes them).  Only the fetch differs: a key row is HD / 16 16-byte
 // chunks plus its scale, and the dequantised bf16 values — exact — are written into the same LDS images (write_fp8, shared
 // with bf_attention_chunk.hip), so everything behind the fetch is the bf16 kernel's and the result is bitwise that kernel's on the dequantised cache.
+//
+// bf_attention_decode_gqa_ring / _ring_kv8 (include/bayeformers_amd_ring.h) run the window form over a ring buffer: the
+// cache holds C = ring_slots rows and the key with sequence index j lives in row j % C.  The tile grid, the splits, the mask
+// and the visibility test stay over sequence indices (Tk is the logical capacity); again only the fetch differs, which
+// reads row key % C — the slot of a tile's first key once per tile, then a conditional subtract per row (the keys a launch
+// reads span at most window + Tq - 1 <= C indices, so one subtract wraps them).  A compile-time form (RING) instantiated
+// with LOCAL alone: the result is bitwise the window entry's on the same keys laid out in sequence order.
 #include "bf_attention_tiles.h"
 
 #include <algorithm>
@@ -64,8 +71,14 @@ struct DecodeKv8Params : DecodeCapParams {
     const float* k_scale;  // [N][Hkv][Tk]
     const float* v_scale;
 };
-template <bool CAP, bool KV8>
-using ParamsOf = std::conditional_t<KV8, DecodeKv8Params, std::conditional_t<CAP, DecodeCapParams, DecodeParams>>;
+// RING: k, v and the kv8 scales hold `ring` rows, key j in row j % ring; a compile-time flag with a parameter block of its
+// own once more (one block for every RING instantiation)
+struct DecodeRingParams : DecodeKv8Params {
+    int ring;
+};
+template <bool CAP, bool KV8, bool RING = false>
+using ParamsOf = std::conditional_t<RING, DecodeRingParams,
+                                    std::conditional_t<KV8, DecodeKv8Params, std::conditional_t<CAP, DecodeCapParams, DecodeParams>>>;
 
 struct Split {
     int n, keys;  // splits, keys per split (a multiple of KT; the last split ends at Tk)
@@ -91,8 +104,9 @@ Split decode_split(const bf_attn_decode_t* s) {
     return Split{(tiles + per - 1) / per, per * KT};
 }
 
-template <typename T, int HD, bool LOCAL, bool CAP, bool KV8 = false>
-__global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p) {
+template <typename T, int HD, bool LOCAL, bool CAP, bool KV8 = false, bool RING = false>
+__global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8, RING> p) {
+    static_assert(LOCAL || !RING, "a ring cache is read through a window");
     using frag = typename Mfma<T>::frag;
     using half4 = typename Mfma<T>::half4;
     using KV = std::conditional_t<KV8, uint8_t, T>;          // what the cache holds
@@ -144,16 +158,26 @@ __global__ __launch_bounds__(256) void decode_kernel(const ParamsOf<CAP, KV8> p)
     float ksc[KV8 ? NLD : 1], vsc[KV8 ? NLD : 1];
     float mr = 0.f;
     auto fetch = [&](int key0) {
+        // RING: the tile's keys are consecutive sequence indices, so its rows are consecutive slots from key0 % ring on; a
+        // key this launch reads lies fewer than ring indices past key0 (k_hi - k_lo <= window + Tq - 1 <= ring)
+        int slot0 = 0;
+        if constexpr (RING) slot0 = key0 % p.ring;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int c = tid + 256 * i, key = key0 + c / CPR, c8 = c % CPR;
             kr[i] = vr[i] = chunk{};
             if constexpr (KV8) ksc[i] = vsc[i] = 0.f;
             if (key < k_hi) {
-                kr[i] = *reinterpret_cast<const chunk*>(kb + (long long)key * p.ks[2] + c8 * (16 / (int)sizeof(KV)));
-                vr[i] = *reinterpret_cast<const chunk*>(vb + (long long)key * p.vs[2] + c8 * (16 / (int)sizeof(KV)));
+                int row = key, rows = p.Tk;  // the cache row of the key, of the rows the cache holds
+                if constexpr (RING) {
+                    row = slot0 + c / CPR;
+                    rows = p.ring;
+                    if (row >= rows) row -= rows;
+                }
+                kr[i] = *reinterpret_cast<const chunk*>(kb + (long long)row * p.ks[2] + c8 * (16 / (int)sizeof(KV)));
+                vr[i] = *reinterpret_cast<const chunk*>(vb + (long long)row * p.vs[2] + c8 * (16 / (int)sizeof(KV)));
                 if constexpr (KV8) {
-                    const long long srow = ((long long)n * p.Hkv + g) * p.Tk + key;
+                    const long long srow = ((long long)n * p.Hkv + g) * rows + row;
                     ksc[i] = p.k_scale[srow];
                     vsc[i] = p.v_scale[srow];
                 }
@@ -253,7 +277,8 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(const DecodeParams p)
 }
 
 // kv8: the FP8 instantiations (bf16 compute); each dtype and head size with and without a window and a cap
-void launch(const DecodeKv8Params& p, int dtype, int D, bool cap, bool kv8, hipStream_t stream) {
+// ring (p.ring != 0): the RING instantiations, which exist beside the LOCAL ones alone (the entries require a window)
+void launch(const DecodeRingParams& p, int dtype, int D, bool cap, bool kv8, hipStream_t stream) {
     const dim3 grid(p.nsplit, p.N * p.Hkv, (p.R + ROWS - 1) / ROWS);
     with_head_size(D, [&](auto hd) {
         constexpr int HD = decltype(hd)::value;
@@ -262,6 +287,12 @@ void launch(const DecodeKv8Params& p, int dtype, int D, bool cap, bool kv8, hipS
                 auto run = [&](auto tag, auto fp8) {
                     using T = typename decltype(tag)::type;
                     constexpr bool LOCAL = decltype(local)::value, CAP = decltype(capped)::value, KV8 = decltype(fp8)::value;
+                    if constexpr (LOCAL) {
+                        if (p.ring) {
+                            decode_kernel<T, HD, true, CAP, KV8, true><<<grid, 256, 0, stream>>>(p);
+                            return;
+                        }
+                    }
                     const ParamsOf<CAP, KV8>& kp = p;
                     decode_kernel<T, HD, LOCAL, CAP, KV8><<<grid, 256, 0, stream>>>(kp);
                 };
@@ -303,11 +334,12 @@ int64_t bf_attention_decode_workspace_bytes(const bf_attn_decode_t* shape) {
 namespace {
 
 // window 0: the plain entries; >= 1: the sliding-window ones.  softcap 0: no cap.  kv8: d_k / d_v are e4m3fn rows with the
-// scales d_k_scale / d_v_scale (bf16 compute)
+// scales d_k_scale / d_v_scale (bf16 compute).  ring 0: k / v hold Tk rows in sequence order; >= 1: that many rows, key j
+// in row j % ring (the ring entries checked the window against it)
 int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
            const unsigned char* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
            const bf_attn_decode_t* shape, int window, float softcap, float scaling, hipStream_t stream, bool kv8 = false,
-           const float* d_k_scale = nullptr, const float* d_v_scale = nullptr) {
+           const float* d_k_scale = nullptr, const float* d_v_scale = nullptr, int ring = 0) {
     if (window < 0) BF_FAIL("%s: window=%d must be at least 1", what, window);
     if (kv8 && dtype != BF_DT_BF16)
         BF_FAIL("%s: dtype must be bf16 (bfloat16: the dequantised rows are exact in it alone)", what);
@@ -326,7 +358,8 @@ int decode(const char* what, const void* d_q, const void* d_k, const void* d_v, 
     const Split sp = decode_split(shape);
     if (sp.n > 1 && !d_workspace) BF_FAIL("%s: %d key splits need a workspace of %lld bytes", what, sp.n,
                                           (long long)workspace_bytes(shape));
-    DecodeKv8Params p = {};
+    DecodeRingParams p = {};
+    p.ring = ring;
     p.q = d_q;
     p.k = d_k;
     p.v = d_v;
@@ -432,4 +465,43 @@ int bf_attention_decode_gqa_kv8(const void* d_q, const void* d_kq, const void* d
     if (d_kv_len && ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
     return decode(what, d_q, d_kq, d_vq, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, softcap,
                   scaling, (hipStream_t)stream, true, d_k_scale, d_v_scale);
+}
+
+namespace {
+
+// the checks the two ring entries share; 0 or the BF_FAIL status
+int check_ring(const char* what, const int64_t* d_kv_len, const bf_attn_decode_t* shape, int ring_slots, int window,
+               float softcap) {
+    if (!shape) BF_FAIL("%s: shape is NULL", what);
+    if (!(softcap >= 0.f) || !(softcap < INFINITY)) BF_FAIL("%s: softcap=%g must be finite and at least 0 (0: no cap)", what, (double)softcap);
+    if (!d_kv_len || ((uintptr_t)d_kv_len & 7)) BF_FAIL("%s: kv_len must be an 8-byte aligned device int64", what);
+    if (ring_slots < 1) BF_FAIL("%s: ring_slots=%d must be at least 1", what, ring_slots);
+    if (window < 1) BF_FAIL("%s: window=%d must be at least 1", what, window);
+    if ((long long)window + shape->Tq - 1 > ring_slots)
+        BF_FAIL("%s: window=%d and Tq=%d need %lld ring slots (ring_slots=%d): a step's keys would overwrite each other", what,
+                window, shape->Tq, (long long)window + shape->Tq - 1, ring_slots);
+    return 0;
+}
+
+}  // namespace
+
+int bf_attention_decode_gqa_ring(const void* d_q, const void* d_k, const void* d_v, const float* d_mask,
+                                 const uint8_t* d_mask_off, const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
+                                 const bf_attn_decode_t* shape, int32_t ring_slots, int32_t window, float softcap,
+                                 float scaling, void* stream) {
+    const char* what = "bf_attention_decode_gqa_ring";
+    if (check_ring(what, d_kv_len, shape, ring_slots, window, softcap)) return 1;
+    return decode(what, d_q, d_k, d_v, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, softcap, scaling,
+                  (hipStream_t)stream, false, nullptr, nullptr, ring_slots);
+}
+
+int bf_attention_decode_gqa_ring_kv8(const void* d_q, const void* d_kq, const void* d_vq, const float* d_k_scale,
+                                     const float* d_v_scale, const float* d_mask, const uint8_t* d_mask_off,
+                                     const int64_t* d_kv_len, void* d_out, void* d_workspace, int dtype,
+                                     const bf_attn_decode_t* shape, int32_t ring_slots, int32_t window, float softcap,
+                                     float scaling, void* stream) {
+    const char* what = "bf_attention_decode_gqa_ring_kv8";
+    if (check_ring(what, d_kv_len, shape, ring_slots, window, softcap)) return 1;
+    return decode(what, d_q, d_kq, d_vq, d_mask, d_mask_off, d_kv_len, d_out, d_workspace, dtype, shape, window, softcap,
+                  scaling, (hipStream_t)stream, true, d_k_scale, d_v_scale, ring_slots);
 }

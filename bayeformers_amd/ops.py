@@ -1367,6 +1367,175 @@ def attention_forward_decode_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Ten
     return out
 
 
+# launches of the ring-buffer KV-cache entries (include/bayeformers_amd_ring.h) from this process: bf_kv_ring_append,
+# bf_kv8_ring_append, bf_attention_decode_gqa_ring, bf_attention_decode_gqa_ring_kv8.  They bump no other counter.
+RING_CALLS = {"append": 0, "kv8_append": 0, "decode": 0, "kv8_decode": 0}
+
+
+def ring_slots(window: Optional[int], capacity: int) -> Optional[int]:
+    """The slots C a sliding-window layer's ring buffer holds (sample_generate(sliding_cache="ring")), or None where the
+    layer stays a plain full-capacity one: no window, or C >= capacity.  C = window + DECODE_MAX_QUERIES - 1: a step that
+    appends Tq <= 16 rows at fill L reads the keys [L - window + 1, L + Tq) at most — window + Tq - 1 <= C of them — so none
+    of the keys it reads was overwritten by the rows it appended.  The one place the rule lives."""
+    if window is None:
+        return None
+    window, capacity = int(window), int(capacity)
+    if window < 1 or capacity < 1:
+        raise ValueError(f"ring_slots: window={window}, capacity={capacity} (each at least 1)")
+    C = window + DECODE_MAX_QUERIES - 1
+    return C if C < capacity else None
+
+
+def _ring_append_check(what: str, k: Tensor, v: Tensor, kc: Tensor, vc: Tensor, pos: Tensor) -> None:
+    """The arguments the two ring appends share: k, v [N, Hkv, T, D] rows for the contiguous caches kc, vc
+    [N, Hkv, ring_slots, D] on one ROCm device, pos one int64 on it."""
+    for name, t in (("k", k), ("v", v), ("kc", kc), ("vc", vc)):
+        _require_device(t, f"{what}: {name}")
+    if kc.dim() != 4 or tuple(vc.shape) != tuple(kc.shape) or not (kc.is_contiguous() and vc.is_contiguous()):
+        raise _C.BayeFormersAMDError(f"{what}: the cache tensors must be contiguous [N, Hkv, ring_slots, D] of one shape "
+                                     f"(got {tuple(kc.shape)}, {tuple(vc.shape)})")
+    if k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or tuple(k.shape[:2]) != tuple(kc.shape[:2]) \
+            or k.shape[3] != kc.shape[3]:
+        raise _C.BayeFormersAMDError(f"{what}: k {tuple(k.shape)}, v {tuple(v.shape)} are not [N, Hkv, T, D] rows of the "
+                                     f"cache {tuple(kc.shape)}")
+    if k.shape[3] not in KV8_HEAD_SIZES:
+        raise _C.BayeFormersAMDError(f"{what}: head size {k.shape[3]} (64, 128 or 256)")
+    if k.shape[2] < 1:
+        raise _C.BayeFormersAMDError(f"{what}: T={k.shape[2]} new rows (at least 1)")
+    if k.stride(3) != 1 or v.stride(3) != 1 or any(st < 0 or st % 8 for t in (k, v) for st in t.stride()[:3]):
+        raise _C.BayeFormersAMDError(f"{what}: k and v need a contiguous feature dimension and (batch, head, token) strides "
+                                     "that are non-negative multiples of 8")
+    if pos.dtype != torch.int64 or pos.numel() != 1 or len({t.device for t in (k, v, kc, vc, pos)}) != 1:
+        raise _C.BayeFormersAMDError(f"{what}: pos must be one int64 on the device of k, v and the cache")
+
+
+def kv_ring_append(k: Tensor, v: Tensor, kc: Tensor, vc: Tensor, pos: Tensor) -> None:
+    """Append the new K and V rows of a forward to a ring-buffer cache (bf_kv_ring_append): k, v [N, Hkv, T, D] bf16 or
+    fp16 with any (batch, head, token) strides that are multiples of 8 and a contiguous feature dimension; kc, vc
+    [N, Hkv, ring_slots, D] of the same dtype, contiguous.  Row i goes to slot (pos + i) % ring_slots, pos a one-element
+    int64 device tensor the kernel reads; of T > ring_slots rows only the last ring_slots are written.  One launch."""
+    what = "kv_ring_append"
+    _ring_append_check(what, k, v, kc, vc, pos)
+    if k.dtype not in (torch.bfloat16, torch.float16) or len({k.dtype, v.dtype, kc.dtype, vc.dtype}) != 1:
+        raise _C.BayeFormersAMDError(f"{what}: k, v and the cache must share bfloat16 or float16 (got {k.dtype}, {v.dtype}, "
+                                     f"{kc.dtype}, {vc.dtype})")
+    N, Hkv, T, D = k.shape
+    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (k, v)]
+    _C.check(_C.lib().bf_kv_ring_append(k.data_ptr(), v.data_ptr(), _TORCH2BF[k.dtype], strides[0], strides[1],
+                                        kc.data_ptr(), vc.data_ptr(), pos.data_ptr(), N, Hkv, T, D, int(kc.shape[2]),
+                                        _stream_ptr()), "bf_kv_ring_append")
+    RING_CALLS["append"] += 1
+
+
+def kv8_ring_append(k: Tensor, v: Tensor, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor) -> None:
+    """kv_ring_append into an FP8 ring (bf_kv8_ring_append): kv8_append's quantisation and arguments — k, v bfloat16, kq /
+    vq [N, Hkv, ring_slots, D] uint8, k_scale / v_scale [N, Hkv, ring_slots] fp32 — with row i bound for slot
+    (pos + i) % ring_slots and, of T > ring_slots rows, only the last ring_slots written."""
+    what = "kv8_ring_append"
+    _kv8_cache_check(what, kq, vq, k_scale, v_scale)
+    _ring_append_check(what, k, v, kq, vq, pos)
+    if k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise _C.BayeFormersAMDError(f"{what}: k and v must be bfloat16 (got {k.dtype}, {v.dtype}): the FP8 cache's "
+                                     "dequantised rows are exact in bfloat16 alone")
+    N, Hkv, T, D = k.shape
+    strides = [(ctypes.c_int64 * 3)(*t.stride()[:3]) for t in (k, v)]
+    _C.check(_C.lib().bf_kv8_ring_append(k.data_ptr(), v.data_ptr(), _C.BF_DT_BF16, strides[0], strides[1], kq.data_ptr(),
+                                         vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(), pos.data_ptr(), N, Hkv, T,
+                                         D, int(kq.shape[2]), _stream_ptr()), "bf_kv8_ring_append")
+    RING_CALLS["kv8_append"] += 1
+
+
+def _ring_decode_shape(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
+                       workspace: Optional[Tensor], window: int, slots: int, capacity: int):
+    """What the two ring decodes share behind their own dtype checks: (out, shape, ws) for q [N, H, Tq, D] against k / v
+    [N, Hkv, ring_slots, D], the shape carrying the logical capacity as its Tk."""
+    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
+            or k.shape[3] != q.shape[3]:
+        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
+                                     "are not [N, H, Tq, D], [N, Hkv, ring_slots, D], [N, Hkv, ring_slots, D]")
+    if not (k.is_cuda and v.is_cuda) or k.device != q.device or v.device != q.device:
+        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one device")
+    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
+        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q, k and v must be contiguous")
+    if kv_len is None or kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device:
+        raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
+    slots, capacity = int(slots), int(capacity)
+    if k.shape[2] != slots:
+        raise _C.BayeFormersAMDError(f"{name}: k and v hold {k.shape[2]} rows, not ring_slots={slots}")
+    if window is None or int(window) < 1 or int(window) + q.shape[2] - 1 > slots:
+        raise _C.BayeFormersAMDError(f"{name}: window={window} with Tq={q.shape[2]} needs window >= 1 and "
+                                     f"window + Tq - 1 <= ring_slots={slots}")
+    N, H, Tq, D = q.shape
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
+    shape = _decode_shape(q, k, v)
+    shape.Tk = capacity  # the grid, the splits, the workspace and the mask follow the logical capacity
+    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
+    if nbytes < 0:
+        _C.check(1, "bf_attention_decode_workspace_bytes")
+    ws = None
+    if nbytes:
+        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+            raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
+    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, capacity)
+                                 or not key_mask.is_contiguous()):
+        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, capacity]")
+    return out, shape, ws
+
+
+def attention_forward_decode_ring(q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
+                                  scaling: float, mask_off: Optional[Tensor] = None, workspace: Optional[Tensor] = None,
+                                  window: Optional[int] = None, ring_slots: Optional[int] = None,
+                                  capacity: Optional[int] = None, softcap: Optional[float] = None) -> Tensor:
+    """attention_forward_decode_len with a window over a ring-buffer cache (bf_attention_decode_gqa_ring): k / v
+    [N, Hkv, ring_slots, D] hold the key with sequence index j in row j % ring_slots; kv_len is the fill L (every row ever
+    appended: it does not wrap), `capacity` the logical capacity — the grid, the key split, the workspace
+    (attention_decode_workspace_bytes of a [N, Hkv, capacity, D] cache) and key_mask [N, capacity] follow it.  Query i
+    sees keys L - Tq + i - window + 1 .. L - Tq + i; window >= 1 and window + Tq - 1 <= ring_slots.  The result is bitwise
+    attention_forward_decode_len(..., window=window)'s on the same keys in a linear cache of `capacity` rows."""
+    name = "attention_forward_decode_ring"
+    _require_device(q, f"{name}: q")
+    if ring_slots is None or capacity is None:
+        raise _C.BayeFormersAMDError(f"{name}: ring_slots and capacity are required")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share bfloat16 or float16")
+    out, shape, ws = _ring_decode_shape(name, q, k, v, kv_len, key_mask, workspace, window, ring_slots, capacity)
+    _C.check(_C.lib().bf_attention_decode_gqa_ring(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
+        mask_off.data_ptr() if mask_off is not None else None, kv_len.data_ptr(), out.data_ptr(),
+        ws.data_ptr() if ws is not None else None, _TORCH2BF[q.dtype], ctypes.byref(shape), int(ring_slots), int(window),
+        float(softcap or 0.0), float(scaling), _stream_ptr()), "bf_attention_decode_gqa_ring")
+    RING_CALLS["decode"] += 1
+    return out
+
+
+def attention_forward_decode_ring_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor, kv_len: Tensor,
+                                      key_mask: Optional[Tensor], scaling: float, mask_off: Optional[Tensor] = None,
+                                      workspace: Optional[Tensor] = None, window: Optional[int] = None,
+                                      ring_slots: Optional[int] = None, capacity: Optional[int] = None,
+                                      softcap: Optional[float] = None) -> Tensor:
+    """attention_forward_decode_ring on an FP8 ring (bf_attention_decode_gqa_ring_kv8): q bfloat16, kq / vq
+    [N, Hkv, ring_slots, D] uint8 (e4m3fn rows), k_scale / v_scale [N, Hkv, ring_slots] fp32 contiguous.  Bitwise
+    attention_forward_decode_kv8(..., window=window)'s result on the same rows in a linear FP8 cache of `capacity` rows."""
+    name = "attention_forward_decode_ring_kv8"
+    _require_device(q, f"{name}: q")
+    if ring_slots is None or capacity is None:
+        raise _C.BayeFormersAMDError(f"{name}: ring_slots and capacity are required")
+    if q.dtype != torch.bfloat16:
+        raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
+                                     "exact in bfloat16 alone")
+    _kv8_cache_check(name, kq, vq, k_scale, v_scale)
+    out, shape, ws = _ring_decode_shape(name, q, kq, vq, kv_len, key_mask, workspace, window, ring_slots, capacity)
+    _C.check(_C.lib().bf_attention_decode_gqa_ring_kv8(
+        q.data_ptr(), kq.data_ptr(), vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+        key_mask.data_ptr() if key_mask is not None else None, mask_off.data_ptr() if mask_off is not None else None,
+        kv_len.data_ptr(), out.data_ptr(), ws.data_ptr() if ws is not None else None, _C.BF_DT_BF16, ctypes.byref(shape),
+        int(ring_slots), int(window), float(softcap or 0.0), float(scaling), _stream_ptr()),
+        "bf_attention_decode_gqa_ring_kv8")
+    RING_CALLS["kv8_decode"] += 1
+    return out
+
+
 # launches of the cached-chunk attention entries (include/bayeformers_amd_chunk.h) from this process: "fwd" of
 # bf_attention_chunk_gqa, "kv8" of bf_attention_chunk_gqa_kv8.  They bump no other counter.
 CHUNK_CALLS = {"fwd": 0, "kv8": 0}

@@ -324,13 +324,19 @@ def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
     return total
 
 
-def kv_cache_bytes(model, samples: int, batch: int, capacity: int, dtype=torch.bfloat16, fp8: bool = False) -> int:
+def kv_cache_bytes(model, samples: int, batch: int, capacity: int, dtype=torch.bfloat16, fp8: bool = False,
+                   ring: bool = False) -> int:
     """Device bytes the static KV cache of sample_generate(static_cache=True) holds for `samples` Monte-Carlo samples of
     `batch` rows at `capacity` slots, counted from the decoder's config (layers, K/V heads, head size): per layer, K/V head
     and slot one K row and one V row of D elements of `dtype` for each of the samples * batch sequences.  Needs no GPU.
 
     fp8=True: what kv_cache="fp8" holds (bf16 compute only) — D e4m3 bytes and one fp32 scale per row, 2 D + 8 bytes a row
-    pair against 4 D in bf16."""
+    pair against 4 D in bf16.
+
+    ring=True: what sliding_cache="ring" holds — each sliding-window layer of a family static generation serves
+    (sampling._sliding_windows, as sampling._static_cache finds them) counts min(capacity, C) slots, C = window + 15
+    (ops.ring_slots), instead of the capacity; every other layer, and every layer of a config without such layers, counts
+    the capacity."""
     if dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise ValueError(f"kv_cache_bytes: dtype {dtype} (float32, bfloat16 or float16)")
     if fp8 and dtype != torch.bfloat16:
@@ -347,4 +353,10 @@ def kv_cache_bytes(model, samples: int, batch: int, capacity: int, dtype=torch.b
     kv_heads = int(getattr(config, "num_key_value_heads", None) or heads)
     D = int(getattr(config, "head_dim", None) or config.hidden_size // heads)
     row_pair = 2 * D + 8 if fp8 else 2 * D * (4 if dtype == torch.float32 else 2)
-    return layers * samples * batch * kv_heads * capacity * row_pair
+    slots = layers * capacity
+    if ring:
+        from .sampling import _sliding_windows
+
+        windows = _sliding_windows(getattr(inner if inner is not None else model, "config", None), capacity)
+        slots = sum(ops.ring_slots(w, capacity) or capacity for w in windows)
+    return slots * samples * batch * kv_heads * row_pair

@@ -765,7 +765,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     graph: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
                     min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                     no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                    kv_cache: Optional[str] = None, prefill_chunk: Optional[int] = None) -> Generation:
+                    kv_cache: Optional[str] = None, prefill_chunk: Optional[int] = None,
+                    sliding_cache: Optional[str] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -837,7 +838,19 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     function (attention over cached, for FP8 quantised, keys), close to, not bitwise, the whole-prompt prefill's.  Without
     keep_weights every span draws the same pinned weights again — S draws of every layer per span — so chunking is best
     combined with keep_weights.  None, or C >= T0, is the whole-prompt prefill, bit for bit; any other value raises
-    ValueError."""
+    ValueError.
+
+    sliding_cache="ring" (implies static_cache; Mistral, Qwen2, Qwen3 and Gemma 2) keeps each sliding-window layer of that
+    static cache as a ring buffer of C = W + 15 slots (ops.ring_slots) instead of the capacity, the key with sequence index
+    j in slot j % C (kv_cache.RingStaticLayer; include/bayeformers_amd_ring.h): plan.kv_cache_bytes(..., ring=True) bytes.
+    A step appends its rows with one bf_kv_ring_append launch per layer and decodes on bf_attention_decode_gqa_ring, which
+    walks the same sequence-index keys as the window kernel and reads each from its slot: the Generation is bitwise the one
+    static_cache=True returns.  Full-attention layers, and sliding layers whose C is not below the capacity, stay plain
+    layers.  It composes with graph=True, with kv_cache="fp8" (e4m3 rings: bf_kv8_ring_append,
+    bf_attention_decode_gqa_ring_kv8), keep_weights, truncation, the logits processors and soft-capping.  Nothing but
+    those kernels can read a ring: a call against one that they do not take raises RuntimeError.  It is refused
+    (ValueError) together with prefill_chunk — a span of more than 16 queries needs more live keys than C — and on a
+    config none of whose layers would get a ring.  None (the default) changes nothing; any other value raises ValueError."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -849,7 +862,12 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     processors = _processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id)
     if kv_cache is not None and not (isinstance(kv_cache, str) and kv_cache == "fp8"):
         raise ValueError(f"sample_generate: kv_cache={kv_cache!r} (None or \"fp8\")")
-    static_cache = bool(static_cache) or bool(graph) or kv_cache is not None
+    if sliding_cache is not None and not (isinstance(sliding_cache, str) and sliding_cache == "ring"):
+        raise ValueError(f"sample_generate: sliding_cache={sliding_cache!r} (None or \"ring\")")
+    if sliding_cache is not None and prefill_chunk is not None:
+        raise ValueError("sample_generate: sliding_cache=\"ring\" does not take prefill_chunk: a span of more than "
+                         f"{_MIN_PREFILL_CHUNK - 1} queries needs more live keys than a ring holds")
+    static_cache = bool(static_cache) or bool(graph) or kv_cache is not None or sliding_cache is not None
     if static_cache and group is not None:
         raise ValueError("sample_generate: static_cache / graph generation runs in a single process (group must be None)")
     if group is not None:
@@ -875,7 +893,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     if static_cache:
         return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
                                 eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph),
-                                truncation, processors, kv_cache, chunk)
+                                truncation, processors, kv_cache, chunk, sliding_cache)
     S, n = samples, max_new_tokens
     B, T0 = input_ids.shape
     dev = input_ids.device
@@ -1074,12 +1092,29 @@ _SLIDING_STATIC_FAMILIES = ("mistral", "qwen2", "qwen3", "gemma2")
 _STATIC_LAYER_HOOK = None  # tests: a StaticLayer subclass every layer of _static_cache's cache is built from instead
 
 
-def _static_cache(model: Model, capacity: int, kv_cache: Optional[str] = None):
+def _sliding_windows(config, capacity: int) -> List[Optional[int]]:
+    """Per cache layer of a decoder config, the window W of a sliding-window layer that static generation serves (the
+    families of _SLIDING_STATIC_FAMILIES), None for every other layer: the layers transformers' StaticCache would build as
+    sliding ones, as _static_cache finds them.  Needs no GPU (the layers allocate lazily)."""
+    from transformers import StaticCache
+
+    text = config.get_text_config(decoder=True) if hasattr(config, "get_text_config") else config
+    layers = StaticCache(config=config, max_cache_len=int(capacity)).layers
+    if getattr(config, "model_type", None) not in _SLIDING_STATIC_FAMILIES:
+        return [None] * len(layers)
+    window = getattr(text, "sliding_window", None)
+    return [int(window) if getattr(layer, "is_sliding", False) and window is not None else None for layer in layers]
+
+
+def _static_cache(model: Model, capacity: int, kv_cache: Optional[str] = None, sliding_cache: Optional[str] = None):
     """A transformers StaticCache of `capacity` tokens for the wrapped decoder, or the reason it cannot serve.  For the
     families of _SLIDING_STATIC_FAMILIES the sliding-window layers get plain full-capacity StaticLayers too (transformers'
     StaticSlidingWindowLayer branches on a host count and rolls its buffer, so one captured graph could not serve every
     step): the mask carries the window and the decode kernel applies it.  Such a layer holds `capacity` slots, not W.
-    kv_cache="fp8": every layer is a kv_cache.Fp8StaticLayer of the same capacity (after the same refusals)."""
+    kv_cache="fp8": every layer is a kv_cache.Fp8StaticLayer of the same capacity (after the same refusals).
+    sliding_cache="ring": a sliding layer whose ops.ring_slots(W, capacity) is below the capacity becomes a
+    kv_cache.RingStaticLayer (Fp8RingStaticLayer with kv_cache="fp8") of that many slots; a config on which no layer does
+    is refused."""
     from transformers import StaticCache
     from transformers.cache_utils import StaticLayer
 
@@ -1103,11 +1138,25 @@ def _static_cache(model: Model, capacity: int, kv_cache: Optional[str] = None):
                          "sliding-window or other non-static cache layers)")
     if kv_cache is not None and kv_cache != "fp8":
         raise ValueError(f"sample_generate: kv_cache={kv_cache!r} (None or \"fp8\")")
+    if sliding_cache is not None and sliding_cache != "ring":
+        raise ValueError(f"sample_generate: sliding_cache={sliding_cache!r} (None or \"ring\")")
     cls = _STATIC_LAYER_HOOK
     if cls is None and kv_cache == "fp8":
         from .kv_cache import Fp8StaticLayer as cls
     if cls is not None:
         cache.layers = [cls(max_cache_len=int(capacity)) for _ in cache.layers]
+    if sliding_cache == "ring":
+        from . import ops
+        from .kv_cache import Fp8RingStaticLayer, RingStaticLayer
+
+        slots = [ops.ring_slots(w, int(capacity)) for w in _sliding_windows(config, int(capacity))]
+        if not any(c is not None for c in slots):
+            raise ValueError("sample_generate: sliding_cache=\"ring\" would change nothing here: the config has no "
+                             "sliding-window layer whose ring (window + "
+                             f"{ops.DECODE_MAX_QUERIES - 1} slots) is smaller than the capacity of {int(capacity)}")
+        ring = Fp8RingStaticLayer if kv_cache == "fp8" else RingStaticLayer
+        cache.layers = [layer if c is None else ring(max_cache_len=int(capacity), ring_slots=c)
+                        for layer, c in zip(cache.layers, slots)]
     return cache
 
 
@@ -1115,13 +1164,15 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
                      temperature: float, eos_token_id: Optional[int], pad_token_id: int,
                      generator: Optional[torch.Generator], keep_weights: Union[bool, str], max_bytes: Optional[int],
                      graph: bool, truncation=None, processors=None, kv_cache: Optional[str] = None,
-                     prefill_chunk: Optional[int] = None) -> Generation:
+                     prefill_chunk: Optional[int] = None, sliding_cache: Optional[str] = None) -> Generation:
     """sample_generate(static_cache=True / graph=True): the prefill of the default path (a DynamicCache, copied into the
     static one), then decode steps of one shape whose bookkeeping is bf_generate_step (after bf_probs_truncate with a
     truncation: the step's inverse-CDF draw over the filtered, unnormalised row samples the renormalised kept set; with
     logits processors, bf_logits_process at the device step and a second mc_predictive choose the token, and
     bf_generate_step_stat_probs reads its probability from the unprocessed row).  prefill_chunk (checked: smaller than
-    T0): the prompt goes in spans straight into the static cache instead, under the full-capacity mask — no DynamicCache."""
+    T0): the prompt goes in spans straight into the static cache instead, under the full-capacity mask — no DynamicCache.
+    sliding_cache="ring": the sliding layers of the static cache are ring buffers (`_static_cache`); the hand-over's
+    `update` keeps the last ring_slots rows of the prompt in their slots, and nothing else changes."""
     from transformers import DynamicCache
     from transformers.cache_utils import DynamicLayer
 
@@ -1129,7 +1180,7 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
 
     B, T0 = input_ids.shape
     dev = input_ids.device
-    static = _static_cache(model, T0 + n - 1, kv_cache)
+    static = _static_cache(model, T0 + n - 1, kv_cache, sliding_cache)
     inner = model.model if model.model is not None else model
     seed = None
     if do_sample:  # the generation's own Philox key: one draw from the caller's generator per call
