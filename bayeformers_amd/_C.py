@@ -284,6 +284,14 @@ LORA_SYMBOLS = {
     "bf_lora_reduce_da": (_i, [_vp, _vp, _u64, _i, _u64, _u32, _u32, _vp, _vp, _vp]),
 }
 
+# what include/bayeformers_amd_spec.h declares (the epilogue of one speculative iteration of sample_generate): (argmax, draft,
+# probs, the three entropies, B, gamma, V, S, state, max_new_tokens, sequences, seq_stride, T0, stats, finished, lengths,
+# verify ids / positions, draft ids / positions, rewind, speculation, eos, pad, stream)
+SPEC_SYMBOLS = {
+    "bf_spec_accept": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+}
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -370,6 +378,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the Bayesian LoRA entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in SPEC_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the speculative-decoding entry): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

@@ -687,3 +687,157 @@ int bf_logits_process(const void* d_logits, int dtype, int64_t R, int64_t V, int
     BF_HIP_CHECK(hipGetLastError());
     return 0;
 }
+
+// ---- bf_spec_accept: the epilogue of one speculative iteration ------------------------------------------------------
+// One workgroup.  Thread b < B counts row b's leading agreements and, once the common run length a is known, walks its
+// a + 1 kept positions (the eos / pad / finished / lengths rules of generate_step_kernel, one gather per kept token);
+// then every thread helps to write the next iteration's ids and to advance the positions.  B * (gamma + 1) <= 16 rows of
+// scalars: nothing here is worth more than one workgroup, and with one there is no arrival count to keep.
+namespace {
+
+constexpr int SPEC_THREADS = 256, SPEC_MAX_ROWS = 16;
+
+struct SpecParams {
+    const int64_t* argmax;  // [B][G + 1]
+    const int64_t* draft;   // [B][G]
+    const float* probs;     // [B * (G + 1)][V]
+    const float* pe;
+    const float* ee;
+    const float* mi;
+    int64_t* state;  // {step, 0}
+    int64_t* seq;
+    float* stats;
+    uint8_t* finished;
+    int64_t* lengths;
+    int64_t* verify_ids;  // [S * B][G + 1]: column 0
+    int64_t* verify_pos;  // [S * B][G + 1]
+    int64_t* draft_ids;   // [B][2]
+    int64_t* draft_pos;   // [B][G + 1]
+    int64_t* rewind;
+    int64_t* speculation;  // {verify steps, drafts proposed, drafts accepted}
+    int64_t B, G, V, n, seq_stride, T0, eos, pad;
+    int S;
+};
+
+__global__ __launch_bounds__(SPEC_THREADS) void spec_accept_kernel(const SpecParams p) {
+    __shared__ int s_run[SPEC_MAX_ROWS];
+    __shared__ int64_t s_last[SPEC_MAX_ROWS];
+
+    const int tid = threadIdx.x;
+    const int64_t B = p.B, G = p.G, V = p.V, n = p.n;
+    const int64_t step = *p.state;
+    if (step >= n) {  // past the last token: the forwards of this iteration still moved both fills by G + 1
+        if (tid == 0) *p.rewind = G + 1;
+        return;
+    }
+    if (tid < B) {
+        const int64_t b = tid;
+        int run = (int)G;
+        if (!(p.eos >= 0 && p.finished[b])) {
+            run = 0;
+            while (run < G && p.draft[b * G + run] == p.argmax[b * (G + 1) + run]) ++run;
+        }
+        s_run[tid] = run;
+        s_last[tid] = p.verify_ids[b * (G + 1)];  // the token the verify forward was fed first (sample 0's row)
+    }
+    __syncthreads();
+    int64_t room = n - step - 1;  // drafts that still fit in front of the iteration's own token
+    room = room < G ? room : G;
+    int64_t a = room;
+    for (int b = 0; b < B; ++b) a = s_run[b] < a ? s_run[b] : a;
+    __syncthreads();
+
+    if (tid < B) {
+        const int64_t b = tid;
+        bool done = p.eos >= 0 && p.finished[b];
+        int64_t len = p.lengths[b], tok = s_last[tid], before = tok;
+        for (int64_t j = 0; j <= a; ++j) {
+            const int64_t r = b * (G + 1) + j;
+            before = tok;
+            tok = done ? p.pad : (j < a ? p.draft[b * G + j] : p.argmax[r]);
+            const bool in = tok >= 0 && tok < V;
+            const float st[4] = {p.pe[r], p.ee[r], p.mi[r], in ? p.probs[r * V + tok] : 0.0f};
+            for (int i = 0; i < 4; ++i) p.stats[(i * B + b) * n + step + j] = done ? 0.0f : st[i];
+            p.seq[b * p.seq_stride + p.T0 + step + j] = tok;
+            if (!done) len += 1;
+            if (p.eos >= 0) done = done || tok == p.eos;
+        }
+        p.lengths[b] = len;
+        if (p.eos >= 0) p.finished[b] = done;
+        p.draft_ids[2 * b] = before;
+        p.draft_ids[2 * b + 1] = tok;
+        s_last[tid] = tok;
+    }
+    __syncthreads();
+    const int64_t rows = (int64_t)p.S * B;
+    for (int64_t i = tid; i < rows; i += SPEC_THREADS) p.verify_ids[i * (G + 1)] = s_last[i % B];
+    if (p.verify_pos)
+        for (int64_t i = tid; i < rows * (G + 1); i += SPEC_THREADS) p.verify_pos[i] += a + 1;
+    if (p.draft_pos)
+        for (int64_t i = tid; i < B * (G + 1); i += SPEC_THREADS) p.draft_pos[i] += a + 1;
+    if (tid == 0) {
+        p.state[0] = step + a + 1;
+        *p.rewind = G - a;
+        p.speculation[0] += 1;
+        p.speculation[1] += room;
+        p.speculation[2] += a;
+    }
+}
+
+}  // namespace
+
+int bf_spec_accept(const int64_t* d_argmax, const int64_t* d_draft, const float* d_probs,
+                   const float* d_predictive_entropy, const float* d_expected_entropy, const float* d_mutual_information,
+                   int64_t B, int64_t gamma, int64_t V, int S, int64_t* d_state, int64_t max_new_tokens,
+                   int64_t* d_sequences, int64_t seq_stride, int64_t T0, float* d_stats, uint8_t* d_finished,
+                   int64_t* d_lengths, int64_t* d_verify_ids, int64_t* d_verify_positions, int64_t* d_draft_ids,
+                   int64_t* d_draft_positions, int64_t* d_rewind, int64_t* d_speculation, int64_t eos_token_id,
+                   int64_t pad_token_id, void* stream) {
+    const char* what = "bf_spec_accept";
+    if (B < 1 || gamma < 1 || B * (gamma + 1) > SPEC_MAX_ROWS)
+        BF_FAIL("%s: B=%lld rows of gamma=%lld + 1 positions must be at least 1 x 2 and at most %d in all", what,
+                (long long)B, (long long)gamma, SPEC_MAX_ROWS);
+    if (V < 1 || S < 1 || max_new_tokens < 1)
+        BF_FAIL("%s: V=%lld, S=%d, max_new_tokens=%lld must be positive", what, (long long)V, S, (long long)max_new_tokens);
+    if (T0 < 0 || seq_stride < T0 + max_new_tokens)
+        BF_FAIL("%s: a sequence row of %lld tokens does not hold T0=%lld + %lld", what, (long long)seq_stride,
+                (long long)T0, (long long)max_new_tokens);
+    if (!d_argmax || !d_draft || !d_probs || !d_predictive_entropy || !d_expected_entropy || !d_mutual_information ||
+        !d_state || !d_sequences || !d_stats || !d_lengths || !d_verify_ids || !d_draft_ids || !d_rewind || !d_speculation)
+        BF_FAIL("%s: NULL argument", what);
+    if (eos_token_id >= 0 && !d_finished) BF_FAIL("%s: an eos token needs the finished flags", what);
+    if (((uintptr_t)d_argmax | (uintptr_t)d_draft | (uintptr_t)d_state | (uintptr_t)d_sequences | (uintptr_t)d_lengths |
+         (uintptr_t)d_verify_ids | (uintptr_t)d_verify_positions | (uintptr_t)d_draft_ids | (uintptr_t)d_draft_positions |
+         (uintptr_t)d_rewind | (uintptr_t)d_speculation) & 7)
+        BF_FAIL("%s: int64 arguments must be 8-byte aligned", what);
+    SpecParams p = {};
+    p.argmax = d_argmax;
+    p.draft = d_draft;
+    p.probs = d_probs;
+    p.pe = d_predictive_entropy;
+    p.ee = d_expected_entropy;
+    p.mi = d_mutual_information;
+    p.state = d_state;
+    p.seq = d_sequences;
+    p.stats = d_stats;
+    p.finished = d_finished;
+    p.lengths = d_lengths;
+    p.verify_ids = d_verify_ids;
+    p.verify_pos = d_verify_positions;
+    p.draft_ids = d_draft_ids;
+    p.draft_pos = d_draft_positions;
+    p.rewind = d_rewind;
+    p.speculation = d_speculation;
+    p.B = B;
+    p.G = gamma;
+    p.V = V;
+    p.n = max_new_tokens;
+    p.seq_stride = seq_stride;
+    p.T0 = T0;
+    p.eos = eos_token_id;
+    p.pad = pad_token_id;
+    p.S = S;
+    spec_accept_kernel<<<1, SPEC_THREADS, 0, (hipStream_t)stream>>>(p);
+    BF_HIP_CHECK(hipGetLastError());
+    return 0;
+}

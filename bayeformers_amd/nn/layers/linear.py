@@ -240,7 +240,10 @@ class Linear(KernelLayer):
         """y = x W^T + b with W ~ N(mu_w, softplus(rho_w)), b ~ N(mu_b, softplus(rho_b))  (linear.py:83-104).
 
         Inside `bnn.Model` with S Monte-Carlo samples in flight the input is [S*B, ..., in_features]
-        (sample-major) and slab s is multiplied by W_s; otherwise S = 1 and one fresh sample index is used."""
+        (sample-major) and slab s is multiplied by W_s; otherwise S = 1 and one fresh sample index is used.
+        Inside `Model.posterior_mean()` nothing is sampled: y = x mu_w^T + mu_b (`_mean_forward`)."""
+        if bfr.STATE.mean is not None:
+            return self._mean_forward(bfr.STATE.mean, input)
         if bfr.STATE.ctx is None:
             again = bfr.recompute_context()
             if again is not None:  # a checkpointed block recomputed during backward: the forward's own epsilon
@@ -319,6 +322,42 @@ class Linear(KernelLayer):
                 y = ops.planned_linear_forward(x2, w_s, b_s, S, N, K, act)
         self._lp_view, self._lp_dirty = slot, True
         return y
+
+    def mean_weights(self, mean=None):
+        """(mu_w in the compute dtype [N, K], mu_b [1, N] fp32 or None): what a forward inside Model.posterior_mean() multiplies
+        by.  The 16-bit copy is made once and kept on the layer; a new mu (another address or version counter), another
+        compute dtype or a later stale epoch (ops.stale_epoch; ops.invalidate_caches drops it too) makes it again.  Inside a
+        keep_weights="fp8" block the centre copy that block already holds is returned instead, and nothing is kept here."""
+        cdt = self.compute_dtype or bfr.get_compute_dtype()
+        mu = self.weight.mu
+        bias = self.bias.mu.detach().to(torch.float32).reshape(1, -1) if isinstance(self.bias, Gaussian) else None
+        center = mean.center(self, cdt) if mean is not None else None
+        if center is not None:
+            return center, bias
+        key = (cdt, mu.device, mu.data_ptr(), mu._version, bfr.STATE.stale_epoch)
+        hit = self.__dict__.get("_mean_cache")
+        if hit is None or hit[0] != key:
+            with torch.inference_mode(False), torch.no_grad():  # (kept across forwards of any mode)
+                hit = self._mean_cache = (key, mu.detach().to(cdt, copy=True).contiguous())
+        return hit[1], bias
+
+    def _mean_forward(self, mean, input: Tensor) -> Tensor:
+        """A forward inside Model.posterior_mean(): y = act(x mu_w^T + mu_b), one row block whatever monte_carlo says; no
+        draw, no log-probs, no sample index.  At most ops.SKINNY_ROWS rows (a decode step): bf_gemm_nt_skinny with S = 1;
+        more (a prefill): the tiled GEMM, as a planned forward runs it."""
+        N, K = self.out_features, self.in_features
+        x2 = input.reshape(-1, K)
+        if x2.shape[0] == 0:
+            return input.new_empty(*input.shape[:-1], N)
+        w, b = self.mean_weights(mean)
+        w = w.view(1, N, K)
+        act = 1 if self.activation == "gelu" else 0
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        if ops.skinny_supported(x2, w, 1, K):
+            y = ops.skinny_linear_forward(x2, w, b, 1, N, K, act)
+        else:
+            y = ops.planned_linear_forward(x2, w, b, 1, N, K, act)
+        return y.view(*input.shape[:-1], N)
 
     def _stacked_forward(self, ctx, x2: Tensor, S: int, base: int = 0, need_grad: bool = False) -> Optional[Tensor]:
         """Layers that read the same activations (query / key / value): whichever of them runs first multiplies x by

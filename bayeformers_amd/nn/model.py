@@ -205,6 +205,23 @@ class _KeptFp8Weights(_KeptWeights):
         return plan.views[id(layer)]
 
 
+class _MeanForward:
+    """What the bnn.Linear layers of a forward inside `Model.posterior_mean()` share: the model, and through it the centre
+    copies of an enclosing pinned_samples(keep_weights="fp8") block."""
+
+    def __init__(self, model: "Model"):
+        self.model = model
+
+    def center(self, layer, cdt: torch.dtype) -> Optional[Tensor]:
+        """The bf16 posterior mean [N, K] the enclosing keep_weights="fp8" block holds for `layer`, once its first forward
+        has made it; None otherwise (the layer then keeps a copy of its own)."""
+        kept = self.model.__dict__.get("_kept")
+        if kept is None or not kept.fp8 or not kept.ready or cdt != torch.bfloat16:
+            return None
+        entry = kept.store.get(id(layer))
+        return entry[0] if entry is not None else None
+
+
 class _KLFn(torch.autograd.Function):
     """[S, 2] per-sample {log_prior, log_q} of the model as a differentiable function of every layer's mu and rho
     (opt-in, bayeformers_amd.set_kl_gradient).  Backward = one bf_kl_grad launch per parameter tensor."""
@@ -259,6 +276,8 @@ class Model(Module):
 
     def __call__(self, *args, **kwargs):
         if bfr.STATE.ctx is not None:  # nested bnn.Model: the outer forward owns the sample indices
+            return super(Model, self).__call__(*args, **kwargs)
+        if bfr.STATE.mean is not None:  # posterior_mean(): no sample indices, no log-prob slots, no plan, no replay
             return super(Model, self).__call__(*args, **kwargs)
         out = auto_forward(self, args, kwargs)  # an evaluation forward seen before: replayed from its HIP graph
         if out is not None:
@@ -413,6 +432,37 @@ class Model(Module):
         finally:
             self._pinned = self._pinned_lp = self._kept = None  # (the kept samples' arenas go with the last reference)
             bfr.commit_samples(total)
+
+    @contextlib.contextmanager
+    def posterior_mean(self):
+        """Run every forward inside on the posterior MEAN of the weights: each bnn.Linear computes x mu_w^T + mu_b and draws
+        nothing.  The input is ONE row block — [B, ...], not the [S*B, ...] of `monte_carlo(S)` — and the forward reserves
+        no sample index, writes no log-probs (log_prob_samples() stays the last sampled forward's) and is never replayed
+        from a HIP graph.  It nests inside `monte_carlo` / `pinned_samples` (keep_weights in any form) and leaves the
+        pinned draws, the kept weights and the sample counter as they are: the sampled forward after it is bitwise what it
+        would have been.  That is the draft model of sample_generate(speculative=...): the same network at 1/S of the weight
+        traffic.
+
+        Each layer multiplies a copy of mu_w in the compute dtype, made at its first mean forward and kept on the layer
+        (Linear.mean_weights; dropped by a new mu, a later stale epoch or ops.invalidate_caches): plan.mean_weight_bytes(model,
+        dtype) bytes, P * 2 in bf16 against the S * P * 2 of keep_weights=True.  Inside keep_weights="fp8" the block's own
+        centre copies are read and nothing is added.  At most ops.SKINNY_ROWS rows run bf_gemm_nt_skinny with S = 1, more
+        rows the tiled GEMM.  Inference only (no gradient); a model with a bnn.Embedding or a bnn.LoRALinear, which have no
+        mean form yet, is refused (ValueError)."""
+        if bfr.STATE.ctx is not None:
+            raise RuntimeError("posterior_mean: entered inside a running forward")
+        if torch.is_grad_enabled():
+            raise RuntimeError("posterior_mean is inference only: enter it under torch.no_grad()")
+        other = sorted({type(l).__name__ for l in self.fused_children() if not isinstance(l, Linear)})
+        if other:
+            raise ValueError(f"posterior_mean: the model has {', '.join(other)} layers, which have no posterior-mean "
+                             "forward (bnn.Linear only)")
+        prev = bfr.STATE.mean
+        bfr.STATE.mean = _MeanForward(self)
+        try:
+            yield self
+        finally:
+            bfr.STATE.mean = prev
 
     def _keep_weights_check(self, max_bytes: Optional[int], fp8: bool = False) -> "_KeptWeights":
         """Everything pinned_samples(keep_weights=True or "fp8") refuses, checked before anything is reserved or allocated."""

@@ -132,6 +132,7 @@ def invalidate_caches(module) -> None:
             m._consts = None
         elif isinstance(m, Model):
             m._plan = None
+        m.__dict__.pop("_mean_cache", None)  # (a bnn.Linear's 16-bit copy of its posterior mean: Model.posterior_mean)
 
 
 def fill_prior(dst: "_C.bf_prior_t", prior, gaussian=None) -> bool:
@@ -1730,6 +1731,70 @@ def generate_step(probs: Tensor, predictive_entropy: Tensor, expected_entropy: T
         _C.check(_C.lib().bf_generate_step_stat_probs(probs.data_ptr(), stat_probs.data_ptr(), *args),
                  "bf_generate_step_stat_probs")
     GENERATE_CALLS[0] += 1
+
+
+SPEC_ACCEPT_CALLS = [0]  # launches of bf_spec_accept through speculative_accept (tests, diagnostics)
+
+
+def speculative_accept(argmax: Tensor, draft: Tensor, probs: Tensor, predictive_entropy: Tensor, expected_entropy: Tensor,
+                       mutual_information: Tensor, samples: int, state: Tensor, sequences: Tensor, T0: int, stats: Tensor,
+                       finished: Optional[Tensor], lengths: Tensor, verify_ids: Tensor, verify_positions: Optional[Tensor],
+                       draft_ids: Tensor, draft_positions: Optional[Tensor], rewind: Tensor, speculation: Tensor,
+                       eos_token_id: Optional[int], pad_token_id: int) -> None:
+    """The epilogue of one speculative iteration in one launch (bf_spec_accept; contract in include/bayeformers_amd_spec.h), at
+    the step state[0]: argmax [B, γ+1] int64 (the model-average argmax of each verified position), draft [B, γ] int64,
+    probs [B·(γ+1), V] fp32 and the three entropies [B·(γ+1)] → the a + 1 kept tokens of every row (a: the shortest run
+    of agreeing drafts over the unfinished rows, clipped to the tokens left) into sequences [B, T0 + n] and stats
+    [4, B, n], finished [B] bool and lengths [B] int64 as generate_step updates them; column 0 of verify_ids
+    [samples·B, γ+1], draft_ids [B, 2], a + 1 added to verify_positions [samples·B, γ+1] and draft_positions [B, γ+1]
+    (or None), state[0] += a + 1, rewind [1] = γ − a and speculation [3] += {1, drafts that had room, a}.  No host
+    synchronisation: capturable."""
+    _require_device(probs, "speculative_accept: probs")
+    if probs.dim() != 2 or probs.dtype != torch.float32 or not probs.is_contiguous():
+        raise _C.BayeFormersAMDError("speculative_accept: probs must be contiguous fp32 [B * (gamma + 1), V]")
+    if draft.dim() != 2 or draft.shape[0] < 1 or draft.shape[1] < 1:
+        raise _C.BayeFormersAMDError("speculative_accept: draft must be int64 [B, gamma] with B, gamma >= 1")
+    B, G = draft.shape
+    R, V = probs.shape
+    n = stats.shape[-1] if stats.dim() == 3 else 0
+    S, dev = int(samples), probs.device
+    if R != B * (G + 1) or R > SKINNY_ROWS:
+        raise _C.BayeFormersAMDError(f"speculative_accept: probs has {R} rows for B={B}, gamma={G}: B * (gamma + 1), at "
+                                     f"most {SKINNY_ROWS}")
+
+    def need(t, what, dtype, shape):
+        if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise _C.BayeFormersAMDError(f"speculative_accept: {what} must be contiguous {dtype} {list(shape)} on {dev}")
+
+    need(argmax, "argmax", torch.int64, (B, G + 1))
+    need(draft, "draft", torch.int64, (B, G))
+    for t, what in ((predictive_entropy, "predictive_entropy"), (expected_entropy, "expected_entropy"),
+                    (mutual_information, "mutual_information")):
+        need(t, what, torch.float32, (R,))
+    need(stats, "stats", torch.float32, (4, B, n))
+    need(state, "state", torch.int64, (2,))
+    need(lengths, "lengths", torch.int64, (B,))
+    need(verify_ids, "verify_ids", torch.int64, (S * B, G + 1))
+    need(draft_ids, "draft_ids", torch.int64, (B, 2))
+    if verify_positions is not None:
+        need(verify_positions, "verify_positions", torch.int64, (S * B, G + 1))
+    if draft_positions is not None:
+        need(draft_positions, "draft_positions", torch.int64, (B, G + 1))
+    need(rewind, "rewind", torch.int64, (1,))
+    need(speculation, "speculation", torch.int64, (3,))
+    if sequences.dim() != 2 or sequences.shape[0] != B or sequences.stride(1) != 1 or sequences.dtype != torch.int64 \
+            or sequences.device != dev:
+        raise _C.BayeFormersAMDError("speculative_accept: sequences must be int64 [B, T0 + n] with contiguous rows")
+    if eos_token_id is not None:
+        need(finished, "finished", torch.bool, (B,))
+    _C.check(_C.lib().bf_spec_accept(
+        argmax.data_ptr(), draft.data_ptr(), probs.data_ptr(), predictive_entropy.data_ptr(), expected_entropy.data_ptr(),
+        mutual_information.data_ptr(), B, G, V, S, state.data_ptr(), n, sequences.data_ptr(), sequences.stride(0), int(T0),
+        stats.data_ptr(), finished.data_ptr() if finished is not None else None, lengths.data_ptr(), verify_ids.data_ptr(),
+        verify_positions.data_ptr() if verify_positions is not None else None, draft_ids.data_ptr(),
+        draft_positions.data_ptr() if draft_positions is not None else None, rewind.data_ptr(), speculation.data_ptr(),
+        int(eos_token_id) if eos_token_id is not None else -1, int(pad_token_id), _stream_ptr()), "bf_spec_accept")
+    SPEC_ACCEPT_CALLS[0] += 1
 
 
 TRUNCATE_CALLS = [0]  # launches of bf_probs_truncate through truncate_probs (tests, diagnostics)

@@ -324,6 +324,20 @@ def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
     return total
 
 
+def mean_weight_bytes(model, dtype) -> int:
+    """Device bytes the forwards of Model.posterior_mean() keep at compute dtype `dtype` (torch.float32, torch.bfloat16 or
+    torch.float16): one copy of every Bayesian Linear's posterior-mean weight, sum(N * K) * element size — P * 2 bytes in
+    bf16 for P Linear weights, against the S * P * 2 of kept_weight_bytes(model, S, dtype).  The fp32 bias means are read
+    where they are.  Inside pinned_samples(keep_weights="fp8") the block's centre copies are read instead and these bytes
+    are not spent.  Needs no GPU."""
+    from .nn.layers.linear import Linear
+
+    if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise ValueError(f"mean_weight_bytes: dtype {dtype} (float32, bfloat16 or float16)")
+    esz = 4 if dtype == torch.float32 else 2
+    return sum(l.out_features * l.in_features * esz for l in model.fused_children() if isinstance(l, Linear))
+
+
 def kv_cache_bytes(model, samples: int, batch: int, capacity: int, dtype=torch.bfloat16, fp8: bool = False,
                    ring: bool = False) -> int:
     """Device bytes the static KV cache of sample_generate(static_cache=True) holds for `samples` Monte-Carlo samples of

@@ -37,6 +37,7 @@ class _State:
         self.next_dropout_site = 1  # ... and one `site` number per module that applies a dropout
         self.stale_epoch = 0        # the library's stale-prior counter as of the running forward (ops.refresh_stale_epoch)
         self.counter_moves = 0      # host-side count of the writes to device_counter (counter_snapshot's cache key)
+        self.mean = None            # inside Model.posterior_mean(): that block's nn.model._MeanForward (no sampling at all)
 
 
 STATE = _State()

@@ -746,6 +746,8 @@ class Generation:
         lengths                     [B] int64    tokens generated, the EOS included
         log_prior                   [S] fp64     per-sample log prior of the pinned weight draws
         log_variational_posterior   [S] fp64     per-sample log q of the same draws
+        speculation                 [3] int64    sample_generate(speculative=...) only, else None: {verify steps, draft
+                                                 tokens proposed, draft tokens accepted}
     The statistics of a step after a row's EOS are 0."""
     sequences: Tensor
     predictive_entropy: Tensor
@@ -755,6 +757,9 @@ class Generation:
     lengths: Tensor
     log_prior: Tensor
     log_variational_posterior: Tensor
+    # (an attribute with a default, deliberately not a dataclass field: fields(), the constructor, == and repr stay the
+    # eight tensors every generation has, so code that walks the fields never meets a None)
+    speculation = None
 
 
 def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor] = None, samples: int = 1,
@@ -766,7 +771,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
                     min_p: Optional[float] = None, repetition_penalty: Optional[float] = None,
                     no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
                     kv_cache: Optional[str] = None, prefill_chunk: Optional[int] = None,
-                    sliding_cache: Optional[str] = None) -> Generation:
+                    sliding_cache: Optional[str] = None, speculative: Optional[int] = None) -> Generation:
     """Generate with a Bayesian decoder (a HuggingFace causal LM converted by `to_bayesian`) and the per-token predictive
     uncertainty of its Monte-Carlo posterior.
 
@@ -850,7 +855,27 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     bf_attention_decode_gqa_ring_kv8), keep_weights, truncation, the logits processors and soft-capping.  Nothing but
     those kernels can read a ring: a call against one that they do not take raises RuntimeError.  It is refused
     (ValueError) together with prefill_chunk — a span of more than 16 queries needs more live keys than C — and on a
-    config none of whose layers would get a ring.  None (the default) changes nothing; any other value raises ValueError."""
+    config none of whose layers would get a ring.  None (the default) changes nothing; any other value raises ValueError.
+
+    speculative=γ (implies static_cache; needs keep_weights) is greedy speculative decoding with the posterior mean as the
+    draft model: an iteration drafts γ tokens per row under `model.posterior_mean()` — the same network on one weight set,
+    1/S of the weight traffic, with a bf16 cache of its own at B rows — then scores the last kept token and the γ drafts
+    under the S pinned draws in ONE forward of γ + 1 queries per row (the same skinny GEMM and decode attention launches
+    as a one-token step), and keeps the longest prefix the model-average argmax agrees with plus the model average's own
+    next token (one bf_spec_accept launch; all rows advance together by the shortest agreeing run over the unfinished
+    rows).  Both caches' fill pointers are then set back by the rejected tokens, on the device.  Every emitted token is the
+    model average's argmax given the tokens before it, and the statistics are those of the verified position: the text and
+    the uncertainties are those of greedy generation on another valid 16-bit route (γ + 1 queries through the decode
+    kernels) — close to, not bitwise, the one-token loop's.  `Generation.speculation` counts {verify steps, drafts
+    proposed, drafts accepted}.  γ must be an int in [1, DECODE_MAX_QUERIES - 1] with B * (γ + 1) <= ops.SKINNY_ROWS.  It
+    composes with graph=True (the whole iteration is one captured graph; the host reads the step counter and the finished
+    flags every 8 replays, and iterations past max_new_tokens write nothing), kv_cache="fp8" (the samples' cache; the
+    draft's stays bf16), temperature, eos_token_id / pad_token_id, prefill_chunk, the sliding-window families on their
+    full-capacity layers and soft-capping.  Refused (ValueError): no keep_weights; do_sample and the truncation
+    arguments (rejection sampling against the draft is not built); the logits processors (they depend on the tokens of
+    earlier positions of the same span); sliding_cache="ring" (a rejected draft's key would already have overwritten a
+    live slot); group; models with a bnn.LoRALinear or a bnn.Embedding (no posterior-mean forward yet).  None (the
+    default) changes nothing, bit for bit."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:
         raise ValueError(f"sample_generate: samples={samples} (at least 1)")
@@ -858,6 +883,9 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         raise ValueError(f"sample_generate: max_new_tokens={max_new_tokens} (at least 1)")
     if not temperature > 0.0:
         raise ValueError(f"sample_generate: temperature={temperature} (must be positive)")
+    gamma = _checked_speculative(speculative, input_ids, do_sample, (top_k, top_p, min_p),
+                                 (repetition_penalty, no_repeat_ngram_size, min_new_tokens), sliding_cache, group,
+                                 keep_weights)
     truncation = _truncation(top_k, top_p, min_p, do_sample)
     processors = _processors(repetition_penalty, no_repeat_ngram_size, min_new_tokens, eos_token_id)
     if kv_cache is not None and not (isinstance(kv_cache, str) and kv_cache == "fp8"):
@@ -867,7 +895,8 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     if sliding_cache is not None and prefill_chunk is not None:
         raise ValueError("sample_generate: sliding_cache=\"ring\" does not take prefill_chunk: a span of more than "
                          f"{_MIN_PREFILL_CHUNK - 1} queries needs more live keys than a ring holds")
-    static_cache = bool(static_cache) or bool(graph) or kv_cache is not None or sliding_cache is not None
+    static_cache = bool(static_cache) or bool(graph) or kv_cache is not None or sliding_cache is not None \
+        or gamma is not None
     if static_cache and group is not None:
         raise ValueError("sample_generate: static_cache / graph generation runs in a single process (group must be None)")
     if group is not None:
@@ -890,6 +919,15 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         raise ValueError(f"sample_generate: kv_cache=\"fp8\" needs bfloat16 compute (set_compute_dtype): at "
                          f"{bfr.get_compute_dtype()} the dequantised cache rows are not exact")
     chunk = _checked_prefill_chunk(model, prefill_chunk, input_ids.shape[1])
+    if gamma is not None:
+        from .nn.layers.linear import Linear
+
+        other = sorted({type(l).__name__ for l in model.fused_children() if not isinstance(l, Linear)})
+        if other:
+            raise ValueError(f"sample_generate: speculative needs a posterior-mean draft, and the model's {', '.join(other)} "
+                             "layers have no posterior-mean forward yet (bnn.Linear only)")
+        return _generate_speculative(model, input_ids, attention_mask, samples, max_new_tokens, gamma, temperature,
+                                     eos_token_id, int(pad_token_id), keep_weights, max_bytes, bool(graph), kv_cache, chunk)
     if static_cache:
         return _generate_static(model, input_ids, attention_mask, samples, max_new_tokens, do_sample, temperature,
                                 eos_token_id, int(pad_token_id), generator, keep_weights, max_bytes, bool(graph),
@@ -1269,3 +1307,222 @@ def _generate_static(model: Model, input_ids: Tensor, attention_mask: Optional[T
             decode(t)
             t += 1
     return Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])
+
+
+# tools/speculative_bench.py: a list that, while set, makes _generate_speculative(graph=True) capture the draft steps, the
+# verify forward and the accept launch as three graphs and append the four events around each iteration's replays
+_SECTION_TIMES = None
+
+
+def _checked_speculative(speculative, input_ids: Tensor, do_sample: bool, truncation_args, processor_args, sliding_cache,
+                         group, keep_weights) -> Optional[int]:
+    """sample_generate's checked speculative=γ (None: off), with everything it is refused together with; needs no device."""
+    if speculative is None:
+        return None
+    from . import ops
+
+    top = ops.DECODE_MAX_QUERIES - 1
+    if isinstance(speculative, bool) or not isinstance(speculative, numbers.Integral) or not 1 <= speculative <= top:
+        raise ValueError(f"sample_generate: speculative={speculative!r} (None or an int in [1, {top}]: a verify step "
+                         f"carries γ + 1 <= {ops.DECODE_MAX_QUERIES} queries)")
+    gamma = int(speculative)
+    B = int(input_ids.shape[0]) if input_ids.dim() == 2 else 1
+    if B * (gamma + 1) > ops.SKINNY_ROWS:
+        raise ValueError(f"sample_generate: speculative={gamma} with {B} prompt rows verifies {B * (gamma + 1)} rows per "
+                         f"sample: the skinny GEMM takes at most {ops.SKINNY_ROWS} (B * (γ + 1) <= {ops.SKINNY_ROWS})")
+    if not keep_weights:
+        raise ValueError("sample_generate: speculative needs keep_weights (True or \"fp8\"): without kept weights there is "
+                         "no S-fold weight stream for the verify step to amortise")
+    if do_sample:
+        raise ValueError("sample_generate: speculative is greedy: do_sample=True would need rejection sampling against "
+                         "the draft's distribution, which is not built")
+    if any(v is not None for v in truncation_args):
+        raise ValueError("sample_generate: speculative does not take top_k / top_p / min_p: they truncate a draw, and "
+                         "speculation is greedy")
+    if any(v is not None for v in processor_args):
+        raise ValueError("sample_generate: speculative does not take repetition_penalty / no_repeat_ngram_size / "
+                         "min_new_tokens: inside a verified span they depend on the tokens of its earlier positions")
+    if sliding_cache is not None:
+        raise ValueError("sample_generate: speculative does not take sliding_cache=\"ring\": a rejected draft's key would "
+                         "already have overwritten a live slot of the ring")
+    if group is not None:
+        raise ValueError("sample_generate: speculative generation runs in a single process (group must be None)")
+    return gamma
+
+
+def _generate_speculative(model: Model, input_ids: Tensor, attention_mask: Optional[Tensor], S: int, n: int, gamma: int,
+                          temperature: float, eos_token_id: Optional[int], pad_token_id: int,
+                          keep_weights: Union[bool, str], max_bytes: Optional[int], graph: bool,
+                          kv_cache: Optional[str] = None, prefill_chunk: Optional[int] = None) -> Generation:
+    """sample_generate(speculative=γ): greedy generation by draft and verify over two static caches of capacity
+    T0 + n + γ — the samples' (S·B rows, FP8 with kv_cache="fp8"), prefilled by _generate_static's routes, and the
+    draft's (B rows, always 16-bit), prefilled by one posterior-mean forward and set back by one token, so that the first
+    draft step of EVERY iteration feeds two tokens: the last kept one and the one after it.  (After a fully accepted run
+    the last draft was never fed to the draft model; after a rejection it was, and is rewritten with the same row.)
+
+    One iteration, of fixed shapes: γ draft steps at B rows under `posterior_mean()` (argmax, fed to the next); one verify
+    forward of [S·B, γ + 1] tokens, whose [S, B·(γ+1), V] logits go through mc_predictive as one batch of rows;
+    bf_spec_accept; every layer of both caches has its fill pointer lowered by the device scalar that launch wrote.  Rows
+    past a fill are overwritten by the next iteration and hidden meanwhile by the causal mask, which is built from the
+    fill.  The host does not know how many tokens an iteration kept: it runs (graph: replays) iterations and reads the step
+    counter and the finished flags — every iteration when eager, every _FINISHED_EVERY replays with a graph; iterations
+    at or past n write nothing but the rewind."""
+    from transformers import DynamicCache
+    from transformers.cache_utils import DynamicLayer
+
+    from . import ops
+
+    B, T0 = input_ids.shape
+    dev = input_ids.device
+    G = int(gamma)
+    # a verify step at step t writes slots T0 + t - 1 .. T0 + t - 1 + γ.  The last one that emits runs at t <= n - 1; an
+    # iteration replayed after the n-th token (t = n: bf_spec_accept then only rewinds) still runs its forwards, one slot on
+    capacity = T0 + n + G
+    static = _static_cache(model, capacity, kv_cache, None)
+    draft = _static_cache(model, capacity, None, None)
+    inner = model.model if model.model is not None else model
+    config = inner.config.get_text_config(decoder=True) if hasattr(inner.config, "get_text_config") else inner.config
+    mask1 = attention_mask.to(torch.long) if attention_mask is not None else None
+    pos1 = (mask1.cumsum(-1) - 1).clamp(min=0) if mask1 is not None else None
+    ids = input_ids.repeat(S, 1)
+    mask = mask1.repeat(S, 1) if mask1 is not None else None
+    pos = pos1.repeat(S, 1) if pos1 is not None else None
+
+    sequences = torch.full((B, T0 + n), int(pad_token_id), dtype=torch.long, device=dev)
+    sequences[:, :T0] = input_ids
+    stats = torch.zeros((4, B, n), dtype=torch.float32, device=dev)
+    lengths = torch.zeros(B, dtype=torch.long, device=dev)
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    state = torch.zeros(2, dtype=torch.long, device=dev)
+    speculation = torch.zeros(3, dtype=torch.long, device=dev)
+    rewind = torch.zeros(1, dtype=torch.long, device=dev)
+    first_ids = torch.empty(S * B, dtype=torch.long, device=dev)
+    verify_ids = torch.zeros((S * B, G + 1), dtype=torch.long, device=dev)
+    draft_ids = torch.zeros((B, 2), dtype=torch.long, device=dev)
+    drafts = torch.zeros((B, G), dtype=torch.long, device=dev)
+    steps = torch.arange(G + 1, device=dev)
+    # positions: the verify forward feeds the last emitted token (the one after the prompt's last, to begin with) and the γ
+    # drafts; the draft steps feed the token in front of it too.  bf_spec_accept advances both by the tokens kept.
+    last = pos1[:, -1:] if pos1 is not None else torch.full((B, 1), T0 - 1, dtype=torch.long, device=dev)
+    draft_pos = (last + steps[None, :]).contiguous()
+    verify_pos = (last + 1 + steps[None, :]).repeat(S, 1).contiguous()
+    if mask is not None:
+        full_mask = torch.cat([mask, mask.new_ones((S * B, capacity - T0))], 1)
+        draft_mask = full_mask[:B].contiguous()
+    else:
+        full_mask = draft_mask = None
+
+    def mean_forward(tokens, positions):
+        with model.posterior_mean():
+            return model(input_ids=tokens, attention_mask=draft_mask, position_ids=positions, past_key_values=draft,
+                         use_cache=True)
+
+    verified = [None]  # the verify forward's Predictive, read by the accept section
+
+    def draft_steps():
+        for i in range(G):  # draft step i feeds draft i - 1 (the first: the last two tokens kept) and proposes draft i
+            out = mean_forward(draft_ids if i == 0 else drafts[:, i - 1:i],
+                               draft_pos[:, :2] if i == 0 else draft_pos[:, i + 1:i + 2])
+            drafts[:, i] = out.logits[:, -1, :].argmax(-1)
+        verify_ids.view(S, B, G + 1)[:, :, 1:] = drafts
+
+    def verify():
+        out = model(input_ids=verify_ids, attention_mask=full_mask, position_ids=verify_pos, past_key_values=static,
+                    use_cache=True)
+        logits = out.logits.reshape(S, B * (G + 1), -1)
+        if temperature != 1.0:
+            logits = logits.float() / temperature
+        verified[0] = mc_predictive(logits)
+
+    def accept():
+        pred = verified[0]
+        ops.speculative_accept(pred.prediction.view(B, G + 1), drafts, pred.probs, pred.predictive_entropy,
+                               pred.expected_entropy, pred.mutual_information, S, state, sequences, T0, stats, finished,
+                               lengths, verify_ids, verify_pos, draft_ids, draft_pos, rewind, speculation, eos_token_id,
+                               pad_token_id)
+        for cache in (static, draft):
+            for layer in cache.layers:
+                layer.cumulative_length.sub_(rewind[0])
+
+    def iteration():
+        draft_steps()
+        verify()
+        accept()
+
+    def done():
+        if eos_token_id is not None:
+            return bool((state[0] >= n) | finished.all())
+        return int(state[0]) >= n
+
+    with model.monte_carlo(S), model.pinned_samples(keep_weights=keep_weights, max_bytes=max_bytes):
+        if prefill_chunk is not None:
+            heads = int(config.num_attention_heads)
+            static.early_initialization(S * B, int(getattr(config, "num_key_value_heads", None) or heads),
+                                        int(getattr(config, "head_dim", None) or config.hidden_size // heads),
+                                        bfr.get_compute_dtype(), dev)
+            out, lp = _chunked_prefill(model, ids, pos, lambda b: full_mask, static, _prefill_spans(T0, prefill_chunk))
+        else:
+            dynamic = DynamicCache(config=getattr(inner, "config", None))
+            dynamic.layers = [DynamicLayer() if getattr(layer, "is_sliding", False) else layer for layer in dynamic.layers]
+            out = model(input_ids=ids, attention_mask=mask, position_ids=pos, past_key_values=dynamic, use_cache=True)
+            lp = model.log_prob_samples().clone()
+            for i, layer in enumerate(dynamic.layers):
+                static.update(layer.keys, layer.values, i)
+                layer.keys = layer.values = None
+            del dynamic
+        # the first token, as _generate_static's step 0 chooses it
+        logits = out.logits[:, -1, :].reshape(S, B, -1)
+        if temperature != 1.0:
+            logits = logits.float() / temperature
+        pred = mc_predictive(logits)
+        ops.generate_step(pred.probs, pred.predictive_entropy, pred.expected_entropy, pred.mutual_information, S, state,
+                          sequences, T0, stats, finished, lengths, first_ids, None, eos_token_id, pad_token_id)
+        del out, pred
+        if n > 1:
+            # the draft's prompt: one posterior-mean forward at B rows (the pinned draws and the kept weights stay as they
+            # are), handed to its static cache; one token back, so that the first draft step rewrites the prompt's last
+            dynamic = DynamicCache(config=getattr(inner, "config", None))
+            dynamic.layers = [DynamicLayer() if getattr(layer, "is_sliding", False) else layer for layer in dynamic.layers]
+            with model.posterior_mean():
+                model(input_ids=input_ids, attention_mask=mask1, position_ids=pos1, past_key_values=dynamic, use_cache=True)
+            for i, layer in enumerate(dynamic.layers):
+                draft.update(layer.keys, layer.values, i)
+                layer.keys = layer.values = None
+            del dynamic
+            for layer in draft.layers:
+                layer.cumulative_length.sub_(1)
+            verify_ids[:, 0] = first_ids
+            draft_ids[:, 0] = input_ids[:, -1]
+            draft_ids[:, 1] = first_ids[:B]
+            if not done():
+                iteration()  # eagerly: plans, workspaces and the mean weights are set up outside any capture
+            if graph and not done():
+                # one graph for the iteration — or, when a tool asks for the time split (_SECTION_TIMES), one per section
+                times = _SECTION_TIMES
+                graphs = []
+                for section in ((iteration,) if times is None else (draft_steps, verify, accept)):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, pool=graphs[0].pool() if graphs else None):
+                        section()
+                    graphs.append(g)
+                replays = 0
+                while True:  # (ends: every iteration short of n emits at least one token)
+                    marks = []
+                    for g in graphs:
+                        if times is not None:
+                            marks.append(torch.cuda.Event(enable_timing=True))
+                            marks[-1].record()
+                        g.replay()
+                    if times is not None:
+                        marks.append(torch.cuda.Event(enable_timing=True))
+                        marks[-1].record()
+                        times.append(marks)
+                    replays += 1
+                    if replays % _FINISHED_EVERY == 0 and done():
+                        break
+                del graphs, g
+            while not done():
+                iteration()
+    gen = Generation(sequences, stats[0], stats[1], stats[2], stats[3], lengths, lp[:, 0], lp[:, 1])
+    gen.speculation = speculation
+    return gen
