@@ -292,6 +292,24 @@ SPEC_SYMBOLS = {
                             _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
 }
 
+# what include/bayeformers_amd_lrt.h declares (bnn.Linear with local = True: the passes around the two products of the local
+# reparameterisation estimator, and the closed-form Gaussian KL terms)
+LRT_SYMBOLS = {
+    "bf_lrt_operands": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "bf_lrt_square": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "bf_lrt_combine": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, _u32, _u32, _vp]),
+    "bf_lrt_zeta": (_i, [_vp, _i, _i, _i, _u64, _u32, _u32, _vp]),
+    "bf_lrt_grad_prepare_workspace_bytes": (_sz, [_i, _i]),
+    "bf_lrt_grad_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _u64, _u32, _u32, _vp, _sz, _vp]),
+    "bf_lrt_dx": (_i, [_vp, _i64, _vp, _vp, _i, _i, _i, _vp]),
+    "bf_lrt_drho": (_i, [_vp, _vp, _vp, _u64, _vp]),
+    "bf_sample_logprob_like": (_i, [_tp, _i, _i, _u64, _u32, _vp, _vp, _sz, _i, _vp]),
+    "bf_kl_gaussian_workspace_bytes": (_sz, []),
+    "bf_kl_gaussian": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp]),
+}
+
+BF_LRT_STREAM = 0x20000000  # csrc/bf_philox.h
+
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
 BF_ACT_NONE, BF_ACT_GELU = 0, 1
 
@@ -386,6 +404,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the speculative-decoding entry): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in LRT_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the local reparameterisation entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

@@ -27,7 +27,7 @@ from .random import (get_compute_dtype, manual_seed, set_compute_dtype, set_kl_g
                      use_device_counter)
 
 __all__ = ["to_bayesian", "to_bayesian_lora", "lora_state_dict", "invalidate_caches", "fuse_activations", "fuse_residual_layernorm", "fuse_shared_inputs", "fuse_ffn_pairs", "fuse_attention", "fuse_embeddings", "fuse_decoder_blocks", "enable_embedding", "nn", "manual_seed", "set_compute_dtype", "get_compute_dtype",
-           "use_device_counter", "set_kl_gradient", "kept_weight_bytes", "kv_cache_bytes"]
+           "use_device_counter", "set_kl_gradient", "kept_weight_bytes", "kv_cache_bytes", "local_reparameterization"]
 
 
 def to_bayesian(model: torch.nn.Module, initialization: Optional[Initialization] = DEFAULT_UNIFORM,
@@ -102,6 +102,47 @@ def lora_state_dict(model: torch.nn.Module) -> dict:
             out[prefix + "lora_A.rho"] = m.lora_A.rho.detach()
             out[prefix + "lora_B"] = m.lora_B.detach()
     return out
+
+
+def local_reparameterization(model: torch.nn.Module, enable: bool = True, kl: str = "sampled") -> int:
+    """Switch every bnn.Linear of `model` to the local reparameterisation estimator (Kingma, Salimans, Welling 2015) or back:
+    the layer samples its pre-activations, y = m + sqrt(v) * zeta with m = x mu^T + mu_b and v = x^2 (sigma^2)^T + sigma_b^2,
+    instead of S weight tensors — noise per row rather than per sample, no sampled weights in memory, and ONE [2][N][K]
+    weight-gradient contraction over all S*M rows (include/bayeformers_amd_lrt.h).  Opt-in: the default
+    estimator and its bits are untouched, and `enable=False` restores them.  bnn.LoRALinear and bnn.Embedding are left alone.
+    Returns the number of layers switched.
+
+    kl="sampled" (default): log_prior / log_variational_posterior are those of the weight draws the default estimator makes
+    for the same seed — the same bits, and set_kl_gradient(True) works unchanged.  kl="analytic": every sample's log-probs are
+    the closed-form expectations E_q log p and E_q log q; Gaussian priors only (what to_bayesian(delta=...) makes), refused
+    otherwise, and refused under set_kl_gradient(True) (no gradient of the closed form yet).
+
+    Works under sample_bayesian, sample_predictive, GraphedSampler, training_step, GraphedTrainingStep, the reference's serial
+    loop and Model.posterior_mean() (nothing is sampled there).  sample_generate and Model.pinned_samples(keep_weights=...)
+    refuse a model with local layers: their contract is one weight draw per text."""
+    from .nn.parameters.gaussian import Gaussian
+
+    if kl not in ("sampled", "analytic"):
+        raise ValueError(f"local_reparameterization: kl={kl!r} (\"sampled\" or \"analytic\")")
+    layers = [m for m in model.modules() if isinstance(m, nn.Linear)]
+    if enable and kl == "analytic":
+        if bfr.STATE.kl_gradient:
+            raise ValueError("local_reparameterization: kl=\"analytic\" has no KL gradient yet — it cannot be combined with "
+                             "set_kl_gradient(True); use kl=\"sampled\"")
+        for l in layers:
+            priors = [l.weight_prior] + ([l.bias_prior] if isinstance(l.bias, Gaussian) else [])
+            if not all(isinstance(p, Gaussian) for p in priors):
+                raise ValueError("local_reparameterization: kl=\"analytic\" needs a Gaussian prior on every layer "
+                                 "(to_bayesian(delta=...)); a layer has a mixture or user-defined prior")
+    for l in layers:
+        l.local, l.local_kl = bool(enable), (kl if enable else "sampled")
+    for m in model.modules():
+        if isinstance(m, Model):
+            m._plan = None  # (the sampling plan holds exactly the layers that draw weights)
+            cache = m.__dict__.get("_graphs")
+            if cache is not None:
+                cache.close()  # captured forwards replay the other estimator's launches
+    return len(layers)
 
 
 def enable_embedding(enable: bool = True) -> None:

@@ -70,7 +70,10 @@ __device__ __forceinline__ void bf_stale_bump(uint32_t* counter) {
 // bf_sample.hip, for bf_sample_logprob / bf_sample_logprob_table / bf_linear_fwd / bf_linear_bwd (bf_api.hip)
 size_t bf_sample_partials_bytes(const bf_tensor_t* tensors, int n_tensors, int S);
 int bf_launch_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, uint64_t seed, uint32_t sample_base,
-                             double* d_logprob_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream);
+                             double* d_logprob_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream,
+                             int like_dt = -1);
+// like_dt >= 0 (bf_sample_logprob_like, bf_lrt.hip): a tensor that is not written runs the kernel instantiation that writes
+// `like_dt` samples (a second tensor: fp32), so the log-probs have the bits of the launch that writes them.
 int bf_launch_sample_table(const void* d_blob, int n_tensors, uint32_t block_begin, uint32_t block_end, int S,
                            uint64_t seed, uint32_t sample_base, double* d_partials, hipStream_t stream, int prior_kinds);
 int bf_launch_reduce_partials(const double* d_partials, uint32_t nrows, int S, double* d_out, hipStream_t stream);

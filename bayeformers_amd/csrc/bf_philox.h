@@ -110,6 +110,15 @@ static inline void bf_normal4_host(uint64_t group, uint32_t sample, uint32_t str
 // The stream (bit 30 set, bit 31 clear) collides neither with the weight streams 2 * layer_id + {0, 1} nor with the
 // dropout streams.  `seed` is the generation's own 64-bit seed (drawn once per call), not the weight seed.
 #define BF_GENERATE_STREAM 0x40000000u
+// ---- local reparameterisation contract ------------------------------------------------------------------------------
+// A bnn.Linear with `local = True` samples its pre-activations, y = m + sqrt(v) * zeta (include/bayeformers_amd_lrt.h).
+// zeta of output element e = i * N + n (row i of sample s, output feature n) is component e & 3 of group g = e >> 2 of
+//   Philox4x32-7(counter = {lo32(g), sample_base + s (+ the device sample counter when set), BF_LRT_STREAM | layer_id, hi32(g)},
+//                key = {lo32(seed), hi32(seed)})
+// through Box-Muller as for eps: a function of the GLOBAL sample index, like eps.  Bit 29 collides neither with the weight
+// streams 2 * layer_id + {0, 1} nor with the dropout (bit 31) and generation (bit 30) streams.  The bias has no draw of its
+// own: its variance is part of v.
+#define BF_LRT_STREAM 0x20000000u
 BF_HD uint32_t bf_dropout_thresh(float p) {
     const float t = p * 65536.0f + 0.5f;
     return t <= 0.f ? 0u : (t >= 65535.f ? 65535u : (uint32_t)t);

@@ -519,8 +519,11 @@ int bf_philox_normal(float* d_out, uint64_t n, int S, uint64_t seed, uint32_t sa
 static int pick_ny(uint32_t blk, int S);
 
 // One launch covers tensors[first .. first+count) (count <= 2, same prior kind; the second is written as fp32).
+// like_dt >= 0: a first tensor that is not written runs the kernel instantiation that writes `like_dt` samples, so its
+// log-probs carry the bits of the launch that does write them (bf_sample_logprob_like).
 static int launch_group(const bf_tensor_t* tensors, int first, int count, uint32_t blk_offset, int S, uint64_t seed,
-                        uint32_t sample_base, double* partials, uint32_t nblk_total_for_layout, hipStream_t stream) {
+                        uint32_t sample_base, double* partials, uint32_t nblk_total_for_layout, hipStream_t stream,
+                        int like_dt = -1) {
     SampleParams p{};
     p.nseg = count;
     p.S = S;
@@ -569,7 +572,7 @@ static int launch_group(const bf_tensor_t* tensors, int first, int count, uint32
     const int ny = pick_ny(blk, S);
     p.ny = ny;
     const dim3 grid(blk, (uint32_t)ny);
-    const int out_dt = tensors[first].d_sample_out ? tensors[first].out_dtype : OUT_NONE;
+    const int out_dt = tensors[first].d_sample_out ? tensors[first].out_dtype : (like_dt >= 0 ? like_dt : OUT_NONE);
     switch (prior_kind) {
         case BF_PRIOR_MIXTURE: launch_prior<BF_PRIOR_MIXTURE>(out_dt, grid, stream, p); break;
         case BF_PRIOR_GAUSSIAN: launch_prior<BF_PRIOR_GAUSSIAN>(out_dt, grid, stream, p); break;
@@ -715,7 +718,7 @@ int bf_reduce_logprob(const double* d_partials, const uint32_t* d_rows, int G, i
 }
 
 int bf_launch_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, uint64_t seed, uint32_t sample_base,
-                             double* d_logprob_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream) {
+                             double* d_logprob_out, void* d_workspace, size_t workspace_bytes, hipStream_t stream, int like_dt) {
     if (n_tensors < 1 || n_tensors > kMaxSeg) BF_FAIL("bf_sample_logprob: n_tensors must be 1 or 2 (got %d)", n_tensors);
     if (S < 1) BF_FAIL("bf_sample_logprob: S must be >= 1 (got %d)", S);
     if (!d_logprob_out) BF_FAIL("bf_sample_logprob: d_logprob_out is NULL");
@@ -741,10 +744,10 @@ int bf_launch_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, u
                    tensors[0].prior.d_sigma1 == tensors[1].prior.d_sigma1 && tensors[0].prior.d_sigma2 == tensors[1].prior.d_sigma2;
     int rc;
     if (n_tensors == 1 || together) {
-        rc = launch_group(tensors, 0, n_tensors, 0, S, seed, sample_base, partials, nblk, stream);
+        rc = launch_group(tensors, 0, n_tensors, 0, S, seed, sample_base, partials, nblk, stream, like_dt);
     } else {
         bf_tensor_t second = tensors[1];
-        rc = launch_group(tensors, 0, 1, 0, S, seed, sample_base, partials, nblk, stream);
+        rc = launch_group(tensors, 0, 1, 0, S, seed, sample_base, partials, nblk, stream, like_dt);
         if (rc) return rc;
         if (second.d_sample_out && second.out_dtype != BF_DT_F32) {
             // a lone tensor is "segment 0": written in its own dtype
@@ -752,7 +755,8 @@ int bf_launch_sample_logprob(const bf_tensor_t* tensors, int n_tensors, int S, u
         } else {
             // written as fp32 through the segment-0 path of the F32 instantiation
             second.out_dtype = BF_DT_F32;
-            rc = launch_group(&second, 0, 1, blocks_for(tensors[0].n), S, seed, sample_base, partials, nblk, stream);
+            rc = launch_group(&second, 0, 1, blocks_for(tensors[0].n), S, seed, sample_base, partials, nblk, stream,
+                              like_dt >= 0 ? BF_DT_F32 : -1);
         }
     }
     if (rc) return rc;

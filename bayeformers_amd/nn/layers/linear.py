@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch import Size, Tensor
 from torch.nn import Module
 
-from ... import ops
+from ... import _C, ops
 from ... import random as bfr
 from ..parameters.base import NoneParameter, Parameter
 from .base import KernelLayer
@@ -203,13 +203,45 @@ class _FFNPairFn(torch.autograd.Function):
         return (dx, None, None, None, None, None, None, None, None, None) + tuple(r1[1:]) + tuple(r2[1:])
 
 
+class _LocalLinearFn(torch.autograd.Function):
+    """Autograd node of a layer with `local = True` (local reparameterisation, include/bayeformers_amd_lrt.h): the forward
+    samples the pre-activations, y = act(m + sqrt(v) * zeta); the backward treats zeta as a constant and regenerates it from
+    the Philox counter.  Saves x (with x^2, as the pair the weight-gradient contraction reads), sqrt(v) and — under a fused
+    activation — the pre-activation.  The log-prob scalars are detached, as in _LinearFn."""
+
+    @staticmethod
+    def forward(ctx, x, mu_w, rho_w, mu_b, rho_b, layer, S, seed, base, act, need_grad=True):
+        ctx.layer, ctx.S, ctx.seed, ctx.base = layer, S, seed, base
+        ctx.counter = bfr.counter_snapshot(need_grad)
+        y, saved = ops.lrt_forward(layer, x, S, seed, base, act, need_grad)
+        if need_grad:
+            ctx.present = [t is not None for t in saved]
+            ctx.save_for_backward(*[t for t in saved if t is not None])
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        it = iter(ctx.saved_tensors)
+        saved = tuple(next(it) if there else None for there in ctx.present)
+        need_x, need_mu_w, _, need_mu_b, _ = ctx.needs_input_grad[:5]
+        with bfr.counter_override(ctx.counter):
+            dx, dmu_w, drho_w, dmu_b, drho_b = ops.lrt_backward(ctx.layer, saved, grad, ctx.S, ctx.seed, ctx.base, need_x,
+                                                                need_mu_w, need_mu_b)
+        return dx, dmu_w, drho_w, dmu_b, drho_b, None, None, None, None, None, None
+
+
 class Linear(KernelLayer):
     """Bayesian Linear layer with Gaussian weight/bias posteriors and a prior per parameter.
 
     Attributes (as the reference): in_features, out_features, initialization, weight, weight_prior, bias,
     bias_prior, log_prior, log_variational_posterior.  Additional: layer_id (Philox stream), compute_dtype
-    (None = bayeformers_amd.get_compute_dtype()), log_prob_samples ([S, 2] float64 of the last forward).
+    (None = bayeformers_amd.get_compute_dtype()), log_prob_samples ([S, 2] float64 of the last forward); local (False: sample
+    the weights; True: sample the pre-activations instead, bayeformers_amd.local_reparameterization) with local_kl ("sampled":
+    the log-probs of the weight draws the default estimator would make; "analytic": their closed-form expectations).
     """
+
+    local = False
+    local_kl = "sampled"
 
     def __init__(self, in_features: int, out_features: int, bias: Optional[bool] = True,
                  initialization: Optional[Initialization] = DEFAULT_UNIFORM,
@@ -265,6 +297,9 @@ class Linear(KernelLayer):
         want_act = self.activation == "gelu"
         need_grad = torch.is_grad_enabled() and any(
             t is not None and t.requires_grad for t in (x2, self.weight.mu, self.weight.rho, mu_b, rho_b))
+        if self.local:
+            y = self._local_forward(ctx, x2, mu_b, rho_b, S, base, slot, want_act, need_grad)
+            return y.view(*input.shape[:-1], self.out_features)
         if ctx is not None and ctx.kept is not None and id(self) in ctx.plan.group_of:
             return self._kept_forward(ctx, x2, S, slot, want_act).view(*input.shape[:-1], self.out_features)
         rows_per_sample = x2.shape[0] // S
@@ -294,6 +329,52 @@ class Linear(KernelLayer):
             y = torch.nn.functional.gelu(y)
         self._end(ctx, slot)
         return y.view(*input.shape[:-1], self.out_features)
+
+    def _local_forward(self, ctx, x2: Tensor, mu_b, rho_b, S: int, base: int, slot: Tensor, want_act: bool,
+                       need_grad: bool) -> Tensor:
+        """A forward with `local = True`: the per-layer path (never the sampling plan, a stacked launch, the FFN pair or
+        the deferred gradient table).  The activation is fused into the combine pass where the kernels run and applied to
+        the composite's pre-activation otherwise; either way the node stores the pre-activation itself."""
+        if ctx is not None and ctx.kept is not None:
+            raise RuntimeError("pinned_samples(keep_weights=...) keeps one weight draw per sample; a layer under local "
+                               "reparameterisation (local = True) has no weight draw")
+        if x2.shape[0] % S:
+            raise ValueError(f"Linear: input rows ({x2.shape[0]}) are not a multiple of the sample count S={S}")
+        self._local_logprobs(S, base, slot)
+        y = _LocalLinearFn.apply(x2, self.weight.mu, self.weight.rho, mu_b, rho_b, self, S, bfr.STATE.seed, base,
+                                 1 if want_act else 0, need_grad)
+        self._end(ctx, slot)
+        return y
+
+    def _local_logprobs(self, S: int, base: int, slot: Tensor) -> None:
+        """The [S, 2] slot of a local forward.  "sampled": {log_prior, log_q} of the weight draws the default estimator makes
+        for the same seed and sample indices (the draws themselves are not stored).  "analytic": every sample's row holds the
+        closed-form expectations E_q log p and E_q log q (Gaussian priors; bf_kl_gaussian)."""
+        gs = [self.weight] + ([self.bias] if isinstance(self.bias, Gaussian) else [])
+        prs = [self.weight_prior] + ([self.bias_prior] if isinstance(self.bias, Gaussian) else [])
+        if self.local_kl == "analytic":
+            if bfr.STATE.kl_gradient and torch.is_grad_enabled():
+                raise RuntimeError("local reparameterisation with kl=\"analytic\" has no KL gradient yet: use kl=\"sampled\" "
+                                   "under set_kl_gradient(True)")
+            if not all(isinstance(pr, Gaussian) for pr in prs):
+                raise RuntimeError("local reparameterisation with kl=\"analytic\" needs Gaussian priors "
+                                   "(to_bayesian(delta=...)); this layer has a mixture or user-defined prior")
+            lp = ops.kl_gaussian(gs[0], prs[0])
+            for g, pr in zip(gs[1:], prs[1:]):
+                lp = lp + ops.kl_gaussian(g, pr)
+            slot.copy_(lp.view(1, 2).expand(S, 2))
+            return
+        sids = [2 * self.layer_id + i for i in range(len(gs))]
+        known = all(ops.fill_prior(_C.bf_prior_t(), pr, None) for pr in prs)  # built-in priors: the kernel evaluates them
+        if known:
+            # (nothing is written; the bits are those of the per-layer forward that draws the weights at this compute dtype)
+            cdt = self.compute_dtype or bfr.get_compute_dtype()
+            _, lp = ops.sample_logprob(gs, prs, sids, S, bfr.STATE.seed, base, like_dtype=cdt)
+        else:  # a user-defined prior: its own log_prob on each fp32 draw, as the default estimator's generic path
+            outs, lp = ops.sample_logprob(gs, [NoneParameter()] * len(gs), sids, S, bfr.STATE.seed, base, out_dtype=torch.float32)
+            for s in range(S):
+                lp[s, 0] = sum(pr.log_prob(o[s]) for pr, o in zip(prs, outs))
+        slot.copy_(lp)
 
     def _kept_forward(self, ctx, x2: Tensor, S: int, slot: Tensor, want_act: bool) -> Tensor:
         """A forward inside Model.pinned_samples(keep_weights=True or "fp8") (no gradient): the weights were sampled by the

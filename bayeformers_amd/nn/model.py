@@ -308,13 +308,14 @@ class Model(Module):
                     buf = self._lp_buf = torch.zeros((len(layers), S, 2), dtype=torch.float64, device=dev)
             slots = {id(l): buf[i] for i, l in enumerate(layers)}
         plan = None
-        linears = [l for l in layers if isinstance(l, Linear)]
+        # (a layer under local reparameterisation draws no weights: it is never in the sampling plan)
+        linears = [l for l in layers if isinstance(l, Linear) and not l.local]
         kept = self.__dict__.get("_kept")
         if kept is not None:
             pass  # the block's own plan (below, once the forward's context exists); Model._plan is left as it is
         elif linears and self.cross_layer_sampling and SamplePlan.plannable(linears):
             # layers seen with <= 64 rows per sample run the single fused kernel instead (Linear.forward marks them)
-            planned = [(i, l) for i, l in enumerate(layers) if isinstance(l, Linear) and not l._small_m]
+            planned = [(i, l) for i, l in enumerate(layers) if isinstance(l, Linear) and not l._small_m and not l.local]
             if planned:
                 cdt = bfr.get_compute_dtype()
                 pl = [l for _, l in planned]
@@ -469,6 +470,9 @@ class Model(Module):
         from .. import plan as bplan
 
         mode = _KeptFp8Weights.mode if fp8 else _KeptWeights.mode
+        if any(isinstance(l, Linear) and l.local for l in self.fused_children()):
+            raise ValueError(f"pinned_samples({mode}) keeps one weight draw per sample; this model runs local "
+                             "reparameterisation (local_reparameterization), which has no weight draw — switch it off first")
         if torch.is_grad_enabled():
             raise RuntimeError(f"pinned_samples({mode}) is inference only: enter it under torch.no_grad()")
         if self.training:

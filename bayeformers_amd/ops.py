@@ -133,6 +133,7 @@ def invalidate_caches(module) -> None:
         elif isinstance(m, Model):
             m._plan = None
         m.__dict__.pop("_mean_cache", None)  # (a bnn.Linear's 16-bit copy of its posterior mean: Model.posterior_mean)
+        m.__dict__.pop("_mean_cache_lrt", None)  # (... and of [mu; sigma^2]: a local layer's forwards without gradients)
 
 
 def fill_prior(dst: "_C.bf_prior_t", prior, gaussian=None) -> bool:
@@ -180,11 +181,13 @@ def fill_tensor(dst: "_C.bf_tensor_t", gaussian, prior, stream_id: int) -> bool:
     return fill_prior(dst.prior, prior, gaussian)
 
 
-def sample_logprob(gaussians, priors, stream_ids, S: int, seed: int, sample_base: int, out_dtype=None):
+def sample_logprob(gaussians, priors, stream_ids, S: int, seed: int, sample_base: int, out_dtype=None, like_dtype=None):
     """Fused sampling + log-probs of 1 or 2 Gaussian parameters (bf_sample_logprob).
 
     Returns (samples, logprob) where samples is a list of [S, *shape] tensors (or None when out_dtype is None)
-    and logprob is a [S, 2] float64 tensor {log_prior, log_variational_posterior} summed over the parameters."""
+    and logprob is a [S, 2] float64 tensor {log_prior, log_variational_posterior} summed over the parameters.
+    like_dtype (with out_dtype None): nothing is written, and the log-probs have the bits of the per-layer forward that
+    draws `like_dtype` weights (bf_sample_logprob_like)."""
     n = len(gaussians)
     arr = (_C.bf_tensor_t * n)()
     dev = gaussians[0].mu.device
@@ -200,6 +203,10 @@ def sample_logprob(gaussians, priors, stream_ids, S: int, seed: int, sample_base
     need = lib.bf_sample_logprob_workspace_bytes(arr, n, S)
     ws = workspace(dev, need)
     lp = torch.empty((S, 2), dtype=torch.float64, device=dev)
+    if out_dtype is None and like_dtype is not None:
+        _C.check(lib.bf_sample_logprob_like(arr, n, S, seed, sample_base & 0xFFFFFFFF, lp.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), _TORCH2BF[like_dtype], _stream_ptr()), "bf_sample_logprob_like")
+        return None, lp
     _C.check(lib.bf_sample_logprob(arr, n, S, seed, sample_base & 0xFFFFFFFF, lp.data_ptr(), ws.data_ptr(),
                                    ws.numel(), _stream_ptr()), "bf_sample_logprob")
     return (outs if out_dtype is not None else None), lp
@@ -3097,3 +3104,258 @@ def lora_backward(x: Tensor, dy: Tensor, a_s: Tensor, b: Tensor, h: Tensor, w0: 
     da = (float(scale) * torch.bmm(g.transpose(1, 2), x.view(S, M, K))).float()
     db = (float(scale) * torch.matmul(dy.t(), h.reshape(S * M, r))).float() if need_b else None
     return dx, da, db
+
+
+# bnn.Linear with local = True (include/bayeformers_amd_lrt.h): the layer samples its pre-activations,
+# y = act(m + sqrt(v) * zeta) with m = x mu^T + mu_b and v = x^2 (sigma^2)^T + sigma_b^2, instead of its weights.  The two
+# products run on the GEMMs above with the sample axis used as the pair axis; the bf_lrt_* passes form their operands and
+# combine their results.  What lrt_supported() refuses runs the same formula as framework ops on the same zeta.
+LRT_CALLS = {"fwd": 0, "bwd": 0, "composite_fwd": 0, "composite_bwd": 0, "gemm_nn": 0, "gemm_tn": 0, "matmul": 0,
+             "operands": 0, "kl": 0}
+LRT_ONE_LAUNCH = True  # [m; v] as ONE bf_gemm_nt_act launch (S = 2, M = R) rather than two S = 1 launches (tools/lrt_bench.py)
+
+
+def lrt_kernel_wins(N: int, K: int, rows: int, backward: bool) -> bool:
+    """Where the kernel route beats the framework composite on one MI355X (profiles/local_reparameterization.md): every
+    measured class, forward and backward — the composite runs the same two products and a chain of a dozen elementwise
+    passes over the [rows, N] activations around them."""
+    return True
+
+
+def lrt_supported(dtype: torch.dtype, N: int, K: int, *tensors: Tensor, rows: int = 0, backward: Optional[bool] = None) -> bool:
+    """Do the bf_lrt_* entries take this layer?  bf16 compute (in fp16 x^2 overflows above |x| = 256 and a MOPED sigma^2
+    underflows), K % 8 == 0, N % 8 == 0; `tensors` (optional): the operands, each on a ROCm device, contiguous and 16-byte
+    aligned.  backward = False / True: also whether that direction's kernels are the faster route (lrt_kernel_wins).
+    The one predicate that routes a call to the kernels or to the framework composite."""
+    if dtype != torch.bfloat16 or K % 8 or N % 8:
+        return False
+    if backward is not None and not lrt_kernel_wins(N, K, rows, backward):
+        return False
+    return all(t is None or (t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+def _lrt_has_bias(layer) -> bool:
+    from .nn.parameters.base import NoneParameter
+
+    return not isinstance(layer.bias, NoneParameter)
+
+
+def lrt_operands(layer, keep: bool = False):
+    """(w2 [2, N, K] bf16 = [mu; sigma^2], b2 [2, N] fp32 = [mu_b; sigma_b^2] or None) of a layer (bf_lrt_operands).  Without
+    gradients (keep) the pair is made once and kept on the layer, exactly as Linear.mean_weights keeps its copy (a new mu or
+    rho — another address or version counter —, a later stale epoch or ops.invalidate_caches makes it again); a step that
+    records gradients redoes it in its forward and in its backward: the optimizer moves the masters every step, and 2 N K
+    16-bit values per layer are not held from one to the other."""
+    mu, rho = layer.weight.mu, layer.weight.rho
+    _require_device(mu, "mu")
+    N, K = layer.out_features, layer.in_features
+    has_bias = _lrt_has_bias(layer)
+    key = None
+    # (a forward being captured into a HIP graph makes the pair inside the graph: a replay after an optimizer step must read
+    # the masters again, and a kept pair would be baked in by address)
+    keep = keep and not torch.cuda.is_current_stream_capturing()
+    if keep:
+        key = (mu.device, mu.data_ptr(), mu._version, rho.data_ptr(), rho._version, bfr.STATE.stale_epoch)
+        if has_bias:
+            key += (layer.bias.mu.data_ptr(), layer.bias.mu._version, layer.bias.rho.data_ptr(), layer.bias.rho._version)
+        hit = layer.__dict__.get("_mean_cache_lrt")
+        if hit is not None and hit[0] == key:
+            return hit[1], hit[2]
+    with torch.inference_mode(False), torch.no_grad():
+        w2 = torch.empty((2, N, K), dtype=torch.bfloat16, device=mu.device)
+        b2 = torch.empty((2, N), dtype=torch.float32, device=mu.device) if has_bias else None
+    if not (mu.is_contiguous() and rho.is_contiguous() and mu.dtype == torch.float32 and rho.dtype == torch.float32):
+        raise _C.BayeFormersAMDError("mu/rho must be contiguous fp32 tensors")
+    _C.check(_C.lib().bf_lrt_operands(mu.data_ptr(), rho.data_ptr(), layer.bias.mu.data_ptr() if has_bias else None,
+                                      layer.bias.rho.data_ptr() if has_bias else None, w2.data_ptr(),
+                                      b2.data_ptr() if has_bias else None, _C.BF_DT_BF16, N, K, _stream_ptr()), "bf_lrt_operands")
+    LRT_CALLS["operands"] += 1
+    if keep:
+        layer.__dict__["_mean_cache_lrt"] = (key, w2, b2)
+    return w2, b2
+
+
+def lrt_square(x: Tensor, R_pad: int, pair: bool = True) -> Tensor:
+    """xx [2, R_pad, K] bf16 with xx[1] = x^2 and (pair) xx[0] = x, rows past x's written as zeros (bf_lrt_square)."""
+    R, K = x.shape
+    xx = torch.empty((2, R_pad, K), dtype=x.dtype, device=x.device)
+    _C.check(_C.lib().bf_lrt_square(x.data_ptr(), xx.data_ptr(), _TORCH2BF.get(x.dtype, -1), R, R_pad, K, int(pair), _stream_ptr()),
+             "bf_lrt_square")
+    return xx
+
+
+def lrt_combine(m: Tensor, v: Tensor, S: int, seed: int, sample_base: int, layer_id: int, act: int = 0,
+                want_pre: bool = False, want_sd: bool = False):
+    """(y, pre or None, sqrt(v) or None), all [S*M, N] bf16, from the fp32 moments m, v [S*M, N] (bf_lrt_combine)."""
+    R, N = m.shape
+    y = torch.empty((R, N), dtype=torch.bfloat16, device=m.device)
+    pre = torch.empty_like(y) if want_pre else None
+    sd = torch.empty_like(y) if want_sd else None
+    _C.check(_C.lib().bf_lrt_combine(m.data_ptr(), v.data_ptr(), y.data_ptr(), pre.data_ptr() if want_pre else None,
+                                     sd.data_ptr() if want_sd else None, _C.BF_DT_BF16, S, R // S, N, int(act), seed,
+                                     sample_base & 0xFFFFFFFF, int(layer_id), _stream_ptr()), "bf_lrt_combine")
+    return y, pre, sd
+
+
+def lrt_zeta(S: int, M: int, N: int, seed: int, sample_base: int, layer_id: int, device="cuda") -> Tensor:
+    """zeta [S*M, N] fp32 of a local layer (bf_lrt_zeta): ops.philox_normal(M*N, S, seed, sample_base, BF_LRT_STREAM |
+    layer_id) plus the device sample counter when one is set."""
+    out = torch.empty((S * M, N), dtype=torch.float32, device=device)
+    _C.check(_C.lib().bf_lrt_zeta(out.data_ptr(), S, M, N, seed, sample_base & 0xFFFFFFFF, int(layer_id), _stream_ptr()),
+             "bf_lrt_zeta")
+    return out
+
+
+def lrt_grad_prepare(dy: Tensor, pre: Optional[Tensor], sd: Tensor, S: int, R_pad: int, seed: int, sample_base: int,
+                     layer_id: int):
+    """(dmdv [2, R_pad, N] bf16, colsum [2, N] fp32) from dy, sqrt(v) (and the pre-activation of a fused GELU), zeta
+    regenerated (bf_lrt_grad_prepare)."""
+    R, N = dy.shape
+    lib = _C.lib()
+    dmdv = torch.empty((2, R_pad, N), dtype=dy.dtype, device=dy.device)
+    colsum = torch.empty((2, N), dtype=torch.float32, device=dy.device)
+    need = lib.bf_lrt_grad_prepare_workspace_bytes(R_pad, N)
+    ws = workspace(dy.device, need)
+    _C.check(lib.bf_lrt_grad_prepare(dy.data_ptr(), pre.data_ptr() if pre is not None else None, sd.data_ptr(), dmdv.data_ptr(),
+                                     colsum.data_ptr(), _TORCH2BF.get(dy.dtype, -1), S, R // S, R_pad, N,
+                                     1 if pre is not None else 0, seed, sample_base & 0xFFFFFFFF, int(layer_id), ws.data_ptr(),
+                                     ws.numel(), _stream_ptr()), "bf_lrt_grad_prepare")
+    return dmdv, colsum
+
+
+def lrt_dx(ab: Tensor, x: Tensor) -> Tensor:
+    """dx = a + 2 x o b from ab [2, R_pad, K] and x [R, K] (bf_lrt_dx)."""
+    R, K = x.shape
+    dx = torch.empty_like(x)
+    _C.check(_C.lib().bf_lrt_dx(ab.data_ptr(), ab.shape[1] * K, x.data_ptr(), dx.data_ptr(), _TORCH2BF.get(x.dtype, -1), R, K,
+                                _stream_ptr()), "bf_lrt_dx")
+    return dx
+
+
+def lrt_drho(dsig2: Tensor, rho: Tensor) -> Tensor:
+    """drho = dsigma^2 * 2 sigma sigmoid(rho) (bf_lrt_drho); fp32, any shape with a multiple of 4 elements."""
+    drho = torch.empty_like(rho, dtype=torch.float32)
+    _C.check(_C.lib().bf_lrt_drho(dsig2.data_ptr(), rho.data_ptr(), drho.data_ptr(), rho.numel(), _stream_ptr()), "bf_lrt_drho")
+    return drho
+
+
+def kl_gaussian(gaussian, prior) -> Tensor:
+    """[2] float64 {E_q log p, E_q log q} of one Gaussian tensor under a Gaussian prior, in closed form (bf_kl_gaussian)."""
+    mu, rho, pmu, prho = gaussian.mu, gaussian.rho, prior.mu, prior.rho
+    _require_device(mu, "mu")
+    if not all(t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == mu.numel() for t in (mu, rho, pmu, prho)):
+        raise _C.BayeFormersAMDError("kl_gaussian: mu, rho and the prior's mu, rho must be contiguous fp32 tensors of one size "
+                                     "on a ROCm device")
+    lib = _C.lib()
+    out = torch.empty(2, dtype=torch.float64, device=mu.device)
+    ws = workspace(mu.device, lib.bf_kl_gaussian_workspace_bytes())
+    _C.check(lib.bf_kl_gaussian(mu.data_ptr(), rho.data_ptr(), pmu.data_ptr(), prho.data_ptr(), mu.numel(), out.data_ptr(),
+                                ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_kl_gaussian")
+    LRT_CALLS["kl"] += 1
+    return out
+
+
+def _lrt_pad(rows: int) -> int:
+    return (rows + 63) // 64 * 64  # (bf_gemm_tn's contraction runs in steps of 64 rows)
+
+
+def lrt_forward(layer, x: Tensor, S: int, seed: int, sample_base: int, act: int = 0, need_grad: bool = False):
+    """(y, saved) of a local bnn.Linear for S samples: y[s] = act(m + sqrt(v) * zeta), x: [S*M, K].  `saved` is what
+    lrt_backward needs (None unless need_grad): on the kernel route (xx [2, R_pad, K] = [x; x^2], sqrt(v), pre or None), on
+    the composite route (x, sqrt(v), pre or None, zeta).  Kernels where lrt_supported(), else the same formula as framework
+    ops — in x's dtype for bf16, in fp32 for fp16 and fp32 inputs."""
+    _require_device(x, "input")
+    N, K = layer.out_features, layer.in_features
+    x = x if x.is_contiguous() else x.contiguous()
+    R = x.shape[0]
+    if R % S:
+        raise _C.BayeFormersAMDError(f"input rows ({R}) are not a multiple of the sample count S={S}")
+    M = R // S
+    if lrt_supported(x.dtype, N, K, x, rows=R, backward=False) and layer.weight.mu.dtype == torch.float32:
+        w2, b2 = lrt_operands(layer, keep=not need_grad)
+        R_pad = _lrt_pad(R) if need_grad else R
+        one = LRT_ONE_LAUNCH or need_grad
+        xx = lrt_square(x, R_pad, pair=one)
+        mv = torch.empty((2, R, N), dtype=torch.float32, device=x.device)
+        if one:
+            gemm_nt(xx, w2, b2, 2, R, N, K, R_pad * K, torch.float32, out=mv)
+        else:
+            gemm_nt(x, w2[0:1], b2[0:1] if b2 is not None else None, 1, R, N, K, R * K, torch.float32, out=mv[0:1])
+            gemm_nt(xx[1], w2[1:2], b2[1:2] if b2 is not None else None, 1, R, N, K, R * K, torch.float32, out=mv[1:2])
+        y, pre, sd = lrt_combine(mv[0], mv[1], S, seed, sample_base, layer.layer_id, act, want_pre=bool(act) and need_grad,
+                                 want_sd=need_grad)
+        LRT_CALLS["fwd"] += 1
+        return y, ((xx, sd, pre) if need_grad else None)
+    LRT_CALLS["composite_fwd"] += 1
+    cd = x.dtype if x.dtype == torch.bfloat16 else torch.float32
+    has_bias = _lrt_has_bias(layer)
+    sig2 = torch.nn.functional.softplus(layer.weight.rho.detach().float()).square()
+    xc = x.to(cd)
+    m = torch.nn.functional.linear(xc, layer.weight.mu.detach().to(cd), layer.bias.mu.detach().to(cd) if has_bias else None)
+    v = torch.nn.functional.linear(xc * xc, sig2.to(cd),
+                                   torch.nn.functional.softplus(layer.bias.rho.detach().float()).square().to(cd) if has_bias else None)
+    zeta = lrt_zeta(S, M, N, seed, sample_base, layer.layer_id, x.device)
+    sd = torch.sqrt(torch.clamp_min(v, 0))
+    pre = m + sd * zeta.to(cd)
+    y = torch.nn.functional.gelu(pre) if act else pre
+    return y.to(x.dtype), ((x, sd, pre if act else None, zeta) if need_grad else None)
+
+
+def lrt_backward(layer, saved, dy: Tensor, S: int, seed: int, sample_base: int, need_x: bool = True, need_mu: bool = True,
+                 need_mu_b: bool = True):
+    """(dx, dmu, drho, dmu_b, drho_b) of lrt_forward, zeta a constant: dm = g, dv = g zeta / (2 sqrt(v)) (0 where v == 0),
+    dx = dm mu + 2 x o (dv sigma^2), dmu = dm^T x, dsigma^2 = dv^T x^2, drho = dsigma^2 * 2 sigma sigmoid(rho) and the column
+    sums for the bias.  Run it under the forward's counter (bfr.counter_override)."""
+    N, K = layer.out_features, layer.in_features
+    has_bias = _lrt_has_bias(layer)
+    if len(saved) == 3:
+        xx, sd, pre = saved
+        R_pad = xx.shape[1]
+        R = sd.shape[0]
+        x = xx[0, :R]
+        dy = dy.reshape(R, N)
+        dy = (dy if dy.dtype == x.dtype else dy.to(x.dtype)).contiguous()
+        dmdv, colsum = lrt_grad_prepare(dy, pre, sd, S, R_pad, seed, sample_base, layer.layer_id)
+        w2, _ = lrt_operands(layer)
+        dx = None
+        if need_x:
+            if _gemm_nn_takes(x.dtype, R_pad, N, K):
+                ab = gemm_nn(dmdv, w2)
+                LRT_CALLS["gemm_nn"] += 1
+            else:
+                ab = torch.bmm(dmdv, w2)
+                LRT_CALLS["matmul"] += 1
+            dx = lrt_dx(ab, x)
+        dw = gemm_tn(dmdv, xx)  # [2, N, K] fp32: dmu, dsigma^2
+        LRT_CALLS["gemm_tn"] += 1
+        LRT_CALLS["bwd"] += 1
+        dmu = dw[0] if need_mu else None
+        drho = lrt_drho(dw[1], layer.weight.rho)
+        dmu_b = drho_b = None
+        if has_bias:
+            dmu_b = colsum[0] if need_mu_b else None
+            drho_b = lrt_drho(colsum[1], layer.bias.rho)
+        return dx, dmu, drho, dmu_b, drho_b
+    LRT_CALLS["composite_bwd"] += 1
+    x, sd, pre, zeta = saved
+    cd = sd.dtype
+    R = x.shape[0]
+    g = dy.reshape(R, N).to(cd)
+    if pre is not None:
+        pf = pre.float()
+        g = (g.float() * (0.5 * torch.erfc(-pf * 0.7071067811865476) + pf * torch.exp(-0.5 * pf * pf) * 0.3989422804014327)).to(cd)
+    dv = torch.where(sd > 0, g * zeta.to(cd) / (2 * sd), torch.zeros_like(g))
+    xc = x.to(cd)
+    rho = layer.weight.rho.detach().float()
+    sigma = torch.nn.functional.softplus(rho)
+    dx = None
+    if need_x:
+        dx = (torch.matmul(g, layer.weight.mu.detach().to(cd)) + 2 * xc * torch.matmul(dv, sigma.square().to(cd))).to(x.dtype)
+    dmu = torch.matmul(g.t(), xc).float() if need_mu else None
+    drho = torch.matmul(dv.t(), xc * xc).float() * (2 * sigma * torch.sigmoid(rho))
+    dmu_b = drho_b = None
+    if has_bias:
+        rho_b = layer.bias.rho.detach().float()
+        dmu_b = g.float().sum(0) if need_mu_b else None
+        drho_b = dv.float().sum(0) * (2 * torch.nn.functional.softplus(rho_b) * torch.sigmoid(rho_b))
+    return dx, dmu, drho, dmu_b, drho_b

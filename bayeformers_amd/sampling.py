@@ -903,6 +903,10 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
         raise NotImplementedError("sample_generate: S-sharded generation is not supported (single process)")
     if not isinstance(model, Model):
         raise TypeError("sample_generate: model must be a bnn.Model (bayeformers_amd.to_bayesian)")
+    if any(getattr(l, "local", False) for l in model.fused_children()):
+        raise ValueError("sample_generate: this model runs local reparameterisation (local_reparameterization), which "
+                         "draws fresh activation noise at every forward; a generated text is one weight draw per sample "
+                         "— switch it off first (local_reparameterization(model, False))")
     if model.training:
         raise RuntimeError("sample_generate: put the model in eval mode (model.eval())")
     if torch.is_grad_enabled():
