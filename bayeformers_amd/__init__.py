@@ -21,6 +21,11 @@ from .nn.model import Model
 from .nn.parameters.base import Parameter
 from .nn.parameters.gaussian import DEFAULT_SCALED_GAUSSIAN_MIXTURE
 from .nn.parameters.initializations import DEFAULT_UNIFORM, Initialization
+from .attention import (_ATTENTION_NAME, _CHUNKED_ATTENTION, _attention_interface, _causal_attention,  # noqa: F401
+                        _marks_of, _padding_mask_interface, _softcap_eager, chunked_attention, chunked_attention_enabled,
+                        encoder_ragged_attention, encoder_ragged_attention_enabled, fuse_attention, packed_attention,
+                        packed_attention_enabled, ragged_attention, ragged_attention_enabled, softcap_attention,
+                        softcap_attention_enabled)
 from .ops import invalidate_caches  # noqa: F401
 from .plan import kept_weight_bytes, kv_cache_bytes  # noqa: F401
 from .random import (get_compute_dtype, manual_seed, set_compute_dtype, set_kl_gradient,  # noqa: F401
@@ -425,728 +430,6 @@ def fuse_shared_inputs(model: torch.nn.Module, names=("query", "key", "value")) 
     return fused
 
 
-_ATTENTION_NAME = "bayeformers_amd"
-
-
-def _attention_interface(module, query, key, value, attention_mask, dropout: float = 0.0, scaling=None, **kwargs):
-    """Attention function in the HuggingFace `AttentionInterface` convention: query/key/value [B, H, T, D], returns
-    ([B, T, H, D], None).  Runs bf_attention_fwd (with bf_attention_bwd as its backward when a gradient is needed) when
-    it applies (head size 64, T a multiple of 128, no mask or a key-padding mask; attention_probs_dropout runs inside the
-    kernels on the Philox keep-mask of csrc/bf_philox.h); anything else goes to the
-    framework's scaled-dot-product attention.  Causal calls (decoders) go to `_causal_attention`, whose kernels take any
-    sequence length; the T % 128 limit here is the encoder kernels' alone, and `encoder_ragged_attention()` (off by default)
-    lifts it: other lengths then run bf_attention_fwd_any / bf_attention_bwd_any, the same kernels' tail forms."""
-    from transformers.integrations.sdpa_attention import sdpa_attention_forward
-
-    from . import ops
-
-    if getattr(key, "_bf_ring", None) is not None:  # a ring-buffer cache (kv_cache.RingStaticLayer), 16-bit or e4m3 rows
-        return _ring_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs)
-    if getattr(key, "_bf_kv8_scale", None) is not None:  # an FP8 cache (kv_cache.Fp8StaticLayer): key / value are e4m3 rows
-        return _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs)
-    need_grad = torch.is_grad_enabled() and (query.requires_grad or key.requires_grad or value.requires_grad)
-    # causal: a mask _padding_mask_interface marked causal (the mask itself carries the structure), else what the caller
-    # says with is_causal, else — with no mask — the module's own flag (HF decoders set module.is_causal and pass no mask
-    # when nothing is padded); an explicit is_causal wins over the module flag, as in the framework's sdpa_attention_forward
-    explicit = kwargs.get("is_causal", None)
-    causal = bool(getattr(attention_mask, "_bf_causal", False) or getattr(attention_mask, "_bf_decode", False)
-                  or getattr(attention_mask, "_bf_window", None) is not None
-                  or getattr(attention_mask, "_bf_band", None) is not None) or (
-        bool(explicit) if explicit is not None else (attention_mask is None and bool(getattr(module, "is_causal", False))))
-    if causal:
-        return _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs)
-    # attention_probs_dropout (training mode) runs inside the kernels, forward and backward, for any supported length
-    usable = ops.attention_supported(query, key, value)
-    # under encoder_ragged_attention() (off by default): a length the kernels above refuse runs their tail forms
-    # (bf_attention_fwd_any and its siblings) — the same masks, the same dropout contract, inference and training alike
-    any_length = (not usable and encoder_ragged_attention_enabled() and ops.attention_any_supported(query, key, value))
-    usable = usable or any_length
-    key_mask = mask_off = None
-    ready = getattr(attention_mask, "_bf_key_mask", None) if attention_mask is not None else None
-    if usable and ready is not None and ready.shape == (query.shape[0], query.shape[2]):
-        # built once per forward by _padding_mask_interface: additive fp32 [B, T] + the device flag "hides nothing"
-        key_mask, mask_off = ready, attention_mask._bf_mask_off
-    elif usable and attention_mask is not None:
-        m = attention_mask
-        B, H, T, _ = query.shape
-        # a padding mask: [B, 1, 1 or T (broadcast), T]; per-query structure is not handled here
-        if m.dim() == 4 and m.shape[0] == B and m.shape[1] == 1 and m.shape[3] == T and (m.shape[2] == 1 or m.stride(2) == 0):
-            row = m[:, 0, 0, :]
-            if row.dtype == torch.bool:
-                key_mask = torch.where(row, 0.0, float("-inf")).to(torch.float32)
-            else:
-                key_mask = row.to(torch.float32).contiguous()
-        else:
-            usable = False
-    if not usable:
-        if attention_mask is not None and attention_mask.dtype not in (torch.bool, query.dtype):
-            attention_mask = attention_mask.to(query.dtype)  # the framework's kernels want bool or the query's dtype
-        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
-    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-    drop = ops.Dropout(dropout, bfr.STATE.seed, bfr.dropout_call(), bfr.dropout_site(module), bfr.dropout_origin(),
-                       bfr.dropout_counter()) if dropout > 0.0 else None
-    if any_length:
-        if need_grad:
-            return ops.AttentionAnyFn.apply(query, key, value, key_mask, mask_off, scale, drop), None
-        return ops.attention_forward_any(query, key, value, key_mask, scale, mask_off, drop=drop), None
-    if need_grad:  # training: the same kernel, with bf_attention_bwd behind it
-        return ops.AttentionFn.apply(query, key, value, key_mask, mask_off, scale, drop), None
-    return ops.attention_forward(query, key, value, key_mask, scale, mask_off, drop=drop), None
-
-
-def _ring_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs):
-    """_attention_interface for a call against a ring-buffer cache: `key` and `value` are the [N, Hkv, ring_slots, D] tensors
-    of a kv_cache.RingStaticLayer (Fp8RingStaticLayer: e4m3 rows with `_bf_kv8_scale`), marked `_bf_ring = (ring_slots,
-    capacity)`, the key with sequence index j in row j % ring_slots.  A decode step — the mask carries the fill `_bf_kv_len`
-    and the window `_bf_window`, at most 16 queries, no gradient, no dropout, no attention sinks, no key mask or a
-    [N, capacity] one, the module's `sliding_window` agreeing with the mask's, a soft-cap only under `softcap_attention()` —
-    runs bf_attention_decode_gqa_ring (bf_attention_decode_gqa_ring_kv8 on e4m3 rows).  ops.decode_kernel_wins is not
-    consulted: nothing else can read a ring.  Every other call raises RuntimeError with the reason: the framework's
-    attention would read the rows as if they lay in sequence order and be silently wrong."""
-    from . import ops
-
-    def refuse(why):
-        raise RuntimeError("bayeformers_amd: the keys of this call are a ring-buffer cache (sliding_cache=\"ring\"), which only "
-                           f"the ring decode kernels read, and {why}")
-
-    slots, capacity = key._bf_ring
-    if getattr(value, "_bf_ring", None) != key._bf_ring:
-        refuse("its values are not the same ring's")
-    k_scale, v_scale = getattr(key, "_bf_kv8_scale", None), getattr(value, "_bf_kv8_scale", None)
-    if (k_scale is None) != (v_scale is None):
-        refuse("only one of its keys and values carries FP8 scales")
-    marked = attention_mask is not None
-    kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
-    window = getattr(attention_mask, "_bf_window", None) if marked else None
-    key_mask = getattr(attention_mask, "_bf_key_mask", None) if marked else None
-    softcap = kwargs.get("softcap", None)
-    Tq = query.shape[2]
-    if Tq > ops.DECODE_MAX_QUERIES:
-        refuse(f"it carries {Tq} queries: a step takes at most {ops.DECODE_MAX_QUERIES} (a ring of window + "
-               f"{ops.DECODE_MAX_QUERIES - 1} slots holds no more live keys; prefill_chunk is not supported)")
-    if kv_len is None or window is None:
-        refuse("its mask is not the sliding-window mask of a fixed-capacity cache (no `_bf_kv_len` or no `_bf_window`)")
-    if torch.is_grad_enabled() and query.requires_grad:
-        refuse("it needs a gradient")
-    if dropout != 0.0:
-        refuse(f"it carries attention dropout ({dropout})")
-    if kwargs.get("s_aux", None) is not None:
-        refuse("it carries attention sinks (s_aux)")
-    if softcap is not None and not softcap_attention_enabled():
-        refuse("it carries a logit soft-cap with softcap_attention() off")
-    if "sliding_window" in kwargs and kwargs["sliding_window"] != window:
-        refuse(f"the module's sliding_window={kwargs['sliding_window']!r} disagrees with the mask's window {window}")
-    if window + Tq - 1 > slots:
-        refuse(f"window {window} with {Tq} queries needs {window + Tq - 1} slots, the ring has {slots}")
-    if key_mask is not None and tuple(key_mask.shape) != (query.shape[0], capacity):
-        refuse(f"its key mask is {tuple(key_mask.shape)}, not [N, capacity] = {(query.shape[0], capacity)}")
-    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-    mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-    cap = float(softcap) if softcap is not None else None
-    if k_scale is not None:
-        if not ops.attention_decode_kv8_supported(query, key, value):
-            refuse("bf_attention_decode_gqa_ring_kv8 does not take its shapes, dtypes or strides")
-        return ops.attention_forward_decode_ring_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
-                                                     None, window, slots, capacity, softcap=cap), None
-    if not ops.attention_decode_supported(query, key, value):
-        refuse("bf_attention_decode_gqa_ring does not take its shapes, dtypes or strides")
-    return ops.attention_forward_decode_ring(query, key, value, kv_len, key_mask, scale, mask_off, None, window, slots,
-                                             capacity, softcap=cap), None
-
-
-def _kv8_attention(module, query, key, value, attention_mask, dropout, scaling, **kwargs):
-    """_attention_interface for a call against an FP8 cache: `key` and `value` are the uint8 e4m3 rows of a
-    kv_cache.Fp8StaticLayer, carrying their fp32 row scales as `_bf_kv8_scale`.  A decode step — the mask carries the fill
-    `_bf_kv_len`, at most 16 queries, no gradient, no dropout, no attention sinks, no key mask or a [B, capacity] one, the
-    module's `sliding_window` agreeing with the mask's — runs bf_attention_decode_gqa_kv8 on the rows as they are, with the
-    mask's window and, under `softcap_attention()`, the call's soft-cap.  ops.decode_kernel_wins is not consulted: the FP8
-    cache is a memory option and no other attention reads it.  Under `chunked_attention()` a cached chunk of more than 16
-    queries (`_cached_chunk`) runs bf_attention_chunk_gqa_kv8 on the rows as they are, likewise.  Every other call dequantises the cache into bf16 first
-    (ops.kv8_dequantize, the whole capacity: correct but slow) and then takes the path the bf16 tensors would have taken;
-    the framework never sees the uint8 tensors."""
-    from . import ops
-
-    k_scale, v_scale = key._bf_kv8_scale, getattr(value, "_bf_kv8_scale", None)
-    if v_scale is None:
-        raise ValueError("bayeformers_amd: the keys of this call are FP8 cache rows but its values carry no scales")
-    marked = attention_mask is not None
-    kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
-    window = getattr(attention_mask, "_bf_window", None) if marked else None
-    key_mask = getattr(attention_mask, "_bf_key_mask", None) if marked else None
-    softcap = kwargs.get("softcap", None)
-    need_grad = torch.is_grad_enabled() and query.requires_grad
-    if (kv_len is not None and query.shape[2] <= ops.DECODE_MAX_QUERIES and not need_grad and dropout == 0.0
-            and kwargs.get("s_aux", None) is None
-            and not (window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window)
-            and (softcap is None or softcap_attention_enabled())
-            and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2]))
-            and ops.attention_decode_kv8_supported(query, key, value)):
-        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-        return ops.attention_forward_decode_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
-                                                window=window,
-                                                softcap=float(softcap) if softcap is not None else None), None
-    if (_cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs)
-            and (softcap is None or softcap_attention_enabled()) and ops.attention_chunk_kv8_supported(query, key, value)):
-        # a chunk of the chunked prefill: the rows as they are, no capacity-wide dequantise
-        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-        return ops.attention_forward_chunk_kv8(query, key, value, k_scale, v_scale, kv_len, key_mask, scale, mask_off,
-                                               window=window, softcap=float(softcap) if softcap is not None else None,
-                                               key_origin=getattr(attention_mask, "_bf_key_origin", 0)), None
-    return _attention_interface(module, query, ops.kv8_dequantize(key, k_scale), ops.kv8_dequantize(value, v_scale),
-                                attention_mask, dropout, scaling, **kwargs)
-
-
-def _cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs) -> bool:
-    """Whether a call is a cached chunk for the chunk entries (bf_attention_chunk_gqa and its kv8 sibling), under
-    `chunked_attention()`: more than 16 new queries (fewer run the decode kernels) and no more than the keys, no gradient,
-    no dropout, no attention sinks, one of _padding_mask_interface's cached-step masks (`_bf_decode`, or `_bf_kv_len` on a
-    fixed-capacity cache — the first chunk into a static cache included) whose window, if any, the module's
-    `sliding_window` agrees with, and no key mask or a [N, Tk] one.  The callers read the mask's fields themselves."""
-    from . import ops
-
-    if not chunked_attention_enabled() or attention_mask is None or need_grad or dropout != 0.0 \
-            or kwargs.get("s_aux", None) is not None:
-        return False
-    if not ops.DECODE_MAX_QUERIES < query.shape[2] <= key.shape[2]:
-        return False
-    if not (bool(getattr(attention_mask, "_bf_decode", False)) or getattr(attention_mask, "_bf_kv_len", None) is not None):
-        return False
-    window = getattr(attention_mask, "_bf_window", None)
-    if window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window:
-        return False
-    key_mask = getattr(attention_mask, "_bf_key_mask", None)
-    return key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])
-
-
-def _causal_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, **kwargs):
-    """The causal half of _attention_interface: bf_attention_fwd_gqa (bf_attention_bwd_gqa behind it) for equal query and
-    key lengths — any length: one that is no multiple of 128 runs the kernels' tail forms, unless `ragged_attention(False)`
-    or BF_NO_RAGGED_ATTENTION sends it to the framework — with no mask or _padding_mask_interface's causal mask; a decode
-    step against a KV cache (fewer than 17 new queries, no gradient, no dropout) on bf_attention_decode_gqa, or on
-    bf_attention_decode_gqa_len when the cache has
-    a fixed capacity (the mask carries the filled length `_bf_kv_len`); other masks, longer cached chunks and attention
-    dropout go to the framework's scaled-dot-product attention.  A sliding-window mask (`_bf_window`) takes the window
-    siblings of the same entries, unless the module's own `sliding_window` argument disagrees with it.  A call that carries
-    attention sinks (`s_aux`), which the kernels do not apply, goes to the framework with or without a window, on the
-    prefill, decode and fixed-capacity paths alike.  Logit soft-capping (`softcap`, Gemma 2) takes the soft-cap entries
-    (`_softcap_attention`) when `softcap_attention()` is on; with the switch off (the default) such a call goes to the
-    framework's scaled-dot-product attention too, which does NOT apply the cap.  Head size 256 (Gemma): a full-attention
-    forward without gradients and without a mask stays on the framework's attention too, whose is_causal form measured
-    faster (ops.prefill_kernel_wins).  Under `chunked_attention()` (off by default) a cached chunk of more than 16 queries
-    (`_cached_chunk`) runs bf_attention_chunk_gqa instead of the framework's attention, on a dynamic or a fixed-capacity
-    cache, with or without a window."""
-    from transformers.integrations.sdpa_attention import sdpa_attention_forward
-
-    from . import ops
-
-    band = getattr(attention_mask, "_bf_band", None) if attention_mask is not None else None
-    if band is not None and kwargs.get("softcap", None) is None:
-        return _packed_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, band, **kwargs)
-    window = getattr(attention_mask, "_bf_window", None) if attention_mask is not None else None
-    if (window is not None and "sliding_window" in kwargs and kwargs["sliding_window"] != window) \
-            or kwargs.get("s_aux", None) is not None \
-            or (kwargs.get("softcap", None) is not None and not softcap_attention_enabled()):
-        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
-    if kwargs.get("softcap", None) is not None:
-        return _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window,
-                                  float(kwargs["softcap"]), **{k: v for k, v in kwargs.items() if k != "softcap"})
-    kv_len = getattr(attention_mask, "_bf_kv_len", None) if attention_mask is not None else None
-    if _cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs) \
-            and ops.attention_chunk_supported(query, key, value) \
-            and ops.chunk_kernel_wins(query.shape[1], key.shape[1], query.shape[2], key.shape[2], query.shape[3], window):
-        # a chunk of the chunked prefill (chunked_attention(), off by default): bf_attention_chunk_gqa
-        key_mask = getattr(attention_mask, "_bf_key_mask", None)
-        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-        scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-        return ops.attention_forward_chunk(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
-                                           key_origin=getattr(attention_mask, "_bf_key_origin", 0)), None
-    # the keys a decode step reads: all Tk, or with a window the ~W + Tq - 1 some query sees (decode_kernel_wins' Tk)
-    read = key.shape[2] if window is None else min(key.shape[2], window + query.shape[2] - 1)
-    if kv_len is not None:  # a step against a fixed-capacity cache: _padding_mask_interface's mask carries the fill
-        key_mask = getattr(attention_mask, "_bf_key_mask", None)
-        if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
-                and ops.attention_decode_supported(query, key, value)
-                and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], read, query.shape[3])
-                and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2]))):
-            scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-            return ops.attention_forward_decode_len(query, key, value, kv_len, key_mask, scale,
-                                                    getattr(attention_mask, "_bf_mask_off", None), window=window), None
-        # (the bool mask hides the keys past the fill: the framework's attention over the whole capacity is exact)
-        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
-    if (query.shape[2] < key.shape[2] and not need_grad and dropout == 0.0
-            and ops.attention_decode_supported(query, key, value)
-            and ops.decode_kernel_wins(query.shape[1], key.shape[1], query.shape[2], read, query.shape[3])):
-        # no mask: nothing padded (a one-query step sees every cached key); else only the mask _padding_mask_interface built
-        ready = attention_mask is None or bool(getattr(attention_mask, "_bf_decode", False))
-        key_mask = getattr(attention_mask, "_bf_key_mask", None) if attention_mask is not None else None
-        if ready and (key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])):
-            mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-            scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-            return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off, window=window), None
-    key_mask = mask_off = None
-    usable = (dropout == 0.0 and query.shape[2] == key.shape[2]
-              and (query.shape[2] % 128 == 0 or ragged_attention_enabled())
-              and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1])
-              and ops.prefill_kernel_wins(query.shape[1], key.shape[1], query.shape[2], query.shape[3], need_grad, window,
-                                          masked=attention_mask is not None))
-    if usable and window is not None:  # the sliding mask of the cache-free sequence (key mask None: nothing padded)
-        key_mask = getattr(attention_mask, "_bf_key_mask", None)
-        usable = key_mask is None or tuple(key_mask.shape) == (query.shape[0], key.shape[2])
-        mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-    elif usable and attention_mask is not None:
-        key_mask = getattr(attention_mask, "_bf_key_mask", None)
-        usable = getattr(attention_mask, "_bf_causal", False) and key_mask is not None and \
-            tuple(key_mask.shape) == (query.shape[0], key.shape[2])
-        mask_off = getattr(attention_mask, "_bf_mask_off", None)
-    if not usable:
-        if attention_mask is not None and attention_mask.dtype not in (torch.bool, query.dtype):
-            attention_mask = attention_mask.to(query.dtype)
-        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
-    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-    if window is not None:
-        if need_grad:
-            return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True, window), None
-        return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off, window=window), None
-    if need_grad:
-        return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True), None
-    return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off), None
-
-
-def _packed_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, band, **kwargs):
-    """_causal_attention for a packed-sequence mask (`_bf_band = (lo, hi)`, `_bf_band_window`: `_packed_mask`), without
-    soft-capping: bf_attention_fwd_gqa_band (bf_attention_bwd_gqa_band behind it when a gradient is needed) under
-    `packed_attention()`, for equal query and key lengths of any size (subject to `ragged_attention`) and the shapes
-    ops.attention_supported takes.  Attention sinks (`s_aux`), a `sliding_window` argument that disagrees with the mask's
-    window, attention dropout, unsupported shapes and the classes ops.prefill_kernel_wins sends there run the framework's
-    scaled-dot-product attention over the dense mask, as every such call did before."""
-    from transformers.integrations.sdpa_attention import sdpa_attention_forward
-
-    from . import ops
-
-    window = getattr(attention_mask, "_bf_band_window", None)
-    B, H, T, D = query.shape
-    usable = (packed_attention_enabled() and kwargs.get("s_aux", None) is None
-              and not ("sliding_window" in kwargs and kwargs["sliding_window"] != window)
-              and dropout == 0.0 and T == key.shape[2] and (T % 128 == 0 or ragged_attention_enabled())
-              and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1])
-              and tuple(band[0].shape) == (B, T) and tuple(band[1].shape) == (B, T)
-              and ops.prefill_kernel_wins(H, key.shape[1], T, D, need_grad, window, masked=True))
-    if not usable:
-        return sdpa_attention_forward(module, query, key, value, attention_mask, dropout=dropout, scaling=scaling, **kwargs)
-    scale = scaling if scaling is not None else D ** -0.5
-    if need_grad:
-        return ops.AttentionGqaBandFn.apply(query, key, value, band[0], band[1], scale), None
-    return ops.attention_forward_gqa_band(query, key, value, band[0], scale), None
-
-
-def _softcap_attention(module, query, key, value, attention_mask, dropout, scaling, need_grad, window, softcap, **kwargs):
-    """_causal_attention for a call with logit soft-capping (HF Gemma2Attention: softcap = attn_logit_softcapping), under
-    `softcap_attention()`: the same cases on the soft-cap entries — bf_attention_fwd_gqa_softcap (with
-    bf_attention_bwd_gqa_softcap behind it) for prefill and training at any length (subject to `ragged_attention`),
-    bf_attention_decode_gqa_softcap for a step against a cache, with the fill `_bf_kv_len` when its capacity is fixed, each
-    with or without a window and a padding key mask.  The dispatch rules that weigh the kernels against the framework's
-    attention are not consulted: that attention does not compute this function.  What the kernels do not take (attention
-    dropout, a cached chunk of more than 16 queries, other masks, unsupported shapes or dtypes) runs `_softcap_eager`,
-    never the framework's scaled-dot-product attention.  Under `chunked_attention()` such a cached chunk (`_cached_chunk`)
-    runs bf_attention_chunk_gqa with the cap instead."""
-    from . import ops
-
-    scale = scaling if scaling is not None else query.shape[-1] ** -0.5
-    Tq, Tk = query.shape[2], key.shape[2]
-    marked = attention_mask is not None
-    key_mask = getattr(attention_mask, "_bf_key_mask", None) if marked else None
-    mask_off = getattr(attention_mask, "_bf_mask_off", None) if key_mask is not None else None
-    keys_ok = key_mask is None or tuple(key_mask.shape) == (query.shape[0], Tk)
-    kv_len = getattr(attention_mask, "_bf_kv_len", None) if marked else None
-    plain = not need_grad and dropout == 0.0 and keys_ok
-    if _cached_chunk(query, key, attention_mask, need_grad, dropout, kwargs) \
-            and ops.attention_chunk_supported(query, key, value):
-        # a chunk of the chunked prefill (chunked_attention()): bf_attention_chunk_gqa with the cap (kwargs: the call's other
-        # arguments, for the sinks and the module's own window, which _causal_attention sends to the framework before this)
-        return ops.attention_forward_chunk(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
-                                           softcap=softcap, key_origin=getattr(attention_mask, "_bf_key_origin", 0)), None
-    if kv_len is not None:  # a step against a fixed-capacity cache
-        if Tq < Tk and plain and ops.attention_decode_supported(query, key, value):
-            return ops.attention_forward_decode_len(query, key, value, kv_len, key_mask, scale, mask_off, window=window,
-                                                    softcap=softcap), None
-    elif Tq < Tk:  # a step against a cache: no mask (one query, nothing padded) or _padding_mask_interface's
-        if plain and ops.attention_decode_supported(query, key, value) \
-                and (not marked or bool(getattr(attention_mask, "_bf_decode", False))):
-            return ops.attention_forward_decode(query, key, value, key_mask, scale, mask_off, window=window,
-                                                softcap=softcap), None
-    elif (dropout == 0.0 and Tq == Tk and keys_ok and (Tq % 128 == 0 or ragged_attention_enabled())
-          and ops.attention_supported(query, key, value, causal=True, kv_heads=key.shape[1])
-          # no mask, the sliding mask (key mask None: nothing padded) or the causal padding mask
-          and (not marked or window is not None or (getattr(attention_mask, "_bf_causal", False) and key_mask is not None))):
-        if need_grad:
-            return ops.AttentionGqaFn.apply(query, key, value, key_mask, mask_off, scale, True, window, softcap), None
-        return ops.attention_forward_gqa(query, key, value, key_mask, scale, True, mask_off, window=window,
-                                         softcap=softcap), None
-    return _softcap_eager(module, query, key, value, attention_mask, dropout, scale, softcap), None
-
-
-def _softcap_eager(module, query, key, value, attention_mask, dropout, scaling, softcap):
-    """The fallback of `_softcap_attention`: the model's own eager chain (transformers' gemma2 eager_attention_forward:
-    repeat_kv, matmul, `/ softcap`, tanh, `* softcap`, `+ mask`, fp32 softmax, dropout, matmul) in plain torch.  The mask
-    arrives in the SDPA format (bool, True = visible) and is turned into the additive one the chain adds; no mask means
-    causal, bottom-right aligned (the module's is_causal).  Returns [B, Tq, H, D]."""
-    B, H, Tq, D = query.shape
-    Tk, rep = key.shape[2], H // key.shape[1]
-    if rep > 1:
-        key = key[:, :, None].expand(B, key.shape[1], rep, Tk, D).reshape(B, H, Tk, D)
-        value = value[:, :, None].expand(B, value.shape[1], rep, Tk, D).reshape(B, H, Tk, D)
-    w = torch.matmul(query, key.transpose(2, 3)) * scaling
-    w = torch.tanh(w / softcap) * softcap
-    lowest = torch.finfo(w.dtype).min
-    if attention_mask is None:
-        if Tq > 1:
-            seen = torch.ones((Tq, Tk), dtype=torch.bool, device=w.device).tril(Tk - Tq)
-            w = w + torch.where(seen, 0.0, lowest).to(w.dtype)
-    elif attention_mask.dtype == torch.bool:
-        w = w + torch.where(attention_mask, 0.0, lowest).to(w.dtype)
-    else:
-        w = w + attention_mask.to(w.dtype)
-    w = torch.nn.functional.softmax(w, dim=-1, dtype=torch.float32).to(query.dtype)
-    w = torch.nn.functional.dropout(w, p=dropout, training=bool(getattr(module, "training", False)))
-    return torch.matmul(w, value).transpose(1, 2).contiguous()
-
-
-def _closure_cell(fn, name):
-    """What the closure of `fn` holds under the free variable `name` (None: not a closure over it)."""
-    code = getattr(fn, "__code__", None)
-    if code is None or name not in code.co_freevars or fn.__closure__ is None:
-        return None
-    return fn.__closure__[code.co_freevars.index(name)].cell_contents
-
-
-def _packed_sequence_of(mask_function):
-    """(ids, W) when mask_function is exactly the composition transformers builds for packed sequences
-    (masking_utils._preprocess_mask_arguments: position_ids that restart, no attention mask) — and_masks(f,
-    packed_sequence_mask_function(ids)) over exactly two functions, f being causal_mask_function (W = None) or
-    sliding_window_causal_mask_function(W) — else None.  `ids` is the [B, T] tensor of document indices, non-decreasing
-    along T as find_packed_sequence_indices returns it (a cumulative sum)."""
-    from transformers import masking_utils as mu
-
-    if getattr(mask_function, "__code__", None) is not mu.and_masks(mu.causal_mask_function).__code__:
-        return None
-    fns = _closure_cell(mask_function, "mask_functions")
-    if not isinstance(fns, tuple) or len(fns) != 2:
-        return None
-    if getattr(fns[1], "__code__", None) is not mu.packed_sequence_mask_function(None).__code__:
-        return None
-    ids = _closure_cell(fns[1], "packed_sequence_mask")
-    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.dtype.is_floating_point or ids.dtype == torch.bool:
-        return None
-    if fns[0] is mu.causal_mask_function:
-        return ids, None
-    window = _sliding_window_of(fns[0])
-    return (ids, window) if window is not None else None
-
-
-def _packed_mask(batch_size, q_length, kv_length, q_offset, kv_offset, ids, window, attention_mask, **kwargs):
-    """The packed-sequence mask _padding_mask_interface builds on the device (NotImplemented: not the case it takes): the
-    cache-free sequence, no padding mask, ids [batch_size, kv_length].  Query i sees key j iff j <= i, both lie in one
-    document and — with a window — i - j < window: sdpa_mask's [B, 1, T, T] bool mask, carrying the bounds of banded
-    causal attention `_bf_band = (lo, hi)` (ops.band_bounds) and `_bf_band_window` for the band entries."""
-    from . import ops
-
-    local_size = kwargs.get("local_size", None)
-    if (kwargs.get("use_vmap", False) or attention_mask is not None or q_length is None or q_length != kv_length
-            or not (isinstance(q_offset, int) and isinstance(kv_offset, int) and q_offset == 0 and kv_offset == 0)
-            or tuple(ids.shape) != (batch_size, kv_length)
-            or (local_size is not None and local_size != window)):
-        return NotImplemented
-    pos = torch.arange(kv_length, device=ids.device)
-    seen = (pos[None, :] <= pos[:, None])[None, :, :] & (ids[:, :, None] == ids[:, None, :])
-    if window is not None:
-        seen = seen & (pos[None, :] > pos[:, None] - window)[None, :, :]
-    out = seen[:, None, :, :]
-    out._bf_band = ops.band_bounds(ids, window)
-    out._bf_band_window = window
-    return out
-
-
-def _sliding_window_of(mask_function):
-    """W when mask_function is exactly transformers' sliding_window_causal_mask_function(W) — and_masks over the two
-    functions (sliding_window_overlay(W)'s inner function, causal_mask_function) and nothing else — else None."""
-    from transformers import masking_utils as mu
-
-    cell = _closure_cell
-    if getattr(mask_function, "__code__", None) is not mu.and_masks(mu.causal_mask_function).__code__:
-        return None
-    fns = cell(mask_function, "mask_functions")
-    if not isinstance(fns, tuple) or len(fns) != 2 or fns[1] is not mu.causal_mask_function:
-        return None
-    if getattr(fns[0], "__code__", None) is not mu.sliding_window_overlay(1).__code__:
-        return None
-    w = cell(fns[0], "sliding_window")
-    return w if isinstance(w, int) and not isinstance(w, bool) and w >= 1 else None
-
-
-def _sliding_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, attention_mask, **kwargs):
-    """The three sliding-window causal masks _padding_mask_interface builds on the device (NotImplemented: not one of
-    them; None: sdpa_mask's answer when the window hides nothing and nothing is padded).
-    Query i (index q_offset + i) sees key j (index kv_offset + j) iff q_offset + i - window < kv_offset + j <= q_offset + i
-    and the key is not padding — sdpa_mask's [B, 1, Tq, Tk] bool mask, carrying `_bf_window` and the key mask."""
-    local_size = kwargs.get("local_size", None)
-    if kwargs.get("use_vmap", False) or (local_size is not None and local_size != window) or q_length is None \
-            or kv_length is None or not 0 < q_length <= kv_length:
-        return NotImplemented
-    if isinstance(q_offset, torch.Tensor):  # a fixed-capacity cache (see the causal case below): q_offset is its fill
-        if kv_offset != 0 or not (attention_mask is None or (attention_mask.dim() == 2
-                                                              and attention_mask.shape == (batch_size, kv_length))):
-            return NotImplemented
-        device = q_offset.device
-        keys = torch.arange(kv_length, device=device)
-        last = q_offset.reshape(()) + torch.arange(q_length, device=device)  # each query's own index
-        tri = (keys[None, :] <= last[:, None]) & (keys[None, :] > last[:, None] - window)
-        visible = None if attention_mask is None else (attention_mask if attention_mask.dtype == torch.bool
-                                                       else attention_mask != 0)
-        out = _with_keys(tri, visible, batch_size, q_length, kv_length)
-        out._bf_decode = True
-        out._bf_kv_len = (q_offset.reshape(()) + q_length).reshape(1)
-        out._bf_window = window
-        return out
-    if not (isinstance(q_offset, int) and isinstance(kv_offset, int) and kv_offset >= 0
-            and q_offset - kv_offset == kv_length - q_length):
-        return NotImplemented
-    if attention_mask is not None and not (attention_mask.dim() == 2
-                                           and attention_mask.shape == (batch_size, kv_offset + kv_length)):
-        return NotImplemented
-    if attention_mask is None and kwargs.get("allow_is_causal_skip", True) and kv_length < window \
-            and (q_length == 1 or q_length == kv_length):
-        return None  # as sdpa_mask answers: the window hides nothing, module.is_causal routes the call
-    device = attention_mask.device if attention_mask is not None else kwargs.get("device", "cpu")
-    keys = torch.arange(kv_offset, kv_offset + kv_length, device=device)
-    last = torch.arange(q_offset, q_offset + q_length, device=device)
-    tri = (keys[None, :] <= last[:, None]) & (keys[None, :] > last[:, None] - window)
-    visible = None
-    if attention_mask is not None:
-        visible = attention_mask[:, kv_offset:kv_offset + kv_length]
-        visible = visible if visible.dtype == torch.bool else visible != 0
-    out = _with_keys(tri, visible, batch_size, q_length, kv_length)
-    if q_length < kv_length:
-        out._bf_decode = True  # a step against a cache (bottom-right aligned)
-    out._bf_window = window
-    out._bf_key_origin = kv_offset  # the sequence index of key 0 (a sliding cache kept its last keys): the chunk entries' tile grid
-    return out
-
-
-def _with_keys(tri, visible, batch_size, q_length, kv_length):
-    """tri [Tq, Tk] & the padding key mask visible [B, Tk] (None: nothing padded) as [B, 1, Tq, Tk], carrying the
-    additive fp32 key mask and the device flag "nothing is hidden" (both None without padding)."""
-    if visible is None:
-        out = tri[None, None, :, :].expand(batch_size, 1, q_length, kv_length)
-        out._bf_key_mask = out._bf_mask_off = None
-        return out
-    out = tri[None, None, :, :] & visible[:, None, None, :]
-    out._bf_key_mask = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
-    out._bf_mask_off = visible.all().reshape(1)
-    return out
-
-
-def _padding_mask_interface(batch_size, q_length=None, kv_length=None, q_offset=0, kv_offset=0, mask_function=None,
-                            attention_mask=None, **kwargs):
-    """Mask function in the HuggingFace `AttentionMaskInterface` convention for models routed through
-    `_attention_interface`.  A plain bidirectional padding mask [B, T] becomes, ONCE per forward and without a host
-    round trip, the additive fp32 key mask bf_attention_fwd reads plus a one-byte device flag "nothing is hidden" that
-    lets the kernel skip the mask (the framework's own function answers that question with `mask.all()` on the host —
-    a device synchronisation in every forward, and a different code path under HIP-graph capture).  The 4-D tensor
-    returned ([B, 1, 1, T] additive) is what the framework's attention takes when the kernel does not apply.
-    A decoder's causal mask for a step against a KV cache (q_offset = kv_length - q_length, a 2-D padding mask or none)
-    is built on the device too: the [B, 1, Tq, Tk] bool mask the framework's attention takes, carrying the key mask and
-    the causal marker `_bf_decode` for bf_attention_decode_gqa (None for one query and no padding mask, as the framework answers).
-    A step against a fixed-capacity cache (q_offset a device tensor: the fill of a transformers StaticCache, kv_length its
-    capacity) gets the [B, 1, Tq, capacity] bool mask built on the device (causal from q_offset, the keys past the fill
-    hidden) with the key mask and a snapshot of the fill after this step, `_bf_kv_len`, for bf_attention_decode_gqa_len.
-    A sliding-window causal mask (exactly transformers' sliding_window_causal_mask_function(W)) is built the same three
-    ways — the cache-free sequence, a step against a cache (a DynamicSlidingWindowLayer's kv_offset > 0 included: its
-    key mask is the 2-D mask's slice at kv_offset) and a fixed-capacity cache — and carries `_bf_window = W` for the
-    window entries; it is never None when the window hides something.
-    Packed sequences (exactly and_masks(causal_mask_function or sliding_window_causal_mask_function(W),
-    packed_sequence_mask_function(ids)), the cache-free sequence, no padding mask: `_packed_mask`) get the same dense bool
-    mask carrying `_bf_band = (lo, hi)` and `_bf_band_window` for the band entries — and none of the other markers.
-    Anything else (4-D masks, extra mask functions, other offsets) goes to the framework's scaled-dot-product mask."""
-    from transformers.masking_utils import bidirectional_mask_function, causal_mask_function, sdpa_mask
-
-    window = _sliding_window_of(mask_function) if mask_function is not causal_mask_function else None
-    packed = _packed_sequence_of(mask_function) if mask_function is not causal_mask_function and window is None else None
-    if packed is not None:
-        out = _packed_mask(batch_size, q_length, kv_length, q_offset, kv_offset, packed[0], packed[1], attention_mask,
-                           **kwargs)
-        if out is not NotImplemented:
-            return out
-    if window is not None:
-        out = _sliding_mask(batch_size, q_length, kv_length, q_offset, kv_offset, window, attention_mask, **kwargs)
-        if out is not NotImplemented:
-            return out
-
-    if (mask_function is causal_mask_function and isinstance(q_offset, torch.Tensor) and kv_offset == 0
-            and q_length is not None and kv_length is not None and 0 < q_length <= kv_length
-            and not kwargs.get("use_vmap", False)
-            and (attention_mask is None or (attention_mask.dim() == 2 and attention_mask.shape == (batch_size, kv_length)))):
-        # a fixed-capacity cache (transformers' StaticLayer: q_offset is its fill count, a device tensor, and kv_length its
-        # capacity).  Tested before the comparisons below: on a tensor they synchronise with the host (or fail a capture).
-        # Query i sees keys 0 .. q_offset + i, which hides the keys past the fill; the snapshot kv_len is the fill after
-        # this forward's update (the cache bumps its counter in place during the forward)
-        device = q_offset.device
-        kv_len = (q_offset.reshape(()) + q_length).reshape(1)
-        keys = torch.arange(kv_length, device=device)
-        tri = keys[None, :] <= (q_offset.reshape(()) + torch.arange(q_length, device=device))[:, None]
-        if attention_mask is None:
-            out = tri[None, None, :, :].expand(batch_size, 1, q_length, kv_length)
-            out._bf_key_mask = out._bf_mask_off = None
-        else:
-            visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
-            out = tri[None, None, :, :] & visible[:, None, None, :]
-            out._bf_key_mask = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
-            out._bf_mask_off = visible.all().reshape(1)
-        out._bf_decode = True
-        out._bf_kv_len = kv_len
-        return out
-
-    if (mask_function is causal_mask_function and kv_offset == 0 and q_length is not None and kv_length is not None
-            and 0 < q_length < kv_length and q_offset == kv_length - q_length and not kwargs.get("use_vmap", False)
-            and (attention_mask is None or (attention_mask.dim() == 2 and attention_mask.shape == (batch_size, kv_length)))):
-        if attention_mask is None and q_length == 1:
-            return None  # the new query sees every cached key: module.is_causal routes the call
-        device = attention_mask.device if attention_mask is not None else kwargs.get("device", "cpu")
-        keys = torch.arange(kv_length, device=device)
-        tri = keys[None, :] <= torch.arange(q_offset, kv_length, device=device)[:, None]  # query i sees 0 .. q_offset + i
-        if attention_mask is None:
-            out = tri[None, None, :, :].expand(batch_size, 1, q_length, kv_length)
-            out._bf_key_mask = out._bf_mask_off = None
-        else:
-            visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
-            out = tri[None, None, :, :] & visible[:, None, None, :]
-            out._bf_key_mask = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
-            out._bf_mask_off = visible.all().reshape(1)
-        out._bf_decode = True  # causal, bottom-right aligned (_bf_causal stays the cache-free marker)
-        return out
-
-    if (mask_function is causal_mask_function and q_offset == 0 and kv_offset == 0 and q_length == kv_length
-            and not kwargs.get("use_vmap", False)
-            and (attention_mask is None or (attention_mask.dim() == 2 and attention_mask.shape == (batch_size, kv_length)))):
-        # a decoder's causal mask over the cache-free sequence: None when nothing is padded (the framework's answer too:
-        # the attention is then causal by module.is_causal); with a padding mask, sdpa_mask's [B, 1, T, T] bool mask built
-        # on the device without a host round trip, carrying the key mask and "causal" for bf_attention_fwd_gqa
-        if attention_mask is None:
-            return None
-        visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
-        additive = torch.where(visible, 0.0, float("-inf")).to(torch.float32)
-        tri = torch.ones((q_length, kv_length), dtype=torch.bool, device=visible.device).tril()
-        out = tri[None, None, :, :] & visible[:, None, None, :]
-        out._bf_key_mask = additive
-        out._bf_mask_off = visible.all().reshape(1)
-        out._bf_causal = True
-        return out
-    plain = (attention_mask is not None and attention_mask.dim() == 2 and mask_function is bidirectional_mask_function
-             and not kwargs.get("use_vmap", False) and q_offset == 0 and kv_offset == 0
-             and attention_mask.shape == (batch_size, kv_length))
-    if attention_mask is None and mask_function is bidirectional_mask_function:
-        return None
-    if not plain:
-        return sdpa_mask(batch_size=batch_size, q_length=q_length, kv_length=kv_length, q_offset=q_offset,
-                         kv_offset=kv_offset, mask_function=mask_function, attention_mask=attention_mask, **kwargs)
-    visible = attention_mask if attention_mask.dtype == torch.bool else attention_mask != 0
-    additive = torch.where(visible, 0.0, float("-inf")).to(torch.float32)  # one launch (fp32 already: .to is a no-op)
-    out = additive[:, None, None, :]
-    out._bf_key_mask = additive
-    out._bf_mask_off = visible.all().reshape(1)  # stays on the device
-    return out
-
-
-_RAGGED_ATTENTION = [True]
-
-
-def ragged_attention(enable: bool = True) -> None:
-    """Switch the causal attention kernels for sequence lengths that are no multiple of 128 (the tail forms of
-    bf_attention_fwd_gqa / bf_attention_bwd_gqa and their window siblings) on or off for this process;
-    BF_NO_RAGGED_ATTENTION in the environment switches them off too.  Off: such a prefill or training step runs the
-    framework's scaled-dot-product attention, as every length but the multiples of 128 did before.  The switch is part of
-    what a captured forward bakes in (graphs.baked_state): a replayed forward is captured again after a flip."""
-    _RAGGED_ATTENTION[0] = bool(enable)
-
-
-def ragged_attention_enabled() -> bool:
-    return _RAGGED_ATTENTION[0] and os.environ.get("BF_NO_RAGGED_ATTENTION") is None
-
-
-_PACKED_ATTENTION = [True]
-
-
-def packed_attention(enable: bool = True) -> None:
-    """Switch the band attention kernels for packed sequences (bf_attention_fwd_gqa_band / bf_attention_bwd_gqa_band:
-    position ids that restart at each document, no attention mask) on or off for this process; BF_NO_PACKED_ATTENTION in
-    the environment switches them off too.  Off: such a prefill or training step runs the framework's scaled-dot-product
-    attention over the dense [B, 1, T, T] mask, as it did before.  The switch is part of what a captured forward bakes in
-    (graphs.baked_state): a replayed forward is captured again after a flip."""
-    _PACKED_ATTENTION[0] = bool(enable)
-
-
-def packed_attention_enabled() -> bool:
-    return _PACKED_ATTENTION[0] and os.environ.get("BF_NO_PACKED_ATTENTION") is None
-
-
-_SOFTCAP_ATTENTION = [False]
-
-
-def softcap_attention(enable: bool = True) -> None:
-    """Switch the soft-cap attention kernels (bf_attention_fwd_gqa_softcap / bf_attention_bwd_gqa_softcap /
-    bf_attention_decode_gqa_softcap) on or off for this process; BF_SOFTCAP_ATTENTION in the environment switches them on
-    too.  OFF by default.  On: a causal attention call that carries `softcap` (HF Gemma 2: attn_logit_softcapping) runs
-    them — prefill, training, cached decode and fixed-capacity decode — and what they do not take runs the model's eager
-    chain with the cap.  Off: such a call goes to the framework's scaled-dot-product attention, which ignores `softcap`:
-    the result is then NOT the model's function (keep such a model on its `eager` attention, or switch this on).  The
-    switch is part of what a captured forward bakes in (graphs.baked_state): a replayed forward is captured again after a
-    flip."""
-    _SOFTCAP_ATTENTION[0] = bool(enable)
-
-
-def softcap_attention_enabled() -> bool:
-    return _SOFTCAP_ATTENTION[0] or os.environ.get("BF_SOFTCAP_ATTENTION") is not None
-
-
-_CHUNKED_ATTENTION = [False]
-
-
-def chunked_attention(enable: bool = True) -> None:
-    """Switch the cached-chunk attention kernels (bf_attention_chunk_gqa / bf_attention_chunk_gqa_kv8) on or off for this
-    process; BF_CHUNKED_ATTENTION in the environment switches them on too.  OFF by default.  On: a forward of more than 16
-    new tokens against a KV cache — a chunk of a chunked prefill — without gradient, dropout or attention sinks runs them
-    (`_cached_chunk`): on a dynamic cache, on a fixed-capacity one (the fill is a device scalar), on an FP8 cache without
-    dequantising it, with a sliding window, and with soft-capping under `softcap_attention()`.  Off: such a call goes
-    where it always went — the framework's scaled-dot-product attention over the dense mask, the capped eager chain, or a
-    capacity-wide dequantise first.  `sample_generate(prefill_chunk=...)` turns it on for its prefill and restores it."""
-    _CHUNKED_ATTENTION[0] = bool(enable)
-
-
-def chunked_attention_enabled() -> bool:
-    return _CHUNKED_ATTENTION[0] or os.environ.get("BF_CHUNKED_ATTENTION") is not None
-
-
-_ENCODER_RAGGED_ATTENTION = [False]
-
-
-def encoder_ragged_attention(enable: bool = True) -> None:
-    """Switch the any-length encoder attention kernels (bf_attention_fwd_any / bf_attention_bwd_any and their dropout and
-    rows siblings: the tail forms of the encoder kernels) on or off for this process; BF_ENCODER_RAGGED_ATTENTION in the
-    environment switches them on too.  OFF by default.  On: a non-causal attention call of head size 64 whose length is
-    no multiple of 128 (a batch padded to its longest sentence, a ViT's 197 tokens) runs them — inference, training with
-    attention_probs_dropout on the Philox keep-masks (the dropout contract of csrc/bf_philox.h then holds at every
-    length), and the [CLS] row of a pooled head's last layer — with the masks `_attention_interface` takes.  Off: such
-    a call runs the framework's scaled-dot-product attention over the dense mask, dropout from the framework's generator.
-    The switch is part of what a captured forward bakes in (graphs.baked_state): a replayed forward is captured again
-    after a flip.  profiles/encoder_ragged_attention.md says when it pays."""
-    _ENCODER_RAGGED_ATTENTION[0] = bool(enable)
-
-
-def encoder_ragged_attention_enabled() -> bool:
-    return _ENCODER_RAGGED_ATTENTION[0] or os.environ.get("BF_ENCODER_RAGGED_ATTENTION") is not None
-
-
 _POOLED_LAST_LAYER = [True]
 _POOLED_ACTIVE = threading.local()  # .layers: ids of the last layers whose head said "narrow" for the call running on this thread
 
@@ -1279,9 +562,9 @@ def _pooled_last_layer_forward(self, hidden_states, attention_mask=None, encoder
     rows_any = not rows_attention and encoder_ragged_attention_enabled() and ops.attention_any_supported(q, k, v)
     rows_attention = rows_attention or rows_any
     if rows_attention and attention_mask is not None:
-        ready = getattr(attention_mask, "_bf_key_mask", None)
-        if ready is not None and ready.shape == (Bt, T):
-            key_mask, mask_off = ready, attention_mask._bf_mask_off
+        marks = _marks_of(attention_mask)
+        if marks.key_mask is not None and marks.key_mask.shape == (Bt, T):
+            key_mask, mask_off = marks.key_mask, marks.mask_off
         else:
             rows_attention = False
     if rows_attention:
@@ -1809,40 +1092,3 @@ def fuse_decoder_blocks(model: torch.nn.Module, backward: Union[bool, str] = Fal
                     m._bf_blocks_backward = True
             fused += 1
     return fused
-
-
-def fuse_attention(model: torch.nn.Module) -> bool:
-    """Route the wrapped HuggingFace model's attention through bf_attention_fwd: registers an attention function in
-    transformers' AttentionInterface (mask format: the scaled-dot-product one) and selects it in the model's config.
-    The function falls back to the framework's attention for anything it does not take.  A decoder's causal attention
-    (Llama, Mistral, Qwen2, Gemma: grouped heads, sliding windows, head size 64, 128 or 256) runs bf_attention_fwd_gqa
-    at any sequence length (`ragged_attention(False)` or BF_NO_RAGGED_ATTENTION: at multiples of 128 only); a call with
-    attention sinks (gpt-oss) goes to the framework.  Logit soft-capping (Gemma 2) runs the soft-cap entries
-    (bf_attention_fwd_gqa_softcap and its backward and decode siblings) once `softcap_attention()` or BF_SOFTCAP_ATTENTION
-    switches them on; with that switch off, the default, such a call goes to the framework's scaled-dot-product attention,
-    which ignores the cap — the model then computes another function than its `eager` attention.  Packed sequences
-    (position ids that restart at each document, no attention mask, no cache) run the band entries
-    (bf_attention_fwd_gqa_band / bf_attention_bwd_gqa_band) unless `packed_attention(False)` or BF_NO_PACKED_ATTENTION
-    sends them to the framework's attention over the dense mask.  The ops around the
-    attention of those families (norms, rotary embedding, gate) are fuse_decoder_blocks's, opt-in by its `families`.  Returns False (and changes
-    nothing) when the model has no HuggingFace config or transformers lacks the interface.
-    A BertForSequenceClassification also gets the narrow last encoder layer (`_pooled_last_layer_forward`): in evaluation
-    forwards that ask for neither hidden states nor attentions, everything behind the last layer's key / value
-    projections runs on the [CLS] rows alone (`pooled_last_layer(False)` or BF_NO_POOLED_LAST_LAYER: on every row)."""
-    try:
-        from transformers import AttentionInterface
-        from transformers.masking_utils import AttentionMaskInterface, sdpa_mask
-    except ImportError:
-        return False
-    inner = model.model if isinstance(model, Model) and model.model is not None else model
-    config = getattr(inner, "config", None)
-    if config is None or not hasattr(config, "_attn_implementation"):
-        return False
-    AttentionInterface.register(_ATTENTION_NAME, _attention_interface)
-    AttentionMaskInterface.register(_ATTENTION_NAME, _padding_mask_interface)
-    for m in inner.modules():
-        c = getattr(m, "config", None)
-        if c is not None and hasattr(c, "_attn_implementation"):
-            c._attn_implementation = _ATTENTION_NAME
-    _install_pooled_last_layer(inner)
-    return True

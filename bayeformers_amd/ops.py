@@ -1042,25 +1042,37 @@ DECODE_CALLS = {"fwd": 0, "len": 0, "window": 0, "len_window": 0}
 DECODE_MAX_QUERIES = 16
 
 
-def attention_decode_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bool = True) -> bool:
-    """What bf_attention_decode_gqa takes: q [N, H, Tq, D] (1 <= Tq <= 16), k and v [N, Hkv, Tk, D] with Tq <= Tk, Hkv
-    dividing H, D 64, 128 or 256, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8
-    elements) and a contiguous feature dimension.  check_device=False judges the shapes, dtypes and strides alone (CPU or
-    meta tensors)."""
+def _cached_layout_ok(q: Tensor, k: Tensor, v: Tensor, check_device: bool, fp8: bool, chunk: bool) -> bool:
+    """The one layout test behind the four `*_supported` predicates of the cached entries: q [N, H, Tq, D], k and v
+    [N, Hkv, Tk, D] with Hkv dividing H, D 64, 128 or 256, a contiguous feature dimension, 16-byte aligned, and (batch, head,
+    token) strides that are non-negative multiples of 16 bytes — 8 elements of q and of a 16-bit cache (bf16 or fp16, one
+    dtype), 16 of an e4m3 one (fp8: q bfloat16, k / v uint8).  chunk: any 1 <= Tq <= Tk; else a decode step, Tq at most
+    DECODE_MAX_QUERIES.  check_device=False judges the shapes, dtypes and strides alone (CPU or meta tensors)."""
     if check_device and not (q.is_cuda and k.is_cuda and v.is_cuda):
         return False
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+    if fp8:
+        if q.dtype != torch.bfloat16 or k.dtype != torch.uint8 or v.dtype != torch.uint8:
+            return False
+    elif q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
         return False
     if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape:
         return False
     N, H, Tq, D = q.shape
     Hkv, Tk = k.shape[1], k.shape[2]
-    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in (64, 128, 256):
+    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in KV8_HEAD_SIZES or not 1 <= Tq <= Tk:
         return False
-    if not (1 <= Tq <= DECODE_MAX_QUERIES and Tq <= Tk) or N * Hkv > 65535:
+    if (N > 65535 or H > 65535 or Tk >= 2 ** 31) if chunk else (Tq > DECODE_MAX_QUERIES or N * Hkv > 65535):  # the grids
         return False
-    return all(t.stride(3) == 1 and all(st >= 0 and st % 8 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
-               for t in (q, k, v))
+    return all(t.stride(3) == 1 and all(st >= 0 and st % granule == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
+               for t, granule in ((q, 8), (k, 16 if fp8 else 8), (v, 16 if fp8 else 8)))
+
+
+def attention_decode_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bool = True) -> bool:
+    """What bf_attention_decode_gqa takes: q [N, H, Tq, D] (1 <= Tq <= 16), k and v [N, Hkv, Tk, D] with Tq <= Tk, Hkv
+    dividing H, D 64, 128 or 256, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8
+    elements) and a contiguous feature dimension.  check_device=False judges the shapes, dtypes and strides alone (CPU or
+    meta tensors)."""
+    return _cached_layout_ok(q, k, v, check_device, fp8=False, chunk=False)
 
 
 def decode_kernel_wins(H: int, Hkv: int, Tq: int, Tk: int, D: int) -> bool:
@@ -1139,36 +1151,59 @@ def attention_decode_workspace_bytes(q: Tensor, k: Tensor, v: Tensor) -> int:
     return n
 
 
-def _attention_decode(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
-                      scaling: float, mask_off: Optional[Tensor], workspace: Optional[Tensor],
-                      window: Optional[int], softcap: Optional[float] = None) -> Tensor:
-    """attention_forward_decode (kv_len None) and attention_forward_decode_len; `name` is the caller's, for the messages."""
+def _cached_call(name: str, q: Tensor, k: Tensor, v: Tensor, scales, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
+                 workspace: Optional[Tensor] = None, decode: bool = True, Tk: Optional[int] = None):
+    """What the decode, ring and chunk wrappers check and allocate alike, 16-bit and FP8; `name` is the caller's, for the
+    messages.  q [N, H, Tq, D] against k / v [N, Hkv, rows, D] on one ROCm device with contiguous feature dimensions — one
+    16-bit dtype, or with `scales` = (k_scale, v_scale) q bfloat16 and the four tensors of an FP8 cache; kv_len None or one
+    int64 on the device; key_mask None or contiguous fp32 [N, Tk] there, Tk being the rows unless stated (a ring states its
+    logical capacity, which the grid, the splits and the workspace follow too).  Returns (out [N, Tq, H, D], the
+    bf_attn_decode_t shape, ws); decode: ws is `workspace` or a fresh tensor of bf_attention_decode_workspace_bytes (None
+    when the shape needs none), else None."""
     _require_device(q, f"{name}: q")
+    if scales is not None:
+        if q.dtype != torch.bfloat16:
+            raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
+                                         "exact in bfloat16 alone")
+        _kv8_cache_check(name, k, v, *scales)
+    elif q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one dtype, bfloat16 or float16 (got {q.dtype}, "
+                                     f"{k.dtype}, {v.dtype})")
     if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
             or k.shape[3] != q.shape[3]:
         raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
                                      "are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
-    if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
-            or v.device != q.device:
-        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one dtype and one device")
+    if not (k.is_cuda and v.is_cuda) or k.device != q.device or v.device != q.device:
+        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one device")
     if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
         raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q, k and v must be contiguous")
     if kv_len is not None and (kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device):
         raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
     N, H, Tq, D = q.shape
-    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
     shape = _decode_shape(q, k, v)
-    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
-    if nbytes < 0:
-        _C.check(1, "bf_attention_decode_workspace_bytes")
+    if Tk is not None:
+        shape.Tk = int(Tk)
+    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, shape.Tk)
+                                 or not key_mask.is_contiguous() or key_mask.device != q.device):
+        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk] = {(N, shape.Tk)} on the device of q")
+    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
     ws = None
-    if nbytes:
-        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
-            raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
-    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, k.shape[2])
-                                 or not key_mask.is_contiguous()):
-        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk]")
+    if decode:
+        nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
+        if nbytes < 0:
+            _C.check(1, "bf_attention_decode_workspace_bytes")
+        if nbytes:
+            ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+            if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
+                raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
+    return out, shape, ws
+
+
+def _attention_decode(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
+                      scaling: float, mask_off: Optional[Tensor], workspace: Optional[Tensor],
+                      window: Optional[int], softcap: Optional[float] = None) -> Tensor:
+    """attention_forward_decode (kv_len None) and attention_forward_decode_len; `name` is the caller's, for the messages."""
+    out, shape, ws = _cached_call(name, q, k, v, None, kv_len, key_mask, workspace)
     args = [q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
             mask_off.data_ptr() if mask_off is not None else None, out.data_ptr(), ws.data_ptr() if ws is not None else None,
             _TORCH2BF[q.dtype], ctypes.byref(shape)]
@@ -1309,22 +1344,7 @@ def kv8_dequantize(q: Tensor, scale: Tensor, out: Optional[Tensor] = None) -> Te
 def attention_decode_kv8_supported(q: Tensor, kq: Tensor, vq: Tensor, check_device: bool = True) -> bool:
     """What bf_attention_decode_gqa_kv8 takes: attention_decode_supported's shapes with q bfloat16 and kq / vq uint8
     [N, Hkv, Tk, D] whose (batch, head, token) strides are multiples of 16 bytes."""
-    if check_device and not (q.is_cuda and kq.is_cuda and vq.is_cuda):
-        return False
-    if q.dtype != torch.bfloat16 or kq.dtype != torch.uint8 or vq.dtype != torch.uint8:
-        return False
-    if q.dim() != 4 or kq.dim() != 4 or kq.shape != vq.shape:
-        return False
-    N, H, Tq, D = q.shape
-    Hkv, Tk = kq.shape[1], kq.shape[2]
-    if kq.shape[0] != N or kq.shape[3] != D or Hkv < 1 or H % Hkv or D not in KV8_HEAD_SIZES:
-        return False
-    if not (1 <= Tq <= DECODE_MAX_QUERIES and Tq <= Tk) or N * Hkv > 65535:
-        return False
-    if q.stride(3) != 1 or any(st < 0 or st % 8 for st in q.stride()[:3]) or q.data_ptr() % 16:
-        return False
-    return all(t.stride(3) == 1 and all(st >= 0 and st % 16 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
-               for t in (kq, vq))
+    return _cached_layout_ok(q, kq, vq, check_device, fp8=True, chunk=False)
 
 
 def attention_forward_decode_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Tensor, v_scale: Tensor,
@@ -1336,35 +1356,7 @@ def attention_forward_decode_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Ten
     key_mask, mask_off, workspace (attention_decode_workspace_bytes of the shape), window and softcap as there.  The rows
     are dequantised in registers on their way to LDS; the result is bitwise that of the bf16 entry on
     kv8_dequantize(kq, k_scale), kv8_dequantize(vq, v_scale)."""
-    name = "attention_forward_decode_kv8"
-    _require_device(q, f"{name}: q")
-    if q.dtype != torch.bfloat16:
-        raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
-                                     "exact in bfloat16 alone")
-    _kv8_cache_check(name, kq, vq, k_scale, v_scale)
-    if q.dim() != 4 or kq.shape[0] != q.shape[0] or kq.shape[3] != q.shape[3]:
-        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, kq {tuple(kq.shape)} are not [N, H, Tq, D], "
-                                     "[N, Hkv, Tk, D]")
-    if kq.device != q.device:
-        raise _C.BayeFormersAMDError(f"{name}: q and the cache must share one device")
-    if q.stride(3) != 1 or kq.stride(3) != 1 or vq.stride(3) != 1:
-        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q, kq and vq must be contiguous")
-    if kv_len is not None and (kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device):
-        raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
-    N, H, Tq, D = q.shape
-    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
-    shape = _decode_shape(q, kq, vq)
-    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
-    if nbytes < 0:
-        _C.check(1, "bf_attention_decode_workspace_bytes")
-    ws = None
-    if nbytes:
-        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
-            raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
-    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, kq.shape[2])
-                                 or not key_mask.is_contiguous()):
-        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk]")
+    out, shape, ws = _cached_call("attention_forward_decode_kv8", q, kq, vq, (k_scale, v_scale), kv_len, key_mask, workspace)
     _C.check(_C.lib().bf_attention_decode_gqa_kv8(
         q.data_ptr(), kq.data_ptr(), vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
         key_mask.data_ptr() if key_mask is not None else None, mask_off.data_ptr() if mask_off is not None else None,
@@ -1453,41 +1445,20 @@ def kv8_ring_append(k: Tensor, v: Tensor, kq: Tensor, vq: Tensor, k_scale: Tenso
     RING_CALLS["kv8_append"] += 1
 
 
-def _ring_decode_shape(name: str, q: Tensor, k: Tensor, v: Tensor, kv_len: Tensor, key_mask: Optional[Tensor],
-                       workspace: Optional[Tensor], window: int, slots: int, capacity: int):
-    """What the two ring decodes share behind their own dtype checks: (out, shape, ws) for q [N, H, Tq, D] against k / v
-    [N, Hkv, ring_slots, D], the shape carrying the logical capacity as its Tk."""
-    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
-            or k.shape[3] != q.shape[3]:
-        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
-                                     "are not [N, H, Tq, D], [N, Hkv, ring_slots, D], [N, Hkv, ring_slots, D]")
-    if not (k.is_cuda and v.is_cuda) or k.device != q.device or v.device != q.device:
-        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one device")
-    if q.stride(3) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
-        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q, k and v must be contiguous")
-    if kv_len is None or kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device:
+def _ring_call(name: str, q: Tensor, k: Tensor, v: Tensor, scales, kv_len: Tensor, key_mask: Optional[Tensor],
+               workspace: Optional[Tensor], window: int, slots: Optional[int], capacity: Optional[int]):
+    """_cached_call for the two ring decodes — k / v [N, Hkv, ring_slots, D], the shape carrying the logical capacity as its
+    Tk — behind what a ring alone requires: the fill, and a window that fits the slots with the queries."""
+    if slots is None or capacity is None:
+        raise _C.BayeFormersAMDError(f"{name}: ring_slots and capacity are required")
+    if kv_len is None:
         raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
-    slots, capacity = int(slots), int(capacity)
-    if k.shape[2] != slots:
-        raise _C.BayeFormersAMDError(f"{name}: k and v hold {k.shape[2]} rows, not ring_slots={slots}")
-    if window is None or int(window) < 1 or int(window) + q.shape[2] - 1 > slots:
+    out, shape, ws = _cached_call(name, q, k, v, scales, kv_len, key_mask, workspace, Tk=capacity)
+    if k.shape[2] != int(slots):
+        raise _C.BayeFormersAMDError(f"{name}: k and v hold {k.shape[2]} rows, not ring_slots={int(slots)}")
+    if window is None or int(window) < 1 or int(window) + q.shape[2] - 1 > int(slots):
         raise _C.BayeFormersAMDError(f"{name}: window={window} with Tq={q.shape[2]} needs window >= 1 and "
-                                     f"window + Tq - 1 <= ring_slots={slots}")
-    N, H, Tq, D = q.shape
-    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
-    shape = _decode_shape(q, k, v)
-    shape.Tk = capacity  # the grid, the splits, the workspace and the mask follow the logical capacity
-    nbytes = int(_C.lib().bf_attention_decode_workspace_bytes(ctypes.byref(shape)))
-    if nbytes < 0:
-        _C.check(1, "bf_attention_decode_workspace_bytes")
-    ws = None
-    if nbytes:
-        ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-        if ws.numel() * ws.element_size() < nbytes or not ws.is_cuda:
-            raise _C.BayeFormersAMDError(f"{name}: the workspace needs {nbytes} device bytes")
-    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (N, capacity)
-                                 or not key_mask.is_contiguous()):
-        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, capacity]")
+                                     f"window + Tq - 1 <= ring_slots={int(slots)}")
     return out, shape, ws
 
 
@@ -1501,13 +1472,8 @@ def attention_forward_decode_ring(q: Tensor, k: Tensor, v: Tensor, kv_len: Tenso
     (attention_decode_workspace_bytes of a [N, Hkv, capacity, D] cache) and key_mask [N, capacity] follow it.  Query i
     sees keys L - Tq + i - window + 1 .. L - Tq + i; window >= 1 and window + Tq - 1 <= ring_slots.  The result is bitwise
     attention_forward_decode_len(..., window=window)'s on the same keys in a linear cache of `capacity` rows."""
-    name = "attention_forward_decode_ring"
-    _require_device(q, f"{name}: q")
-    if ring_slots is None or capacity is None:
-        raise _C.BayeFormersAMDError(f"{name}: ring_slots and capacity are required")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share bfloat16 or float16")
-    out, shape, ws = _ring_decode_shape(name, q, k, v, kv_len, key_mask, workspace, window, ring_slots, capacity)
+    out, shape, ws = _ring_call("attention_forward_decode_ring", q, k, v, None, kv_len, key_mask, workspace, window, ring_slots,
+                                capacity)
     _C.check(_C.lib().bf_attention_decode_gqa_ring(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
         mask_off.data_ptr() if mask_off is not None else None, kv_len.data_ptr(), out.data_ptr(),
@@ -1525,15 +1491,8 @@ def attention_forward_decode_ring_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale
     """attention_forward_decode_ring on an FP8 ring (bf_attention_decode_gqa_ring_kv8): q bfloat16, kq / vq
     [N, Hkv, ring_slots, D] uint8 (e4m3fn rows), k_scale / v_scale [N, Hkv, ring_slots] fp32 contiguous.  Bitwise
     attention_forward_decode_kv8(..., window=window)'s result on the same rows in a linear FP8 cache of `capacity` rows."""
-    name = "attention_forward_decode_ring_kv8"
-    _require_device(q, f"{name}: q")
-    if ring_slots is None or capacity is None:
-        raise _C.BayeFormersAMDError(f"{name}: ring_slots and capacity are required")
-    if q.dtype != torch.bfloat16:
-        raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
-                                     "exact in bfloat16 alone")
-    _kv8_cache_check(name, kq, vq, k_scale, v_scale)
-    out, shape, ws = _ring_decode_shape(name, q, kq, vq, kv_len, key_mask, workspace, window, ring_slots, capacity)
+    out, shape, ws = _ring_call("attention_forward_decode_ring_kv8", q, kq, vq, (k_scale, v_scale), kv_len, key_mask, workspace,
+                                window, ring_slots, capacity)
     _C.check(_C.lib().bf_attention_decode_gqa_ring_kv8(
         q.data_ptr(), kq.data_ptr(), vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
         key_mask.data_ptr() if key_mask is not None else None, mask_off.data_ptr() if mask_off is not None else None,
@@ -1549,56 +1508,26 @@ def attention_forward_decode_ring_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale
 CHUNK_CALLS = {"fwd": 0, "kv8": 0}
 
 
-def _chunk_shape_ok(q: Tensor, k: Tensor) -> bool:
-    N, H, Tq, D = q.shape
-    Hkv, Tk = k.shape[1], k.shape[2]
-    if k.shape[0] != N or k.shape[3] != D or Hkv < 1 or H % Hkv or D not in (64, 128, 256):
-        return False
-    return 1 <= Tq <= Tk and N <= 65535 and H <= 65535 and Tk < 2 ** 31
-
-
 def attention_chunk_supported(q: Tensor, k: Tensor, v: Tensor, check_device: bool = True) -> bool:
     """What bf_attention_chunk_gqa takes: q [N, H, Tq, D] with any 1 <= Tq <= Tk, k and v [N, Hkv, Tk, D], Hkv dividing H, D
     64, 128 or 256, bf16 or fp16, each with its own (batch, head, token) strides (non-negative multiples of 8 elements) and a
     contiguous feature dimension.  check_device=False judges the shapes, dtypes and strides alone (CPU or meta tensors)."""
-    if check_device and not (q.is_cuda and k.is_cuda and v.is_cuda):
-        return False
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        return False
-    if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or not _chunk_shape_ok(q, k):
-        return False
-    return all(t.stride(3) == 1 and all(st >= 0 and st % 8 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
-               for t in (q, k, v))
+    return _cached_layout_ok(q, k, v, check_device, fp8=False, chunk=True)
 
 
 def attention_chunk_kv8_supported(q: Tensor, kq: Tensor, vq: Tensor, check_device: bool = True) -> bool:
     """What bf_attention_chunk_gqa_kv8 takes: attention_chunk_supported's shapes with q bfloat16 and kq / vq uint8
     [N, Hkv, Tk, D] whose (batch, head, token) strides are multiples of 16 bytes."""
-    if check_device and not (q.is_cuda and kq.is_cuda and vq.is_cuda):
-        return False
-    if q.dtype != torch.bfloat16 or kq.dtype != torch.uint8 or vq.dtype != torch.uint8:
-        return False
-    if q.dim() != 4 or kq.dim() != 4 or kq.shape != vq.shape or not _chunk_shape_ok(q, kq):
-        return False
-    if q.stride(3) != 1 or any(st < 0 or st % 8 for st in q.stride()[:3]) or q.data_ptr() % 16:
-        return False
-    return all(t.stride(3) == 1 and all(st >= 0 and st % 16 == 0 for st in t.stride()[:3]) and t.data_ptr() % 16 == 0
-               for t in (kq, vq))
+    return _cached_layout_ok(q, kq, vq, check_device, fp8=True, chunk=True)
 
 
-def _chunk_args_check(name: str, q: Tensor, k: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
-                      mask_off: Optional[Tensor], window: Optional[int], softcap: Optional[float], key_origin: int) -> None:
-    """What the two chunk wrappers check alike, after q and the cache tensors themselves."""
-    if q.stride(3) != 1 or k.stride(3) != 1:
-        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q and of the cache must be contiguous")
+def _chunk_call(name: str, q: Tensor, k: Tensor, v: Tensor, scales, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
+                mask_off: Optional[Tensor], window: Optional[int], softcap: Optional[float], key_origin: int):
+    """_cached_call for the two chunk wrappers (no workspace), and the arguments only they check."""
+    out, shape, _ = _cached_call(name, q, k, v, scales, kv_len, key_mask, decode=False)
     if not 1 <= q.shape[2] <= k.shape[2]:
         raise _C.BayeFormersAMDError(f"{name}: Tq={q.shape[2]} new queries against Tk={k.shape[2]} cached keys "
                                      "(1 <= Tq <= Tk)")
-    if kv_len is not None and (kv_len.dtype != torch.int64 or kv_len.numel() != 1 or kv_len.device != q.device):
-        raise _C.BayeFormersAMDError(f"{name}: kv_len must be one int64 on the device of q")
-    if key_mask is not None and (key_mask.dtype != torch.float32 or tuple(key_mask.shape) != (q.shape[0], k.shape[2])
-                                 or not key_mask.is_contiguous() or key_mask.device != q.device):
-        raise _C.BayeFormersAMDError(f"{name}: key_mask must be contiguous fp32 [N, Tk] on the device of q")
     if mask_off is not None and (mask_off.numel() != 1 or mask_off.element_size() != 1 or mask_off.device != q.device):
         raise _C.BayeFormersAMDError(f"{name}: mask_off must be one byte on the device of q")
     if window is not None and (isinstance(window, bool) or not isinstance(window, int) or window < 1):
@@ -1607,6 +1536,7 @@ def _chunk_args_check(name: str, q: Tensor, k: Tensor, kv_len: Optional[Tensor],
         raise _C.BayeFormersAMDError(f"{name}: softcap={softcap!r} (None or finite and positive)")
     if isinstance(key_origin, bool) or not isinstance(key_origin, int) or not 0 <= key_origin < 2 ** 31:
         raise _C.BayeFormersAMDError(f"{name}: key_origin={key_origin!r} (an int >= 0)")
+    return out, shape
 
 
 def attention_forward_chunk(q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Tensor], key_mask: Optional[Tensor],
@@ -1621,23 +1551,7 @@ def attention_forward_chunk(q: Tensor, k: Tensor, v: Tensor, kv_len: Optional[Te
     index in its sequence of k's key 0 (a sliding-window cache that kept its last keys only): the kernel lays its key tiles on
     the sequence's tile grid, so the rows round as the same rows of attention_forward_gqa over the whole sequence.  Forward only.
     Returns [N, Tq, H, D] contiguous (a query with no visible key gives 0)."""
-    name = "attention_forward_chunk"
-    _require_device(q, f"{name}: q")
-    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
-            or k.shape[3] != q.shape[3]:
-        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} "
-                                     "are not [N, H, Tq, D], [N, Hkv, Tk, D], [N, Hkv, Tk, D]")
-    if k.dtype != q.dtype or v.dtype != q.dtype or not (k.is_cuda and v.is_cuda) or k.device != q.device \
-            or v.device != q.device:
-        raise _C.BayeFormersAMDError(f"{name}: q, k and v must share one dtype and one device")
-    if q.dtype not in (torch.bfloat16, torch.float16):
-        raise _C.BayeFormersAMDError(f"{name}: dtype {q.dtype} (bfloat16 or float16)")
-    if v.stride(3) != 1:
-        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q and of the cache must be contiguous")
-    _chunk_args_check(name, q, k, kv_len, key_mask, mask_off, window, softcap, key_origin)
-    N, H, Tq, D = q.shape
-    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
-    shape = _decode_shape(q, k, v)
+    out, shape = _chunk_call("attention_forward_chunk", q, k, v, None, kv_len, key_mask, mask_off, window, softcap, key_origin)
     _C.check(_C.lib().bf_attention_chunk_gqa(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask.data_ptr() if key_mask is not None else None,
         mask_off.data_ptr() if mask_off is not None else None, kv_len.data_ptr() if kv_len is not None else None,
@@ -1655,23 +1569,8 @@ def attention_forward_chunk_kv8(q: Tensor, kq: Tensor, vq: Tensor, k_scale: Tens
     [N, Hkv, Tk, D] uint8 (e4m3fn rows), k_scale / v_scale [N, Hkv, Tk] fp32 contiguous; the other arguments as there.  The
     rows are dequantised in registers on their way to LDS — rows and scales past the fill are never read — and the result
     is bitwise that of attention_forward_chunk on kv8_dequantize(kq, k_scale), kv8_dequantize(vq, v_scale)."""
-    name = "attention_forward_chunk_kv8"
-    _require_device(q, f"{name}: q")
-    if q.dtype != torch.bfloat16:
-        raise _C.BayeFormersAMDError(f"{name}: q must be bfloat16 (got {q.dtype}): the FP8 cache's dequantised rows are "
-                                     "exact in bfloat16 alone")
-    _kv8_cache_check(name, kq, vq, k_scale, v_scale)
-    if q.dim() != 4 or kq.shape[0] != q.shape[0] or kq.shape[3] != q.shape[3]:
-        raise _C.BayeFormersAMDError(f"{name}: q {tuple(q.shape)}, kq {tuple(kq.shape)} are not [N, H, Tq, D], "
-                                     "[N, Hkv, Tk, D]")
-    if kq.device != q.device:
-        raise _C.BayeFormersAMDError(f"{name}: q and the cache must share one device")
-    if vq.stride(3) != 1:
-        raise _C.BayeFormersAMDError(f"{name}: the feature dimension of q and of the cache must be contiguous")
-    _chunk_args_check(name, q, kq, kv_len, key_mask, mask_off, window, softcap, key_origin)
-    N, H, Tq, D = q.shape
-    out = torch.empty((N, Tq, H, D), dtype=q.dtype, device=q.device)
-    shape = _decode_shape(q, kq, vq)
+    out, shape = _chunk_call("attention_forward_chunk_kv8", q, kq, vq, (k_scale, v_scale), kv_len, key_mask, mask_off, window,
+                             softcap, key_origin)
     _C.check(_C.lib().bf_attention_chunk_gqa_kv8(
         q.data_ptr(), kq.data_ptr(), vq.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
         key_mask.data_ptr() if key_mask is not None else None, mask_off.data_ptr() if mask_off is not None else None,

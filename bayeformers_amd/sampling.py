@@ -1009,7 +1009,7 @@ def _checked_prefill_chunk(model: Model, prefill_chunk, T0: int) -> Optional[int
         raise ValueError(f"sample_generate: prefill_chunk={prefill_chunk!r} (None or an int >= {_MIN_PREFILL_CHUNK})")
     if prefill_chunk >= T0:
         return None
-    from . import _ATTENTION_NAME
+    from .attention import _ATTENTION_NAME
 
     inner = model.model if model.model is not None else model
     if getattr(getattr(inner, "config", None), "_attn_implementation", None) != _ATTENTION_NAME:
@@ -1026,7 +1026,7 @@ def _chunked_prefill(model: Model, ids: Tensor, pos: Optional[Tensor], mask_to, 
     Returns (out, lp): lp the log-probs of the pinned draws, read after the first span (every span draws the same)."""
     import inspect
 
-    from . import _CHUNKED_ATTENTION
+    from .attention import _CHUNKED_ATTENTION
 
     inner = model.model if model.model is not None else model
     try:
@@ -1160,7 +1160,7 @@ def _static_cache(model: Model, capacity: int, kv_cache: Optional[str] = None, s
     from transformers import StaticCache
     from transformers.cache_utils import StaticLayer
 
-    from . import _ATTENTION_NAME, softcap_attention_enabled
+    from .attention import _ATTENTION_NAME, softcap_attention_enabled
 
     inner = model.model if model.model is not None else model
     config = getattr(inner, "config", None)
