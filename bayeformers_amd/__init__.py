@@ -641,35 +641,66 @@ def _blocks_backward(module) -> bool:
     return getattr(module, "_bf_blocks_backward", False)
 
 
-def _rmsnorm_forward(self, hidden_states):
-    """forward of an HF `*RMSNorm` on bf_add_rmsnorm.  A hidden state that the fused layer in front of this norm produced
+def _norm_eps(norm) -> float:
+    return norm.eps if hasattr(norm, "eps") else norm.variance_epsilon
+
+
+def _add_norm(gemma: bool, rec: bool, x, residual, norm, want_sum: bool = True):
+    """(x + residual, its norm under `norm`) by bf_norm_add_rmsnorm with Gemma's (1 + weight) convention, or by
+    bf_add_rmsnorm; rec: through the autograd function over both directions (which returns the norm alone without a
+    residual, and always writes the sum)."""
+    from . import ops
+
+    if gemma:
+        if rec:
+            return ops.NormAddRMSNormFn.apply(x, None, residual, norm.weight, 0.0, _norm_eps(norm), 1)
+        return ops.norm_add_rmsnorm(x, None, residual, norm.weight, 0.0, _norm_eps(norm), 1, want_sum=want_sum)
+    if rec:
+        return ops.AddRMSNormFn.apply(x, residual, norm.weight, _norm_eps(norm))
+    return ops.add_rmsnorm(x, residual, norm.weight, _norm_eps(norm), want_sum=want_sum)
+
+
+def _norm_module_forward(self, hidden_states, gemma: bool):
+    """forward of an HF `*RMSNorm` on bf_add_rmsnorm, or (gemma) of a Gemma*RMSNorm on bf_norm_add_rmsnorm without a first
+    norm or residual, offset 1.  A hidden state that the fused layer in front of this norm produced
     carries this norm's output already (`_bf_normed`, computed in that layer's residual pass): it is handed out as it is.
-    Under recorded gradients (fuse_decoder_blocks(backward=True)) the attached tensor is the second output of the autograd
+    Under recorded gradients the module's own forward runs unless the norm was rewritten with the backward on; then the
+    attached tensor is the second output of the autograd
     function whose first output is the hidden state; it is taken only when it carries a grad_fn — whatever this forward
     returns under recorded gradients must be part of the graph, and reentrant checkpointing or layers run under no_grad
     hand out graph-less ones — and it stays attached, so a recomputation of this forward sees what the first run saw."""
     from . import ops
 
     x = hidden_states
-    rec = _records_grad(x, self)
-    if not ops.rmsnorm_supported(x, None, self) or (rec and not _blocks_backward(self)):
+    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
+    if (not isinstance(x, torch.Tensor) or (rec and not _blocks_backward(self)) or not ops.rmsnorm_supported(x, None, self)):
         return self._bf_plain_rmsnorm_forward(hidden_states)
     ready = x.__dict__.get("_bf_normed") if rec else x.__dict__.pop("_bf_normed", None)
     if ready is not None and ready[1] is self and not (rec and ready[0].grad_fn is None):
         return ready[0]
-    if rec:
-        return ops.AddRMSNormFn.apply(x, None, self.weight, self.variance_epsilon)
-    return ops.add_rmsnorm(x, None, self.weight, self.variance_epsilon, want_sum=False)[1]
+    return _add_norm(gemma, True, x, None, self) if rec else _add_norm(gemma, False, x, None, self, want_sum=False)[1]
 
 
-def _decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
-                           use_cache=False, position_embeddings=None, **kwargs):
-    """forward of an HF Llama / Mistral / Qwen2 decoder layer with its two residual adds folded into the RMSNorm that
-    follows each (bf_add_rmsnorm writes the sum and the normalised row in one pass): the second add feeds the NEXT
+def _rmsnorm_forward(self, hidden_states):
+    """_norm_module_forward for Llama's convention: counts in ops.BLOCK_CALLS["rmsnorm"], backward through ops.AddRMSNormFn."""
+    return _norm_module_forward(self, hidden_states, False)
+
+
+def _gemma_rmsnorm_forward(self, hidden_states):
+    """_norm_module_forward for Gemma's (1 + weight) convention, backward through ops.NormAddRMSNormFn."""
+    return _norm_module_forward(self, hidden_states, True)
+
+
+def _two_norm_layer_forward(self, gemma, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
+                            use_cache=False, position_embeddings=None, **kwargs):
+    """forward of an HF Llama / Mistral / Qwen2 / Qwen3 decoder layer or (gemma) of a GemmaDecoderLayer with its two residual
+    adds folded into the RMSNorm that follows each (bf_add_rmsnorm, or bf_norm_add_rmsnorm with the (1 + weight)
+    convention, writes the sum and the normalised row in one pass): the second add feeds the NEXT
     layer's input norm (or the model's final norm), whose output travels on the returned hidden state as `_bf_normed`.
     The returned tensor is always the true hidden state.  Tensors off the device, a hook on the norm whose forward is
     skipped: the module's own forward; gradients recorded or training mode as well, unless the layer was rewritten with
-    backward=True — then the two passes run through ops.AddRMSNormFn, whose backward is bf_add_rmsnorm_bwd."""
+    the backward on — then the two passes run through ops.AddRMSNormFn / ops.NormAddRMSNormFn, whose backward is
+    bf_add_rmsnorm_bwd / bf_norm_add_rmsnorm_bwd."""
     from . import ops
 
     h = hidden_states
@@ -683,18 +714,31 @@ def _decoder_layer_forward(self, hidden_states, attention_mask=None, position_id
     a, _ = self.self_attn(hidden_states=self.input_layernorm(h), attention_mask=attention_mask, position_ids=position_ids,
                           past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings,
                           **kwargs)
-    add_rmsnorm = ops.AddRMSNormFn.apply if rec else ops.add_rmsnorm
     if ops.rmsnorm_supported(a, h, post):
-        h1, y1 = add_rmsnorm(a, h, post.weight, post.variance_epsilon)
+        h1, y1 = _add_norm(gemma, rec, a, h, post)
     else:
         h1 = h + a
         y1 = post(h1)
     m = self.mlp(y1)
     if not ops.rmsnorm_supported(m, h1, nxt):
         return h1 + m
-    h2, y2 = add_rmsnorm(m, h1, nxt.weight, nxt.variance_epsilon)
+    h2, y2 = _add_norm(gemma, rec, m, h1, nxt)
     h2._bf_normed = (y2, nxt)
     return h2
+
+
+def _decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
+                           use_cache=False, position_embeddings=None, **kwargs):
+    """_two_norm_layer_forward on bf_add_rmsnorm (Llama, Mistral, Qwen2, Qwen3)."""
+    return _two_norm_layer_forward(self, False, hidden_states, attention_mask, position_ids, past_key_values, use_cache,
+                                   position_embeddings, **kwargs)
+
+
+def _gemma_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
+                         use_cache=False, position_embeddings=None, **kwargs):
+    """_two_norm_layer_forward on bf_norm_add_rmsnorm with the (1 + weight) convention (Gemma 1)."""
+    return _two_norm_layer_forward(self, True, hidden_states, attention_mask, position_ids, past_key_values, use_cache,
+                                   position_embeddings, **kwargs)
 
 
 def _decoder_attention_forward(self, hidden_states, position_embeddings=None, attention_mask=None, past_key_values=None,
@@ -751,10 +795,10 @@ def _decoder_attention_forward(self, hidden_states, position_embeddings=None, at
     return self.o_proj(attn_output), attn_weights
 
 
-def _swiglu_mlp_forward(self, x):
-    """forward of an HF Llama-style MLP — down_proj(act_fn(gate_proj(x)) * up_proj(x)) — with the SiLU and the product as
-    one launch (bf_swiglu); rewritten with backward=True, under recorded gradients and in training mode too, through
-    ops.SwiGLUFn."""
+def _glu_mlp_forward(self, x, gemma: bool):
+    """forward of an HF Llama- or (gemma) Gemma-style MLP — down_proj(act_fn(gate_proj(x)) * up_proj(x)) — with the SiLU or
+    tanh-GELU and the product as one launch (bf_swiglu / bf_geglu); rewritten with the backward on, under recorded gradients
+    and in training mode too, through ops.SwiGLUFn / ops.GeGLUFn."""
     from . import ops
 
     rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
@@ -764,7 +808,19 @@ def _swiglu_mlp_forward(self, x):
     gate, up = self.gate_proj(x), self.up_proj(x)
     if not ops.swiglu_supported(gate, up):
         return self.down_proj(self.act_fn(gate) * up)
+    if gemma:
+        return self.down_proj(ops.GeGLUFn.apply(gate, up) if rec else ops.geglu(gate, up))
     return self.down_proj(ops.SwiGLUFn.apply(gate, up) if rec else ops.swiglu(gate, up))
+
+
+def _swiglu_mlp_forward(self, x):
+    """_glu_mlp_forward on bf_swiglu / ops.SwiGLUFn (Llama, Mistral, Qwen2, Qwen3)."""
+    return _glu_mlp_forward(self, x, False)
+
+
+def _geglu_mlp_forward(self, x):
+    """_glu_mlp_forward on bf_geglu / ops.GeGLUFn (Gemma 1 / 2 / 3)."""
+    return _glu_mlp_forward(self, x, True)
 
 
 # ---- the Gemma 1 / 2 / 3 and Qwen3 families (fuse_decoder_blocks(families=...)): inference-time forwards, and with
@@ -789,66 +845,6 @@ def _is_gelu_tanh(fn) -> bool:
     if isinstance(fn, torch.nn.GELU):
         return fn.approximate == "tanh"
     return type(fn).__name__ in ("GELUTanh", "PytorchGELUTanh")
-
-
-def _norm_eps(norm) -> float:
-    return norm.eps if hasattr(norm, "eps") else norm.variance_epsilon
-
-
-def _gemma_rmsnorm_forward(self, hidden_states):
-    """forward of an HF Gemma*RMSNorm on bf_norm_add_rmsnorm (no first norm, no residual, offset 1).  A hidden state that
-    the fused layer in front of this norm produced carries this norm's output already (`_bf_normed`, as _rmsnorm_forward
-    describes): it is handed out as it is.  Under recorded gradients the module's own forward runs, unless the norm was
-    rewritten with backward="all": then _rmsnorm_forward's rules for the attached tensor hold and the norm runs through
-    ops.NormAddRMSNormFn."""
-    from . import ops
-
-    x = hidden_states
-    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
-    if (not isinstance(x, torch.Tensor) or (rec and not _blocks_backward(self)) or not x.is_cuda
-            or not ops.norm_add_rmsnorm_supported(x, None, None, self)):
-        return self._bf_plain_rmsnorm_forward(hidden_states)
-    ready = x.__dict__.get("_bf_normed") if rec else x.__dict__.pop("_bf_normed", None)
-    if ready is not None and ready[1] is self and not (rec and ready[0].grad_fn is None):
-        return ready[0]
-    if rec:
-        return ops.NormAddRMSNormFn.apply(x, None, None, self.weight, 0.0, self.eps, 1)
-    return ops.norm_add_rmsnorm(x, None, None, self.weight, 0.0, self.eps, 1, want_sum=False)[1]
-
-
-def _gemma_layer_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_values=None,
-                         use_cache=False, position_embeddings=None, **kwargs):
-    """forward of an HF GemmaDecoderLayer: _decoder_layer_forward's structure (each residual add folded into the norm that
-    follows it, the second one's output travelling on the hidden state as `_bf_normed`) through bf_norm_add_rmsnorm with the
-    (1 + weight) convention.  Tensors off the device or a hook on the norm whose forward is skipped send the layer to its
-    own forward; gradients recorded or training mode as well, unless the layer was rewritten with backward="all" — then the
-    two passes run through ops.NormAddRMSNormFn, whose backward is bf_norm_add_rmsnorm_bwd."""
-    from . import ops
-
-    h = hidden_states
-    post, nxt = self.post_attention_layernorm, self._bf_next_norm[0]
-    rec = isinstance(h, torch.Tensor) and _records_grad(h, self, nxt)
-    if (not isinstance(h, torch.Tensor) or ((self.training or rec) and not _blocks_backward(self)) or _hooked(post)
-            or not ops.norm_add_rmsnorm_supported(h, None, None, post)
-            or not ops.norm_add_rmsnorm_supported(h, None, None, nxt)):
-        return self._bf_plain_layer_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids,
-                                            past_key_values=past_key_values, use_cache=use_cache,
-                                            position_embeddings=position_embeddings, **kwargs)
-    a, _ = self.self_attn(hidden_states=self.input_layernorm(h), attention_mask=attention_mask, position_ids=position_ids,
-                          past_key_values=past_key_values, use_cache=use_cache, position_embeddings=position_embeddings,
-                          **kwargs)
-    norm_add_rmsnorm = ops.NormAddRMSNormFn.apply if rec else ops.norm_add_rmsnorm
-    if ops.norm_add_rmsnorm_supported(a, None, h, post):
-        h1, y1 = norm_add_rmsnorm(a, None, h, post.weight, 0.0, post.eps, 1)
-    else:
-        h1 = h + a
-        y1 = post(h1)
-    m = self.mlp(y1)
-    if not ops.norm_add_rmsnorm_supported(m, None, h1, nxt):
-        return h1 + m
-    h2, y2 = norm_add_rmsnorm(m, None, h1, nxt.weight, 0.0, nxt.eps, 1)
-    h2._bf_normed = (y2, nxt)
-    return h2
 
 
 def _sandwich_layer_forward(self, hidden_states, position_embeddings=None, attention_mask=None, position_ids=None,
@@ -954,22 +950,6 @@ def _family_attention_forward(self, hidden_states, position_embeddings=None, att
                                                     scaling=self.scaling, **kwargs)
     attn_output = attn_output.reshape(*input_shape, -1).contiguous()
     return self.o_proj(attn_output), attn_weights
-
-
-def _geglu_mlp_forward(self, x):
-    """forward of an HF Gemma-style MLP — down_proj(gelu_tanh(gate_proj(x)) * up_proj(x)) — with the activation and the
-    product as one launch (bf_geglu); rewritten with backward="all", under recorded gradients and in training mode too,
-    through ops.GeGLUFn."""
-    from . import ops
-
-    rec = isinstance(x, torch.Tensor) and _records_grad(x, self)
-    if (not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in ops._TORCH2BF or _hooked(self.act_fn)
-            or ((self.training or rec) and not _blocks_backward(self))):
-        return self._bf_plain_mlp_forward(x)
-    gate, up = self.gate_proj(x), self.up_proj(x)
-    if not ops.geglu_supported(gate, up):
-        return self.down_proj(self.act_fn(gate) * up)
-    return self.down_proj(ops.GeGLUFn.apply(gate, up) if rec else ops.geglu(gate, up))
 
 
 def _fuse_family_layer(layer, nxt, family) -> bool:

@@ -2177,18 +2177,16 @@ def layernorm_supported(x: Tensor, residual: Optional[Tensor], ln) -> bool:
 
 
 # ------------------------------------------------------------------------------- decoder blocks: RMSNorm, RoPE, SwiGLU
+# Twelve public ops over six bodies (_norm_forward, _norm_backward, _rope, _glu_forward, _glu_backward and the rotary
+# predicate): the Llama / Mistral / Qwen2 ops are the Gemma 1 / 2 / 3 and Qwen3 ones with the first norm, the weight offset, the
+# q / k gammas and head size 256 taken away; each keeps its own C entry and its own counter.
 # launches of bf_add_rmsnorm / bf_rope_qk / bf_swiglu from this process (tests, diagnostics)
 BLOCK_CALLS = {"rmsnorm": 0, "rope": 0, "swiglu": 0}
 
 
 def rmsnorm_supported(x: Tensor, residual: Optional[Tensor], norm) -> bool:
     """Does bf_add_rmsnorm take x (and the residual) under `norm` (a module with `weight` [N])?"""
-    n = x.shape[-1]
-    w = norm.weight
-    return (x.is_cuda and x.dtype in _TORCH2BF and x.dim() >= 1 and n % 8 == 0 and n <= 8192 and x.numel() > 0 and
-            (residual is None or (residual.shape == x.shape and residual.dtype == x.dtype and residual.is_cuda)) and
-            w.is_cuda and w.dim() == 1 and w.shape[0] == n and w.dtype in (torch.float32, x.dtype) and w.is_contiguous()
-            and w.data_ptr() % 16 == 0)
+    return norm_add_rmsnorm_supported(x, None, residual, norm)
 
 
 def _rows_of(t: Tensor, n: int) -> Tensor:
@@ -2196,40 +2194,60 @@ def _rows_of(t: Tensor, n: int) -> Tensor:
     return t2 if t2.is_contiguous() and t2.data_ptr() % 16 == 0 else t2.clone(memory_format=torch.contiguous_format)
 
 
-def add_rmsnorm(x: Tensor, residual: Optional[Tensor], gamma: Tensor, eps: float, want_sum: bool = True):
-    """(z, y) with z = x + residual and y = z * rsqrt(mean(z^2) + eps) * gamma over the last axis, one pass
-    (bf_add_rmsnorm).  z is bitwise torch's `residual + x`; residual None: z is x itself.  want_sum=False (or no
-    residual): z is not written and None is returned in its place."""
-    _require_device(x, "add_rmsnorm input")
+def _norm_forward(who: str, x: Tensor, gamma_pre: Optional[Tensor], residual: Optional[Tensor], gamma_out: Tensor,
+                  eps_pre: float, eps_out: float, weight_offset: Optional[int], want_sum: bool):
+    """The body of add_rmsnorm (weight_offset None: bf_add_rmsnorm, which has neither an offset nor a first norm) and of
+    norm_add_rmsnorm (bf_norm_add_rmsnorm)."""
+    _require_device(x, who + " input")
     N = x.shape[-1]
     x2 = _rows_of(x, N)
     r2 = None
     if residual is not None:
         if residual.shape != x.shape or residual.dtype != x.dtype:
-            raise _C.BayeFormersAMDError("add_rmsnorm: residual must match the input's shape and dtype")
+            raise _C.BayeFormersAMDError(f"{who}: residual must match the input's shape and dtype")
         r2 = _rows_of(residual, N)
-    if gamma.dtype not in (torch.float32, x.dtype):
-        raise _C.BayeFormersAMDError("add_rmsnorm: gamma must be float32 or have the input's dtype")
+    if weight_offset is None:
+        if gamma_out.dtype not in (torch.float32, x.dtype):
+            raise _C.BayeFormersAMDError(f"{who}: gamma must be float32 or have the input's dtype")
+    else:
+        for g in (gamma_pre, gamma_out):
+            if g is not None and (g.dtype != gamma_out.dtype or g.dtype not in (torch.float32, x.dtype) or g.numel() != N):
+                raise _C.BayeFormersAMDError(f"{who}: the gammas must be [N], of one dtype: float32 or the input's")
     out = torch.empty_like(x2)
-    z = torch.empty_like(x2) if (want_sum and r2 is not None) else None
-    _C.check(_C.lib().bf_add_rmsnorm(x2.data_ptr(), r2.data_ptr() if r2 is not None else None, gamma.data_ptr(),
-                                     _TORCH2BF[gamma.dtype], z.data_ptr() if z is not None else None, out.data_ptr(),
-                                     _TORCH2BF[x.dtype], x2.shape[0], N, float(eps), _stream_ptr()), "bf_add_rmsnorm")
-    BLOCK_CALLS["rmsnorm"] += 1
+    changed = r2 is not None or gamma_pre is not None
+    z = torch.empty_like(x2) if (want_sum and changed) else None
+    if weight_offset is None:
+        _C.check(_C.lib().bf_add_rmsnorm(x2.data_ptr(), r2.data_ptr() if r2 is not None else None, gamma_out.data_ptr(),
+                                         _TORCH2BF[gamma_out.dtype], z.data_ptr() if z is not None else None, out.data_ptr(),
+                                         _TORCH2BF[x.dtype], x2.shape[0], N, float(eps_out), _stream_ptr()), "bf_add_rmsnorm")
+    else:
+        _C.check(_C.lib().bf_norm_add_rmsnorm(
+            x2.data_ptr(), gamma_pre.data_ptr() if gamma_pre is not None else None, r2.data_ptr() if r2 is not None else None,
+            gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype], int(weight_offset), z.data_ptr() if z is not None else None,
+            out.data_ptr(), _TORCH2BF[x.dtype], x2.shape[0], N, float(eps_pre), float(eps_out), _stream_ptr()),
+            "bf_norm_add_rmsnorm")
     if z is not None:
         z = z.view(x.shape)
-    elif want_sum and r2 is None:
+    elif want_sum and not changed:
         z = x
     return z, out.view(x.shape)
 
 
-def rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor) -> bool:
-    """q [B, H, T, D], k [B, Hkv, T, D] with a contiguous feature dimension of 64 or 128 and (batch, head, token) strides
-    that are multiples of 8; cos / sin contiguous [1 or B, T, D] of q's dtype or fp32: what bf_rope_qk takes."""
+def add_rmsnorm(x: Tensor, residual: Optional[Tensor], gamma: Tensor, eps: float, want_sum: bool = True):
+    """(z, y) with z = x + residual and y = z * rsqrt(mean(z^2) + eps) * gamma over the last axis, one pass
+    (bf_add_rmsnorm).  z is bitwise torch's `residual + x`; residual None: z is x itself.  want_sum=False (or no
+    residual): z is not written and None is returned in its place."""
+    out = _norm_forward("add_rmsnorm", x, None, residual, gamma, eps, eps, None, want_sum)
+    BLOCK_CALLS["rmsnorm"] += 1
+    return out
+
+
+def _rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, gamma_q: Optional[Tensor], gamma_k: Optional[Tensor],
+                    head_dims) -> bool:
     if not (q.is_cuda and q.dtype in _TORCH2BF and k.dtype == q.dtype and k.is_cuda and q.dim() == 4 and k.dim() == 4):
         return False
     B, H, T, D = q.shape
-    if D not in (64, 128) or k.shape[0] != B or k.shape[2] != T or k.shape[3] != D or q.numel() == 0 or k.numel() == 0:
+    if D not in head_dims or k.shape[0] != B or k.shape[2] != T or k.shape[3] != D or q.numel() == 0 or k.numel() == 0:
         return False
     if B * T * (H + k.shape[1]) * (D // 16) >= 2 ** 31:
         return False
@@ -2239,17 +2257,36 @@ def rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor) -> bool:
             return False
     if cos.shape != sin.shape or cos.dtype != sin.dtype:
         return False
+    if gamma_q is not None or gamma_k is not None:
+        gs = [g for g in (gamma_q, gamma_k) if g is not None]
+        if not all(_gamma_ok(g, D, q.dtype) and g.dtype == gs[0].dtype for g in gs):
+            return False
     return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
                for t in (q, k))
 
 
-def rope_qk(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, inplace: bool = False):
-    """(q', k') = (q cos + rotate_half(q) sin, k cos + rotate_half(k) sin), HF's apply_rotary_pos_emb, in one launch
-    (bf_rope_qk).  Shapes as rope_supported describes.  inplace: q and k are overwritten and returned; else the results
-    are new tensors laid out [B, T, heads, D] and returned as their [B, heads, T, D] views."""
-    _require_device(q, "rope_qk input")
-    if not rope_supported(q, k, cos, sin):
-        raise _C.BayeFormersAMDError("rope_qk: unsupported shapes, strides or dtypes (see ops.rope_supported)")
+def rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor) -> bool:
+    """q [B, H, T, D], k [B, Hkv, T, D] with a contiguous feature dimension of 64 or 128 and (batch, head, token) strides
+    that are multiples of 8; cos / sin contiguous [1 or B, T, D] of q's dtype or fp32: what bf_rope_qk takes."""
+    return _rope_supported(q, k, cos, sin, None, None, (64, 128))
+
+
+def _rope(who: str, llama: bool, backward: bool, q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, x_q: Optional[Tensor],
+          x_k: Optional[Tensor], gamma_q: Optional[Tensor], gamma_k: Optional[Tensor], eps: float, weight_offset: int,
+          inplace: bool):
+    """The body of the four rotary ops: q / k are what is rotated (backward: the gradients of the rotated tensors), x_q / x_k
+    the backward's forward inputs.  llama: bf_rope_qk[_bwd], else bf_qknorm_rope[_bwd].  Returns (q', k', dgamma_q,
+    dgamma_k)."""
+    _require_device(q, who + " input")
+    if backward:
+        q, k = _rope_grad(q, q), _rope_grad(k, q)
+    if not _rope_supported(q, k, cos, sin, gamma_q, gamma_k, (64, 128) if llama else (64, 128, 256)):
+        raise _C.BayeFormersAMDError(f"{who}: unsupported shapes, strides or dtypes "
+                                     f"(see ops.{'rope_supported' if llama else 'qknorm_rope_supported'})")
+    if backward:
+        for g, x, like in ((gamma_q, x_q, q), (gamma_k, x_k, k)):
+            if g is not None and (x is None or x.shape != like.shape or x.dtype != like.dtype or not x.is_cuda):
+                raise _C.BayeFormersAMDError(f"{who}: a gamma needs the forward's input of the gradient's shape and dtype")
     B, H, T, D = q.shape
     Hkv = k.shape[1]
     if inplace:
@@ -2260,9 +2297,38 @@ def rope_qk(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, inplace: bool = Fals
     s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
     for name, t in (("q_stride", q), ("k_stride", k), ("q_out_stride", qo), ("k_out_stride", ko)):
         getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    _C.check(_C.lib().bf_rope_qk(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
-                                 qo.data_ptr(), ko.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()),
-             "bf_rope_qk")
+    lib = _C.lib()
+    if llama:
+        entry = "bf_rope_qk_bwd" if backward else "bf_rope_qk"
+        _C.check(getattr(lib, entry)(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
+                                     qo.data_ptr(), ko.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()), entry)
+        return qo, ko, None, None
+    g = gamma_q if gamma_q is not None else gamma_k
+    gdt = _TORCH2BF[g.dtype] if g is not None else _C.BF_DT_F32
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    if not backward:
+        _C.check(lib.bf_qknorm_rope(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
+                                    ptr(gamma_q), ptr(gamma_k), gdt, int(weight_offset), float(eps), qo.data_ptr(),
+                                    ko.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()), "bf_qknorm_rope")
+        return qo, ko, None, None
+    xq = _bthd(x_q) if gamma_q is not None else None
+    xk = _bthd(x_k) if gamma_k is not None else None
+    dgq = torch.empty(D, dtype=torch.float32, device=q.device) if gamma_q is not None else None
+    dgk = torch.empty(D, dtype=torch.float32, device=q.device) if gamma_k is not None else None
+    nbytes = lib.bf_qknorm_rope_bwd_workspace_bytes(ctypes.byref(s), int(g is not None))
+    ws = workspace(q.device, nbytes) if nbytes else None
+    _C.check(lib.bf_qknorm_rope_bwd(q.data_ptr(), k.data_ptr(), ptr(xq), ptr(xk), cos.data_ptr(), sin.data_ptr(),
+                                    _TORCH2BF[cos.dtype], ptr(gamma_q), ptr(gamma_k), gdt, int(weight_offset), float(eps),
+                                    qo.data_ptr(), ko.data_ptr(), ptr(dgq), ptr(dgk), ptr(ws), ws.numel() if ws is not None else 0,
+                                    _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()), "bf_qknorm_rope_bwd")
+    return qo, ko, dgq, dgk
+
+
+def rope_qk(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, inplace: bool = False):
+    """(q', k') = (q cos + rotate_half(q) sin, k cos + rotate_half(k) sin), HF's apply_rotary_pos_emb, in one launch
+    (bf_rope_qk).  Shapes as rope_supported describes.  inplace: q and k are overwritten and returned; else the results
+    are new tensors laid out [B, T, heads, D] and returned as their [B, heads, T, D] views."""
+    qo, ko, _, _ = _rope("rope_qk", True, False, q, k, cos, sin, None, None, None, None, 0.0, 0, inplace)
     BLOCK_CALLS["rope"] += 1
     return qo, ko
 
@@ -2296,20 +2362,27 @@ def _row_stride(t: Tensor) -> Optional[int]:
     return rs if rs >= n and rs % 8 == 0 else None
 
 
-def swiglu(gate: Tensor, up: Tensor) -> Tensor:
-    """silu(gate) * up in one launch (bf_swiglu): one rounding, against the framework's two."""
-    _require_device(gate, "swiglu input")
+def _glu_forward(who: str, gate: Tensor, up: Tensor) -> Tensor:
+    """The body of swiglu and geglu: the entry is bf_<who>."""
+    _require_device(gate, who + " input")
     if not swiglu_supported(gate, up):
-        raise _C.BayeFormersAMDError("swiglu: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
+        raise _C.BayeFormersAMDError(f"{who}: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
     N = gate.shape[-1]
     out = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
-    _C.check(_C.lib().bf_swiglu(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), out.data_ptr(), N,
-                                _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()), "bf_swiglu")
+    entry = "bf_" + who
+    _C.check(getattr(_C.lib(), entry)(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), out.data_ptr(), N,
+                                      _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()), entry)
+    return out
+
+
+def swiglu(gate: Tensor, up: Tensor) -> Tensor:
+    """silu(gate) * up in one launch (bf_swiglu): one rounding, against the framework's two."""
+    out = _glu_forward("swiglu", gate, up)
     BLOCK_CALLS["swiglu"] += 1
     return out
 
 
-# ---- the Gemma 1 / 2 / 3 and Qwen3 siblings (bf_family_blocks.hip): norm -> add -> norm, q / k norm + RoPE, GeGLU
+# ---- the Gemma 1 / 2 / 3 and Qwen3 siblings: norm -> add -> norm, q / k norm + RoPE, GeGLU
 # launches of bf_norm_add_rmsnorm / bf_qknorm_rope / bf_geglu from this process (BLOCK_CALLS keeps its three keys)
 FAMILY_BLOCK_CALLS = {"norm_add_norm": 0, "qknorm_rope": 0, "geglu": 0}
 
@@ -2335,55 +2408,16 @@ def norm_add_rmsnorm(x: Tensor, gamma_pre: Optional[Tensor], residual: Optional[
     z = residual + u rounded (u itself without a residual), y = z normalised under gamma_out; both norms multiply by
     (weight_offset + gamma): 1 for Gemma's modules, 0 for Llama's.  want_sum=False: z is not written and None is returned
     in its place; without gamma_pre and residual z is x itself."""
-    _require_device(x, "norm_add_rmsnorm input")
-    N = x.shape[-1]
-    x2 = _rows_of(x, N)
-    r2 = None
-    if residual is not None:
-        if residual.shape != x.shape or residual.dtype != x.dtype:
-            raise _C.BayeFormersAMDError("norm_add_rmsnorm: residual must match the input's shape and dtype")
-        r2 = _rows_of(residual, N)
-    for g in (gamma_pre, gamma_out):
-        if g is not None and (g.dtype != gamma_out.dtype or g.dtype not in (torch.float32, x.dtype) or g.numel() != N):
-            raise _C.BayeFormersAMDError("norm_add_rmsnorm: the gammas must be [N], of one dtype: float32 or the input's")
-    out = torch.empty_like(x2)
-    changed = r2 is not None or gamma_pre is not None
-    z = torch.empty_like(x2) if (want_sum and changed) else None
-    _C.check(_C.lib().bf_norm_add_rmsnorm(
-        x2.data_ptr(), gamma_pre.data_ptr() if gamma_pre is not None else None, r2.data_ptr() if r2 is not None else None,
-        gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype], int(weight_offset), z.data_ptr() if z is not None else None,
-        out.data_ptr(), _TORCH2BF[x.dtype], x2.shape[0], N, float(eps_pre), float(eps_out), _stream_ptr()),
-        "bf_norm_add_rmsnorm")
+    out = _norm_forward("norm_add_rmsnorm", x, gamma_pre, residual, gamma_out, eps_pre, eps_out, int(weight_offset), want_sum)
     FAMILY_BLOCK_CALLS["norm_add_norm"] += 1
-    if z is not None:
-        z = z.view(x.shape)
-    elif want_sum and not changed:
-        z = x
-    return z, out.view(x.shape)
+    return out
 
 
 def qknorm_rope_supported(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, gamma_q: Optional[Tensor] = None,
                           gamma_k: Optional[Tensor] = None) -> bool:
     """rope_supported's layouts at head size 64, 128 or 256; the gammas (each may be None) [D] contiguous tensors of one
     dtype, q's or fp32: what bf_qknorm_rope takes."""
-    if not (q.is_cuda and q.dtype in _TORCH2BF and k.dtype == q.dtype and k.is_cuda and q.dim() == 4 and k.dim() == 4):
-        return False
-    B, H, T, D = q.shape
-    if D not in (64, 128, 256) or k.shape[0] != B or k.shape[2] != T or k.shape[3] != D or q.numel() == 0 or k.numel() == 0:
-        return False
-    if B * T * (H + k.shape[1]) * (D // 16) >= 2 ** 31:
-        return False
-    for c in (cos, sin):
-        if not (c.is_cuda and c.dtype in (torch.float32, q.dtype) and c.dim() == 3 and c.shape[0] in (1, B)
-                and tuple(c.shape[1:]) == (T, D) and c.is_contiguous() and c.data_ptr() % 16 == 0):
-            return False
-    if cos.shape != sin.shape or cos.dtype != sin.dtype:
-        return False
-    gs = [g for g in (gamma_q, gamma_k) if g is not None]
-    if not all(_gamma_ok(g, D, q.dtype) and g.dtype == gs[0].dtype for g in gs):
-        return False
-    return all(t.stride(3) == 1 and all(s >= 0 and s % 8 == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
-               for t in (q, k))
+    return _rope_supported(q, k, cos, sin, gamma_q, gamma_k, (64, 128, 256))
 
 
 def qknorm_rope(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, gamma_q: Optional[Tensor] = None,
@@ -2392,26 +2426,7 @@ def qknorm_rope(q: Tensor, k: Tensor, cos: Tensor, sin: Tensor, gamma_q: Optiona
     (bf_qknorm_rope): n = x rsqrt(mean_D(x^2) + eps) (weight_offset + gamma) kept in fp32, then n cos + rotate_half(n) sin,
     rounded once.  A tensor whose gamma is None is only rotated.  Shapes as qknorm_rope_supported describes; inplace and
     the returned layouts as rope_qk's."""
-    _require_device(q, "qknorm_rope input")
-    if not qknorm_rope_supported(q, k, cos, sin, gamma_q, gamma_k):
-        raise _C.BayeFormersAMDError("qknorm_rope: unsupported shapes, strides or dtypes (see ops.qknorm_rope_supported)")
-    B, H, T, D = q.shape
-    Hkv = k.shape[1]
-    if inplace:
-        qo, ko = q, k
-    else:
-        qo = torch.empty((B, T, H, D), dtype=q.dtype, device=q.device).transpose(1, 2)
-        ko = torch.empty((B, T, Hkv, D), dtype=k.dtype, device=k.device).transpose(1, 2)
-    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
-    for name, t in (("q_stride", q), ("k_stride", k), ("q_out_stride", qo), ("k_out_stride", ko)):
-        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    g = gamma_q if gamma_q is not None else gamma_k
-    _C.check(_C.lib().bf_qknorm_rope(q.data_ptr(), k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
-                                     gamma_q.data_ptr() if gamma_q is not None else None,
-                                     gamma_k.data_ptr() if gamma_k is not None else None,
-                                     _TORCH2BF[g.dtype] if g is not None else _C.BF_DT_F32, int(weight_offset), float(eps),
-                                     qo.data_ptr(), ko.data_ptr(), _TORCH2BF[q.dtype], ctypes.byref(s), _stream_ptr()),
-             "bf_qknorm_rope")
+    qo, ko, _, _ = _rope("qknorm_rope", False, False, q, k, cos, sin, None, None, gamma_q, gamma_k, eps, weight_offset, inplace)
     FAMILY_BLOCK_CALLS["qknorm_rope"] += 1
     return qo, ko
 
@@ -2423,13 +2438,7 @@ def geglu_supported(gate: Tensor, up: Tensor) -> bool:
 
 def geglu(gate: Tensor, up: Tensor) -> Tensor:
     """gelu(gate, approximate="tanh") * up in one launch (bf_geglu): one rounding, against the framework's two."""
-    _require_device(gate, "geglu input")
-    if not geglu_supported(gate, up):
-        raise _C.BayeFormersAMDError("geglu: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
-    N = gate.shape[-1]
-    out = torch.empty(gate.shape, dtype=gate.dtype, device=gate.device)
-    _C.check(_C.lib().bf_geglu(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), out.data_ptr(), N,
-                               _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()), "bf_geglu")
+    out = _glu_forward("geglu", gate, up)
     FAMILY_BLOCK_CALLS["geglu"] += 1
     return out
 
@@ -2448,28 +2457,63 @@ def _grad_rows(g: Tensor, like: Tensor, n: int) -> Tensor:
     return _rows_of(g if g.dtype == like.dtype else g.to(like.dtype), n)
 
 
+def _norm_backward(who: str, x: Optional[Tensor], z: Tensor, gamma_pre: Optional[Tensor], gamma_out: Tensor,
+                   grad_out: Optional[Tensor], eps_pre: float, eps_out: float, weight_offset: Optional[int],
+                   grad_sum: Optional[Tensor], want_dz: bool):
+    """The body of add_rmsnorm_backward (weight_offset None: bf_add_rmsnorm_bwd) and of norm_add_rmsnorm_backward
+    (bf_norm_add_rmsnorm_bwd): (dx, dz, dgamma_pre, dgamma_out) as the latter describes them."""
+    _require_device(z, who + " input")
+    N = z.shape[-1]
+    pre = gamma_pre is not None
+    if weight_offset is None:
+        if gamma_out.dtype not in (torch.float32, z.dtype):
+            raise _C.BayeFormersAMDError(f"{who}: gamma must be float32 or have the input's dtype")
+        if grad_out.shape != z.shape or (grad_sum is not None and grad_sum.shape != z.shape):
+            raise _C.BayeFormersAMDError(f"{who}: the gradients must have the input's shape")
+    else:
+        if grad_out is None and grad_sum is None:
+            raise _C.BayeFormersAMDError(f"{who}: no gradient")
+        for g in (gamma_pre, gamma_out):
+            if g is not None and (g.dtype != gamma_out.dtype or g.dtype not in (torch.float32, z.dtype) or g.numel() != N):
+                raise _C.BayeFormersAMDError(f"{who}: the gammas must be [N], of one dtype: float32 or the input's")
+        if any(t is not None and t.shape != z.shape for t in (grad_out, grad_sum, x if pre else None)):
+            raise _C.BayeFormersAMDError(f"{who}: the gradients and x must have z's shape")
+        if pre and (x is None or x.dtype != z.dtype):
+            raise _C.BayeFormersAMDError(f"{who}: gamma_pre needs the forward's input x")
+    z2 = _rows_of(z, N)
+    g2 = _grad_rows(grad_out, z, N) if grad_out is not None else None
+    h2 = _grad_rows(grad_sum, z, N) if grad_sum is not None else None
+    dz = torch.empty_like(z2) if (want_dz or not pre) else None
+    dg_out = torch.empty(N, dtype=torch.float32, device=z.device)
+    lib = _C.lib()
+    if weight_offset is None:
+        ws = workspace(z.device, lib.bf_add_rmsnorm_bwd_workspace_bytes(z2.shape[0], N))
+        _C.check(lib.bf_add_rmsnorm_bwd(z2.data_ptr(), gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype], g2.data_ptr(),
+                                        h2.data_ptr() if h2 is not None else None, dz.data_ptr(), dg_out.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _TORCH2BF[z.dtype], z2.shape[0], N, float(eps_out),
+                                        _stream_ptr()), "bf_add_rmsnorm_bwd")
+        dz = dz.view(z.shape)
+        return dz, dz, None, dg_out
+    x2 = _rows_of(x, N) if pre else None
+    dx = torch.empty_like(z2) if pre else None
+    dg_pre = torch.empty(N, dtype=torch.float32, device=z.device) if pre else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    ws = workspace(z.device, lib.bf_norm_add_rmsnorm_bwd_workspace_bytes(z2.shape[0], N, int(pre)))
+    _C.check(lib.bf_norm_add_rmsnorm_bwd(ptr(x2), z2.data_ptr(), ptr(gamma_pre), gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype],
+                                         int(weight_offset), ptr(g2), ptr(h2), ptr(dz), ptr(dx), ptr(dg_pre), dg_out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _TORCH2BF[z.dtype], z2.shape[0], N, float(eps_pre),
+                                         float(eps_out), _stream_ptr()), "bf_norm_add_rmsnorm_bwd")
+    dz = dz.view(z.shape) if dz is not None else None
+    return (dx.view(z.shape) if pre else dz), dz, dg_pre, dg_out
+
+
 def add_rmsnorm_backward(z: Tensor, gamma: Tensor, grad_out: Tensor, eps: float, grad_sum: Optional[Tensor] = None):
     """Gradients of add_rmsnorm (bf_add_rmsnorm_bwd) from the sum z it returned (x itself without a residual): (dz,
     dgamma).  dz is the gradient of both x and the residual, dgamma is fp32.  grad_sum: the gradient that reached z
     through its other consumer, added to dz inside the kernel."""
-    _require_device(z, "add_rmsnorm_backward input")
-    N = z.shape[-1]
-    if gamma.dtype not in (torch.float32, z.dtype):
-        raise _C.BayeFormersAMDError("add_rmsnorm_backward: gamma must be float32 or have the input's dtype")
-    if grad_out.shape != z.shape or (grad_sum is not None and grad_sum.shape != z.shape):
-        raise _C.BayeFormersAMDError("add_rmsnorm_backward: the gradients must have the input's shape")
-    z2, g2 = _rows_of(z, N), _grad_rows(grad_out, z, N)
-    h2 = _grad_rows(grad_sum, z, N) if grad_sum is not None else None
-    dz = torch.empty_like(z2)
-    dgamma = torch.empty(N, dtype=torch.float32, device=z.device)
-    lib = _C.lib()
-    ws = workspace(z.device, lib.bf_add_rmsnorm_bwd_workspace_bytes(z2.shape[0], N))
-    _C.check(lib.bf_add_rmsnorm_bwd(z2.data_ptr(), gamma.data_ptr(), _TORCH2BF[gamma.dtype], g2.data_ptr(),
-                                    h2.data_ptr() if h2 is not None else None, dz.data_ptr(), dgamma.data_ptr(), ws.data_ptr(),
-                                    ws.numel(), _TORCH2BF[z.dtype], z2.shape[0], N, float(eps), _stream_ptr()),
-             "bf_add_rmsnorm_bwd")
+    _, dz, _, dgamma = _norm_backward("add_rmsnorm_backward", None, z, None, gamma, grad_out, eps, eps, None, grad_sum, True)
     BLOCK_BWD_CALLS["rmsnorm"] += 1
-    return dz.view(z.shape), dgamma
+    return dz, dgamma
 
 
 class AddRMSNormFn(torch.autograd.Function):
@@ -2509,20 +2553,7 @@ def rope_qk_backward(grad_q: Tensor, grad_k: Tensor, cos: Tensor, sin: Tensor):
     """Gradients of rope_qk (bf_rope_qk_bwd), its transpose: grad_q [B, H, T, D] / grad_k [B, Hkv, T, D] in any layout
     rope_supported takes (read where the attention backward left them) -> (dq, dk), new tensors laid out [B, T, heads, D]
     — what the backward of the projections reads — and returned as their [B, heads, T, D] views."""
-    _require_device(grad_q, "rope_qk_backward input")
-    grad_q, grad_k = _rope_grad(grad_q, grad_q), _rope_grad(grad_k, grad_q)
-    if not rope_supported(grad_q, grad_k, cos, sin):
-        raise _C.BayeFormersAMDError("rope_qk_backward: unsupported shapes, strides or dtypes (see ops.rope_supported)")
-    B, H, T, D = grad_q.shape
-    Hkv = grad_k.shape[1]
-    dq = torch.empty((B, T, H, D), dtype=grad_q.dtype, device=grad_q.device).transpose(1, 2)
-    dk = torch.empty((B, T, Hkv, D), dtype=grad_k.dtype, device=grad_k.device).transpose(1, 2)
-    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
-    for name, t in (("q_stride", grad_q), ("k_stride", grad_k), ("q_out_stride", dq), ("k_out_stride", dk)):
-        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    _C.check(_C.lib().bf_rope_qk_bwd(grad_q.data_ptr(), grad_k.data_ptr(), cos.data_ptr(), sin.data_ptr(), _TORCH2BF[cos.dtype],
-                                     dq.data_ptr(), dk.data_ptr(), _TORCH2BF[grad_q.dtype], ctypes.byref(s), _stream_ptr()),
-             "bf_rope_qk_bwd")
+    dq, dk, _, _ = _rope("rope_qk_backward", True, True, grad_q, grad_k, cos, sin, None, None, None, None, 0.0, 0, False)
     BLOCK_BWD_CALLS["rope"] += 1
     return dq, dk
 
@@ -2547,12 +2578,11 @@ def swiglu_bwd_supported(gate: Tensor, up: Tensor) -> bool:
     return swiglu_supported(gate, up)
 
 
-def swiglu_backward(gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool = False):
-    """Gradients of swiglu (bf_swiglu_bwd): (dgate, dup) from the forward's inputs.  stacked: the two are the halves of
-    one [..., 2N] buffer (the layout a stacked gate / up projection's backward reads) instead of two tensors."""
-    _require_device(gate, "swiglu_backward input")
-    if not swiglu_bwd_supported(gate, up) or grad_out.shape != gate.shape:
-        raise _C.BayeFormersAMDError("swiglu_backward: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
+def _glu_backward(who: str, gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool):
+    """The body of swiglu_backward and geglu_backward: the entry is bf_<who>_bwd."""
+    _require_device(gate, who + "_backward input")
+    if not swiglu_supported(gate, up) or grad_out.shape != gate.shape:
+        raise _C.BayeFormersAMDError(f"{who}_backward: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
     g = grad_out if grad_out.dtype == gate.dtype else grad_out.to(gate.dtype)
     if not g.is_cuda or _row_stride(g) is None:
         g = g.contiguous()
@@ -2562,12 +2592,20 @@ def swiglu_backward(gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool = 
         dgate, dup = both[..., :N], both[..., N:]
     else:
         dgate, dup = (torch.empty(gate.shape, dtype=gate.dtype, device=gate.device) for _ in range(2))
-    _C.check(_C.lib().bf_swiglu_bwd(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), g.data_ptr(),
-                                    _row_stride(g), dgate.data_ptr(), 2 * N if stacked else N, dup.data_ptr(),
-                                    2 * N if stacked else N, _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()),
-             "bf_swiglu_bwd")
-    BLOCK_BWD_CALLS["swiglu"] += 1
+    entry = f"bf_{who}_bwd"
+    _C.check(getattr(_C.lib(), entry)(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), g.data_ptr(),
+                                      _row_stride(g), dgate.data_ptr(), 2 * N if stacked else N, dup.data_ptr(),
+                                      2 * N if stacked else N, _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()),
+             entry)
     return dgate, dup
+
+
+def swiglu_backward(gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool = False):
+    """Gradients of swiglu (bf_swiglu_bwd): (dgate, dup) from the forward's inputs.  stacked: the two are the halves of
+    one [..., 2N] buffer (the layout a stacked gate / up projection's backward reads) instead of two tensors."""
+    out = _glu_backward("swiglu", gate, up, grad_out, stacked)
+    BLOCK_BWD_CALLS["swiglu"] += 1
+    return out
 
 
 class SwiGLUFn(torch.autograd.Function):
@@ -2597,36 +2635,10 @@ def norm_add_rmsnorm_backward(x: Optional[Tensor], z: Tensor, gamma_pre: Optiona
     gamma_pre dx is dz and dgamma_pre None.  The dgammas are fp32.  grad_sum: the gradient that reached z through its
     other consumer, added inside the kernel; grad_out None: only the sum was consumed (dgamma_out is then zero).
     want_dz=False (with gamma_pre, no residual): dz is not written and None is returned in its place."""
-    _require_device(z, "norm_add_rmsnorm_backward input")
-    N = z.shape[-1]
-    if grad_out is None and grad_sum is None:
-        raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: no gradient")
-    for g in (gamma_pre, gamma_out):
-        if g is not None and (g.dtype != gamma_out.dtype or g.dtype not in (torch.float32, z.dtype) or g.numel() != N):
-            raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: the gammas must be [N], of one dtype: float32 or the input's")
-    if any(t is not None and t.shape != z.shape for t in (grad_out, grad_sum, x if gamma_pre is not None else None)):
-        raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: the gradients and x must have z's shape")
-    pre = gamma_pre is not None
-    if pre and (x is None or x.dtype != z.dtype):
-        raise _C.BayeFormersAMDError("norm_add_rmsnorm_backward: gamma_pre needs the forward's input x")
-    z2 = _rows_of(z, N)
-    x2 = _rows_of(x, N) if pre else None
-    g2 = _grad_rows(grad_out, z, N) if grad_out is not None else None
-    h2 = _grad_rows(grad_sum, z, N) if grad_sum is not None else None
-    dz = torch.empty_like(z2) if (want_dz or not pre) else None
-    dx = torch.empty_like(z2) if pre else None
-    dg_out = torch.empty(N, dtype=torch.float32, device=z.device)
-    dg_pre = torch.empty(N, dtype=torch.float32, device=z.device) if pre else None
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    lib = _C.lib()
-    ws = workspace(z.device, lib.bf_norm_add_rmsnorm_bwd_workspace_bytes(z2.shape[0], N, int(pre)))
-    _C.check(lib.bf_norm_add_rmsnorm_bwd(ptr(x2), z2.data_ptr(), ptr(gamma_pre), gamma_out.data_ptr(), _TORCH2BF[gamma_out.dtype],
-                                         int(weight_offset), ptr(g2), ptr(h2), ptr(dz), ptr(dx), ptr(dg_pre), dg_out.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), _TORCH2BF[z.dtype], z2.shape[0], N, float(eps_pre),
-                                         float(eps_out), _stream_ptr()), "bf_norm_add_rmsnorm_bwd")
+    out = _norm_backward("norm_add_rmsnorm_backward", x, z, gamma_pre, gamma_out, grad_out, eps_pre, eps_out,
+                         int(weight_offset), grad_sum, want_dz)
     FAMILY_BLOCK_BWD_CALLS["norm_add_norm"] += 1
-    dz = dz.view(z.shape) if dz is not None else None
-    return (dx.view(z.shape) if pre else dz), dz, dg_pre, dg_out
+    return out
 
 
 class NormAddRMSNormFn(torch.autograd.Function):
@@ -2679,36 +2691,9 @@ def qknorm_rope_backward(grad_q: Tensor, grad_k: Tensor, cos: Tensor, sin: Tenso
     tensors laid out [B, T, heads, D] — what the backward of the projections reads — returned as their [B, heads, T, D]
     views, the dgammas fp32 [D] (None for a tensor without a gamma).  q / k: the forward's inputs, needed for a tensor that
     has a gamma."""
-    _require_device(grad_q, "qknorm_rope_backward input")
-    grad_q, grad_k = _rope_grad(grad_q, grad_q), _rope_grad(grad_k, grad_q)
-    if not qknorm_rope_supported(grad_q, grad_k, cos, sin, gamma_q, gamma_k):
-        raise _C.BayeFormersAMDError("qknorm_rope_backward: unsupported shapes, strides or dtypes (see ops.qknorm_rope_supported)")
-    for g, x, like in ((gamma_q, q, grad_q), (gamma_k, k, grad_k)):
-        if g is not None and (x is None or x.shape != like.shape or x.dtype != like.dtype or not x.is_cuda):
-            raise _C.BayeFormersAMDError("qknorm_rope_backward: a gamma needs the forward's input of the gradient's shape and dtype")
-    B, H, T, D = grad_q.shape
-    Hkv = grad_k.shape[1]
-    xq = _bthd(q) if gamma_q is not None else None
-    xk = _bthd(k) if gamma_k is not None else None
-    dq = torch.empty((B, T, H, D), dtype=grad_q.dtype, device=grad_q.device).transpose(1, 2)
-    dk = torch.empty((B, T, Hkv, D), dtype=grad_k.dtype, device=grad_k.device).transpose(1, 2)
-    dgq = torch.empty(D, dtype=torch.float32, device=grad_q.device) if gamma_q is not None else None
-    dgk = torch.empty(D, dtype=torch.float32, device=grad_q.device) if gamma_k is not None else None
-    s = _C.bf_rope_t(B, T, H, Hkv, D, cos.shape[0])
-    for name, t in (("q_stride", grad_q), ("k_stride", grad_k), ("q_out_stride", dq), ("k_out_stride", dk)):
-        getattr(s, name)[:] = [t.stride(0), t.stride(1), t.stride(2)]
-    g = gamma_q if gamma_q is not None else gamma_k
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    lib = _C.lib()
-    nbytes = lib.bf_qknorm_rope_bwd_workspace_bytes(ctypes.byref(s), int(g is not None))
-    ws = workspace(grad_q.device, nbytes) if nbytes else None
-    _C.check(lib.bf_qknorm_rope_bwd(grad_q.data_ptr(), grad_k.data_ptr(), ptr(xq), ptr(xk), cos.data_ptr(), sin.data_ptr(),
-                                    _TORCH2BF[cos.dtype], ptr(gamma_q), ptr(gamma_k),
-                                    _TORCH2BF[g.dtype] if g is not None else _C.BF_DT_F32, int(weight_offset), float(eps),
-                                    dq.data_ptr(), dk.data_ptr(), ptr(dgq), ptr(dgk), ptr(ws), ws.numel() if ws is not None else 0,
-                                    _TORCH2BF[grad_q.dtype], ctypes.byref(s), _stream_ptr()), "bf_qknorm_rope_bwd")
+    out = _rope("qknorm_rope_backward", False, True, grad_q, grad_k, cos, sin, q, k, gamma_q, gamma_k, eps, weight_offset, False)
     FAMILY_BLOCK_BWD_CALLS["qknorm_rope"] += 1
-    return dq, dk, dgq, dgk
+    return out
 
 
 class QKNormRopeFn(torch.autograd.Function):
@@ -2735,24 +2720,9 @@ class QKNormRopeFn(torch.autograd.Function):
 
 def geglu_backward(gate: Tensor, up: Tensor, grad_out: Tensor, stacked: bool = False):
     """Gradients of geglu (bf_geglu_bwd): (dgate, dup) from the forward's inputs; stacked as swiglu_backward's."""
-    _require_device(gate, "geglu_backward input")
-    if not geglu_supported(gate, up) or grad_out.shape != gate.shape:
-        raise _C.BayeFormersAMDError("geglu_backward: unsupported shapes, strides or dtypes (see ops.swiglu_supported)")
-    g = grad_out if grad_out.dtype == gate.dtype else grad_out.to(gate.dtype)
-    if not g.is_cuda or _row_stride(g) is None:
-        g = g.contiguous()
-    N = gate.shape[-1]
-    if stacked:
-        both = torch.empty((*gate.shape[:-1], 2 * N), dtype=gate.dtype, device=gate.device)
-        dgate, dup = both[..., :N], both[..., N:]
-    else:
-        dgate, dup = (torch.empty(gate.shape, dtype=gate.dtype, device=gate.device) for _ in range(2))
-    _C.check(_C.lib().bf_geglu_bwd(gate.data_ptr(), _row_stride(gate), up.data_ptr(), _row_stride(up), g.data_ptr(),
-                                   _row_stride(g), dgate.data_ptr(), 2 * N if stacked else N, dup.data_ptr(),
-                                   2 * N if stacked else N, _TORCH2BF[gate.dtype], gate.numel() // N, N, _stream_ptr()),
-             "bf_geglu_bwd")
+    out = _glu_backward("geglu", gate, up, grad_out, stacked)
     FAMILY_BLOCK_BWD_CALLS["geglu"] += 1
-    return dgate, dup
+    return out
 
 
 class GeGLUFn(torch.autograd.Function):

@@ -19,7 +19,7 @@
 
 Device events around `iters` back-to-back calls, every candidate warmed up first, the candidates interleaved inside each
 round; the figures are the median (and the minimum) over the rounds.  Bytes are the algorithmic ones: what the op has to
-read and write once (for the backward kernels: the figures in each kernel's comment in bf_family_blocks.hip).
+read and write once (for the backward kernels: the figures in each kernel's comment in bf_decoder_blocks.hip).
 Launches are device kernels as torch.profiler counts them in one call.  One JSON line per
 measurement; profiles/family_blocks.md holds the numbers."""
 import argparse
