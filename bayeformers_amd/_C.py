@@ -308,6 +308,21 @@ LRT_SYMBOLS = {
     "bf_kl_gaussian": (_i, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _sz, _vp]),
 }
 
+# what include/bayeformers_amd_moe.h declares (bnn.Experts: the route of the slots to their (sample, expert) groups, the two
+# grouped products over the tile table and the weighted sum over a row's k slots)
+MOE_SYMBOLS = {
+    "bf_moe_max_tiles": (_sz, [_i, _i, _i, _i]),
+    "bf_moe_route_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "bf_moe_route": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_moe_gate_up_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "bf_moe_gate_up": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_moe_down_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "bf_moe_down": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "bf_moe_combine_workspace_bytes": (_sz, [_i, _i, _i]),
+    "bf_moe_combine": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+}
+BF_MOE_TILE_ROWS, BF_MOE_MAX_TOPK, BF_MOE_MAX_GROUPS = 16, 16, 4096  # include/bayeformers_amd_moe.h
+
 BF_LRT_STREAM = 0x20000000  # csrc/bf_philox.h
 
 BF_PROF_SAMPLE, BF_PROF_GEMM, BF_PROF_FUSED_SMALL, BF_PROF_FUSED_WS = 0, 1, 2, 3
@@ -412,6 +427,14 @@ def lib():
             if fn is None:  # likewise
                 raise BayeFormersAMDError(
                     f"{LIB_PATH} lacks {name} (the local reparameterisation entries): rebuild it with "
+                    "`python -m bayeformers_amd.build`")
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in MOE_SYMBOLS.items():
+            fn = getattr(l, name, None)
+            if fn is None:  # likewise
+                raise BayeFormersAMDError(
+                    f"{LIB_PATH} lacks {name} (the mixture-of-experts entries): rebuild it with "
                     "`python -m bayeformers_amd.build`")
             fn.restype = res
             fn.argtypes = args

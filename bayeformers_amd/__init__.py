@@ -37,17 +37,27 @@ __all__ = ["to_bayesian", "to_bayesian_lora", "lora_state_dict", "invalidate_cac
 
 def to_bayesian(model: torch.nn.Module, initialization: Optional[Initialization] = DEFAULT_UNIFORM,
                 prior: Optional[Parameter] = DEFAULT_SCALED_GAUSSIAN_MIXTURE, delta: float = None,
-                freeze: bool = False) -> Model:
+                freeze: bool = False, experts: bool = False) -> Model:
     """Deep-copy `model`, swap every layer whose exact class is in TORCH2BAYE for its Bayesian equivalent
     (`from_frequentist(layer, initialization, prior, delta, freeze)`, children visited in `named_children` order,
     depth first) and wrap the result in `bnn.Model`.
 
     Arguments / keyword arguments are the reference's: `delta` not None selects MOPED initialisation from the
-    pretrained weights (Krishnan et al., arXiv:1906.05323), `freeze` freezes the posterior means."""
+    pretrained weights (Krishnan et al., arXiv:1906.05323), `freeze` freezes the posterior means.
+
+    experts=True (an extension, off by default: the conversion and its state dict are otherwise what they were): also swap
+    every child that is a mixture-of-experts block's experts module BY STRUCTURE (nn.layers.experts.is_experts_module: 3-D
+    parameters gate_up_proj [E, 2I, H] and down_proj [E, H, I], `num_experts` and `act_fn`, no other parameter of its own —
+    transformers' MixtralExperts, Qwen3MoeExperts and their relatives) for a bnn.Experts with the same arguments.  Routers
+    stay deterministic; experts with biases (gpt-oss) stay untouched; a shared expert made of nn.Linear layers (Qwen2-MoE)
+    converts as it always did."""
+    from .nn.layers.experts import is_experts_module
 
     def swap(module):
         for name, child in module.named_children():
             bayesian_cls = TORCH2BAYE.get(child.__class__)
+            if bayesian_cls is None and experts and is_experts_module(child):
+                bayesian_cls = nn.Experts
             if bayesian_cls is not None:
                 setattr(module, name, bayesian_cls.from_frequentist(child, initialization, prior, delta, freeze))
             swap(child)
@@ -990,7 +1000,8 @@ def fuse_decoder_blocks(model: torch.nn.Module, backward: Union[bool, str] = Fal
     rewritten when its class is exactly LlamaDecoderLayer, MistralDecoderLayer or Qwen2DecoderLayer with the attribute
     shape those have (RMSNorm modules with `weight` and `variance_epsilon`, an MLP of gate / up / down projections around
     a SiLU, an attention module with q / k / v / o projections and head_dim 64 or 128); with the default `families`, Qwen3
-    (q / k norms), Gemma (1 + weight), OLMo and mixture-of-experts layers are left alone.  By default an inference-time
+    (q / k norms), Gemma (1 + weight), OLMo and mixture-of-experts decoder layers keep their own norms, RoPE and glue (the
+    experts of such a layer are converted by to_bayesian(experts=True) and run on the bf_moe_* kernels).  By default an inference-time
     rewrite like the other fuse_* functions: with gradients recorded, in training mode, off the device or on shapes the
     kernels refuse, the modules' own forwards run.  backward=True: the fast forms also run under recorded gradients and in
     training mode, through autograd functions whose backward is one launch each (bf_add_rmsnorm_bwd, bf_rope_qk_bwd,

@@ -17,7 +17,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libbayeformers_amd.so")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
-SOURCES = ["bf_api.hip", "bf_sample.hip", "bf_gemm.hip", "bf_gemm256.hip", "bf_gemm256_r5.hip", "bf_gemm_schedule.hip", "bf_backward.hip", "bf_fused_small.hip", "bf_gemm_skinny.hip", "bf_gemm_skinny_fp8.hip", "bf_norm.hip", "bf_decoder_blocks.hip", "bf_attention.hip", "bf_attention_bwd.hip", "bf_attention_gqa.hip", "bf_attention_decode.hip", "bf_attention_chunk.hip", "bf_kv8.hip", "bf_kv_ring.hip", "bf_predictive.hip", "bf_generate.hip", "bf_lora.hip", "bf_lrt.hip"]
+SOURCES = ["bf_api.hip", "bf_sample.hip", "bf_gemm.hip", "bf_gemm256.hip", "bf_gemm256_r5.hip", "bf_gemm_schedule.hip", "bf_backward.hip", "bf_fused_small.hip", "bf_gemm_skinny.hip", "bf_gemm_skinny_fp8.hip", "bf_norm.hip", "bf_decoder_blocks.hip", "bf_attention.hip", "bf_attention_bwd.hip", "bf_attention_gqa.hip", "bf_attention_decode.hip", "bf_attention_chunk.hip", "bf_kv8.hip", "bf_kv_ring.hip", "bf_predictive.hip", "bf_generate.hip", "bf_lora.hip", "bf_lrt.hip", "bf_moe.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
 

@@ -7,6 +7,7 @@ conversion registry `TORCH2BAYE`, which `to_bayesian` consults by EXACT class, a
 import torch.nn as _torch_nn
 
 from .layers.embedding import Embedding
+from .layers.experts import Experts
 from .layers.linear import Linear
 from .layers.lora import LoRALinear
 from .model import Model, is_module_bayesian
@@ -14,7 +15,7 @@ from .parameters.base import NoneParameter, Parameter
 from .parameters.gaussian import DEFAULT_SCALED_GAUSSIAN_MIXTURE, Gaussian, ScaledGaussianMixture
 from .parameters.initializations import DEFAULT_UNIFORM, Initialization, Uniform
 
-__all__ = ["Linear", "LoRALinear", "Embedding", "Model", "is_module_bayesian", "Parameter", "NoneParameter", "Gaussian",
+__all__ = ["Linear", "LoRALinear", "Experts", "Embedding", "Model", "is_module_bayesian", "Parameter", "NoneParameter", "Gaussian",
            "ScaledGaussianMixture", "DEFAULT_SCALED_GAUSSIAN_MIXTURE", "Initialization", "Uniform", "DEFAULT_UNIFORM",
            "TORCH2BAYE"]
 

@@ -98,6 +98,7 @@ class _KeptWeights:
         self.watch = []  # (tensor, data_ptr, _version) of every mu / rho the samples were drawn from
         self.ready = False  # the block's first forward has run prepare()
         self.lora = {}  # id(bnn.LoRALinear) -> its 16-bit A_s [S, r, K], drawn by the layer's first forward of the block
+        self.experts = {}  # id(bnn.Experts) -> its two draws ([S, E, 2I, H], [S, E, H, I]), likewise
 
     def prepare(self, model, layers, ctx) -> SamplePlan:
         """The plan of the block; in its first forward also the one sampling launch over all groups."""
@@ -118,7 +119,7 @@ class _KeptWeights:
         shared = tuple(sorted({id(l._shared_input): l._shared_input for l in pl
                                if l._shared_input is not None}.values(), key=lambda t: t[0].layer_id))
         self.ready = True
-        if not pl:  # only LoRA layers are Bayesian: nothing to plan, each keeps its own A_s (lora_sample)
+        if not pl:  # only LoRA / Experts layers are Bayesian: nothing to plan, each keeps its own draws (lora_sample, ...)
             return None
         self.plan = self._draw(pl, [i for i, _ in linears], shared, ctx)
         from .parameters.gaussian import Gaussian
@@ -137,6 +138,15 @@ class _KeptWeights:
             a_s = self.lora[id(layer)] = layer.sample_a(S, seed, base, slot, x_dtype)
             self.watch += [(t, t.data_ptr(), t._version) for t in (layer.lora_A.mu, layer.lora_A.rho)]
         return a_s
+
+    def experts_sample(self, layer, S: int, seed: int, base: int, slot: Tensor, x_dtype: torch.dtype):
+        """The kept draws of a bnn.Experts: both tensors drawn by one launch (with their log-probs, into `slot`) at the layer's
+        first forward of the block, read by every later one.  Always the 16-bit (or fp32-compute) draws, never FP8."""
+        w = self.experts.get(id(layer))
+        if w is None:
+            w = self.experts[id(layer)] = layer.sample_weights(S, seed, base, slot, x_dtype)
+            self.watch += [(t, t.data_ptr(), t._version) for g in (layer.gate_up_proj, layer.down_proj) for t in (g.mu, g.rho)]
+        return w
 
     def _draw(self, pl, index, shared, ctx) -> SamplePlan:
         plan = SamplePlan(pl, self.S, self.cdt, pl[0].weight.mu.device, index=index, shared=shared, keep=True)
@@ -406,7 +416,9 @@ class Model(Module):
         tiled GEMM (fp32 compute: the fp32 GEMM).  The draws and log-probs are the bits the cross-layer plan gives.  Costs
         plan.kept_weight_bytes(model, S, compute dtype) bytes — S * P * 2 in bf16 for P Linear weights — checked before
         anything is allocated against max_bytes (default plan.ARENA_BYTES): above it, ValueError.  A forward after a
-        posterior mu / rho was changed inside the block raises.  bnn.Embedding layers keep their own path.
+        posterior mu / rho was changed inside the block raises.  bnn.Embedding layers keep their own path.  A bnn.LoRALinear
+        keeps its A_s and a bnn.Experts its two weight draws, each drawn at the layer's first forward of the block (the
+        bf_moe_* kernels of later forwards read them: a decode step with experts samples nothing).
 
         keep_weights="fp8" (bf16 compute only): the same block on fewer bytes.  One bf16 copy of each layer's posterior mean is
         kept for all samples, and of each draw only its deviation from that mean, in e4m3 with a power-of-two scale per output
@@ -414,7 +426,8 @@ class Model(Module):
         instead of 2 * S * P, plus a transient 16-bit ring of at most plan.ARENA_BYTES.  Every forward of the block, prefill and
         decode alike, multiplies by the dequantised weights W^, which differ from the bf16 draws by 2^-4 of the DEVIATION (0.3 %
         of |mu| at MOPED delta = 0.05), not of the weight.  Decode steps run bf_gemm_nt_skinny_fp8 on the bytes; the other
-        GEMMs read W^ dequantised into the ring.  log_prob_samples() is that of the unrounded draws, bitwise keep_weights=True's."""
+        GEMMs read W^ dequantised into the ring.  log_prob_samples() is that of the unrounded draws, bitwise keep_weights=True's.
+        A model with bnn.Experts layers is refused (ValueError naming them): their kept draws have no FP8 form."""
         if self.__dict__.get("_pinned") is not None:
             raise RuntimeError("pinned_samples: already pinned")
         if keep_weights != "fp8" and (isinstance(keep_weights, str) or keep_weights not in (True, False)):
@@ -448,8 +461,8 @@ class Model(Module):
         (Linear.mean_weights; dropped by a new mu, a later stale epoch or ops.invalidate_caches): plan.mean_weight_bytes(model,
         dtype) bytes, P * 2 in bf16 against the S * P * 2 of keep_weights=True.  Inside keep_weights="fp8" the block's own
         centre copies are read and nothing is added.  At most ops.SKINNY_ROWS rows run bf_gemm_nt_skinny with S = 1, more
-        rows the tiled GEMM.  Inference only (no gradient); a model with a bnn.Embedding or a bnn.LoRALinear, which have no
-        mean form yet, is refused (ValueError)."""
+        rows the tiled GEMM.  Inference only (no gradient); a model with a bnn.Embedding, a bnn.LoRALinear or a bnn.Experts,
+        which have no mean form yet, is refused (ValueError naming the layer types)."""
         if bfr.STATE.ctx is not None:
             raise RuntimeError("posterior_mean: entered inside a running forward")
         if torch.is_grad_enabled():
@@ -486,10 +499,14 @@ class Model(Module):
         if need > limit:
             raise ValueError(f"pinned_samples({mode}): the kept samples need {need} bytes (S={S}, {cdt}), "
                              f"above max_bytes={limit}")
+        from .layers.experts import Experts
         from .layers.lora import LoRALinear
 
+        if fp8 and any(isinstance(l, Experts) for l in self.fused_children()):
+            raise ValueError(f"pinned_samples({mode}): the model has Experts layers, whose kept draws have no FP8 form "
+                             "(bnn.Linear only) — use keep_weights=True")
         linears = [l for l in self.fused_children() if isinstance(l, Linear)]
-        if not linears and not any(isinstance(l, LoRALinear) for l in self.fused_children()):
+        if not linears and not any(isinstance(l, (LoRALinear, Experts)) for l in self.fused_children()):
             raise ValueError(f"pinned_samples({mode}): the model has no Bayesian Linear layer")
         if linears and not SamplePlan.plannable(linears):
             raise ValueError(f"pinned_samples({mode}) needs every Bayesian Linear on one ROCm device, with built-in "
@@ -497,11 +514,16 @@ class Model(Module):
         return (_KeptFp8Weights if fp8 else _KeptWeights)(S, cdt)
 
     def fused_children(self) -> List[KernelLayer]:
-        """The kernel-backed children (bnn.Linear, bnn.Embedding) in registration order; their layer_id (Philox
-        stream) is that order."""
+        """The kernel-backed children (bnn.Linear, bnn.Embedding, bnn.LoRALinear, bnn.Experts) in registration order; their
+        layer_id (Philox stream) is that order, with the bnn.Experts layers numbered after all the others."""
         if self._fused is None:
             self._fused = [m for m in self.modules() if isinstance(m, KernelLayer)]
-            for i, l in enumerate(self._fused):
+            # bnn.Experts layers (to_bayesian(experts=True)) are numbered after all the others: every other layer keeps the
+            # stream, and so the draws, it has in the conversion without them
+            from .layers.experts import Experts
+
+            order = [l for l in self._fused if not isinstance(l, Experts)] + [l for l in self._fused if isinstance(l, Experts)]
+            for i, l in enumerate(order):
                 l.layer_id = i
         return self._fused
 

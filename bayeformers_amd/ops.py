@@ -3228,3 +3228,230 @@ def lrt_backward(layer, saved, dy: Tensor, S: int, seed: int, sample_base: int, 
         dmu_b = g.float().sum(0) if need_mu_b else None
         drho_b = dv.float().sum(0) * (2 * torch.nn.functional.softplus(rho_b) * torch.sigmoid(rho_b))
     return dx, dmu, drho, dmu_b, drho_b
+
+
+# ------------------------------------------------------------------------------------------- Bayesian mixture of experts
+# bnn.Experts (include/bayeformers_amd_moe.h): every (sample, expert) pair has weight matrices of its own, so the layer is a
+# grouped GEMM over S * E groups whose sizes the router decides.  bf_moe_route lays the slots out by group on the device (no
+# host round trip: the launches have a fixed grid, so a decode step with such a layer can be graph-captured), bf_moe_gate_up
+# and bf_moe_down run the two products over the tile table, bf_moe_combine adds a row's k results.  What moe_supported()
+# refuses runs moe_composite, the framework's loop per (sample, expert) on the same sampled weights — it waits for the
+# device, so such a call cannot be captured.
+MOE_TILE_ROWS, MOE_MAX_TOPK, MOE_MAX_GROUPS = _C.BF_MOE_TILE_ROWS, _C.BF_MOE_MAX_TOPK, _C.BF_MOE_MAX_GROUPS
+MOE_CALLS = {"route": 0, "gate_up": 0, "down": 0, "combine": 0, "composite_fwd": 0, "composite_bwd": 0, "sample": 0}
+
+
+def moe_is_silu(act) -> bool:
+    """Is `act` (an experts module's act_fn, or a name) SiLU — the one activation bf_moe_gate_up applies?"""
+    if isinstance(act, str):
+        return act in ("silu", "swish")
+    return (act is torch.nn.functional.silu or isinstance(act, torch.nn.SiLU)
+            or (act.__class__.__name__ == "SiLUActivation" and not list(act.parameters())))
+
+
+MOE_KERNEL_ROWS_PER_GROUP = 128
+
+
+def moe_kernel_wins(S: int, E: int, k: int, rows: int) -> bool:
+    """Where the kernel route beats the framework loop on one MI355X, eager (profiles/bayesian_moe.md; bf16, S 4): by the rows
+    a (sample, expert) group holds on average, rows * k / (S * E).  Measured wins: decode steps (at most one row per group:
+    0.33x the loop's time on a Mixtral-shaped layer, 0.02x on a Qwen3-MoE-shaped one) and 64 rows per group (Qwen3-MoE-shaped
+    prefill, 0.07x: the loop is bound by its 7717 launches).  Measured loss: 256 rows per group (Mixtral-shaped prefill, 4.3x):
+    every 16-row tile streams its group's weights again, where the loop's per-expert GEMMs are tiled.  Sizes between the two go
+    with the nearer in ratio: up to MOE_KERNEL_ROWS_PER_GROUP rows per group the kernels.  A capturing stream never asks:
+    the loop cannot be captured."""
+    return rows * k <= MOE_KERNEL_ROWS_PER_GROUP * S * E
+
+
+def moe_supported(dtype: torch.dtype, H: int, I: int, E: int, k: int, act, *tensors: Tensor, S: int = 1,
+                  rows: Optional[int] = None) -> bool:
+    """Do the bf_moe_* entries take this layer?  16-bit compute, H % 8 == 0, I % 8 == 0, SiLU, 1 <= k <= MOE_MAX_TOPK,
+    S * E <= MOE_MAX_GROUPS; `tensors` (optional): the operands, each on a ROCm device, contiguous and 16-byte aligned.
+    rows (optional): also whether the kernels are the faster route for that many rows (moe_kernel_wins) — what moe_forward
+    asks outside a graph capture; None: the kernels' class alone.
+    The one predicate that routes a call to the kernels or to the framework composite."""
+    if dtype not in (torch.bfloat16, torch.float16) or H < 8 or I < 8 or H % 8 or I % 8 or not moe_is_silu(act):
+        return False
+    if not 1 <= k <= MOE_MAX_TOPK or E < 1 or S < 1 or S * E > MOE_MAX_GROUPS:
+        return False
+    if rows is not None and not moe_kernel_wins(S, E, k, rows) and not (
+            torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        return False
+    return all(t is None or (t.is_cuda and t.is_contiguous() and t.data_ptr() % 16 == 0) for t in tensors)
+
+
+def moe_max_tiles(S: int, E: int, R: int, k: int) -> int:
+    """Tiles the grouped GEMMs are launched with: R*k / MOE_TILE_ROWS + min(S*E, R*k), known without the routing."""
+    return (R * k) // MOE_TILE_ROWS + min(S * E, R * k)
+
+
+def moe_route(top_k_index: Tensor, S: int, E: int):
+    """(offsets [S*E + 1], slots [R*k], tiles [max_tiles, 3]) int32 of bf_moe_route for top_k_index [R, k] int64: the slots
+    (row * k + j) sorted by group s * E + index, stable; an index equal to E is dropped.  slots past offsets[-1] and nothing
+    else are left unwritten.  Nothing is read back to the host."""
+    _require_device(top_k_index, "top_k_index")
+    if top_k_index.dim() != 2 or top_k_index.dtype != torch.int64 or not top_k_index.is_contiguous():
+        raise _C.BayeFormersAMDError("moe_route: top_k_index must be a contiguous [R, k] int64 tensor")
+    R, k = top_k_index.shape
+    dev = top_k_index.device
+    lib = _C.lib()
+    offsets = torch.empty(max(S * E, 0) + 1, dtype=torch.int32, device=dev)
+    slots = torch.empty(R * k, dtype=torch.int32, device=dev)
+    tiles = torch.empty((moe_max_tiles(S, E, R, k), 3), dtype=torch.int32, device=dev)
+    need = lib.bf_moe_route_workspace_bytes(S, E, R, k)
+    ws = workspace(dev, need)
+    _C.check(lib.bf_moe_route(top_k_index.data_ptr(), offsets.data_ptr(), slots.data_ptr(), tiles.data_ptr(), S, E, R, k,
+                              ws.data_ptr(), ws.numel(), _stream_ptr()), "bf_moe_route")
+    MOE_CALLS["route"] += 1
+    return offsets, slots, tiles
+
+
+def _moe_dims(w_gu: Tensor, w_d: Optional[Tensor] = None):
+    if w_gu.dim() != 4 or w_gu.shape[2] % 2 or (w_d is not None and (
+            w_d.dim() != 4 or w_d.shape[:2] != w_gu.shape[:2] or w_d.shape[2] != w_gu.shape[3]
+            or 2 * w_d.shape[3] != w_gu.shape[2])):
+        raise _C.BayeFormersAMDError(f"moe: w_gu {tuple(w_gu.shape)} must be [S, E, 2I, H]"
+                                     + (f" and w_d {tuple(w_d.shape)} [S, E, H, I]" if w_d is not None else ""))
+    S, E, I2, H = w_gu.shape
+    return S, E, H, I2 // 2
+
+
+def moe_gate_up(x: Tensor, w_gu: Tensor, route, k: int) -> Tensor:
+    """h [R*k, I] of x's dtype: h[slot] = silu(gate) * up with [gate | up] = x[slot // k] w_gu[s, e]^T (bf_moe_gate_up).
+    x: [R, H] 16-bit, w_gu: [S, E, 2I, H] of the same dtype, route: what moe_route returned.  Rows of dropped slots are not
+    written.  Refusals raise."""
+    _require_device(x, "x")
+    S, E, H, I = _moe_dims(w_gu)
+    _, slots, tiles = route
+    if x.dim() != 2 or x.shape[1] != H or w_gu.dtype != x.dtype:
+        raise _C.BayeFormersAMDError(f"bf_moe_gate_up: x {tuple(x.shape)} {x.dtype} must be [R, H={H}] of w_gu's dtype "
+                                     f"{w_gu.dtype} (16-bit compute)")
+    if not (x.is_contiguous() and w_gu.is_contiguous()):
+        raise _C.BayeFormersAMDError("bf_moe_gate_up: operands must be contiguous")
+    R = x.shape[0]
+    if slots.numel() != R * k or tiles.shape[0] != moe_max_tiles(S, E, R, k):
+        raise _C.BayeFormersAMDError("bf_moe_gate_up: the route was made for another problem")
+    h = torch.empty((R * k, I), dtype=x.dtype, device=x.device)
+    _C.check(_C.lib().bf_moe_gate_up(x.data_ptr(), w_gu.data_ptr(), slots.data_ptr(), tiles.data_ptr(), h.data_ptr(),
+                                     _TORCH2BF.get(x.dtype, -1), S, E, R, k, H, I, None, 0, _stream_ptr()), "bf_moe_gate_up")
+    MOE_CALLS["gate_up"] += 1
+    return h
+
+
+def moe_down(h: Tensor, w_d: Tensor, route, k: int) -> Tensor:
+    """y [R, k, H] fp32: y[r, j] = h[r * k + j] w_d[s, e]^T (bf_moe_down).  h: [R*k, I] 16-bit, w_d: [S, E, H, I] of the same
+    dtype.  Rows of dropped slots are not written.  Refusals raise."""
+    _require_device(h, "h")
+    if w_d.dim() != 4:
+        raise _C.BayeFormersAMDError(f"bf_moe_down: w_d {tuple(w_d.shape)} must be [S, E, H, I]")
+    S, E, H, I = w_d.shape
+    _, slots, tiles = route
+    if h.dim() != 2 or h.shape[1] != I or h.shape[0] % k or w_d.dtype != h.dtype:
+        raise _C.BayeFormersAMDError(f"bf_moe_down: h {tuple(h.shape)} {h.dtype} must be [R*k, I={I}] of w_d's dtype "
+                                     f"{w_d.dtype} (16-bit compute)")
+    if not (h.is_contiguous() and w_d.is_contiguous()):
+        raise _C.BayeFormersAMDError("bf_moe_down: operands must be contiguous")
+    R = h.shape[0] // k
+    if slots.numel() != R * k or tiles.shape[0] != moe_max_tiles(S, E, R, k):
+        raise _C.BayeFormersAMDError("bf_moe_down: the route was made for another problem")
+    y = torch.empty((R, k, H), dtype=torch.float32, device=h.device)
+    _C.check(_C.lib().bf_moe_down(h.data_ptr(), w_d.data_ptr(), slots.data_ptr(), tiles.data_ptr(), y.data_ptr(),
+                                  _TORCH2BF.get(h.dtype, -1), S, E, R, k, H, I, None, 0, _stream_ptr()), "bf_moe_down")
+    MOE_CALLS["down"] += 1
+    return y
+
+
+def moe_combine(y: Tensor, top_k_index: Tensor, top_k_weights: Tensor, E: int, dtype: torch.dtype) -> Tensor:
+    """out [R, H] of `dtype`: out[r] = sum_j top_k_weights[r, j] * y[r, j] in j order, in fp32, rounded once; slots whose
+    index is not an expert (E: dropped) count as zero (bf_moe_combine).  top_k_weights: fp32 or `dtype`."""
+    _require_device(y, "y")
+    if y.dim() != 3 or y.dtype != torch.float32 or top_k_index.shape != y.shape[:2] or top_k_weights.shape != y.shape[:2]:
+        raise _C.BayeFormersAMDError("bf_moe_combine: y must be [R, k, H] fp32, top_k_index and top_k_weights [R, k]")
+    if top_k_index.dtype != torch.int64:
+        raise _C.BayeFormersAMDError("bf_moe_combine: top_k_index must be int64")
+    if not (y.is_contiguous() and top_k_index.is_contiguous() and top_k_weights.is_contiguous()):
+        raise _C.BayeFormersAMDError("bf_moe_combine: operands must be contiguous")
+    R, k, H = y.shape
+    out = torch.empty((R, H), dtype=dtype, device=y.device)
+    _C.check(_C.lib().bf_moe_combine(y.data_ptr(), top_k_index.data_ptr(), top_k_weights.data_ptr(),
+                                     _TORCH2BF.get(top_k_weights.dtype, -1), out.data_ptr(), _TORCH2BF.get(dtype, -1), E, R, k, H,
+                                     None, 0, _stream_ptr()), "bf_moe_combine")
+    MOE_CALLS["combine"] += 1
+    return out
+
+
+def moe_composite(x: Tensor, top_k_index: Tensor, top_k_weights: Tensor, w_gu: Tensor, w_d: Tensor, S: int, act) -> Tensor:
+    """The framework's expert loop (transformers' `*Experts.forward`) once per sample on that sample's weights: for every
+    expert that was hit, gather its rows, two F.linear calls around act(gate) * up, scale by the routing weight, index_add.
+    Differentiable in x, top_k_weights, w_gu and w_d — the backward of bnn.Experts runs it under autograd — and the route of
+    every call the kernels do not take.  It reads the hit experts back to the host: it cannot be graph-captured."""
+    R, H = x.shape
+    M = R // S
+    E = w_gu.shape[1]
+    if w_gu.dtype != x.dtype:
+        w_gu, w_d = w_gu.to(x.dtype), w_d.to(x.dtype)
+    outs = []
+    for s in range(S):
+        xs, ids, ws = x[s * M:(s + 1) * M], top_k_index[s * M:(s + 1) * M], top_k_weights[s * M:(s + 1) * M]
+        out = torch.zeros_like(xs)
+        for e in torch.unique(ids).tolist():
+            if not 0 <= e < E:
+                continue  # (E: the dropped-slot sentinel)
+            tok, pos = torch.where(ids == e)
+            gate, up = torch.nn.functional.linear(xs[tok], w_gu[s, e]).chunk(2, dim=-1)
+            cur = torch.nn.functional.linear(act(gate) * up, w_d[s, e]) * ws[tok, pos, None]
+            out = out.index_add(0, tok, cur.to(out.dtype))
+        outs.append(out)
+    return torch.cat(outs) if S > 1 else outs[0]
+
+
+def moe_forward(x: Tensor, top_k_index: Tensor, top_k_weights: Tensor, w_gu: Tensor, w_d: Tensor, S: int, act) -> Tensor:
+    """out [R, H] of bnn.Experts for S samples on the sampled weights w_gu [S, E, 2I, H] and w_d [S, E, H, I] (as
+    ops.sample_logprob drew them): four entries — route, gate_up, down, combine — where moe_supported(), else moe_composite.
+    While a graph is being captured an unsupported call raises: the composite waits for the device."""
+    _require_device(x, "hidden_states")
+    _, E, H, I = _moe_dims(w_gu, w_d)
+    R, k = top_k_index.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    idx = top_k_index if top_k_index.is_contiguous() else top_k_index.contiguous()
+    wts = top_k_weights if top_k_weights.is_contiguous() else top_k_weights.contiguous()
+    if (w_gu.dtype == x.dtype and w_d.dtype == x.dtype and idx.dtype == torch.int64 and wts.dtype in (torch.float32, x.dtype)
+            and moe_supported(x.dtype, H, I, E, k, act, x, w_gu, w_d, S=S, rows=R)):
+        route = moe_route(idx, S, E)
+        h = moe_gate_up(x, w_gu, route, k)
+        y = moe_down(h, w_d, route, k)
+        return moe_combine(y, idx, wts, E, x.dtype)
+    if torch.cuda.is_current_stream_capturing():
+        raise _C.BayeFormersAMDError(
+            f"moe_forward: this call is outside the bf_moe_* kernels' class (dtype {x.dtype}, H={H}, I={I}, E={E}, k={k}, S={S}, "
+            f"act {act.__class__.__name__}) and the framework loop that serves it waits for the device: it cannot be captured")
+    MOE_CALLS["composite_fwd"] += 1
+    return moe_composite(x, idx, wts, w_gu, w_d, S, act)
+
+
+def moe_backward(x: Tensor, dy: Tensor, top_k_index: Tensor, top_k_weights: Tensor, w_gu: Tensor, w_d: Tensor, S: int, act,
+                 need_x: bool = True, need_wts: bool = True, need_w: bool = True):
+    """(dx, d top_k_weights, dW_gu [S, E, 2I, H] fp32, dW_d [S, E, H, I] fp32) of moe_forward — each None when not needed — by
+    autograd through moe_composite on the saved x, the sampled weights and the routing.  (Backward kernels: not yet.)"""
+    MOE_CALLS["composite_bwd"] += 1
+    with torch.enable_grad():
+        xd = x.detach().requires_grad_(need_x)
+        wt = top_k_weights.detach().requires_grad_(need_wts)
+        gu = w_gu.detach().requires_grad_(need_w)
+        dn = w_d.detach().requires_grad_(need_w)
+        out = moe_composite(xd, top_k_index, wt, gu, dn, S, act)
+        wanted = [t for t, need in ((xd, need_x), (wt, need_wts), (gu, need_w), (dn, need_w)) if need]
+        grads = list(torch.autograd.grad(out, wanted, dy.reshape(out.shape).to(out.dtype), allow_unused=True))
+    res = []
+    for t, need in ((xd, need_x), (wt, need_wts), (gu, need_w), (dn, need_w)):
+        g = grads.pop(0) if need else None
+        res.append(torch.zeros_like(t) if need and g is None else g)
+    dx, dwt, dgu, ddn = res
+    return dx, dwt, dgu.float() if dgu is not None else None, ddn.float() if ddn is not None else None
+
+
+def reduce_param_grad(dw: Tensor, gaussian, stream_id: int, S: int, seed: int, sample_base: int, need_mu: bool = True):
+    """(dmu or None, drho) of one Gaussian from its per-sample weight gradients dw [S, *shape] fp32: dmu = sum_s dw_s,
+    drho = (sum_s dw_s o eps_s) o softplus'(rho), eps regenerated from the counter (bf_launch_param_grad — what
+    lora_reduce_da does for LoRA's dA, here for any sampled tensor: the two expert tensors of bnn.Experts)."""
+    return lora_reduce_da(dw.reshape(S, -1), gaussian, stream_id, S, seed, sample_base, need_mu)

@@ -295,11 +295,13 @@ class SamplePlan:
 def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
     """Device bytes Model.pinned_samples(keep_weights=True) keeps for `S` samples at compute dtype `dtype` (torch.float32,
     torch.bfloat16 or torch.float16): S * sum(N * K) * element size over the model's Bayesian Linear layers, plus S * N fp32 per
-    bias.  (The arenas round each slice up to 256 bytes.)  Needs no GPU.
+    bias, plus S * r * K per bnn.LoRALinear (its A_s) and S * 3 * E * I * H per bnn.Experts (its two draws).  (The arenas round
+    each slice up to 256 bytes.)  Needs no GPU.
 
     fp8=True: what keep_weights="fp8" keeps (bf16 compute only) — per layer the 16-bit centre N * K * 2 shared by the samples,
     and per sample N * K bytes of e4m3 deviations with N fp32 row scales; the fp32 biases as above.  Exactly the bytes of the
     block's store: each piece is a tensor of its own, nothing is padded."""
+    from .nn.layers.experts import Experts
     from .nn.layers.linear import Linear
     from .nn.layers.lora import LoRALinear
     from .nn.parameters.base import NoneParameter
@@ -321,6 +323,9 @@ def kept_weight_bytes(model, S: int, dtype, fp8: bool = False) -> int:
                 total += S * N * 4
         elif isinstance(l, LoRALinear):
             total += S * l.r * l.in_features * esz  # its A_s [S, r, K] in the compute dtype (never FP8): the base is shared
+        elif isinstance(l, Experts):
+            # its two draws [S, E, 2I, H] and [S, E, H, I] in the compute dtype (keep_weights="fp8" refuses such a model)
+            total += S * 3 * l.num_experts * l.intermediate_dim * l.hidden_dim * esz
     return total
 
 

@@ -874,7 +874,7 @@ def sample_generate(model: Model, input_ids: Tensor, attention_mask: Optional[Te
     full-capacity layers and soft-capping.  Refused (ValueError): no keep_weights; do_sample and the truncation
     arguments (rejection sampling against the draft is not built); the logits processors (they depend on the tokens of
     earlier positions of the same span); sliding_cache="ring" (a rejected draft's key would already have overwritten a
-    live slot); group; models with a bnn.LoRALinear or a bnn.Embedding (no posterior-mean forward yet).  None (the
+    live slot); group; models with a bnn.LoRALinear, a bnn.Embedding or a bnn.Experts (no posterior-mean forward yet).  None (the
     default) changes nothing, bit for bit."""
     samples, max_new_tokens = int(samples), int(max_new_tokens)
     if samples < 1:

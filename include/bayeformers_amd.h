@@ -840,5 +840,6 @@ int bf_mc_predictive_finish(const void* d_partial, int64_t R, int64_t C, int S_t
 #include "bayeformers_amd_ring.h"          /* the ring-buffer KV cache of sliding-window layers: appends and decode attention, likewise */
 #include "bayeformers_amd_spec.h"          /* speculative decoding: the epilogue of one draft-and-verify iteration, likewise */
 #include "bayeformers_amd_lrt.h"           /* local reparameterisation of bnn.Linear: the passes around its two products, likewise */
+#include "bayeformers_amd_moe.h"           /* Bayesian mixture-of-experts layers: routing, grouped GEMMs, combine, likewise */
 
 #endif /* BAYEFORMERS_AMD_H */
